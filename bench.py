@@ -18,10 +18,20 @@ Workloads.
   --config 3            SURVEY §8(d) config 3: global batch 64 drawn by ONE prepare_noise(seed) call on the whole
                         batch (ksampler_util.py:274-311), sharded 64/N per GPU (CFG batch 2*64/N), strong scaling.
 
-Timing.  W warm-up steps, then `--repeats` (default 3) timed regions of EXACTLY K steps each, every region bracketed
-by barrier + torch.cuda.synchronize() on both sides, MAX over ranks per region, median over regions -> `value`.
+Timing.  W warm-up steps, then `--repeats` timed regions of EXACTLY K steps each (default: one region, so that
+--steps K is the number of timed steps; three with --full), every region bracketed by barrier + torch.cuda.synchronize()
+on both sides, MAX over ranks per region, median over regions -> `value`.
 
-Prints ONE JSON line on rank 0 (contract in the task prompt) with extra objects:
+Plain run vs --full.  A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the
+line; `roofline`, `cpu_baseline`, `parity_check`, `secondary`, `timing.rccl_direct` and `timing.config3_e2e` are null.
+--full adds every leg below (the --no-* switches still drop single legs of it).
+
+--dump-outputs DIR  after the timed regions, rank 0 writes what the last timed step handed back as float32 .npy files:
+                    `latents` (the gathered final latents), `denoised_uncond` / `denoised_cond` (the last CFG evaluation,
+                    this rank's shard); 64 MB at most in all (a larger array is replaced by a seeded sample of its elements).
+                    Weights, prompts and noise are seeded, so equal arguments give equal inputs on every run.
+
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...); with --full it carries the extra objects:
   roofline      dominant kernel = the single (kernel, op shape) with the largest share of step time, algorithmic FLOP/s
                 from per-op HIP events recorded on the launch stream (ldx_profile mode 2) against the dense bf16 MFMA
                 peak (2.5 PFLOP/s, MI355X_MICROARCH.md); HBM traffic per launch from the committed PMC passes
@@ -58,7 +68,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps each; the median is reported (default 1, with --full 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: per-kernel roofline, secondary configs, reference parity check, CPU baseline, "
+                         "direct-RCCL and config-3 decode checks (off: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (final latents, last CFG evaluation) to DIR/<name>.npy, float32, <= 64 MB in all")
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--latent", type=int, default=128)
     ap.add_argument("--config", type=int, default=2, choices=(2, 3), help="SURVEY §8(d) config: 2 = one image per GPU (weak), 3 = global batch 64 sharded (strong)")
@@ -76,7 +91,10 @@ def parse_args(argv=None):
     ap.add_argument("--private-weights", action="store_true", help="N > 1: every rank synthesises its own state dict (default: local rank 0 publishes one under /dev/shm)")
     ap.add_argument("--stub-engine", action="store_true",
                     help="TEST ONLY (tests/test_bench_gloo.py): CPU + gloo, an analytic per-sample stand-in for the UNet; the line is marked stub")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    return args
 
 
 def free_port():
@@ -429,6 +447,23 @@ def run_preflight(ldx, dist, rank, world, local_rank, dev, stub):
             "rccl_direct": direct, "ranks": infos}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as float32 DIR/<name>.npy.  An array above its even share of DUMP_BYTES is replaced by a fixed, seeded sample
+    of its flattened elements (same size -> same positions on every run), so two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().contiguous().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def parity_check(ldx, eng, dtype):
     """Did the timed loop time the RIGHT work?  Runs BASELINE config 2 exactly as the reference golden was captured (oracle/ref_capture_full20.py:
     KSampler.sample, sample_euler / normal, 20 steps, cfg 7, seed 42, multiscale off, zero latent 128^2, the fixture's own prompt tensors) through the
@@ -548,6 +583,8 @@ def main(argv=None):
     x = (noise * torch.sqrt(1.0 + sigmas[0] ** 2.0)).to(dev)
     model = ldx.sampling.CFGDenoiser(eng, pos, neg, 7.0, pb, lat, lat)
 
+    last = {}
+
     def run_steps(i0, n):
         for i in range(i0, i0 + n):
             du, dc = model(x, sigmas[i])
@@ -555,6 +592,7 @@ def main(argv=None):
                 stub_step(x, du, dc, 7.0, sigmas[i], sigmas[i + 1] - sigmas[i])
             else:
                 ldx.sampling._step(0, x, du, dc, 7.0, sigmas[i], sigmas[i + 1] - sigmas[i])
+            last["du"], last["dc"] = du, dc          # views of the engine's output buffer: valid until its next evaluation
 
     def fence():
         sync()
@@ -589,12 +627,14 @@ def main(argv=None):
             gpu_ms.append(ev0.elapsed_time(ev1) / args.steps)
     assert gathered.shape[0] == gb, (gathered.shape, gb)
     assert torch.isfinite(gathered).all(), "non-finite latents"
+    if args.dump_outputs and rank == 0:          # before any other evaluation reuses the engine's output buffer
+        dump_outputs(args.dump_outputs, {"latents": gathered, "denoised_uncond": last["du"], "denoised_cond": last["dc"]})
 
     # The same collective once more through the DIRECT RCCL path (ctypes on librccl.so: ncclCommInitRank + ncclAllGather on this stream; the unique id
     # travels through the process group's store, not a data-path collective).  Outside the timed regions and guarded: the first multi-GPU run of this
     # code must not lose its headline to an untested call; the line reports whether it ran, its time, and that it returned the same bytes.
     rccl_direct = None
-    if world > 1 and not stub:
+    if args.full and world > 1 and not stub:
         try:
             def _xchg(r, make_id):
                 box = [make_id() if r == 0 else None]
@@ -614,7 +654,7 @@ def main(argv=None):
     # 3 MiB per image against 64 KiB per latent, so the images stay with the rank that made them and only the latents are gathered).  After the timed
     # regions, guarded like the direct RCCL check: reported next to the headline, never part of it.
     e2e3 = None
-    if args.config == 3 and not stub and not args.tiny:
+    if args.full and args.config == 3 and not stub and not args.tiny:
         try:
             vcfg = ldx.VAEConfig()
             vae = ldx.VAEDecoderEngine(vcfg, ldx.weights.synth_state_dict(ldx.weights.vae_decoder_state_dict_spec(vcfg), seed=1, dtype=torch.float32), device=local_rank, dtype="bf16")
@@ -661,7 +701,7 @@ def main(argv=None):
     info = eng.plan_info()
     # ---- per-kernel roofline leg: same process, same data, HIP events per op on the launch stream ----
     roof = None
-    if rank == 0 and not stub:
+    if args.full and rank == 0 and not stub:
         eng.set_graph_mode(False)
         eng._lib.ldx_profile(eng._h, 2, 1)            # mode 2: keyed by kernel class AND op shape
         xs = x_start.clone()
@@ -720,7 +760,7 @@ def main(argv=None):
                 "kernels": kern}
 
     secondary = None
-    if rank == 0 and world == 1 and not stub and not args.no_secondary and not args.tiny and args.config == 2 and pb == 1:
+    if args.full and rank == 0 and world == 1 and not stub and not args.no_secondary and not args.tiny and args.config == 2 and pb == 1:
         secondary = secondary_lines(ldx, eng, cfg, lat, args.steps)
         if lat == 128 and not args.no_configs:
             # SURVEY §8(d) configs 3, 4, 5 on the driver's clock (each guarded: a failure is reported in the line, the headline stays valid)
@@ -744,14 +784,14 @@ def main(argv=None):
 
     # ---- did the timed regions time the right work?  (N = 1, headline engine, after every timed region; fixture comparison only) ----
     parity = None
-    if rank == 0 and world == 1 and not stub and not args.tiny and not args.no_parity_check:
+    if args.full and rank == 0 and world == 1 and not stub and not args.tiny and not args.no_parity_check:
         try:
             parity = parity_check(ldx, eng, args.dtype)
         except Exception as e:      # noqa: BLE001 — reported in the line
             parity = {"ok": False, "error": repr(e)[:300]}
 
     cpu = None
-    if rank == 0 and world == 1 and not stub and not args.no_cpu_baseline and not args.tiny:
+    if args.full and rank == 0 and world == 1 and not stub and not args.no_cpu_baseline and not args.tiny:
         cpu = cpu_baseline(cfg, sd)
         cpu["reference_cpu"] = reference_cpu()
 

@@ -3,7 +3,7 @@
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp; export TMPDIR=/tmp
 rm -rf /tmp/pm
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES SQ_WAIT_INST_LDS -d /tmp/pm -o p --output-format csv -- python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph > /tmp/pm.log 2>&1 || tail -3 /tmp/pm.log
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES SQ_WAIT_INST_LDS -d /tmp/pm -o p --output-format csv -- python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-graph > /tmp/pm.log 2>&1 || tail -3 /tmp/pm.log
 python - <<'PY'
 import csv, glob, collections
 fs = glob.glob("/tmp/pm/**/*counter_collection.csv", recursive=True)

@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/prof_r06
 mkdir -p $OUT; : > $OUT/pmc_kernels.txt; rm -f $OUT/pmc_step_kernels.json
 cd /tmp; export TMPDIR=/tmp
 if [ "$1" != "pmc-only" ]; then
-rocprofv3 --kernel-trace --stats -d $OUT -o bench --output-format csv -- python $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --no-graph > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats -d $OUT -o bench --output-format csv -- python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --no-graph > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 python $ROOT/profiles/analyze_trace.py $(find $OUT -name "bench_kernel_trace.csv" | head -1) 40 > $OUT/forward_breakdown.txt 2>&1
 find $OUT -name "bench_kernel_trace.csv" -delete
 find $OUT -name "bench_kernel_stats.csv" -exec cp {} $OUT/bench_kernel_stats.csv \; 2>/dev/null

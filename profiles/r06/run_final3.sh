@@ -3,7 +3,7 @@ mkdir -p gpurun_out/r06final3
 O=gpurun_out/r06final3
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
 timeout 3000 python -m pytest tests -m gpu -q --durations=5 > $O/gputests.log 2>&1; echo "gpu tests rc $?"; tail -10 $O/gputests.log
-timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
+timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
 python - <<PY
 import json
 d=json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1])

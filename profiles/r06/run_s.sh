@@ -2,7 +2,7 @@
 cd /root/repo
 for rep in 1 2; do
   for g in 1 0; do
-    LDX_EP_GENERAL=$g python bench.py --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('LDX_EP_GENERAL=$g', d['ms_per_step'], 'ms/step', d['value'], 'it/s', 'parity', d['parity_check']['rel_l2'])"
+    LDX_EP_GENERAL=$g python bench.py --full --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('LDX_EP_GENERAL=$g', d['ms_per_step'], 'ms/step', d['value'], 'it/s', 'parity', d['parity_check']['rel_l2'])"
   done
 done
 for g in 1 0; do
