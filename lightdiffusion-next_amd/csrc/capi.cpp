@@ -293,13 +293,13 @@ int ldx_plan_info(ldx_engine* e, int64_t* n_launches, double* flops, int64_t* ar
     if (!e) { set_error("null engine"); return LDX_EINVAL; }
     if (n_launches) *n_launches = e->impl->n_launches();
     if (flops) *flops = e->impl->algorithmic_flops();
-    if (arena_bytes) *arena_bytes = (int64_t)e->impl->arena_cap;
+    if (arena_bytes) *arena_bytes = (int64_t)e->impl->cur.arena_cap;
     return LDX_OK;
 }
 int ldx_plan_flops(ldx_engine* e, double* executed, double* shared) {
     if (!e) { set_error("null engine"); return LDX_EINVAL; }
     if (executed) *executed = e->impl->steady_flops();
-    if (shared) *shared = e->impl->flops_shared;
+    if (shared) *shared = e->impl->cur.flops_shared;
     return LDX_OK;
 }
 int ldx_unet_cfg_share(ldx_engine* e, int enable) {

@@ -22,6 +22,12 @@ namespace ldx {
 
 thread_local std::string g_last_error;
 void set_error(const std::string& s) { g_last_error = s; }
+int launch_status() {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return LDX_OK;
+    set_error(std::string("kernel launch: ") + hipGetErrorString(e));
+    return LDX_EHIP;
+}
 
 #define HIP_OK(expr)                                                                         \
     do {                                                                                     \
@@ -111,10 +117,9 @@ Engine::Engine(const ldx_unet_config& c, int dev) : cfg(c), device(dev) {
 Engine::~Engine() {
     (void)hipSetDevice(device);
     for (void* p : dev_allocs) (void)hipFree(p);
-    if (arena) (void)hipFree(arena);
     if (d_sigma_cfg) (void)hipFree(d_sigma_cfg);
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    for (PlanSnap& s : plan_cache) { if (s.arena) (void)hipFree(s.arena); if (s.graph_exec) (void)hipGraphExecDestroy(s.graph_exec); }
+    cur.release();
+    for (Plan& p : plan_cache) p.release();
     for (hipEvent_t ev : prof_events) (void)hipEventDestroy(ev);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
 }
@@ -555,12 +560,12 @@ void Engine::op_gemm(const char* name, Act A, const LinearW& w, Act C, Act R, bo
     g.R = R.valid ? ptr(R) : nullptr; g.ldr = R.ld;
     g.C = ptr(C); g.ldc = C.ld; g.Cf = nullptr;
     g.splitk = gemm_choose_splitk(g.M, g.N, g.K, geglu);
-    if (g.splitk > 1) { g.ws = (float*)((uintptr_t)arena + ws_alloc(gemm_sk_ws_floats(g.M, g.N, g.splitk) * 4)); g.sk_count = sk_counters(); }
+    if (g.splitk > 1) { g.ws = (float*)((uintptr_t)cur.arena + ws_alloc(gemm_sk_ws_floats(g.M, g.N, g.splitk) * 4)); g.sk_count = sk_counters(); }
     o.flops = 2.0 * g.M * (double)g.N * g.K;
     o.bytes = 2.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * (geglu ? g.N / 2 : g.N) * (R.valid ? 2 : 1));
     snprintf(o.klabel, sizeof(o.klabel), "gemm_kernel<%s,0>", dt == DT_BF16 ? "bf16" : "f16");
-    ops.push_back(o);
-    flops += o.flops;
+    cur.ops.push_back(o);
+    cur.flops += o.flops;
 }
 void Engine::op_conv(const char* name, Act X, int B, int Hin, int Win, int Cin, const LinearW& w, int stride, int Hout, int Wout,
                      Act Y, Act R, const float* rowvec, int rv_ld, float* Cf, int ldcf) {
@@ -574,21 +579,21 @@ void Engine::op_conv(const char* name, Act X, int B, int Hin, int Win, int Cin, 
     g.R = R.valid ? ptr(R) : nullptr; g.ldr = R.ld;
     g.C = Y.valid ? ptr(Y) : nullptr; g.ldc = Y.ld; g.Cf = Cf; g.ldcf = ldcf;
     g.splitk = gemm_choose_splitk(g.M, g.N, g.K, false);
-    if (g.splitk > 1) { g.ws = (float*)((uintptr_t)arena + ws_alloc(gemm_sk_ws_floats(g.M, g.N, g.splitk) * 4)); g.sk_count = sk_counters(); }
+    if (g.splitk > 1) { g.ws = (float*)((uintptr_t)cur.arena + ws_alloc(gemm_sk_ws_floats(g.M, g.N, g.splitk) * 4)); g.sk_count = sk_counters(); }
     o.flops = 2.0 * g.M * (double)g.N * g.K;
     o.bytes = 2.0 * ((double)B * Hin * Win * Cin + (double)g.N * g.K + (double)g.M * g.N * (R.valid ? 2 : 1));
     snprintf(o.klabel, sizeof(o.klabel), "gemm_kernel<%s,1>", dt == DT_BF16 ? "bf16" : "f16");
-    ops.push_back(o);
-    flops += o.flops;
+    cur.ops.push_back(o);
+    cur.flops += o.flops;
 }
 void Engine::op_gn(const char* name, Act X, Act Y, int B, int HW, const NormW& n, float eps, bool silu) {
     Op o{}; o.kind = OP_GN; o.name = name;
     GroupNormArgs& g = o.gn;
     g.X = ptr(X); g.ldx = X.ld; g.Y = ptr(Y); g.ldy = Y.ld; g.B = B; g.HW = HW; g.C = n.C; g.G = 32; g.eps = eps; g.silu = silu;
-    g.gamma = n.g; g.beta = n.b; g.partial = (float*)(arena ? (char*)arena + gn_ws_off : nullptr);
+    g.gamma = n.g; g.beta = n.b; g.partial = (float*)(cur.arena ? (char*)cur.arena + cur.gn_ws_off : nullptr);
     o.bytes = 2.0 * 3.0 * (double)B * HW * n.C;       // read (stats) + read + write (apply)
     snprintf(o.klabel, sizeof(o.klabel), "gn_stats+gn_apply");
-    ops.push_back(o);
+    cur.ops.push_back(o);
 }
 // SURVEY §8 a10-a11 / VERDICT r2 item 1c: GroupNorm statistics from the producing conv / GEMM epilogue.  A GroupNorm whose input tensor was written by
 // the op right before it (so nothing else touches the shared statistics workspace in between) and whose producer launch can do it
@@ -596,30 +601,30 @@ void Engine::op_gn(const char* name, Act X, Act Y, int B, int HW, const NormW& n
 // of the activation and one launch.  The sums are still deterministic (fixed order per tile, then per tile row); what is given up is the
 // bit-for-bit equality between different BATCH SIZES (the producer's tile shape, hence the summation order, depends on M).
 void Engine::fuse_gn_stats() {
-    for (size_t i = 1; i < ops.size(); ++i) {
-        if (ops[i].kind == OP_GN && ops[i - 1].kind == OP_ROWGEMM) {          // row-block producer (proj_out + residual): statistics from its output stage
-            RowGemmArgs& r = ops[i - 1].rg;
-            GroupNormArgs& n = ops[i].gn;
+    for (size_t i = 1; i < cur.ops.size(); ++i) {
+        if (cur.ops[i].kind == OP_GN && cur.ops[i - 1].kind == OP_ROWGEMM) {          // row-block producer (proj_out + residual): statistics from its output stage
+            RowGemmArgs& r = cur.ops[i - 1].rg;
+            GroupNormArgs& n = cur.ops[i].gn;
             const int bm = 128 * 320 / r.K;
             static const bool off = getenv("LDX_GN_FUSE") && atoi(getenv("LDX_GN_FUSE")) == 0;
             if (off || r.pro == 2 || r.Y != n.X || r.ldy != n.ldx || r.N != n.C || r.N != r.K || n.G != 32 || (long)r.M != (long)n.B * n.HW || n.HW % bm || n.HW / bm > gn_ws_rows ||
                 gn_uses_small_kernel(n.B, n.HW, n.C, n.G)) continue;      // last term: the one-launch small GroupNorm kernel takes it (norm.hip)
             r.gn_out = n.partial; r.gn_nchunk = n.HW / bm; r.HW = n.HW;
             n.stats_chunks = n.HW / bm;
-            ops[i].bytes = 2.0 * 2.0 * (double)n.B * n.HW * n.C;
-            snprintf(ops[i].klabel, sizeof(ops[i].klabel), "gn_apply(fused stats)");
+            cur.ops[i].bytes = 2.0 * 2.0 * (double)n.B * n.HW * n.C;
+            snprintf(cur.ops[i].klabel, sizeof(cur.ops[i].klabel), "gn_apply(fused stats)");
             continue;
         }
-        if (ops[i].kind != OP_GN || ops[i - 1].kind != OP_GEMM) continue;
-        GemmArgs& g = ops[i - 1].g;
-        GroupNormArgs& n = ops[i].gn;
+        if (cur.ops[i].kind != OP_GN || cur.ops[i - 1].kind != OP_GEMM) continue;
+        GemmArgs& g = cur.ops[i - 1].g;
+        GroupNormArgs& n = cur.ops[i].gn;
         if (g.C != n.X || g.ldc != n.ldx || g.N != n.C || (long)g.M != (long)n.B * n.HW) continue;
         const int nchunk = gemm_gn_fuse(g, n.HW, n.G, gn_ws_rows);
         if (!nchunk) continue;
         g.gn_partial = n.partial;
         n.stats_chunks = nchunk;
-        ops[i].bytes = 2.0 * 2.0 * (double)n.B * n.HW * n.C;       // read + write (apply only)
-        snprintf(ops[i].klabel, sizeof(ops[i].klabel), "gn_apply(fused stats)");
+        cur.ops[i].bytes = 2.0 * 2.0 * (double)n.B * n.HW * n.C;       // read + write (apply only)
+        snprintf(cur.ops[i].klabel, sizeof(cur.ops[i].klabel), "gn_apply(fused stats)");
     }
 }
 // Planner rule for the row-block kernels (rowgemm / xattn_block / ff_block): one workgroup per row block and one workgroup per CU, so below ~3/4 of the
@@ -627,11 +632,11 @@ void Engine::fuse_gn_stats() {
 // separate launches.  LDX_ROWBLOCK_MINWG moves the limit (0: always).
 // In a shared CFG prefix (half the batch: 128 row blocks at 1024^2, bs = 1) the limit is lower: the alternative there is the SAME number of rows on LayerNorm +
 // tile-GEMM launches, which measured slower (LN 12.1 + GEMM 46.3 us against 40.6 for the row-block launch of the full batch; profiles/r06/share_*.txt).
-static bool g_rowblock_prefix = false;          // set by emit_xf / fuse_gn_rowgemm while they emit prefix ops (planning is single-threaded per engine call)
-static bool rowblock_fills_chip(long workgroups) {
+// rowblock_prefix is set by emit_xf / fuse_gn_rowgemm while they emit prefix ops.
+bool Engine::rowblock_fills_chip(long workgroups) const {
     static const long min_wg = getenv("LDX_ROWBLOCK_MINWG") ? atol(getenv("LDX_ROWBLOCK_MINWG")) : 192;
     static const long min_wg_prefix = getenv("LDX_ROWBLOCK_MINWG_PREFIX") ? atol(getenv("LDX_ROWBLOCK_MINWG_PREFIX")) : 96;
-    return workgroups >= (g_rowblock_prefix ? (min_wg_prefix < min_wg ? min_wg_prefix : min_wg) : min_wg);
+    return workgroups >= (rowblock_prefix ? (min_wg_prefix < min_wg ? min_wg_prefix : min_wg) : min_wg);
 }
 // Row-block GEMM (rowgemm.hip) in place of [LayerNorm +] an N = 320 k, K = 320 projection; false (nothing emitted) when the kernel does not take it
 bool Engine::op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R, int pro, const NormW* nw) {
@@ -649,32 +654,32 @@ bool Engine::op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R,
     o.flops = 2.0 * a.M * (double)a.N * a.K;
     o.bytes = 2.0 * ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N * (R.valid ? 2 : 1));
     snprintf(o.klabel, sizeof(o.klabel), "rowgemm<%s,%d>", dt == DT_BF16 ? "bf16" : "f16", pro);
-    ops.push_back(o);
-    flops += o.flops;
+    cur.ops.push_back(o);
+    cur.flops += o.flops;
     return true;
 }
 // GroupNorm (no SiLU, C = 320, statistics already written by its producer) directly followed by the N = K = 320 GEMM that reads its output
 // (SpatialTransformer norm + proj_in): the pair becomes one rowgemm launch with the GroupNorm apply as its prologue.  Runs after fuse_gn_stats().
 void Engine::fuse_gn_rowgemm() {
-    for (size_t i = 0; i + 1 < ops.size(); ++i) {
-        g_rowblock_prefix = i < prefix_end;
-        if (ops[i].kind != OP_GN || ops[i + 1].kind != OP_GEMM) continue;
-        const GroupNormArgs& n = ops[i].gn;
-        const GemmArgs& g = ops[i + 1].g;
+    for (size_t i = 0; i + 1 < cur.ops.size(); ++i) {
+        rowblock_prefix = i < cur.prefix_end;
+        if (cur.ops[i].kind != OP_GN || cur.ops[i + 1].kind != OP_GEMM) continue;
+        const GroupNormArgs& n = cur.ops[i].gn;
+        const GemmArgs& g = cur.ops[i + 1].g;
         if (n.silu || n.stats_chunks <= 0 || n.stats_chunks > GN_NCHUNK || n.G != 32 || g.A != n.Y || g.lda != n.ldy || g.mode != 0 || g.K != n.C || g.geglu || g.ln_c1 ||
-            g.f8 || g.C8 || g.Cf || g.rowvec || g.splitk > 1 || g.gate || g.R2 || g.act || g.oscale != 0.f || g.gn_partial || (long)g.M != (long)n.B * n.HW || !g.C) continue;
+            g.f8 || g.C8 || g.Cf || g.rowvec || g.splitk > 1 || g.gate || g.R2 || g.act || g.oscale != 0.f || g.gn_partial || g.dup_rows || (long)g.M != (long)n.B * n.HW || !g.C) continue;
         RowGemmArgs a{};
         a.X = n.X; a.ldx = n.ldx; a.Y = g.C; a.ldy = g.ldc; a.M = g.M; a.N = g.N; a.K = g.K; a.W = g.W; a.bias = g.bias; a.R = g.R; a.ldr = g.ldr;
         a.pro = 2; a.g = n.gamma; a.b = n.beta; a.eps = n.eps; a.partial = n.partial; a.nchunk = n.stats_chunks; a.HW = n.HW; a.G = n.G;
         if (!rowgemm_ok(a) || !rowblock_fills_chip((a.M + 128 * 320 / a.K - 1) / (128 * 320 / a.K) * (a.K / 320))) continue;
-        Op o{}; o.kind = OP_ROWGEMM; o.name = ops[i + 1].name; o.rg = a;
-        o.flops = ops[i + 1].flops; o.bytes = ops[i + 1].bytes;
+        Op o{}; o.kind = OP_ROWGEMM; o.name = cur.ops[i + 1].name; o.rg = a;
+        o.flops = cur.ops[i + 1].flops; o.bytes = cur.ops[i + 1].bytes;
         snprintf(o.klabel, sizeof(o.klabel), "rowgemm<%s,2>", dt == DT_BF16 ? "bf16" : "f16");
-        ops[i] = o;
-        ops.erase(ops.begin() + (long)i + 1);
-        if (i + 1 < prefix_end) --prefix_end;
+        cur.ops[i] = o;
+        cur.ops.erase(cur.ops.begin() + (long)i + 1);
+        if (i + 1 < cur.prefix_end) --cur.prefix_end;
     }
-    g_rowblock_prefix = false;
+    rowblock_prefix = false;
 }
 void Engine::op_ln(const char* name, Act X, Act Y, const NormW& n) {
     Op o{}; o.kind = OP_LN; o.name = name;
@@ -682,7 +687,7 @@ void Engine::op_ln(const char* name, Act X, Act Y, const NormW& n) {
     l.X = ptr(X); l.ldx = X.ld; l.Y = ptr(Y); l.ldy = Y.ld; l.rows = X.rows; l.C = n.C; l.eps = 1e-5f; l.gamma = n.g; l.beta = n.b;
     o.bytes = 2.0 * 2.0 * (double)X.rows * n.C;
     snprintf(o.klabel, sizeof(o.klabel), "ln_kernel");
-    ops.push_back(o);
+    cur.ops.push_back(o);
 }
 void Engine::op_attn(const char* name, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, Act O, int B, int H, int Nq, int Mk, int D) {
     Op o{}; o.kind = OP_ATTN; o.name = name;
@@ -690,11 +695,11 @@ void Engine::op_attn(const char* name, const void* Q, int ldq, const void* K, in
     a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = ptr(O); a.ldo = O.ld;
     a.B = B; a.H = H; a.Nq = Nq; a.Mk = Mk; a.D = D; a.scale = 1.0f / std::sqrt((float)D); a.causal = 0;
     if (attn_pipe_ok(a) || attn_pipe128_ok(a)) {       // key-block norms for the pipelined kernels' score bound (attn_pipe.hip): a few KiB, live for this op only
-        const size_t off = a_alloc((size_t)B * H * ((Mk + 63) / 64) * 4); a.knorm_ws = (float*)((uintptr_t)arena + off); a_free(off);
+        const size_t off = a_alloc((size_t)B * H * ((Mk + 63) / 64) * 4); a.knorm_ws = (float*)((uintptr_t)cur.arena + off); a_free(off);
     }
     if (attn512_ok(a)) {              // D = 512 (VAE): key splits when the query blocks alone leave CUs idle; fp32 partials live for this op only
         a.nsplit = attn512_splits(a);
-        if (a.nsplit > 1) { const size_t off = a_alloc(attn512_ws_floats(a, a.nsplit) * 4); a.split_ws = (float*)((uintptr_t)arena + off); a_free(off); }
+        if (a.nsplit > 1) { const size_t off = a_alloc(attn512_ws_floats(a, a.nsplit) * 4); a.split_ws = (float*)((uintptr_t)cur.arena + off); a_free(off); }
     }
     o.flops = 4.0 * B * H * (double)Nq * Mk * D;
     o.bytes = 2.0 * (double)B * H * D * (2.0 * Nq + 2.0 * Mk);
@@ -706,23 +711,23 @@ void Engine::op_attn(const char* name, const void* Q, int ldq, const void* K, in
         else if (cls == 1 || cls == 2) snprintf(o.klabel, sizeof(o.klabel), "%s<%s>%s", cls == 1 ? "attn40p_kernel" : "attn128p_kernel", dt == DT_BF16 ? "bf16" : "f16", Nq == Mk ? "self" : "cross");
         else snprintf(o.klabel, sizeof(o.klabel), "attn_kernel<%s,%d,%d>%s", dt == DT_BF16 ? "bf16" : "f16", ks, dtl, Nq == Mk ? "self" : "cross");
     }
-    ops.push_back(o);
-    flops += o.flops;
+    cur.ops.push_back(o);
+    cur.flops += o.flops;
 }
 
 // rows [0, rows) of the view -> rows [rows, 2 * rows): the second half of a CFG batch takes over what was computed once for both (plan(): share)
 void Engine::op_dup(const Act& a, int rows) {
     Op o{}; o.kind = OP_DUP; o.name = "cfg.dup";
-    o.p0 = ptr(a); o.p1 = arena ? (char*)ptr(a) + (size_t)rows * a.ld * 2 : nullptr; o.i0 = rows; o.i1 = a.C; o.i2 = a.ld;
+    o.p0 = ptr(a); o.p1 = cur.arena ? (char*)ptr(a) + (size_t)rows * a.ld * 2 : nullptr; o.i0 = rows; o.i1 = a.C; o.i2 = a.ld;
     o.bytes = 2.0 * 2.0 * (double)rows * a.C;
     snprintf(o.klabel, sizeof(o.klabel), "dup_rows");
-    ops.push_back(o);
+    cur.ops.push_back(o);
 }
 
 void Engine::dup_second_half(const DupReq& d) {
     static const bool copy_only = getenv("LDX_CFG_SHARE_COPY") && atoi(getenv("LDX_CFG_SHARE_COPY")) != 0;      // A/B switch: always the copy launch
-    if (!copy_only && d.producer < ops.size()) {
-        Op& o = ops[d.producer];
+    if (!copy_only && d.producer < cur.ops.size()) {
+        Op& o = cur.ops[d.producer];
         if (o.kind == OP_GEMM && o.g.C == ptr(d.a) && o.g.ldc == d.a.ld && o.g.M == d.rows && !o.g.geglu && !o.g.C8) { o.g.dup_rows = d.rows; return; }
         if (o.kind == OP_ROWGEMM && o.rg.Y == ptr(d.a) && o.rg.ldy == d.a.ld && o.rg.M == d.rows) { o.rg.dup_rows = d.rows; return; }
     }
@@ -745,7 +750,7 @@ void Engine::emit_res(const ResW& r, Act X, Act OUT, int B, int H, int W) {
     Act t1 = new_act(M, r.Cin);
     op_gn("res.gn1", X, t1, B, H * W, r.gn1, r.eps, true);
     Act t2 = new_act(M, r.Cout);
-    if (r.has_emb) op_conv("res.conv1", t1, B, H, W, r.Cin, r.conv1, 1, H, W, t2, Act{}, d_emb_all ? d_emb_all + r.emb_off : nullptr, emb_total);
+    if (r.has_emb) op_conv("res.conv1", t1, B, H, W, r.Cin, r.conv1, 1, H, W, t2, Act{}, cur.d_emb_all ? cur.d_emb_all + r.emb_off : nullptr, emb_total);
     else op_conv("res.conv1", t1, B, H, W, r.Cin, r.conv1, 1, H, W, t2, Act{});
     release(t1);
     Act t3 = new_act(M, r.Cout);
@@ -753,7 +758,7 @@ void Engine::emit_res(const ResW& r, Act X, Act OUT, int B, int H, int W) {
     release(t2);
     if (r.has_skip && r.fused_skip) {
         op_conv("res.conv2+skip", t3, B, H, W, r.Cout, r.conv2, 1, H, W, OUT, Act{});
-        GemmArgs& g = ops.back().g;
+        GemmArgs& g = cur.ops.back().g;
         g.A2 = ptr(X); g.lda2 = X.ld; g.Cin2 = r.Cin;
     } else if (r.has_skip) {
         Act t4 = new_act(M, r.Cout);
@@ -772,7 +777,7 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
     // Shared CFG prefix (plan(): share): up to the first cross-attention both halves of the batch hold the same values, so norm / proj_in / norm1 / q|k|v /
     // self-attention / to_out of the FIRST transformer block run on the first Bq samples (rows [0, Mq)) only
     int Bq = Bshare > 0 ? Bshare : B, Mq = Bq * H * W;
-    g_rowblock_prefix = Bq != B;
+    rowblock_prefix = Bq != B;
     auto head = [&](const Act& a) { Act v = a; v.rows = Mq; v.owned = false; return v; };      // the first Mq rows of a buffer
     Act t1 = new_act(M, C);
     op_gn("xf.norm", X, t1, Bq, H * W, x.gn, 1e-6f, false);
@@ -794,7 +799,7 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
     auto ln_gemm = [&](const char* ln_name, const char* name, const NormW& ln, const LinearW& w, const float* c1, Act Cc, bool geglu) {
         if (fold && gemm_choose_splitk(Mq, w.N, w.K, geglu) == 1) {
             op_gemm(name, head(h), w, head(Cc), Act{}, geglu);
-            GemmArgs& g = ops.back().g;
+            GemmArgs& g = cur.ops.back().g;
             g.ln_c1 = c1; g.ln_eps = 1e-5f;
             return;
         }
@@ -812,19 +817,19 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
         Act a = new_act(M, C);
         const char* base = (const char*)ptr(qkv);
         op_attn("xf.attn1", base, 3 * C, base + (size_t)C * 2, 3 * C, base + (size_t)2 * C * 2, 3 * C, a, Bq, heads, H * W, H * W, D);
-        if (q_prescale()) ops.back().at.scale = 1.0f / 1.44269504088896340736f;       // the q rows of the projection already carry scale * log2(e)
+        if (q_prescale()) cur.ops.back().at.scale = 1.0f / 1.44269504088896340736f;       // the q rows of the projection already carry scale * log2(e)
         release(qkv);
         if (!op_rowgemm("xf.o1", head(a), b.o1, head(h), head(h), 0, nullptr))
             op_gemm("xf.o1", head(a), b.o1, head(h), head(h));                   // x += attn1(norm1(x))   (in place)
         if (Bq != B) {
             // the context enters here: from now on the halves differ.  The second half's rows take over the shared results that full-batch ops still read.
-            prefix_end = ops.size();                               // every op so far ran on one half of the batch
+            cur.prefix_end = cur.ops.size();                               // every op so far ran on one half of the batch
             if (dups) for (const DupReq& dq : *dups) dup_second_half(dq);
-            dup_second_half(DupReq{h, Mq, ops.size() - 1});       // the op just emitted (to_out + residual) wrote h
-            Bq = B; Mq = M; g_rowblock_prefix = false;
+            dup_second_half(DupReq{h, Mq, cur.ops.size() - 1});       // the op just emitted (to_out + residual) wrote h
+            Bq = B; Mq = M; rowblock_prefix = false;
         }
         // k|v of the context come from the one batched projection emitted at the start of the forward
-        const char* kvb = (const char*)((uintptr_t)arena + kv_all_off) + (size_t)b.kv_off * 2;
+        const char* kvb = (const char*)((uintptr_t)cur.arena + cur.kv_all_off) + (size_t)b.kv_off * 2;
         XAttnArgs xa{};
         xa.H = ptr(h); xa.ldh = h.ld; xa.M = M; xa.N = H * W; xa.C = C; xa.heads = heads; xa.ln_g = b.ln2.g; xa.ln_b = b.ln2.b; xa.eps = 1e-5f;
         xa.Wq = b.q2.w; xa.Wo = b.o2.w; xa.bo = b.o2.b; xa.K = kvb; xa.ldk = kv_total; xa.V = kvb + (size_t)C * 2; xa.ldv = kv_total; xa.Mk = Mc;
@@ -835,8 +840,8 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
             o.flops = 2.0 * 2.0 * M * (double)C * C + 4.0 * B * heads * (double)(H * W) * Mc * D;
             o.bytes = 2.0 * 2.0 * (double)M * C;
             snprintf(o.klabel, sizeof(o.klabel), "xattn_block<%s>", dt == DT_BF16 ? "bf16" : "f16");
-            ops.push_back(o);
-            flops += o.flops;
+            cur.ops.push_back(o);
+            cur.flops += o.flops;
             release(a);
         } else {
             Act q = new_act(M, C);
@@ -844,7 +849,7 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
             if (!x2 || fold || b.q2.b || !op_rowgemm("xf.ln2+q2", h, b.q2, q, Act{}, 1, &b.ln2))          // C = 640: LayerNorm + q projection as one row-block launch
                 ln_gemm("xf.ln2", "xf.q2", b.ln2, fold ? b.q2_f : b.q2, b.c1_q2, q, false);
             op_attn("xf.attn2", ptr(q), C, kvb, kv_total, kvb + (size_t)C * 2, kv_total, a, B, heads, H * W, Mc, D);
-            if (q_prescale()) ops.back().at.scale = 1.0f / 1.44269504088896340736f;       // the q rows of the projection already carry scale * log2(e)
+            if (q_prescale()) cur.ops.back().at.scale = 1.0f / 1.44269504088896340736f;       // the q rows of the projection already carry scale * log2(e)
             release(q);
             if (!x2 || !op_rowgemm("xf.o2", a, b.o2, h, h, 0, nullptr))
                 op_gemm("xf.o2", a, b.o2, h, h);                   // x += attn2(norm2(x), ctx)
@@ -859,8 +864,8 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
             o.flops = 2.0 * M * (double)C * (8.0 * C) + 2.0 * M * (double)C * (4.0 * C);
             o.bytes = 2.0 * 2.0 * (double)M * C;
             snprintf(o.klabel, sizeof(o.klabel), "ff_block<%s>", dt == DT_BF16 ? "bf16" : "f16");
-            ops.push_back(o);
-            flops += o.flops;
+            cur.ops.push_back(o);
+            cur.flops += o.flops;
         } else {
             Act f = new_act(M, 4 * C);
             ln_gemm("xf.ln3", "xf.ff1", b.ln3, fold ? b.ff1_f : b.ff1, b.c1_ff1, f, true);        // GEGLU
@@ -886,25 +891,15 @@ int Engine::share_for(int B2, int h, int w, int xB, bool denoise, bool concat) c
 }
 
 int Engine::plan(int B2, int h, int w, int Mc, int share) {
-    // dry run (arena == nullptr) measures the peak; second run binds real pointers
-    for (int pass = 0; pass < 2; ++pass) {
-        prefix_end = 0; g_rowblock_prefix = false;
-        ops.clear(); flops = 0; free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0;
-        if (pass == 1) {
-            if (arena && arena_cap < arena_peak_dry) { HIP_OK(hipFree(arena)); arena = nullptr; }
-            if (!arena) { HIP_OK(hipMalloc(&arena, arena_peak_dry)); arena_cap = arena_peak_dry; }
-        }
-        const bool bind = pass == 1;
-        void* saved_arena = arena;
-        if (!bind) arena = nullptr;
+    return build_plan(PlanKey{B2, h, w, Mc, share}, [&]() -> int {
         const int mc = cfg.model_channels, ted = 4 * mc;
         // fixed small buffers
         const size_t o_temb = a_alloc((size_t)B2 * mc * 4), o_e1 = a_alloc((size_t)B2 * ted * 4), o_e2 = a_alloc((size_t)B2 * ted * 4);
         const size_t o_emb = a_alloc((size_t)B2 * emb_total * 4);
-        gn_ws_off = a_alloc(gn_ws_bytes(B2, (long)h * w));
+        cur.gn_ws_off = a_alloc(gn_ws_bytes(B2, (long)h * w));
         const size_t o_eps = a_alloc((size_t)B2 * h * w * cfg.out_channels * 4);
-        auto f32p = [&](size_t off) { return bind ? (float*)((char*)arena + off) : (float*)nullptr; };
-        d_temb_out = f32p(o_temb); d_e1 = f32p(o_e1); d_e2 = f32p(o_e2); d_emb_all = f32p(o_emb); d_eps = f32p(o_eps);
+        auto f32p = [&](size_t off) { return cur.arena ? (float*)((char*)cur.arena + off) : (float*)nullptr; };
+        cur.d_temb_out = f32p(o_temb); cur.d_e1 = f32p(o_e1); cur.d_e2 = f32p(o_e2); cur.d_emb_all = f32p(o_emb); cur.d_eps = f32p(o_eps);
 
         // ---- level geometry & concat buffers (so skips are written in place, no torch.cat copy) ----
         struct Skip { Act act; int H, W; };
@@ -927,21 +922,21 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
         auto skip_view = [&](int s) { const int k = n_skips - 1 - s; return view(cat[k], out_hch[k], in_ch[s]); };
 
         // ---- ops ----
-        Op po{}; po.kind = OP_PREP; po.name = "prep"; ops.push_back(po);          // pointers filled per call
+        Op po{}; po.kind = OP_PREP; po.name = "prep"; cur.ops.push_back(po);          // pointers filled per call
         Act xin = new_act(B2 * h * w, 64);
-        prep_xc_off = xin.off;
+        cur.prep_xc_off = xin.off;
         Act ctx16 = new_act(B2 * Mc, cfg.context_dim);
-        { Op o{}; o.kind = OP_CVT; o.name = "ctx.cvt"; o.cvt_out = ptr(ctx16); o.cvt_n = (size_t)B2 * Mc * cfg.context_dim; o.ctx_only = true; ops.push_back(o); }
+        { Op o{}; o.kind = OP_CVT; o.name = "ctx.cvt"; o.cvt_out = ptr(ctx16); o.cvt_n = (size_t)B2 * Mc * cfg.context_dim; o.ctx_only = true; cur.ops.push_back(o); }
         if (!d_emb_table) {       // per-step time-embedding MLP (LDX_EMB_TABLE=0); otherwise the prep kernel gathers the timestep's row of the table
-            { Op o{}; o.kind = OP_SKINNY; o.name = "time_embed.0"; o.sk = SkinnyArgs{d_temb_out, mc, te0.w, te0.b, d_e1, ted, B2, ted, mc, 0, 1}; ops.push_back(o); }
-            { Op o{}; o.kind = OP_SKINNY; o.name = "time_embed.2"; o.sk = SkinnyArgs{d_e1, ted, te2.w, te2.b, d_e2, ted, B2, ted, ted, 0, 1}; ops.push_back(o); }
-            { Op o{}; o.kind = OP_SKINNY; o.name = "emb_layers"; o.sk = SkinnyArgs{d_e2, ted, emb_all.w, emb_all.b, d_emb_all, emb_total, B2, emb_total, ted, 0, 0}; ops.push_back(o); }
-            flops += 2.0 * B2 * ((double)ted * mc + (double)ted * ted + (double)emb_total * ted);
+            { Op o{}; o.kind = OP_SKINNY; o.name = "time_embed.0"; o.sk = SkinnyArgs{cur.d_temb_out, mc, te0.w, te0.b, cur.d_e1, ted, B2, ted, mc, 0, 1}; cur.ops.push_back(o); }
+            { Op o{}; o.kind = OP_SKINNY; o.name = "time_embed.2"; o.sk = SkinnyArgs{cur.d_e1, ted, te2.w, te2.b, cur.d_e2, ted, B2, ted, ted, 0, 1}; cur.ops.push_back(o); }
+            { Op o{}; o.kind = OP_SKINNY; o.name = "emb_layers"; o.sk = SkinnyArgs{cur.d_e2, ted, emb_all.w, emb_all.b, cur.d_emb_all, emb_total, B2, emb_total, ted, 0, 0}; cur.ops.push_back(o); }
+            cur.flops += 2.0 * B2 * ((double)ted * mc + (double)ted * ted + (double)emb_total * ted);
         }
         Act kvall = new_act(B2 * Mc, kv_total);
-        kv_all_off = kvall.off;
+        cur.kv_all_off = kvall.off;
         op_gemm("xf.kv2_all", ctx16, kv_all, kvall, Act{});
-        ops.back().ctx_only = true;
+        cur.ops.back().ctx_only = true;
 
         int lv = 0, s = 0;
         Act hcur = skip_view(0);
@@ -950,21 +945,21 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
         int Bp = share > 0 ? share : B2;
         std::vector<DupReq> pend;
         op_conv("conv_in", xin, Bp, h, w, 64, conv_in, 1, h, w, hcur, Act{});
-        flops -= 2.0 * Bp * h * w * (double)mc * 9.0 * (64 - cfg.in_channels);   // padded channels are not algorithmic work
+        cur.flops -= 2.0 * Bp * h * w * (double)mc * 9.0 * (64 - cfg.in_channels);   // padded channels are not algorithmic work
         release(xin);
-        if (Bp != B2) pend.push_back({hcur, Bp * h * w, ops.size() - 1});
+        if (Bp != B2) pend.push_back({hcur, Bp * h * w, cur.ops.size() - 1});
         for (auto& blk : in_blocks) {
             ++s;
             Act dst = skip_view(s);
             if (blk.has_down) {
                 op_conv("down", hcur, Bp, Hs[lv], Ws[lv], in_ch[s - 1], blk.down, 2, Hs[lv + 1], Ws[lv + 1], dst, Act{});
                 ++lv;
-                if (Bp != B2) pend.push_back({dst, Bp * Hs[lv] * Ws[lv], ops.size() - 1});
+                if (Bp != B2) pend.push_back({dst, Bp * Hs[lv] * Ws[lv], cur.ops.size() - 1});
             } else if (blk.has_xf) {
                 Act mid = new_act(B2 * Hs[lv] * Ws[lv], blk.res.Cout);
                 emit_res(blk.res, hcur, mid, Bp, Hs[lv], Ws[lv]);
                 if (Bp != B2) {
-                    pend.push_back({mid, Bp * Hs[lv] * Ws[lv], ops.size() - 1});          // proj_out's residual reads it for every sample (emit_res ends with the conv that writes it)
+                    pend.push_back({mid, Bp * Hs[lv] * Ws[lv], cur.ops.size() - 1});          // proj_out's residual reads it for every sample (emit_res ends with the conv that writes it)
                     emit_xf(blk.xf, mid, dst, B2, Hs[lv], Ws[lv], ctx16, Mc, Bp, &pend);
                     Bp = B2; pend.clear();
                 } else {
@@ -973,7 +968,7 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
                 release(mid);
             } else {
                 emit_res(blk.res, hcur, dst, Bp, Hs[lv], Ws[lv]);
-                if (Bp != B2) pend.push_back({dst, Bp * Hs[lv] * Ws[lv], ops.size() - 1});
+                if (Bp != B2) pend.push_back({dst, Bp * Hs[lv] * Ws[lv], cur.ops.size() - 1});
             }
             hcur = dst;
         }
@@ -981,7 +976,7 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
         {
             const int Mm = B2 * Hs[lv] * Ws[lv];
             Act dst = view(cat[0], 0, out_hch[0]);
-            if (!has_middle) { set_error("UNet config without a middle block is not supported by the planner"); arena = saved_arena; return LDX_EINVAL; }
+            if (!has_middle) { set_error("UNet config without a middle block is not supported by the planner"); return LDX_EINVAL; }
             if (mid_has_xf) {
                 Act m0 = new_act(Mm, mid_res0.Cout);
                 emit_res(mid_res0, hcur, m0, B2, Hs[lv], Ws[lv]);
@@ -1009,25 +1004,25 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
                 return new_act(rows, co);
             };
             int sub = 0;
-            Act cur = cat[k];
+            Act x = cat[k];
             Act r_out = target(++sub == nsub, Mrows);
-            emit_res(blk.res, cur, r_out, B2, Hc, Wc);
+            emit_res(blk.res, x, r_out, B2, Hc, Wc);
             release(cat[k]);
-            cur = r_out;
+            x = r_out;
             if (blk.has_xf) {
                 Act x_out = target(++sub == nsub, Mrows);
-                emit_xf(blk.xf, cur, x_out, B2, Hc, Wc, ctx16, Mc);
-                release(cur);
-                cur = x_out;
+                emit_xf(blk.xf, x, x_out, B2, Hc, Wc, ctx16, Mc);
+                release(x);
+                x = x_out;
             }
             if (blk.has_up) {
                 const int Hn = Hs[lv - 1], Wn = Ws[lv - 1];       // output_shape = hs[-1].shape (unet.py:754)
                 Act u_out = target(++sub == nsub, B2 * Hn * Wn);
-                op_conv("up", cur, B2, Hc, Wc, co, blk.up, 1, Hn, Wn, u_out, Act{});
-                release(cur);
-                cur = u_out; --lv;
+                op_conv("up", x, B2, Hc, Wc, co, blk.up, 1, Hn, Wn, u_out, Act{});
+                release(x);
+                x = u_out; --lv;
             }
-            final_h = cur;
+            final_h = x;
             ++k;
         }
         // out: GroupNorm -> SiLU -> conv3x3 (unet.py:663-677), fp32 NHWC eps
@@ -1036,25 +1031,20 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
             Act t = new_act(Mrows, mc);
             op_gn("out.gn", final_h, t, B2, h * w, out_gn, 1e-5f, true);
             release(final_h);
-            op_conv("out.conv", t, B2, h, w, mc, conv_out, 1, h, w, Act{}, Act{}, nullptr, 0, d_eps, cfg.out_channels);
+            op_conv("out.conv", t, B2, h, w, mc, conv_out, 1, h, w, Act{}, Act{}, nullptr, 0, cur.d_eps, cfg.out_channels);
             release(t);
         }
-        { Op o{}; o.kind = OP_FINISH; o.name = "finish"; ops.push_back(o); }
+        { Op o{}; o.kind = OP_FINISH; o.name = "finish"; cur.ops.push_back(o); }
         release(ctx16); release(kvall);
         // what the shared prefix saves: every op in front of the first hand-over copy ran on half the batch (the context-only ops are not part of it)
-        flops_shared = 0;
         if (share > 0) {
-            for (size_t i = 0; i < prefix_end && i < ops.size(); ++i) if (!ops[i].ctx_only) flops_shared += ops[i].flops;
-            flops_shared -= 2.0 * share * h * w * (double)mc * 9.0 * (64 - cfg.in_channels);        // conv_in's padded channels are not algorithmic work (see above)
+            for (size_t i = 0; i < cur.prefix_end && i < cur.ops.size(); ++i) if (!cur.ops[i].ctx_only) cur.flops_shared += cur.ops[i].flops;
+            cur.flops_shared -= 2.0 * share * h * w * (double)mc * 9.0 * (64 - cfg.in_channels);        // conv_in's padded channels are not algorithmic work (see above)
         }
         fuse_gn_stats();
         fuse_gn_rowgemm();
-        if (!bind) { arena_peak_dry = arena_peak; arena = saved_arena; }
-    }
-    pB2 = B2; ph = h; pw = w; pM = Mc; pShare = share;
-    graph_valid = false; warm = false;
-    kv_ptr = nullptr; kv_epoch = 0;          // a fresh arena holds no projected context
-    return LDX_OK;
+        return LDX_OK;
+    });
 }
 
 // The 22 emb_layers outputs for EVERY timestep of the table (ldx_set_tables), by the same three skinny launches a forward would run on its B2 rows:
@@ -1088,79 +1078,102 @@ int Engine::build_emb_table() {
 }
 
 double Engine::steady_flops() const {
-    double f = flops;
-    if (ctx_cache) for (const Op& o : ops) if (o.ctx_only) f -= o.flops;
+    double f = cur.flops;
+    if (ctx_cache) for (const Op& o : cur.ops) if (o.ctx_only) f -= o.flops;
     return f;
 }
 // the reference's arithmetic for the same evaluation: what runs plus what the shared CFG prefix computes once instead of twice
-double Engine::algorithmic_flops() const { return steady_flops() + flops_shared; }
+double Engine::algorithmic_flops() const { return steady_flops() + cur.flops_shared; }
+
+void Plan::release() {
+    if (arena) (void)hipFree(arena);
+    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    arena = nullptr; graph_exec = nullptr;
+}
+
+int Engine::build_plan(const PlanKey& key, const std::function<int()>& emit, bool zero_arena) {
+    auto reset = [&] {
+        free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0; rowblock_prefix = false;
+        cur.ops.clear(); cur.flops = 0; cur.flops_shared = 0; cur.prefix_end = 0;
+    };
+    cur.key = PlanKey{};                  // no plan until the bound pass has completed
+    reset();
+    void* const arena = cur.arena;
+    cur.arena = nullptr;
+    int rc = emit();
+    cur.arena = arena;
+    if (rc) return rc;
+    cur.arena_peak_dry = arena_peak;
+    if (cur.arena && cur.arena_cap < cur.arena_peak_dry) { HIP_OK(hipFree(cur.arena)); cur.arena = nullptr; cur.arena_cap = 0; }
+    if (!cur.arena) { HIP_OK(hipMalloc(&cur.arena, cur.arena_peak_dry)); cur.arena_cap = cur.arena_peak_dry; }
+    if (zero_arena) HIP_OK(hipMemset(cur.arena, 0, cur.arena_cap));
+    reset();
+    if ((rc = emit())) return rc;
+    cur.key = key;
+    cur.graph_valid = false; cur.warm = false;
+    cur.kv_ptr = nullptr; cur.kv_epoch = 0;          // a fresh arena holds no projected context
+    return LDX_OK;
+}
+
+// The UNet and Flux keep the plans of other shapes (plan_cache); the other models re-plan into the current plan, whose arena is reused when
+// it is large enough.
+int Engine::select_plan(const PlanKey& key, hipStream_t st, const std::function<int()>& replan, bool* switched) {
+    if (key == cur.key) return LDX_OK;
+    HIP_OK(hipStreamSynchronize(st));
+    if (switched) *switched = true;
+    if (kind == KIND_UNET || kind == KIND_FLUX) {
+        if (cur.key.B > 0) plan_stash();
+        if (plan_restore(key)) return LDX_OK;
+    }
+    return replan();
+}
 
 void Engine::plan_stash() {
-    PlanSnap s;
-    s.B2 = pB2; s.h = ph; s.w = pw; s.M = pM; s.share = pShare; s.ops = std::move(ops); s.flops = flops; s.flops_shared = flops_shared; s.arena = arena; s.arena_cap = arena_cap; s.arena_peak_dry = arena_peak_dry;
-    s.gn_ws_off = gn_ws_off; s.prep_xc_off = prep_xc_off; s.kv_all_off = kv_all_off;
-    s.d_temb_out = d_temb_out; s.d_e1 = d_e1; s.d_e2 = d_e2; s.d_emb_all = d_emb_all; s.d_eps = d_eps;
-    s.kv_ptr = kv_ptr; s.kv_epoch = kv_epoch; s.kv_stream = kv_stream; s.g_ctxc = g_ctxc;
-    s.graph_exec = graph_exec; s.graph_valid = graph_valid; s.warm = warm; s.g_x = g_x; s.g_s = g_s; s.g_ctx = g_ctx; s.g_out = g_out; s.g_den = g_den; s.g_xB = g_xB; s.g_cc = g_cc; s.g_ccn = g_ccn; s.g_t = g_t;
-    s.fx_temb = fx_temb; s.fx_gemb = fx_gemb; s.fx_h1 = fx_h1; s.fx_vec = fx_vec; s.fx_svec = fx_svec; s.fx_mod = fx_mod; s.fx_tok = fx_tok;
-    s.fb_s0 = fb_s0; s.fb_s1 = fb_s1; s.fb_x = fb_x; s.fb_first = fb_first; s.fb_res = fb_res; s.fb_part = fb_part;
-    s.fb_B = fb_B; s.fb_L = fb_L; s.fb_Lt = fb_Lt; s.fb_C = fb_C; s.fb_a_end = fb_a_end; s.fb_b_end = fb_b_end;
-    ops.clear(); arena = nullptr; arena_cap = 0; graph_exec = nullptr; graph_valid = false; warm = false; pB2 = ph = pw = pM = 0; pShare = 0;
-    plan_cache.push_back(std::move(s));
+    plan_cache.push_back(std::move(cur));
+    cur = Plan{};
     // every cached plan keeps its own arena resident: bound the cache by count (4) AND by bytes (LDX_PLAN_CACHE_GIB, default 16 GiB of
     // stashed arenas — a Flux plan per prompt length, a 2048^2 VAE plan of several GiB ...); oldest first, the newest entry always stays
     static const size_t cap_bytes = (size_t)((getenv("LDX_PLAN_CACHE_GIB") ? atof(getenv("LDX_PLAN_CACHE_GIB")) : 16.0) * (double)(1ull << 30));
-    auto cached_bytes = [&]() { size_t b = 0; for (const PlanSnap& c : plan_cache) b += c.arena_cap; return b; };
+    auto cached_bytes = [&]() { size_t n = 0; for (const Plan& p : plan_cache) n += p.arena_cap; return n; };
     while (plan_cache.size() > 4 || (plan_cache.size() > 1 && cached_bytes() > cap_bytes)) {
-        PlanSnap& o = plan_cache.front();
-        if (o.arena) (void)hipFree(o.arena);
-        if (o.graph_exec) (void)hipGraphExecDestroy(o.graph_exec);
+        plan_cache.front().release();
         plan_cache.erase(plan_cache.begin());
     }
 }
-bool Engine::plan_restore(int B2, int h, int w, int Mc, int share) {
+bool Engine::plan_restore(const PlanKey& key) {
     for (size_t i = 0; i < plan_cache.size(); ++i) {
-        PlanSnap& s = plan_cache[i];
-        if (s.B2 != B2 || s.h != h || s.w != w || s.M != Mc || s.share != share) continue;
-        ops = std::move(s.ops); flops = s.flops; flops_shared = s.flops_shared; arena = s.arena; arena_cap = s.arena_cap; arena_peak_dry = s.arena_peak_dry;
-        gn_ws_off = s.gn_ws_off; prep_xc_off = s.prep_xc_off; kv_all_off = s.kv_all_off;
-        d_temb_out = s.d_temb_out; d_e1 = s.d_e1; d_e2 = s.d_e2; d_emb_all = s.d_emb_all; d_eps = s.d_eps;
-        kv_ptr = s.kv_ptr; kv_epoch = s.kv_epoch; kv_stream = s.kv_stream; g_ctxc = s.g_ctxc;
-        graph_exec = s.graph_exec; graph_valid = s.graph_valid; warm = s.warm; g_x = s.g_x; g_s = s.g_s; g_ctx = s.g_ctx; g_out = s.g_out; g_den = s.g_den; g_xB = s.g_xB; g_cc = s.g_cc; g_ccn = s.g_ccn; g_t = s.g_t;
-        fx_temb = s.fx_temb; fx_gemb = s.fx_gemb; fx_h1 = s.fx_h1; fx_vec = s.fx_vec; fx_svec = s.fx_svec; fx_mod = s.fx_mod; fx_tok = s.fx_tok;
-        fb_s0 = s.fb_s0; fb_s1 = s.fb_s1; fb_x = s.fb_x; fb_first = s.fb_first; fb_res = s.fb_res; fb_part = s.fb_part;
-        fb_B = s.fb_B; fb_L = s.fb_L; fb_Lt = s.fb_Lt; fb_C = s.fb_C; fb_a_end = s.fb_a_end; fb_b_end = s.fb_b_end;
-        pB2 = B2; ph = h; pw = w; pM = Mc; pShare = share;
-        plan_cache.erase(plan_cache.begin() + i);
+        if (plan_cache[i].key != key) continue;
+        cur = std::move(plan_cache[i]);
+        plan_cache.erase(plan_cache.begin() + (long)i);
         return true;
     }
     return false;
 }
 
 int Engine::exec_ops(hipStream_t ls, size_t op_begin, size_t op_end, int ctx_sel) {
-    if (op_end > ops.size()) op_end = ops.size();
+    if (op_end > cur.ops.size()) op_end = cur.ops.size();
     const bool prof_now = profiling && !prof_graph;
-    if (prof_now && prof_events.size() < 2 * ops.size()) {
+    if (prof_now && prof_events.size() < 2 * cur.ops.size()) {
         const size_t old = prof_events.size();
-        prof_events.resize(2 * ops.size());
+        prof_events.resize(2 * cur.ops.size());
         for (size_t i = old; i < prof_events.size(); ++i) HIP_OK(hipEventCreate(&prof_events[i]));
     }
     for (size_t oi = op_begin; oi < op_end; ++oi) {
-        const Op& o = ops[oi];
+        const Op& o = cur.ops[oi];
         if ((ctx_sel == 1 && o.ctx_only) || (ctx_sel == 2 && !o.ctx_only)) continue;
         if (prof_now) HIP_OK(hipEventRecord(prof_events[2 * oi], ls));
         switch (o.kind) {
             case OP_PREP: {
                 PrepArgs p{};
-                p.x = b_x; p.sigma = b_s; p.B = pB2; p.C = cfg.in_channels; p.H = ph; p.W = pw; p.Cpad = 64;
-                p.xc = (char*)arena + prep_xc_off; p.log_sigmas = d_log_sigmas; p.n_sigmas = n_sigmas;
-                p.temb_table = d_temb; p.temb_dim = cfg.model_channels; p.temb_out = d_temb_out; p.t_out = nullptr;
-                p.scale_input = b_den ? 1 : 0; p.t_in = b_den ? b_t : b_s; p.xB = b_xB;      // b_t: indices from the caller (null: looked up from sigma on the device)
-                p.cc = b_cc; p.Cx = cfg.in_channels - b_ccn;
-                if (kind == KIND_UNET && d_emb_table) { p.emb_table = d_emb_table; p.emb_n = emb_total; p.emb_out = d_emb_all; }
+                p.x = bind.x; p.sigma = bind.s; p.B = cur.key.B; p.C = cfg.in_channels; p.H = cur.key.h; p.W = cur.key.w; p.Cpad = 64;
+                p.xc = (char*)cur.arena + cur.prep_xc_off; p.log_sigmas = d_log_sigmas; p.n_sigmas = n_sigmas;
+                p.temb_table = d_temb; p.temb_dim = cfg.model_channels; p.temb_out = cur.d_temb_out; p.t_out = nullptr;
+                p.scale_input = bind.den ? 1 : 0; p.t_in = bind.den ? bind.t : bind.s; p.xB = bind.xB;      // bind.t: indices from the caller (null: looked up from sigma on the device)
+                p.cc = bind.cc; p.Cx = cfg.in_channels - bind.ccn;
+                if (kind == KIND_UNET && d_emb_table) { p.emb_table = d_emb_table; p.emb_n = emb_total; p.emb_out = cur.d_emb_all; }
                 launch_prep(p, dt, ls);
             } break;
-            case OP_CVT: launch_f32_to_t(b_ctx, o.cvt_out, o.cvt_n, dt, ls); break;
+            case OP_CVT: launch_f32_to_t(bind.ctx, o.cvt_out, o.cvt_n, dt, ls); break;
             case OP_SKINNY: launch_skinny(o.sk, dt, ls); break;
             case OP_GEMM: {
                 launch_gemm(o.g, dt, ls);
@@ -1190,34 +1203,34 @@ int Engine::exec_ops(hipStream_t ls, size_t op_begin, size_t op_end, int ctx_sel
             case OP_GN: launch_groupnorm(o.gn, dt, ls); break;
             case OP_LN: launch_layernorm(o.ln, dt, ls); break;
             case OP_ATTN:
-                if (o.i3 == 1) { AttnArgs a = o.at; a.bias = b_bias; launch_attention(a, dt, ls); }      // per-call bias table (T5)
+                if (o.i3 == 1) { AttnArgs a = o.at; a.bias = bind.bias; launch_attention(a, dt, ls); }      // per-call bias table (T5)
                 else launch_attention(o.at, dt, ls);
                 break;
             case OP_FINISH: {
                 FinishArgs f{};
-                f.eps = d_eps; f.ld = cfg.out_channels; f.x = b_den ? b_x : nullptr; f.sigma = b_s; f.out = b_out;
-                f.B = pB2; f.C = cfg.out_channels; f.HW = ph * pw; f.xB = b_xB;
+                f.eps = cur.d_eps; f.ld = cfg.out_channels; f.x = bind.den ? bind.x : nullptr; f.sigma = bind.s; f.out = bind.out;
+                f.B = cur.key.B; f.C = cfg.out_channels; f.HW = cur.key.h * cur.key.w; f.xB = bind.xB;
                 launch_finish(f, ls);
             } break;
-            case OP_VAEPREP: launch_vae_prep(b_x, o.p1, o.i0, o.i1, o.i2, o.i3, vae_pq, vae_pq ? vae_pq + o.i1 * o.i1 : nullptr, dt, ls); break;
+            case OP_VAEPREP: launch_vae_prep(bind.x, o.p1, o.i0, o.i1, o.i2, o.i3, vae_pq, vae_pq ? vae_pq + o.i1 * o.i1 : nullptr, dt, ls); break;
             case OP_SOFTMAX: launch_softmax_rows(o.p1, o.i0, o.i1, o.i2, o.f0, dt, ls); break;
-            case OP_CLAMP: launch_clamp01((const float*)o.p0, b_out, (size_t)o.i0, ls); break;
-            case OP_EMBED: launch_clip_embed(b_ids, kind == KIND_T5 ? t5_tok : clip_tok, kind == KIND_T5 ? nullptr : clip_pos, o.p1, o.i0, o.i1, o.i2, o.i3,
+            case OP_CLAMP: launch_clamp01((const float*)o.p0, bind.out, (size_t)o.i0, ls); break;
+            case OP_EMBED: launch_clip_embed(bind.ids, kind == KIND_T5 ? t5_tok : clip_tok, kind == KIND_T5 ? nullptr : clip_pos, o.p1, o.i0, o.i1, o.i2, o.i3,
                                               kind == KIND_T5 ? nullptr : clip_extra, kind == KIND_T5 ? 0 : clip_extra_n, dt, ls); break;
-            case OP_CVT_OUT: if ((o.i3 ? b_out2 : b_out) != nullptr) launch_t_to_f32(o.p0, o.i3 ? b_out2 : b_out, (size_t)o.i0, dt, ls); break;
-            case OP_PIXPREP: launch_pixels_prep(b_x, o.p1, o.i0, o.i1, o.i2, o.i3, o.f0, o.f1, dt, ls); break;
-            case OP_COPY_OUT: HIP_OK(hipMemcpyAsync(b_out, o.p0, (size_t)o.cvt_n, hipMemcpyDeviceToDevice, ls)); break;
-            case OP_MOMENTS: launch_mix_nhwc_to_nchw((const float*)o.p0, o.i1, b_out, o.i0, o.i1, o.i2, enc_qc, enc_qc ? enc_qc + o.i1 * o.i1 : nullptr, ls); break;
+            case OP_CVT_OUT: if ((o.i3 ? bind.out2 : bind.out) != nullptr) launch_t_to_f32(o.p0, o.i3 ? bind.out2 : bind.out, (size_t)o.i0, dt, ls); break;
+            case OP_PIXPREP: launch_pixels_prep(bind.x, o.p1, o.i0, o.i1, o.i2, o.i3, o.f0, o.f1, dt, ls); break;
+            case OP_COPY_OUT: HIP_OK(hipMemcpyAsync(bind.out, o.p0, (size_t)o.cvt_n, hipMemcpyDeviceToDevice, ls)); break;
+            case OP_MOMENTS: launch_mix_nhwc_to_nchw((const float*)o.p0, o.i1, bind.out, o.i0, o.i1, o.i2, enc_qc, enc_qc ? enc_qc + o.i1 * o.i1 : nullptr, ls); break;
             case OP_DUP: launch_dup_rows(o.p0, o.p1, o.i0, o.i1, o.i2, dt, ls); break;
-            case OP_FX_TEMB: launch_flux_temb(o.i0 ? b_guid : b_s, (float*)o.p1, pB2, 256, 1000.0f, ls); break;
+            case OP_FX_TEMB: launch_flux_temb(o.i0 ? bind.guid : bind.s, (float*)o.p1, cur.key.B, 256, 1000.0f, ls); break;
             case OP_FX_SILU: launch_silu_f32((const float*)o.p0, (float*)o.p1, (size_t)o.i0, ls); break;
-            case OP_FX_PATCH: launch_flux_patchify(b_x, o.p1, o.i0, o.i1, o.i2, o.i3, dt, ls); break;
-            case OP_FX_CVT_CTX: launch_f32_to_t(b_ctx, o.cvt_out, o.cvt_n, dt, ls); break;
-            case OP_FX_SKINNY_Y: { SkinnyArgs a = o.sk; a.x = b_y; launch_skinny(a, dt, ls); } break;
+            case OP_FX_PATCH: launch_flux_patchify(bind.x, o.p1, o.i0, o.i1, o.i2, o.i3, dt, ls); break;
+            case OP_FX_CVT_CTX: launch_f32_to_t(bind.ctx, o.cvt_out, o.cvt_n, dt, ls); break;
+            case OP_FX_SKINNY_Y: { SkinnyArgs a = o.sk; a.x = bind.y; launch_skinny(a, dt, ls); } break;
             case OP_FX_SKINNY_G: break;
-            case OP_FX_ROPE: { QkRopeArgs a = o.rp; const int hp = a.D / 2; a.cosT = b_cos + (size_t)o.i0 * hp; a.sinT = b_sin + (size_t)o.i0 * hp;
+            case OP_FX_ROPE: { QkRopeArgs a = o.rp; const int hp = a.D / 2; a.cosT = bind.pe_cos + (size_t)o.i0 * hp; a.sinT = bind.pe_sin + (size_t)o.i0 * hp;
                                if (a.Q8) launch_qk_norm_rope_mx(a, dt, ls); else launch_qk_norm_rope(a, dt, ls); } break;
-            case OP_FX_UNPATCH: launch_flux_unpatchify(fx_tok, 4 * o.i1, b_den ? b_x : nullptr, b_s, b_out, o.i0, o.i1, o.i2, o.i3, ls); break;
+            case OP_FX_UNPATCH: launch_flux_unpatchify(cur.fx_tok, 4 * o.i1, bind.den ? bind.x : nullptr, bind.s, bind.out, o.i0, o.i1, o.i2, o.i3, ls); break;
         }
         if (prof_now) HIP_OK(hipEventRecord(prof_events[2 * oi + 1], ls));
     }
@@ -1225,9 +1238,9 @@ int Engine::exec_ops(hipStream_t ls, size_t op_begin, size_t op_end, int ctx_sel
         HIP_OK(hipStreamSynchronize(ls));
         for (size_t i = op_begin; i < op_end; ++i) {
             float ms = 0.f;
-            if ((ctx_sel == 1 && ops[i].ctx_only) || (ctx_sel == 2 && !ops[i].ctx_only)) continue;
+            if ((ctx_sel == 1 && cur.ops[i].ctx_only) || (ctx_sel == 2 && !cur.ops[i].ctx_only)) continue;
             HIP_OK(hipEventElapsedTime(&ms, prof_events[2 * i], prof_events[2 * i + 1]));
-            const Op& o = ops[i];
+            const Op& o = cur.ops[i];
             std::string key = o.klabel[0] ? o.klabel : o.name;
             if (prof_detail) {
                 char sh[96] = "";
@@ -1289,61 +1302,52 @@ int Engine::run(const float* x, const float* sigma_or_t, const float* ctx, int B
     // CFG evaluation over one latent batch (ldx_unet_denoise_cfg*: xB > 0 and B2 == 2 xB): the two halves are identical up to the first cross-attention, which
     // the plan then computes once (plan(): share).  LDX_CFG_SHARE=0: every op on the full batch, as the concatenated ldx_unet_denoise call runs it.
     const int share = share_for(B2, h, w, xB, denoise, c_concat != nullptr);
-    if (B2 != pB2 || h != ph || w != pw || Mc != pM || share != pShare) {
-        HIP_OK(hipStreamSynchronize(st));
-        if (pB2 > 0) plan_stash();
-        if (!plan_restore(B2, h, w, Mc, share)) {
-            int rc = plan(B2, h, w, Mc, share);
-            if (rc) return rc;
-        }
-    }
+    if (int rc = select_plan(PlanKey{B2, h, w, Mc, share}, st, [&] { return plan(B2, h, w, Mc, share); })) return rc;
+    bind = Bindings{};
+    bind.x = x; bind.s = sigma_or_t; bind.ctx = ctx; bind.out = out; bind.den = denoise; bind.xB = xB; bind.cc = c_concat; bind.ccn = cc_channels; bind.t = t_idx;
+    bind.ctxc = ctx_cache;
     // context cache: the ctx_only ops run here, eagerly, only when this plan's buffers do not hold the projections of (ctx, epoch) yet; every
     // other op (and the captured graph) then leaves them out
-    const bool ctxc = ctx_cache;
-    b_ctx = ctx;
-    if (ctxc && !(kv_ptr == ctx && kv_epoch == ctx_epoch && kv_stream == st)) {
+    if (bind.ctxc && !(cur.kv_ptr == ctx && cur.kv_epoch == ctx_epoch && cur.kv_stream == st)) {
         const bool pg = prof_graph; prof_graph = false;
         const int rc = exec_ops(st, 0, (size_t)-1, 2);
         prof_graph = pg;
         if (rc) return rc;
-        kv_ptr = ctx; kv_epoch = ctx_epoch; kv_stream = st;
+        cur.kv_ptr = ctx; cur.kv_epoch = ctx_epoch; cur.kv_stream = st;
     }
-    const bool same = (g_x == x && g_s == sigma_or_t && g_ctx == ctx && g_out == out && g_den == denoise && g_xB == xB && g_cc == c_concat && g_ccn == cc_channels && g_ctxc == ctxc && g_t == t_idx);
+    const bool same = cur.graph_b == bind;
     // a captured graph has its pointers baked in: once a call arrives with other bindings (in ANY mode — the eager path below re-records
-    // g_*), that graph must never be replayed against the new g_* (round 3: a stale graph was replayed after an eager call had moved g_*)
-    if (!same) graph_valid = false;
-    if (graph_mode && graph_valid && same) {
-        HIP_OK(hipGraphLaunch(graph_exec, st));
+    // graph_b), that graph must never be replayed against the new graph_b (round 3: a stale graph was replayed after an eager call had moved them)
+    if (!same) cur.graph_valid = false;
+    if (graph_mode && cur.graph_valid && same) {
+        HIP_OK(hipGraphLaunch(cur.graph_exec, st));
         ++n_graph_replays;
         return LDX_OK;
     }
     // capture only once the same (plan, pointers) have been run eagerly before: the first eager pass
     // also performs the one-time hipFuncSetAttribute calls, which are illegal during capture.
-    const bool use_graph = graph_mode && warm && same;
-    g_x = x; g_s = sigma_or_t; g_ctx = ctx; g_out = out; g_den = denoise; g_xB = xB; g_cc = c_concat; g_ccn = cc_channels; g_ctxc = ctxc; g_t = t_idx; warm = true;
+    const bool use_graph = graph_mode && cur.warm && same;
+    cur.graph_b = bind; cur.warm = true;
     hipStream_t ls = st;
     if (use_graph) {
-        if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
+        if (cur.graph_exec) { (void)hipGraphExecDestroy(cur.graph_exec); cur.graph_exec = nullptr; }
         if (!cap_stream) HIP_OK(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
         HIP_OK(hipStreamSynchronize(st));
         HIP_OK(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
         ls = cap_stream;
     }
-    b_x = x; b_s = sigma_or_t; b_ctx = ctx; b_out = out; b_den = denoise; b_xB = xB; b_cc = c_concat; b_ccn = cc_channels; b_t = t_idx;
     prof_graph = use_graph;
-    { int rc = exec_ops(ls, 0, (size_t)-1, ctxc ? 1 : 0); if (rc) return rc; }
+    { int rc = exec_ops(ls, 0, (size_t)-1, bind.ctxc ? 1 : 0); if (rc) return rc; }
     if (use_graph) {
         hipGraph_t g = nullptr;
         HIP_OK(hipStreamEndCapture(cap_stream, &g));
-        HIP_OK(hipGraphInstantiate(&graph_exec, g, nullptr, nullptr, 0));
+        HIP_OK(hipGraphInstantiate(&cur.graph_exec, g, nullptr, nullptr, 0));
         (void)hipGraphDestroy(g);
-        graph_valid = true;
+        cur.graph_valid = true;
         ++n_graph_captures;
-        HIP_OK(hipGraphLaunch(graph_exec, st));
+        HIP_OK(hipGraphLaunch(cur.graph_exec, st));
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return LDX_EHIP; }
-    return LDX_OK;
+    return launch_status();
 }
 
 std::string Engine::profile_json() const {
@@ -1360,7 +1364,7 @@ std::string Engine::profile_json() const {
 
 int64_t Engine::n_launches() const {
     int64_t n = 0;
-    for (const Op& o : ops) {
+    for (const Op& o : cur.ops) {
         if (ctx_cache && o.ctx_only) continue;            // steady state of a sampling run: the context's projections are cached
         if (o.kind == OP_ATTN && o.at.nsplit > 1) { n += 2; continue; }      // split keys + merge launch (attn512.hip)
         if (o.kind == OP_GN) n += o.gn.stats_chunks > GN_NCHUNK ? 2 : (o.gn.stats_chunks > 0 ? 1 : 2);      // fold + apply / apply / statistics + apply

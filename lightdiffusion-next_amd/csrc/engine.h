@@ -15,6 +15,7 @@ namespace ldx {
 
 extern thread_local std::string g_last_error;
 void set_error(const std::string& s);
+int launch_status();          // LDX_EHIP (and the error text) when a kernel launch since the last check failed
 
 struct HostTensor {
     int dtype = LDX_F32;
@@ -56,6 +57,54 @@ struct Op {
 };
 struct ProfEntry { long count = 0; double ms = 0, flops = 0, bytes = 0; };
 
+// What a plan was built for.  Per model: UNet (B2, h, w, Mc, share), Flux (B, h, w, Lt), VAE (B, h, w, 1) decode / (B, Hpx, Wpx, 2) encode,
+// CLIP (B, T, 0, inter_layer), T5 (B, L), ESRGAN (B, H, W).  B = 0: no plan.
+struct PlanKey {
+    int B = 0, h = 0, w = 0, m = 0, share = 0;
+    bool operator==(const PlanKey& o) const { return B == o.B && h == o.h && w == o.w && m == o.m && share == o.share; }
+    bool operator!=(const PlanKey& o) const { return !(*this == o); }
+};
+
+// The caller's buffers of one call, read by exec_ops.  Every field takes part in ==.
+struct Bindings {
+    const float *x = nullptr, *s = nullptr, *ctx = nullptr; float* out = nullptr; bool den = false; int xB = 0;
+    const float* cc = nullptr; int ccn = 0;       // UNet c_concat and its channels
+    const float* t = nullptr;                     // UNet: caller-supplied timestep indices (run(): t_idx)
+    bool ctxc = false;                            // UNet: context-cache mode (the ctx_only ops are left out)
+    const int* ids = nullptr; float* out2 = nullptr; const float* bias = nullptr;       // CLIP / T5
+    const float *y = nullptr, *guid = nullptr, *pe_cos = nullptr, *pe_sin = nullptr;     // Flux
+    bool operator==(const Bindings& o) const {
+        return x == o.x && s == o.s && ctx == o.ctx && out == o.out && den == o.den && xB == o.xB && cc == o.cc && ccn == o.ccn && t == o.t &&
+               ctxc == o.ctxc && ids == o.ids && out2 == o.out2 && bias == o.bias && y == o.y && guid == o.guid && pe_cos == o.pe_cos && pe_sin == o.pe_sin;
+    }
+};
+
+// Everything that belongs to one planned input shape: the launch list over one activation arena, the buffers inside that arena and the graph
+// captured from it.  Plans move as a whole (Engine::cur <-> Engine::plan_cache); release() frees what a plan owns.
+struct Plan {
+    PlanKey key;
+    std::vector<Op> ops;
+    double flops = 0;
+    double flops_shared = 0;               // flops the plan does NOT execute because of the shared CFG prefix (the second half's copy of the prefix ops)
+    size_t prefix_end = 0;                 // UNet: number of ops in front of the first cross-attention (they ran on `share` samples)
+    void* arena = nullptr;
+    size_t arena_cap = 0, arena_peak_dry = 0;
+    size_t gn_ws_off = 0;
+    // UNet
+    size_t prep_xc_off = 0, kv_all_off = 0;
+    float *d_temb_out = nullptr, *d_e1 = nullptr, *d_e2 = nullptr, *d_emb_all = nullptr, *d_eps = nullptr;
+    const void* kv_ptr = nullptr; uint64_t kv_epoch = 0;       // context cache: what the kvall buffer holds
+    hipStream_t kv_stream = nullptr;                            // ... and the stream whose order it was filled in: a call on another stream refills (no cross-stream dependency is assumed)
+    hipGraphExec_t graph_exec = nullptr;
+    bool graph_valid = false, warm = false;
+    Bindings graph_b;                      // the bindings of the last eager pass: what a graph captured now has baked in
+    // Flux: buffers inside the arena, first-block-cache buffers and op ranges ([0, fb_a_end) through double block 0, [fb_a_end, fb_b_end) the rest)
+    float *fx_temb = nullptr, *fx_gemb = nullptr, *fx_h1 = nullptr, *fx_vec = nullptr, *fx_svec = nullptr, *fx_mod = nullptr, *fx_tok = nullptr;
+    void *fb_s0 = nullptr, *fb_s1 = nullptr, *fb_x = nullptr; float *fb_first = nullptr, *fb_res = nullptr, *fb_part = nullptr;
+    int fb_B = 0, fb_L = 0, fb_Lt = 0, fb_C = 0; size_t fb_a_end = 0, fb_b_end = 0;
+    void release();                        // the arena and the graph
+};
+
 struct EmbSrc { const HostTensor* w; const HostTensor* b; int n; };
 
 struct VaeAttnW { NormW norm; LinearW q, k, v, proj; LinearW qkv; /* C = 512: fused q | k | v projection [3C][C] for the flash kernel (attn512.hip); bias = [bq | bk | 0], bv folded into proj's */ };
@@ -80,7 +129,7 @@ public:
     int plan_esrgan(int B, int H, int W);
     int run_esrgan(const float* px, int B, int H, int W, float* out, hipStream_t st);
     ldx_t5_config tcfg{};
-    std::vector<T5LayerW> t5_layers; NormW t5_final_ln; float* t5_tok = nullptr; const float* b_bias = nullptr;
+    std::vector<T5LayerW> t5_layers; NormW t5_final_ln; float* t5_tok = nullptr;
     int finalize_t5();
     int plan_t5(int B, int L);
     int run_t5(const int* ids, int B, int L, const float* bias, float* out, hipStream_t st);
@@ -88,9 +137,6 @@ public:
     int finalize_flux();
     // First-block cache (WaveSpeed/first_block_cache.py:105-384, fbcache_nodes.py:8-201): opt-in approximate mode
     float fb_threshold = 0.f; bool fb_have_first = false, fb_have_res = false; float fb_prev_t = 0.f; bool fb_prev_valid = false;
-    size_t fb_a_end = 0, fb_b_end = 0;                 // op ranges: [0, a_end) through double block 0, [a_end, b_end) the rest
-    void *fb_s0 = nullptr, *fb_s1 = nullptr; float *fb_first = nullptr, *fb_res = nullptr, *fb_part = nullptr;
-    void* fb_x = nullptr; int fb_B = 0, fb_L = 0, fb_Lt = 0, fb_C = 0;
     long fb_hits = 0, fb_misses = 0;
     void fb_reset() { fb_have_first = fb_have_res = false; fb_prev_valid = false; }
     // MX fp8 mode (BASELINE config 4 "fp8 MFMA"): the block linears run on block-scaled fp8 operands; opt-in, own parity class
@@ -137,9 +183,6 @@ public:
     //     ldx_unet_context_cache again; the 16-bit copy of ctx and the batched k|v projection of every cross-attention (transformer.py:186-245 recomputes
     //     them every step only because a torch module has no notion of a sampling run) are then computed on the first evaluation of a (plan, ctx) only.
     bool ctx_cache = false; uint64_t ctx_epoch = 1;
-    const void* kv_ptr = nullptr; uint64_t kv_epoch = 0;       // what the CURRENT plan's kvall buffer holds
-    hipStream_t kv_stream = nullptr;                            // ... and the stream whose order it was filled in: a call on another stream refills (no cross-stream dependency is assumed)
-    bool g_ctxc = false;                                        // the captured graph was recorded without the ctx_only ops
     int set_context_cache(int enable) { ctx_cache = enable != 0; ++ctx_epoch; return LDX_OK; }
     double algorithmic_flops() const;                           // steady_flops() + flops_shared
     double steady_flops() const;                                // algorithmic flops of one forward as executed in steady state (cached ops excluded)
@@ -150,10 +193,7 @@ public:
     // samples; its results are copied into the second half's rows where the first cross-attention (and the skip connections) need them (OP_DUP).
     int plan(int B2, int h, int w, int Mc, int share = 0);
     int share_for(int B2, int h, int w, int xB, bool denoise, bool concat) const;
-    int pShare = 0;
     int cfg_share = 1;                     // ldx_unet_cfg_share / LDX_CFG_SHARE: plan CFG evaluations with the shared prefix (0 never, 1 where it pays, 2 whenever possible)
-    size_t prefix_end = 0;                 // plan(): number of ops in front of the first cross-attention (they ran on `share` samples)
-    double flops_shared = 0;               // flops the current plan does NOT execute because of it (the second half's copy of the prefix ops)
     int64_t n_launches() const;
     int64_t n_graph_captures = 0, n_graph_replays = 0;      // ldx_graph_stats (tests: the sampler loops must replay, not re-capture)
     // per-kernel-class HIP-event profile of subsequent forwards (bench.py roofline leg)
@@ -166,10 +206,8 @@ public:
     DType dt;
     bool finalized = false;
     bool graph_mode = false;
-    double flops = 0;
-    size_t arena_cap = 0, arena_peak_dry = 0;
     size_t weight_bytes = 0;
-    int pB2 = 0, ph = 0, pw = 0, pM = 0;
+    Plan cur;                              // the plan being run (while a plan_* runs: being built)
 
 private:
     // weights
@@ -195,16 +233,12 @@ private:
     void fuse_gn_stats();
     void fuse_gn_rowgemm();                               // GroupNorm (producer statistics) + proj_in -> one rowgemm launch
     bool op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R, int pro, const NormW* nw);          // post-pass over ops: GroupNorms whose input was just written by a fusable GEMM / conv get their statistics from its epilogue
-    // per-call bindings read by exec_ops
-    const float* b_x = nullptr; const float* b_s = nullptr; const float* b_ctx = nullptr; float* b_out = nullptr; bool b_den = false; int b_xB = 0, g_xB = 0;
-    const float* b_cc = nullptr; const float* g_cc = nullptr; int b_ccn = 0, g_ccn = 0;
-    const float* b_t = nullptr; const float* g_t = nullptr;       // caller-supplied timestep indices (run(): t_idx)
-    const int* b_ids = nullptr; float* b_out2 = nullptr;
+    Bindings bind;                                        // this call's
     // VAE
     std::vector<std::vector<ResW>> vae_up; std::vector<LinearW> vae_upconv; std::vector<bool> vae_has_up;
     ResW vae_mid1, vae_mid2; VaeAttnW vae_attn; NormW vae_norm_out; float* vae_pq = nullptr;
     // VAE encoder (optional: only when encoder.* weights were loaded)
-    bool vae_has_enc = false; int vae_plan_mode = 0;      // 1 decode plan, 2 encode plan
+    bool vae_has_enc = false;
     std::vector<std::vector<ResW>> enc_down; std::vector<LinearW> enc_downconv;
     ResW enc_mid1, enc_mid2; VaeAttnW enc_attn; NormW enc_norm_out; LinearW enc_conv_in, enc_conv_out; float* enc_qc = nullptr;
     bool mk_vae_attn(const std::string& pre, int C, VaeAttnW& a);
@@ -213,13 +247,10 @@ private:
     LinearW fx_img_in, fx_txt_in, fx_time0, fx_time1, fx_vec0, fx_vec1, fx_gd0, fx_gd1, fx_mod_all, fx_final;
     int fx_mod_total = 0, fx_final_mod_off = 0;
     std::vector<EmbSrc> fx_mod_srcs;
-    const float *b_y = nullptr, *b_guid = nullptr, *b_cos = nullptr, *b_sin = nullptr;
-    float *fx_temb = nullptr, *fx_gemb = nullptr, *fx_h1 = nullptr, *fx_vec = nullptr, *fx_svec = nullptr, *fx_mod = nullptr, *fx_tok = nullptr;
     // CLIP
     std::vector<ClipLayerW> clip_layers; NormW clip_final_ln; float* clip_tok = nullptr; float* clip_pos = nullptr;
     float* clip_extra = nullptr; int clip_extra_n = 0, clip_extra_cap = 0;     // textual-inversion rows for ids >= vocab_size
     float* clip_proj = nullptr;                                                // optional text_projection.weight [E][E] fp32 (CLIPTextModel.py:130,152-163)
-    int clip_inter_planned = -100;
     LinearW te0, te2, conv_in, conv_out, emb_all;
     NormW out_gn;
     std::vector<BlockW> in_blocks, out_blocks;
@@ -230,20 +261,23 @@ private:
     std::vector<EmbSrc> emb_srcs;
     // all cross-attention k|v projections of the context, batched into one GEMM per forward
     struct KvSrc { const HostTensor* k; const HostTensor* v; int C; };
-    std::vector<KvSrc> kv_srcs; int kv_total = 0; LinearW kv_all; size_t kv_all_off = 0;
+    std::vector<KvSrc> kv_srcs; int kv_total = 0; LinearW kv_all;
     float* d_log_sigmas = nullptr; float* d_temb = nullptr; int n_sigmas = 0;
 
-    // plan
-    void* arena = nullptr;
-    std::vector<Op> ops;
+    // planner state of the plan being built (build_plan resets it)
     std::vector<std::pair<size_t, size_t>> free_list;
     std::map<size_t, size_t> live;
     size_t arena_top = 0, arena_peak = 0;
-    size_t gn_ws_off = 0, prep_xc_off = 0;
-    float *d_temb_out = nullptr, *d_e1 = nullptr, *d_e2 = nullptr, *d_emb_all = nullptr, *d_eps = nullptr;
+    bool rowblock_prefix = false;                         // emitting ops of the shared CFG prefix (rowblock_fills_chip)
+    bool rowblock_fills_chip(long workgroups) const;
+    // Two passes of `emit` into cur: a dry one (arena == nullptr) measures the peak, the second binds real pointers into an arena of that
+    // size (the current plan's when it is large enough; zero_arena: zero-filled).  cur.key = key on success.
+    int build_plan(const PlanKey& key, const std::function<int()>& emit, bool zero_arena = false);
+    // make the plan for `key` current (replan: builds it into cur); *switched: cur is another plan than before the call
+    int select_plan(const PlanKey& key, hipStream_t st, const std::function<int()>& replan, bool* switched = nullptr);
     size_t a_alloc(size_t bytes);
     void a_free(size_t off);
-    void* ptr(const Act& a) const { return (void*)((uintptr_t)arena + a.off + (size_t)a.col * 2); }
+    void* ptr(const Act& a) const { return (void*)((uintptr_t)cur.arena + a.off + (size_t)a.col * 2); }
     Act new_act(int rows, int C);
     Act view(const Act& base, int col, int C);
     void release(const Act& a);
@@ -263,30 +297,15 @@ private:
     void op_dup(const Act& a, int rows);          // rows [0, rows) of view a -> rows [rows, 2 rows)
     void dup_second_half(const DupReq& d);        // the producer's dual store (GemmArgs / RowGemmArgs::dup_rows) where it has one, else op_dup
 
-    // UNet plans of other input shapes seen (multi-scale samplers alternate between two resolutions): launch plan, arena and
-    // captured graph are kept per shape, so switching back costs nothing (a re-plan + two eager passes before the graph is
-    // usable again cost ~17 ms per switch)
-    struct PlanSnap {
-        int B2 = 0, h = 0, w = 0, M = 0, share = 0; std::vector<Op> ops; double flops = 0, flops_shared = 0; void* arena = nullptr; size_t arena_cap = 0, arena_peak_dry = 0;
-        size_t gn_ws_off = 0, prep_xc_off = 0, kv_all_off = 0; float *d_temb_out = nullptr, *d_e1 = nullptr, *d_e2 = nullptr, *d_emb_all = nullptr, *d_eps = nullptr;
-        hipGraphExec_t graph_exec = nullptr; bool graph_valid = false, warm = false;
-        const void* kv_ptr = nullptr; uint64_t kv_epoch = 0; hipStream_t kv_stream = nullptr; bool g_ctxc = false;
-        const void *g_x = nullptr, *g_s = nullptr, *g_ctx = nullptr, *g_out = nullptr; bool g_den = false; int g_xB = 0; const float* g_cc = nullptr; int g_ccn = 0; const float* g_t = nullptr;
-        // Flux plans: the per-shape buffers inside the arena and the first-block-cache op ranges
-        float *fx_temb = nullptr, *fx_gemb = nullptr, *fx_h1 = nullptr, *fx_vec = nullptr, *fx_svec = nullptr, *fx_mod = nullptr, *fx_tok = nullptr;
-        void *fb_s0 = nullptr, *fb_s1 = nullptr, *fb_x = nullptr; float *fb_first = nullptr, *fb_res = nullptr, *fb_part = nullptr;
-        int fb_B = 0, fb_L = 0, fb_Lt = 0, fb_C = 0; size_t fb_a_end = 0, fb_b_end = 0;
-    };
-    std::vector<PlanSnap> plan_cache;
+    // UNet / Flux plans of other input shapes seen (multi-scale samplers alternate between two resolutions, prompts of different lengths change
+    // Flux's Lt): launch plan, arena and captured graph are kept per shape, so switching back costs nothing (a re-plan + two eager passes
+    // before the graph is usable again cost ~17 ms per switch)
+    std::vector<Plan> plan_cache;
     void plan_stash();                    // move the current plan into plan_cache (evicting the oldest beyond 4)
-    bool plan_restore(int B2, int h, int w, int Mc, int share = 0);
+    bool plan_restore(const PlanKey& key);
     std::vector<hipEvent_t> prof_events;
     bool prof_graph = false;
-    // graph replay
-    hipGraphExec_t graph_exec = nullptr;
-    hipStream_t cap_stream = nullptr;
-    bool graph_valid = false, warm = false;
-    const void *g_x = nullptr, *g_s = nullptr, *g_ctx = nullptr, *g_out = nullptr; bool g_den = false;
+    hipStream_t cap_stream = nullptr;     // graph capture
 };
 
 }  // namespace ldx

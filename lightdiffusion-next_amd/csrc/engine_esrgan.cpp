@@ -62,24 +62,16 @@ int Engine::finalize_esrgan() {
 int Engine::plan_esrgan(int B, int H, int W) {
     const ldx_esrgan_config& c = ecfg;
     const int nf = c.nf, gc = c.gc, CW = nf + 4 * gc, M = B * H * W;
-    for (int pass = 0; pass < 2; ++pass) {
-        ops.clear(); flops = 0; free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0;
-        if (pass == 1) {
-            if (arena && arena_cap < arena_peak_dry) { HIP_OK(hipFree(arena)); arena = nullptr; }
-            if (!arena) { HIP_OK(hipMalloc(&arena, arena_peak_dry)); arena_cap = arena_peak_dry; }
-            // dense-block convs read a few not-yet-written columns against zero weights: those must hold finite values, and a
-            // new plan lays the buffers over whatever the previous shape left there (fp32 pixels read as 16-bit can be NaN)
-            HIP_OK(hipMemset(arena, 0, arena_cap));
-        }
-        void* saved = arena;
-        if (pass == 0) arena = nullptr;
+    // zero-filled arena: dense-block convs read a few not-yet-written columns against zero weights: those must hold finite values, and a
+    // new plan lays the buffers over whatever the previous shape left there (fp32 pixels read as 16-bit can be NaN)
+    return build_plan(PlanKey{B, H, W}, [&]() -> int {
         auto conv = [&](const char* name, Act X, int Cin, const LinearW& w, int Hin, int Win, int Hout, int Wout, Act Y, Act R, int act) {
             op_conv(name, X, B, Hin, Win, Cin, w, 1, Hout, Wout, Y, R);
-            GemmArgs& g = ops.back().g; g.act = act;
+            GemmArgs& g = cur.ops.back().g; g.act = act;
             if (g.splitk > 1) g.splitk = 1;
         };
         Act x0 = new_act(M, 64);
-        { Op o{}; o.kind = OP_PIXPREP; o.name = "esrgan.prep"; o.p1 = ptr(x0); o.i0 = B; o.i1 = c.in_nc; o.i2 = H * W; o.i3 = 64; o.f0 = 1.0f; o.f1 = 0.0f; ops.push_back(o); }
+        { Op o{}; o.kind = OP_PIXPREP; o.name = "esrgan.prep"; o.p1 = ptr(x0); o.i0 = B; o.i1 = c.in_nc; o.i2 = H * W; o.i3 = 64; o.f0 = 1.0f; o.f1 = 0.0f; cur.ops.push_back(o); }
         Act fea = new_act(M, nf);
         Act cat[3] = {new_act(M, CW), new_act(M, CW), new_act(M, CW)};
         conv("esrgan.conv_first", x0, 64, es_first, H, W, H, W, fea, Act{}, 0);
@@ -92,7 +84,7 @@ int Engine::plan_esrgan(int B, int H, int W) {
                 conv("esrgan.rdb.conv", view(cat[src], 0, cpad), cpad, r.c[j], H, W, H, W, view(cat[src], nf + j * gc, gc), Act{}, 3);
             }
             conv("esrgan.rdb.conv5", view(cat[src], 0, CW), CW, r.c[4], H, W, H, W, view(cat[dst], 0, nf), view(cat[src], 0, nf), 0);
-            GemmArgs& g = ops.back().g; g.oscale = 0.2f;                                      // x5 * 0.2 + x
+            GemmArgs& g = cur.ops.back().g; g.oscale = 0.2f;                                      // x5 * 0.2 + x
             if (rrdb_in) { g.R2 = ptr(*rrdb_in); g.ldr2 = rrdb_in->ld; g.oscale2 = 0.2f; }   // (..) * 0.2 + rrdb input
         };
         for (int i = 0; i < c.num_blocks; ++i) {
@@ -105,42 +97,33 @@ int Engine::plan_esrgan(int B, int H, int W) {
         Act trunk = new_act(M, nf);
         conv("esrgan.trunk_conv", view(cat[in], 0, nf), nf, es_trunk, H, W, H, W, trunk, fea, 0);    // ShortcutBlock: fea + trunk(fea)
         release(cat[0]); release(cat[1]); release(cat[2]); release(fea);
-        Act cur = trunk;
+        Act hcur = trunk;
         int h = H, w = W;
         for (int u = 0; u < c.num_upscale; ++u) {
             Act nx = new_act(B * 4 * h * w, nf);
-            conv("esrgan.upconv", cur, nf, es_up[u], h, w, 2 * h, 2 * w, nx, Act{}, 3);
-            release(cur); cur = nx; h *= 2; w *= 2;
+            conv("esrgan.upconv", hcur, nf, es_up[u], h, w, 2 * h, 2 * w, nx, Act{}, 3);
+            release(hcur); hcur = nx; h *= 2; w *= 2;
         }
         Act hr = new_act(B * h * w, nf);
-        conv("esrgan.hr_conv", cur, nf, es_hr, h, w, h, w, hr, Act{}, 3);
-        release(cur);
+        conv("esrgan.hr_conv", hcur, nf, es_hr, h, w, h, w, hr, Act{}, 3);
+        release(hcur);
         const size_t o_pix = a_alloc((size_t)B * h * w * c.out_nc * 4);
-        float* pix = (float*)((uintptr_t)arena + o_pix);
+        float* pix = (float*)((uintptr_t)cur.arena + o_pix);
         op_conv("esrgan.conv_last", hr, B, h, w, nf, es_last, 1, h, w, Act{}, Act{}, nullptr, 0, pix, c.out_nc);
         release(hr);
-        { Op o{}; o.kind = OP_COPY_OUT; o.name = "esrgan.out"; o.p0 = pix; o.cvt_n = (size_t)B * h * w * c.out_nc * 4; ops.push_back(o); }
-        if (pass == 0) { arena_peak_dry = arena_peak; arena = saved; }
-    }
-    pB2 = B; ph = H; pw = W; pM = 0;
-    return LDX_OK;
+        { Op o{}; o.kind = OP_COPY_OUT; o.name = "esrgan.out"; o.p0 = pix; o.cvt_n = (size_t)B * h * w * c.out_nc * 4; cur.ops.push_back(o); }
+        return LDX_OK;
+    }, true);
 }
 
 int Engine::run_esrgan(const float* px, int B, int H, int W, float* out, hipStream_t st) {
     if (!finalized || kind != KIND_ESRGAN) { set_error("ldx_esrgan_forward: not a finalized ESRGAN engine"); return LDX_ESTATE; }
     if (!px || !out || B <= 0 || H <= 0 || W <= 0) { set_error("ldx_esrgan_forward: bad argument"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
-    if (B != pB2 || H != ph || W != pw) {
-        HIP_OK(hipStreamSynchronize(st));
-        int rc = plan_esrgan(B, H, W);
-        if (rc) return rc;
-    }
-    b_x = px; b_out = out; prof_graph = false;
-    int rc = exec_ops(st);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return LDX_EHIP; }
-    return LDX_OK;
+    if (int rc = select_plan(PlanKey{B, H, W}, st, [&] { return plan_esrgan(B, H, W); })) return rc;
+    bind = Bindings{}; bind.x = px; bind.out = out; prof_graph = false;
+    if (int rc = exec_ops(st)) return rc;
+    return launch_status();
 }
 
 }  // namespace ldx

@@ -146,46 +146,39 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
     const ldx_flux_config& f = fcfg;
     const int C = f.hidden_size, H = f.num_heads, D = C / H, MH = f.mlp_hidden;
     const int Li = (h / 2) * (w / 2), L = Lt + Li, inC = 4 * f.in_channels;
-    for (int pass = 0; pass < 2; ++pass) {
-        ops.clear(); flops = 0; free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0;
-        if (pass == 1) {
-            if (arena && arena_cap < arena_peak_dry) { HIP_OK(hipFree(arena)); arena = nullptr; }
-            if (!arena) { HIP_OK(hipMalloc(&arena, arena_peak_dry)); arena_cap = arena_peak_dry; }
-        }
-        void* saved = arena;
-        if (pass == 0) arena = nullptr;
-        auto f32buf = [&](size_t n) { const size_t off = a_alloc(n * 4); return (float*)((uintptr_t)arena + off); };
-        fx_temb = f32buf((size_t)B * 256); fx_gemb = f32buf((size_t)B * 256); fx_h1 = f32buf((size_t)B * C);
-        fx_vec = f32buf((size_t)B * C); fx_svec = f32buf((size_t)B * C); fx_mod = f32buf((size_t)B * fx_mod_total);
-        fx_tok = f32buf((size_t)B * Li * inC);
+    return build_plan(PlanKey{B, h, w, Lt}, [&]() -> int {
+        auto f32buf = [&](size_t n) { const size_t off = a_alloc(n * 4); return (float*)((uintptr_t)cur.arena + off); };
+        cur.fx_temb = f32buf((size_t)B * 256); cur.fx_gemb = f32buf((size_t)B * 256); cur.fx_h1 = f32buf((size_t)B * C);
+        cur.fx_vec = f32buf((size_t)B * C); cur.fx_svec = f32buf((size_t)B * C); cur.fx_mod = f32buf((size_t)B * fx_mod_total);
+        cur.fx_tok = f32buf((size_t)B * Li * inC);
         // first-block-cache state lives at the head of the arena and is never released: it survives from call to call
-        fb_first = f32buf((size_t)B * Li * C); fb_res = f32buf((size_t)B * L * C); fb_part = f32buf(2 * 1024 + 8);
-        { const size_t o0 = a_alloc((size_t)B * L * C * 2), o1 = a_alloc((size_t)B * L * C * 2); fb_s0 = (void*)((uintptr_t)arena + o0); fb_s1 = (void*)((uintptr_t)arena + o1); }
+        cur.fb_first = f32buf((size_t)B * Li * C); cur.fb_res = f32buf((size_t)B * L * C); cur.fb_part = f32buf(2 * 1024 + 8);
+        { const size_t o0 = a_alloc((size_t)B * L * C * 2), o1 = a_alloc((size_t)B * L * C * 2); cur.fb_s0 = (void*)((uintptr_t)cur.arena + o0); cur.fb_s1 = (void*)((uintptr_t)cur.arena + o1); }
         auto skinny = [&](const char* name, OpKind kind, const float* x, int ldx_, const LinearW& lw, float* out, int out_act, int accum) {
-            Op o{}; o.kind = kind; o.name = name; o.sk = SkinnyArgs{x, ldx_, lw.w, lw.b, out, lw.N, B, lw.N, lw.K, 0, out_act, accum}; ops.push_back(o);
-            flops += 2.0 * B * (double)lw.N * lw.K;
+            Op o{}; o.kind = kind; o.name = name; o.sk = SkinnyArgs{x, ldx_, lw.w, lw.b, out, lw.N, B, lw.N, lw.K, 0, out_act, accum}; cur.ops.push_back(o);
+            cur.flops += 2.0 * B * (double)lw.N * lw.K;
         };
         // vec = time_in(temb(t)) + guidance_in(temb(g)) + vector_in(y)           (Flux.py:683-696)
-        { Op o{}; o.kind = OP_FX_TEMB; o.name = "fx.temb_t"; o.p1 = fx_temb; o.i0 = 0; ops.push_back(o); }
-        skinny("fx.time_in.0", OP_SKINNY, fx_temb, 256, fx_time0, fx_h1, 1, 0);
-        skinny("fx.time_in.1", OP_SKINNY, fx_h1, C, fx_time1, fx_vec, 0, 0);
+        { Op o{}; o.kind = OP_FX_TEMB; o.name = "fx.temb_t"; o.p1 = cur.fx_temb; o.i0 = 0; cur.ops.push_back(o); }
+        skinny("fx.time_in.0", OP_SKINNY, cur.fx_temb, 256, fx_time0, cur.fx_h1, 1, 0);
+        skinny("fx.time_in.1", OP_SKINNY, cur.fx_h1, C, fx_time1, cur.fx_vec, 0, 0);
         if (f.guidance_embed) {
-            { Op o{}; o.kind = OP_FX_TEMB; o.name = "fx.temb_g"; o.p1 = fx_gemb; o.i0 = 1; ops.push_back(o); }
-            skinny("fx.guidance_in.0", OP_SKINNY, fx_gemb, 256, fx_gd0, fx_h1, 1, 0);
-            skinny("fx.guidance_in.1", OP_SKINNY, fx_h1, C, fx_gd1, fx_vec, 0, 1);
+            { Op o{}; o.kind = OP_FX_TEMB; o.name = "fx.temb_g"; o.p1 = cur.fx_gemb; o.i0 = 1; cur.ops.push_back(o); }
+            skinny("fx.guidance_in.0", OP_SKINNY, cur.fx_gemb, 256, fx_gd0, cur.fx_h1, 1, 0);
+            skinny("fx.guidance_in.1", OP_SKINNY, cur.fx_h1, C, fx_gd1, cur.fx_vec, 0, 1);
         }
-        skinny("fx.vector_in.0", OP_FX_SKINNY_Y, nullptr, f.vec_in_dim, fx_vec0, fx_h1, 1, 0);      // x bound per call (y)
-        skinny("fx.vector_in.1", OP_SKINNY, fx_h1, C, fx_vec1, fx_vec, 0, 1);
-        { Op o{}; o.kind = OP_FX_SILU; o.name = "fx.silu_vec"; o.p0 = fx_vec; o.p1 = fx_svec; o.i0 = B * C; ops.push_back(o); }
-        skinny("fx.modulation_all", OP_SKINNY, fx_svec, C, fx_mod_all, fx_mod, 0, 0);
-        if (fx_fp8 && fx_mod_all.w8) { SkinnyArgs& k = ops.back().sk; k.W8 = fx_mod_all.w8; k.SW = fx_mod_all.sw; k.sw_ld = fx_mod_all.N; }
+        skinny("fx.vector_in.0", OP_FX_SKINNY_Y, nullptr, f.vec_in_dim, fx_vec0, cur.fx_h1, 1, 0);      // x bound per call (y)
+        skinny("fx.vector_in.1", OP_SKINNY, cur.fx_h1, C, fx_vec1, cur.fx_vec, 0, 1);
+        { Op o{}; o.kind = OP_FX_SILU; o.name = "fx.silu_vec"; o.p0 = cur.fx_vec; o.p1 = cur.fx_svec; o.i0 = B * C; cur.ops.push_back(o); }
+        skinny("fx.modulation_all", OP_SKINNY, cur.fx_svec, C, fx_mod_all, cur.fx_mod, 0, 0);
+        if (fx_fp8 && fx_mod_all.w8) { SkinnyArgs& k = cur.ops.back().sk; k.W8 = fx_mod_all.w8; k.SW = fx_mod_all.sw; k.sw_ld = fx_mod_all.N; }
 
         // joint token buffer and inputs
         Act X = new_act(B * L, C);
         Act ptok = new_act(B * Li, inC);
-        { Op o{}; o.kind = OP_FX_PATCH; o.name = "fx.patchify"; o.p1 = ptr(ptok); o.i0 = B; o.i1 = f.in_channels; o.i2 = h; o.i3 = w; ops.push_back(o); }
+        { Op o{}; o.kind = OP_FX_PATCH; o.name = "fx.patchify"; o.p1 = ptr(ptok); o.i0 = B; o.i1 = f.in_channels; o.i2 = h; o.i3 = w; cur.ops.push_back(o); }
         Act ctx16 = new_act(B * Lt, f.context_in_dim);
-        { Op o{}; o.kind = OP_FX_CVT_CTX; o.name = "fx.ctx.cvt"; o.cvt_out = ptr(ctx16); o.cvt_n = (size_t)B * Lt * f.context_in_dim; ops.push_back(o); }
+        { Op o{}; o.kind = OP_FX_CVT_CTX; o.name = "fx.ctx.cvt"; o.cvt_out = ptr(ctx16); o.cvt_n = (size_t)B * Lt * f.context_in_dim; cur.ops.push_back(o); }
         auto rows = [&](const Act& t, int r0, int nr) { Act v = t; v.owned = false; v.off = t.off + (size_t)r0 * t.ld * 2; v.rows = nr; return v; };
         auto img_rows = [&](const Act& t, int b) { return rows(t, b * L + Lt, Li); };
         auto txt_rows = [&](const Act& t, int b) { return rows(t, b * L, Lt); };
@@ -202,7 +195,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
         const bool fuse_gemm_q = fuse_mask & 1;
         const int RT = B * L;                                   // rows of every joint buffer = scale-array row stride
         auto new_q8 = [&](int K) { Q8 q; q.K = K; const size_t o8 = a_alloc((size_t)RT * K), os = a_alloc((size_t)(K / 128) * RT * 4);
-                                   q.y = (char*)arena + o8; q.s = (uint32_t*)((char*)arena + os); return q; };
+                                   q.y = (char*)cur.arena + o8; q.s = (uint32_t*)((char*)cur.arena + os); return q; };
         auto row_of = [&](const Act& base, const Act& v) { return (int)((v.off - base.off) / ((size_t)base.ld * 2)); };
         // qo != null: the output goes to the MX shadow of the buffer Y lives in (returns true), not to Y
         auto ln_mod = [&](const char* name, Act Xin, Act Y, const float* shift, const float* scale, int rpb, const Q8* qo = nullptr, const Act* obase = nullptr) {
@@ -213,7 +206,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
             o.bytes = 2.0 * 2.0 * (double)Xin.rows * C; snprintf(o.klabel, sizeof(o.klabel), "ln_kernel");
             const bool fused = fx_fp8 && qo && (fuse_mask & 4);
             if (fused) { const int ro = row_of(*obase, Y); l.Y8 = qo->y + (size_t)ro * qo->K; l.ldy8 = qo->K; l.S8 = qo->s + ro; l.s8_ld = RT; }
-            ops.push_back(o);
+            cur.ops.push_back(o);
             return fused;
         };
         // MX fp8 attention (ldx_flux_set_fp8 mode 1, head dim 128; attn_mx.hip): the QKNorm + RoPE op writes q / k as MX fp8 (+ one scale dword per (row, head)) instead
@@ -223,7 +216,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
         const int Lp = (L + 127) / 128 * 128;
         char *a8_q = nullptr, *a8_k = nullptr, *a8_vt = nullptr; uint32_t *a8_sq = nullptr, *a8_sk = nullptr, *a8_sv = nullptr;
         if (attn8) {
-            auto al = [&](size_t bytes) { return (char*)arena + a_alloc(bytes); };
+            auto al = [&](size_t bytes) { return (char*)cur.arena + a_alloc(bytes); };
             a8_q = al((size_t)RT * C); a8_k = al((size_t)RT * C); a8_vt = al((size_t)B * H * 128 * Lp);
             a8_sq = (uint32_t*)al((size_t)H * RT * 4); a8_sk = (uint32_t*)al((size_t)H * RT * 4); a8_sv = (uint32_t*)al((size_t)B * H * (Lp / 128) * 128 * 4);
         }
@@ -235,20 +228,20 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
                 snprintf(o.klabel, sizeof(o.klabel), "qk_norm_rope_mx");
             }
             o.i0 = tok0;                                 // first token index of this slice in the pe tables
-            ops.push_back(o);
+            cur.ops.push_back(o);
         };
         auto vt_quant = [&](const char* name, Act QKVb, int b) {          // QKVb: the L rows of batch b
             Op o{}; o.kind = OP_MXVT; o.name = name;
             o.vt = MxVtArgs{(const char*)ptr(QKVb) + (size_t)2 * C * 2, QKVb.ld, 1, H, L, a8_vt + (size_t)b * H * 128 * Lp, a8_sv + (size_t)b * H * (Lp / 128) * 128, Lp};
             o.bytes = 3.0 * (double)L * C; snprintf(o.klabel, sizeof(o.klabel), "mx_vt_quant_kernel");
-            ops.push_back(o);
+            cur.ops.push_back(o);
         };
         auto quant = [&](const char* name, const Act& base, const Act& v, const Q8& q, int ncols = 0) {      // v: a row slice of base; its first ncols columns (0 = all)
             Op o{}; o.kind = OP_MXQ; o.name = name;
             const int r0 = row_of(base, v), K = ncols ? ncols : q.K;
             o.mq = MxQuantArgs{ptr(v), v.ld, v.rows, K, q.y + (size_t)r0 * q.K, q.K, q.s + r0, RT};
             o.bytes = 3.0 * (double)v.rows * K; snprintf(o.klabel, sizeof(o.klabel), "mx_quant_kernel");
-            ops.push_back(o);
+            cur.ops.push_back(o);
         };
         // linear on the rows of `v` (a row slice of `base`): 16-bit path, or MX path reading base's shadow q
         // qo != null (MX mode, no gate / residual): the output goes straight to the shadow qo of the buffer Cc lives in, at
@@ -256,7 +249,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
         auto lin = [&](const char* name, const Act& base, const Act& v, const Q8& q, const LinearW& lw, Act Cc, Act R, const float* gate, int rpb, int act,
                        const Q8* qo = nullptr, const Act* obase = nullptr) {
             op_gemm(name, v, lw, Cc, R);
-            GemmArgs& g = ops.back().g;
+            GemmArgs& g = cur.ops.back().g;
             g.gate = gate; g.gate_ld = fx_mod_total; g.rows_per_batch = rpb; g.act = act;
             if (gate && g.splitk > 1) g.splitk = 1;      // gate/act are not replicated in the split-K reduce path for safety
             if (fx_fp8 && lw.w8) {
@@ -264,9 +257,9 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
                 g.f8 = 1; g.A = q.y + (size_t)r0 * q.K; g.lda = q.K; g.SA = q.s + r0; g.sa_ld = RT; g.W = lw.w8; g.SW = lw.sw; g.sw_ld = lw.N;
                 if (!gate) {
                     g.splitk = gemm_choose_splitk(g.M, g.N, g.K / 2, false);
-                    if (g.splitk > 1) { g.ws = (float*)((uintptr_t)arena + ws_alloc(gemm_sk_ws_floats(g.M, g.N, g.splitk) * 4)); g.sk_count = sk_counters(); }
+                    if (g.splitk > 1) { g.ws = (float*)((uintptr_t)cur.arena + ws_alloc(gemm_sk_ws_floats(g.M, g.N, g.splitk) * 4)); g.sk_count = sk_counters(); }
                 }
-                snprintf(ops.back().klabel, sizeof(ops.back().klabel), "gemm_kernel<mxfp8,0>");
+                snprintf(cur.ops.back().klabel, sizeof(cur.ops.back().klabel), "gemm_kernel<mxfp8,0>");
                 if (qo && fuse_gemm_q) {
                     const int ro = (int)((Cc.off - obase->off) / ((size_t)obase->ld * 2));
                     g.C = nullptr; g.C8 = qo->y + (size_t)ro * qo->K; g.ldc8 = qo->K; g.c8_col = Cc.col - obase->col; g.SC = qo->s + ro; g.sc_ld = RT; g.splitk = 1;
@@ -276,11 +269,11 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
         // merge the two independent plain GEMM ops just emitted into one two-problem launch
         static const bool group2 = !(getenv("LDX_FLUX_GROUP") && atoi(getenv("LDX_FLUX_GROUP")) == 0);      // experiment switch
         auto pair_last_two = [&](const char* name) {
-            if (!group2 || ops.size() < 2) return;
-            Op& A = ops[ops.size() - 2]; const Op& Bo = ops.back();
+            if (!group2 || cur.ops.size() < 2) return;
+            Op& A = cur.ops[cur.ops.size() - 2]; const Op& Bo = cur.ops.back();
             if (A.kind != OP_GEMM || Bo.kind != OP_GEMM || A.g.mode || Bo.g.mode || A.g.geglu || Bo.g.geglu || A.g.f8 != Bo.g.f8) return;
             A.kind = OP_GEMM2; A.name = name; A.g2 = Bo.g; A.g.splitk = A.g2.splitk = 1; A.flops += Bo.flops; A.bytes += Bo.bytes;
-            ops.pop_back();
+            cur.ops.pop_back();
         };
         // returns true if the attention kernel wrote the MX shadow qo of obase itself (head dim 128, large grid)
         auto attn = [&](const char* name, Act QKV, Act O, const Q8* qo = nullptr, const Act* obase = nullptr, int b = 0) {
@@ -296,12 +289,12 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
                 else { a.O = ptr(O); a.ldo = O.ld; }
                 o.flops = 4.0 * H * (double)L * L * D; o.bytes = (double)H * D * (2.0 * L + 2.0 * L);
                 snprintf(o.klabel, sizeof(o.klabel), "attn_mx_kernel");
-                ops.push_back(o); flops += o.flops;
+                cur.ops.push_back(o); cur.flops += o.flops;
                 return fuse_out;
             }
             const char* base = (const char*)ptr(QKV);
             op_attn(name, base, QKV.ld, base + (size_t)C * 2, QKV.ld, base + (size_t)2 * C * 2, QKV.ld, O, 1, H, QKV.rows, QKV.rows, D);
-            AttnArgs& a = ops.back().at;
+            AttnArgs& a = cur.ops.back().at;
             if (!fx_fp8 || !qo || !(fuse_mask & 2) || !attention_mx_out_ok(a)) return false;
             const int ro = row_of(*obase, O);
             a.O8 = qo->y + (size_t)ro * qo->K; a.ldo8 = qo->K; a.SO = qo->s + ro; a.so_ld = RT;
@@ -312,10 +305,10 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
         Act QKV = new_act(B * L, 3 * C), AO = new_act(B * L, C), N1 = new_act(B * L, C), MLP = new_act(B * L, MH);
         Q8 qN1, qAO, qMLP, qCAT;
         if (fx_fp8) { qN1 = new_q8(C); qAO = new_q8(C); qMLP = new_q8(MH); qCAT = new_q8(C + MH); }
-        fb_x = ptr(X); fb_B = B; fb_L = L; fb_Lt = Lt; fb_C = C;
+        cur.fb_x = ptr(X); cur.fb_B = B; cur.fb_L = L; cur.fb_Lt = Lt; cur.fb_C = C;
         int blk_i = 0;
         for (const FluxDoubleW& blk : fx_double) {
-            if (blk_i == 1) fb_a_end = ops.size();
+            if (blk_i == 1) cur.fb_a_end = cur.ops.size();
             ++blk_i;
             for (int b = 0; b < B; ++b) {
                 struct S { const FluxStreamW* w; Act x, n, qkv, ao, mlp; int rows; int tok0; };
@@ -323,7 +316,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
                            {&blk.txt, txt_rows(X, b), txt_rows(N1, b), txt_rows(QKV, b), txt_rows(AO, b), txt_rows(MLP, b), Lt, 0}};
                 // the image and the text stream run the same layer shapes on different weights: each pair of linears is one launch
                 for (S& s : st) {
-                    const float* m = fx_mod + (size_t)b * fx_mod_total;
+                    const float* m = cur.fx_mod + (size_t)b * fx_mod_total;
                     const bool lq = ln_mod("fx.d.norm1", s.x, s.n, m + s.w->mod_off + 0 * C, m + s.w->mod_off + 1 * C, s.rows, &qN1, &N1);
                     if (fx_fp8 && !lq) quant("fx.d.q.norm1", N1, s.n, qN1);
                 }
@@ -334,12 +327,12 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
                 const bool aq = attn("fx.d.attn", rows(QKV, b * L, L), rows(AO, b * L, L), &qAO, &AO, b);          // joint [txt ; img] sequence
                 if (fx_fp8 && !aq) quant("fx.d.q.attn", AO, rows(AO, b * L, L), qAO);
                 for (S& s : st) {
-                    const float* m = fx_mod + (size_t)b * fx_mod_total + s.w->mod_off;
+                    const float* m = cur.fx_mod + (size_t)b * fx_mod_total + s.w->mod_off;
                     lin("fx.d.proj", AO, s.ao, qAO, s.w->proj, s.x, s.x, m + 2 * C, s.rows, 0);        // x += gate1 * proj(attn)
                 }
                 pair_last_two("fx.d.proj x2");
                 for (S& s : st) {
-                    const float* m = fx_mod + (size_t)b * fx_mod_total + s.w->mod_off;
+                    const float* m = cur.fx_mod + (size_t)b * fx_mod_total + s.w->mod_off;
                     const bool lq = ln_mod("fx.d.norm2", s.x, s.n, m + 3 * C, m + 4 * C, s.rows, &qN1, &N1);
                     if (fx_fp8 && !lq) quant("fx.d.q.norm2", N1, s.n, qN1);
                 }
@@ -347,19 +340,19 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
                 pair_last_two("fx.d.mlp0 x2");
                 if (fx_fp8 && !fuse_gemm_q) for (S& s : st) quant("fx.d.q.mlp", MLP, s.mlp, qMLP);
                 for (S& s : st) {
-                    const float* m = fx_mod + (size_t)b * fx_mod_total + s.w->mod_off;
+                    const float* m = cur.fx_mod + (size_t)b * fx_mod_total + s.w->mod_off;
                     lin("fx.d.mlp2", MLP, s.mlp, qMLP, s.w->mlp2, s.x, s.x, m + 5 * C, s.rows, 0);     // x += gate2 * mlp(...)
                 }
                 pair_last_two("fx.d.mlp2 x2");
             }
         }
-        if (blk_i == 1) fb_a_end = ops.size();
+        if (blk_i == 1) cur.fb_a_end = cur.ops.size();
         release(MLP);
         // ---- single-stream blocks on the joint sequence ----
         Act CAT = new_act(B * L, C + MH);                      // [attn | gelu(mlp)] : linear2's input (torch.cat, Flux.py:413)
         for (const FluxSingleW& blk : fx_single) {
             for (int b = 0; b < B; ++b) {
-                const float* m = fx_mod + (size_t)b * fx_mod_total + blk.mod_off;
+                const float* m = cur.fx_mod + (size_t)b * fx_mod_total + blk.mod_off;
                 Act xb = rows(X, b * L, L), nb = rows(N1, b * L, L), qb = rows(QKV, b * L, L), cb = rows(CAT, b * L, L);
                 const bool lq = ln_mod("fx.s.pre_norm", xb, nb, m + 0 * C, m + 1 * C, L, &qN1, &N1);
                 if (fx_fp8 && !lq) quant("fx.s.q.norm", N1, nb, qN1);
@@ -374,21 +367,18 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
             }
         }
         release(CAT); release(QKV); release(AO);
-        fb_b_end = ops.size();
+        cur.fb_b_end = cur.ops.size();
         // ---- LastLayer on the img rows ----
         for (int b = 0; b < B; ++b) {
-            const float* m = fx_mod + (size_t)b * fx_mod_total + fx_final_mod_off;
+            const float* m = cur.fx_mod + (size_t)b * fx_mod_total + fx_final_mod_off;
             ln_mod("fx.final.norm", img_rows(X, b), img_rows(N1, b), m + 0 * C, m + 1 * C, Li);       // chunk order: shift, scale
             op_gemm("fx.final.linear", img_rows(N1, b), fx_final, Act{}, Act{});
-            GemmArgs& g = ops.back().g; g.C = nullptr; g.Cf = fx_tok + (size_t)b * Li * inC; g.ldcf = inC;
+            GemmArgs& g = cur.ops.back().g; g.C = nullptr; g.Cf = cur.fx_tok + (size_t)b * Li * inC; g.ldcf = inC;
         }
         release(N1); release(X);
-        { Op o{}; o.kind = OP_FX_UNPATCH; o.name = "fx.unpatchify"; o.i0 = B; o.i1 = f.in_channels; o.i2 = h; o.i3 = w; ops.push_back(o); }
-        if (pass == 0) { arena_peak_dry = arena_peak; arena = saved; }
-    }
-    pB2 = B; ph = h; pw = w; pM = Lt;
-    fb_reset();                                        // new shape: the cached residuals no longer apply (fbcache_nodes.py:56-66)
-    return LDX_OK;
+        { Op o{}; o.kind = OP_FX_UNPATCH; o.name = "fx.unpatchify"; o.i0 = B; o.i1 = f.in_channels; o.i2 = h; o.i3 = w; cur.ops.push_back(o); }
+        return LDX_OK;
+    });
 }
 
 int Engine::run_flux(const float* x, const float* sigma, const float* ctx, const float* y, const float* guidance,
@@ -397,15 +387,13 @@ int Engine::run_flux(const float* x, const float* sigma, const float* ctx, const
     if (!x || !sigma || !ctx || !y || !pe_cos || !pe_sin || !out || B <= 0 || h <= 0 || w <= 0 || Lt <= 0 || (h & 1) || (w & 1) ||
         (fcfg.guidance_embed && !guidance)) { set_error("ldx_flux_forward: bad argument (h, w must be even)"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
-    if (B != pB2 || h != ph || w != pw || Lt != pM) {
-        HIP_OK(hipStreamSynchronize(st));
-        // plans (op list + arena) are kept per shape like the UNet's: the multi-scale samplers alternate two resolutions and prompts
-        // of different lengths change Lt; the first-block cache still resets on every shape change (fbcache_nodes.py:56-66)
-        if (pB2 > 0) plan_stash();
-        if (plan_restore(B, h, w, Lt)) fb_reset();
-        else { int rc = plan_flux(B, h, w, Lt); if (rc) return rc; }
-    }
-    b_x = x; b_s = sigma; b_ctx = ctx; b_y = y; b_guid = guidance; b_cos = pe_cos; b_sin = pe_sin; b_out = out; b_den = denoise;
+    // plans (op list + arena) are kept per shape like the UNet's; the first-block cache still resets on every shape change: the cached
+    // residuals no longer apply (fbcache_nodes.py:56-66)
+    bool switched = false;
+    if (int rc = select_plan(PlanKey{B, h, w, Lt}, st, [&] { return plan_flux(B, h, w, Lt); }, &switched)) return rc;
+    if (switched) fb_reset();
+    bind = Bindings{};
+    bind.x = x; bind.s = sigma; bind.ctx = ctx; bind.y = y; bind.guid = guidance; bind.pe_cos = pe_cos; bind.pe_sin = pe_sin; bind.out = out; bind.den = denoise;
     prof_graph = false;
     int rc = LDX_OK;
     if (fb_threshold <= 0.f) {
@@ -418,42 +406,41 @@ int Engine::run_flux(const float* x, const float* sigma, const float* ctx, const
         HIP_OK(hipMemcpyAsync(&t0, sigma, sizeof(float), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         if (!fb_prev_valid || t0 >= fb_prev_t) fb_reset();
-        const size_t nj = (size_t)fb_B * fb_L * fb_C;
+        const size_t nj = (size_t)cur.fb_B * cur.fb_L * cur.fb_C;
         // double block 0 with a snapshot of the joint stream in front of it (image rows: original_hidden_states)
-        size_t b0_begin = fb_a_end;
-        for (size_t i = 0; i < fb_a_end; ++i) if (std::string(ops[i].name) == "fx.d.norm1") { b0_begin = i; break; }
+        size_t b0_begin = cur.fb_a_end;
+        for (size_t i = 0; i < cur.fb_a_end; ++i) if (std::string(cur.ops[i].name) == "fx.d.norm1") { b0_begin = i; break; }
         rc = exec_ops(st, 0, b0_begin);
         if (rc) return rc;
-        HIP_OK(hipMemcpyAsync(fb_s0, fb_x, nj * 2, hipMemcpyDeviceToDevice, st));
-        rc = exec_ops(st, b0_begin, fb_a_end);
+        HIP_OK(hipMemcpyAsync(cur.fb_s0, cur.fb_x, nj * 2, hipMemcpyDeviceToDevice, st));
+        rc = exec_ops(st, b0_begin, cur.fb_a_end);
         if (rc) return rc;
         bool use = false;
         if (fb_have_first && fb_have_res) {          // get_can_use_cache -> are_two_tensors_similar (:105-148)
-            launch_fb_diff(fb_x, fb_s0, fb_first, fb_B, fb_L, fb_Lt, fb_C, fb_part, fb_part + 2048, dt, st);
+            launch_fb_diff(cur.fb_x, cur.fb_s0, cur.fb_first, cur.fb_B, cur.fb_L, cur.fb_Lt, cur.fb_C, cur.fb_part, cur.fb_part + 2048, dt, st);
             float sums[2] = {0.f, 0.f};
-            HIP_OK(hipMemcpyAsync(sums, fb_part + 2048, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(sums, cur.fb_part + 2048, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
             use = (sums[0] / sums[1]) < fb_threshold;      // mean|prev - cur| / mean|prev| (same element count)
         }
         if (use) {
-            launch_fb_apply(fb_x, fb_res, nj, dt, st);                                   // hidden (+ encoder) states += cached residual
+            launch_fb_apply(cur.fb_x, cur.fb_res, nj, dt, st);                                   // hidden (+ encoder) states += cached residual
             ++fb_hits;
         } else {
-            launch_fb_first(fb_x, fb_s0, fb_first, fb_B, fb_L, fb_Lt, fb_C, dt, st);    // set_buffer("first_hidden_states_residual")
-            HIP_OK(hipMemcpyAsync(fb_s1, fb_x, nj * 2, hipMemcpyDeviceToDevice, st));
-            rc = exec_ops(st, fb_a_end, fb_b_end);
+            launch_fb_first(cur.fb_x, cur.fb_s0, cur.fb_first, cur.fb_B, cur.fb_L, cur.fb_Lt, cur.fb_C, dt, st);    // set_buffer("first_hidden_states_residual")
+            HIP_OK(hipMemcpyAsync(cur.fb_s1, cur.fb_x, nj * 2, hipMemcpyDeviceToDevice, st));
+            rc = exec_ops(st, cur.fb_a_end, cur.fb_b_end);
             if (rc) return rc;
-            launch_fb_residual(fb_x, fb_s1, fb_res, nj, dt, st);                         // final - after block 0, both streams
+            launch_fb_residual(cur.fb_x, cur.fb_s1, cur.fb_res, nj, dt, st);                         // final - after block 0, both streams
             fb_have_first = fb_have_res = true;
             ++fb_misses;
         }
-        rc = exec_ops(st, fb_b_end, ops.size());
+        rc = exec_ops(st, cur.fb_b_end, cur.ops.size());
         fb_prev_t = t0; fb_prev_valid = true;                                            // update_cache_state
     }
-    if (rc) { fb_reset(); return rc; }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fb_reset(); set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return LDX_EHIP; }
-    return LDX_OK;
+    if (!rc) rc = launch_status();
+    if (rc) fb_reset();
+    return rc;
 }
 
 }  // namespace ldx

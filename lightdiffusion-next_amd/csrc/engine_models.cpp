@@ -203,7 +203,7 @@ void Engine::emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int 
           GemmArgs& g = oo.g; g.A = a.v.w; g.lda = C; g.W = hw.w; g.M = C; g.N = N; g.K = C; g.mode = 0; g.rows_per_batch = 1;
           g.C = ptr(vt); g.ldc = N; g.splitk = 1;
           oo.flops = 2.0 * C * (double)N * C; snprintf(oo.klabel, sizeof(oo.klabel), "gemm_kernel<%s,0>", dt == DT_BF16 ? "bf16" : "f16");
-          ops.push_back(oo); flops += oo.flops; (void)wv; }
+          cur.ops.push_back(oo); cur.flops += oo.flops; (void)wv; }
         // Query rows in chunks of Rc: S_c[Rc][N] = q_c k_b^T, row softmax, O_c = P_c V.  The score matrix is never materialised as a whole
         // (N x N at 2048^2 is 8 GiB and was the arena's peak; at 4096^2 it would be 128 GiB): one chunk is <= 2 GiB, so a 1024^2 decode still runs
         // the three launches it always ran and a 2048^2 decode 4 x 3 (measured at 2048^2: one chunk 69.3 ms, 512 MiB chunks 71.9, 128 MiB 72.1; the
@@ -223,7 +223,7 @@ void Engine::emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int 
             { LinearW kw; kw.w = ptr(rows(k, b * N, N)); kw.b = nullptr; kw.N = N; kw.K = C;
               op_gemm("vae.attn.qk", rows(q, b * N + r0, nr), kw, Sc, Act{}); }
             { Op oo{}; oo.kind = OP_SOFTMAX; oo.name = "vae.attn.softmax"; oo.p1 = ptr(Sc); oo.i0 = nr; oo.i1 = N; oo.i2 = N; oo.f0 = 1.0f / std::sqrt((float)C);
-              oo.bytes = 2.0 * 2.0 * nr * (double)N; snprintf(oo.klabel, sizeof(oo.klabel), "softmax_rows"); ops.push_back(oo); }
+              oo.bytes = 2.0 * 2.0 * nr * (double)N; snprintf(oo.klabel, sizeof(oo.klabel), "softmax_rows"); cur.ops.push_back(oo); }
             // O_c[nr][C] = P_c[nr][N] . V[N][C]  with W = V^T[C][N]
             { LinearW vw; vw.w = ptr(vt); vw.b = nullptr; vw.N = C; vw.K = N;
               op_gemm("vae.attn.pv", Sc, vw, rows(o, b * N + r0, nr), Act{}); }
@@ -237,22 +237,15 @@ void Engine::emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int 
 
 int Engine::plan_vae(int B, int h, int w) {
     const ldx_vae_config& v = vcfg;
-    for (int pass = 0; pass < 2; ++pass) {
-        ops.clear(); flops = 0; free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0;
-        if (pass == 1) {
-            if (arena && arena_cap < arena_peak_dry) { HIP_OK(hipFree(arena)); arena = nullptr; }
-            if (!arena) { HIP_OK(hipMalloc(&arena, arena_peak_dry)); arena_cap = arena_peak_dry; }
-        }
-        void* saved = arena;
-        if (pass == 0) arena = nullptr;
-        gn_ws_off = a_alloc(gn_ws_bytes(B, (long)h * w * 64));
+    return build_plan(PlanKey{B, h, w, 1}, [&]() -> int {
+        cur.gn_ws_off = a_alloc(gn_ws_bytes(B, (long)h * w * 64));
         int H = h, W = w;
         Act x0 = new_act(B * H * W, 64);
-        { Op o{}; o.kind = OP_VAEPREP; o.name = "vae.prep"; o.p1 = ptr(x0); o.i0 = B; o.i1 = v.z_channels; o.i2 = H * W; o.i3 = 64; ops.push_back(o); }
+        { Op o{}; o.kind = OP_VAEPREP; o.name = "vae.prep"; o.p1 = ptr(x0); o.i0 = B; o.i1 = v.z_channels; o.i2 = H * W; o.i3 = 64; cur.ops.push_back(o); }
         int C = v.ch * v.ch_mult[v.num_levels - 1];
         Act hcur = new_act(B * H * W, C);
         op_conv("vae.conv_in", x0, B, H, W, 64, conv_in, 1, H, W, hcur, Act{});
-        flops -= 2.0 * B * H * W * (double)C * 9.0 * (64 - v.z_channels);
+        cur.flops -= 2.0 * B * H * W * (double)C * 9.0 * (64 - v.z_channels);
         release(x0);
         auto res = [&](const ResW& r) { Act o = new_act(B * H * W, r.Cout); emit_res(r, hcur, o, B, H, W); release(hcur); hcur = o; };
         res(vae_mid1);
@@ -272,15 +265,13 @@ int Engine::plan_vae(int B, int h, int w) {
         op_gn("vae.norm_out", hcur, t, B, H * W, vae_norm_out, 1e-6f, true);
         release(hcur);
         const size_t o_pix = a_alloc((size_t)B * H * W * v.out_ch * 4);
-        float* pix = (float*)((uintptr_t)arena + o_pix);
+        float* pix = (float*)((uintptr_t)cur.arena + o_pix);
         op_conv("vae.conv_out", t, B, H, W, Cl, conv_out, 1, H, W, Act{}, Act{}, nullptr, 0, pix, v.out_ch);
         release(t);
-        { Op o{}; o.kind = OP_CLAMP; o.name = "vae.clamp"; o.p0 = pix; o.i0 = B * H * W * v.out_ch; ops.push_back(o); }
+        { Op o{}; o.kind = OP_CLAMP; o.name = "vae.clamp"; o.p0 = pix; o.i0 = B * H * W * v.out_ch; cur.ops.push_back(o); }
         fuse_gn_stats();
-        if (pass == 0) { arena_peak_dry = arena_peak; arena = saved; }
-    }
-    pB2 = B; ph = h; pw = w; pM = 0; vae_plan_mode = 1;
-    return LDX_OK;
+        return LDX_OK;
+    });
 }
 
 int Engine::run_vae(const float* z, int B, int h, int w, float* out, hipStream_t st) {
@@ -288,37 +279,23 @@ int Engine::run_vae(const float* z, int B, int h, int w, float* out, hipStream_t
     if (!z || !out || B <= 0 || h <= 0 || w <= 0) { set_error("ldx_vae_decode: bad argument"); return LDX_EINVAL; }
     if ((h * w) % 8) { set_error("ldx_vae_decode: h*w must be a multiple of 8 (attention row length)"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
-    if (B != pB2 || h != ph || w != pw || vae_plan_mode != 1) {
-        HIP_OK(hipStreamSynchronize(st));
-        int rc = plan_vae(B, h, w);
-        if (rc) return rc;
-    }
-    b_x = z; b_out = out; prof_graph = false;
-    int rc = exec_ops(st);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return LDX_EHIP; }
-    return LDX_OK;
+    if (int rc = select_plan(PlanKey{B, h, w, 1}, st, [&] { return plan_vae(B, h, w); })) return rc;
+    bind = Bindings{}; bind.x = z; bind.out = out; prof_graph = false;
+    if (int rc = exec_ops(st)) return rc;
+    return launch_status();
 }
 
 // Encoder.forward (VariationalAE.py:378-413) + quant_conv: pixels -> moments
 int Engine::plan_vae_encode(int B, int Hpx, int Wpx) {
     const ldx_vae_config& v = vcfg;
-    for (int pass = 0; pass < 2; ++pass) {
-        ops.clear(); flops = 0; free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0;
-        if (pass == 1) {
-            if (arena && arena_cap < arena_peak_dry) { HIP_OK(hipFree(arena)); arena = nullptr; }
-            if (!arena) { HIP_OK(hipMalloc(&arena, arena_peak_dry)); arena_cap = arena_peak_dry; }
-        }
-        void* saved = arena;
-        if (pass == 0) arena = nullptr;
-        gn_ws_off = a_alloc(gn_ws_bytes(B, (long)Hpx * Wpx));
+    return build_plan(PlanKey{B, Hpx, Wpx, 2}, [&]() -> int {
+        cur.gn_ws_off = a_alloc(gn_ws_bytes(B, (long)Hpx * Wpx));
         int H = Hpx, W = Wpx;
         Act x0 = new_act(B * H * W, 64);
-        { Op o{}; o.kind = OP_PIXPREP; o.name = "vae.enc.prep"; o.p1 = ptr(x0); o.i0 = B; o.i1 = 3; o.i2 = H * W; o.i3 = 64; o.f0 = 2.0f; o.f1 = -1.0f; ops.push_back(o); }
+        { Op o{}; o.kind = OP_PIXPREP; o.name = "vae.enc.prep"; o.p1 = ptr(x0); o.i0 = B; o.i1 = 3; o.i2 = H * W; o.i3 = 64; o.f0 = 2.0f; o.f1 = -1.0f; cur.ops.push_back(o); }
         Act hcur = new_act(B * H * W, v.ch);
         op_conv("vae.enc.conv_in", x0, B, H, W, 64, enc_conv_in, 1, H, W, hcur, Act{});
-        flops -= 2.0 * B * H * W * (double)v.ch * 9.0 * (64 - 3);
+        cur.flops -= 2.0 * B * H * W * (double)v.ch * 9.0 * (64 - 3);
         release(x0);
         auto res = [&](const ResW& r) { Act o = new_act(B * H * W, r.Cout); emit_res(r, hcur, o, B, H, W); release(hcur); hcur = o; };
         for (int lv = 0; lv < v.num_levels; ++lv) {
@@ -328,7 +305,7 @@ int Engine::plan_vae_encode(int B, int Hpx, int Wpx) {
                 const int Cc = enc_down[lv].back().Cout, Ho = H / 2, Wo = W / 2;
                 Act o = new_act(B * Ho * Wo, Cc);
                 op_conv("vae.enc.down", hcur, B, H, W, Cc, enc_downconv[lv], 2, Ho, Wo, o, Act{});
-                ops.back().g.pad0 = 1;
+                cur.ops.back().g.pad0 = 1;
                 release(hcur); hcur = o; H = Ho; W = Wo;
             }
         }
@@ -340,15 +317,13 @@ int Engine::plan_vae_encode(int B, int Hpx, int Wpx) {
         op_gn("vae.enc.norm_out", hcur, t, B, H * W, enc_norm_out, 1e-6f, true);
         release(hcur);
         const size_t o_m = a_alloc((size_t)B * H * W * zc2 * 4);
-        float* mom = (float*)((uintptr_t)arena + o_m);
+        float* mom = (float*)((uintptr_t)cur.arena + o_m);
         op_conv("vae.enc.conv_out", t, B, H, W, Cl, enc_conv_out, 1, H, W, Act{}, Act{}, nullptr, 0, mom, zc2);
         release(t);
-        { Op o{}; o.kind = OP_MOMENTS; o.name = "vae.enc.quant_conv"; o.p0 = mom; o.i0 = B; o.i1 = zc2; o.i2 = H * W; ops.push_back(o); }
+        { Op o{}; o.kind = OP_MOMENTS; o.name = "vae.enc.quant_conv"; o.p0 = mom; o.i0 = B; o.i1 = zc2; o.i2 = H * W; cur.ops.push_back(o); }
         fuse_gn_stats();
-        if (pass == 0) { arena_peak_dry = arena_peak; arena = saved; }
-    }
-    pB2 = B; ph = Hpx; pw = Wpx; pM = 0; vae_plan_mode = 2;
-    return LDX_OK;
+        return LDX_OK;
+    });
 }
 
 int Engine::run_vae_encode(const float* px, int B, int H, int W, float* moments, hipStream_t st) {
@@ -360,17 +335,10 @@ int Engine::run_vae_encode(const float* px, int B, int H, int W, float* moments,
     if (!px || !moments || B <= 0 || H < f || W < f || ((H / f) * (W / f)) % 8) {
         set_error("ldx_vae_encode: bad argument (H, W >= downscale factor; latent h*w multiple of 8)"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
-    if (B != pB2 || H != ph || W != pw || vae_plan_mode != 2) {
-        HIP_OK(hipStreamSynchronize(st));
-        int rc = plan_vae_encode(B, H, W);
-        if (rc) return rc;
-    }
-    b_x = px; b_out = moments; prof_graph = false;
-    int rc = exec_ops(st);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return LDX_EHIP; }
-    return LDX_OK;
+    if (int rc = select_plan(PlanKey{B, H, W, 2}, st, [&] { return plan_vae_encode(B, H, W); })) return rc;
+    bind = Bindings{}; bind.x = px; bind.out = moments; prof_graph = false;
+    if (int rc = exec_ops(st)) return rc;
+    return launch_status();
 }
 
 // =============================================================================================
@@ -429,16 +397,9 @@ int Engine::finalize_clip() {
 int Engine::plan_clip(int B, int T, int inter) {
     const ldx_clip_config& c = ccfg;
     const int E = c.hidden_size, M = B * T, heads = c.num_heads, D = E / heads;
-    for (int pass = 0; pass < 2; ++pass) {
-        ops.clear(); flops = 0; free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0;
-        if (pass == 1) {
-            if (arena && arena_cap < arena_peak_dry) { HIP_OK(hipFree(arena)); arena = nullptr; }
-            if (!arena) { HIP_OK(hipMalloc(&arena, arena_peak_dry)); arena_cap = arena_peak_dry; }
-        }
-        void* saved = arena;
-        if (pass == 0) arena = nullptr;
+    return build_plan(PlanKey{B, T, 0, inter}, [&]() -> int {
         Act x = new_act(M, E);
-        { Op o{}; o.kind = OP_EMBED; o.name = "clip.embed"; o.p1 = ptr(x); o.i0 = B; o.i1 = T; o.i2 = E; o.i3 = c.vocab_size; ops.push_back(o); }
+        { Op o{}; o.kind = OP_EMBED; o.name = "clip.embed"; o.p1 = ptr(x); o.i0 = B; o.i1 = T; o.i2 = E; o.i3 = c.vocab_size; cur.ops.push_back(o); }
         Act n = new_act(M, E), qkv = new_act(M, 3 * E), a = new_act(M, E), f = new_act(M, c.intermediate_size);
         Act xi = new_act(M, E);
         for (int l = 0; l < c.num_layers; ++l) {
@@ -447,23 +408,21 @@ int Engine::plan_clip(int B, int T, int inter) {
             op_gemm("clip.qkv", n, L.qkv, qkv, Act{});
             const char* base = (const char*)ptr(qkv);
             op_attn("clip.attn", base, 3 * E, base + (size_t)E * 2, 3 * E, base + (size_t)2 * E * 2, 3 * E, a, B, heads, T, T, D);
-            ops.back().at.causal = 1;
+            cur.ops.back().at.causal = 1;
             op_gemm("clip.out", a, L.out, x, x);                 // x += self_attn(ln1(x))
             op_ln("clip.ln2", x, n, L.ln2);
             op_gemm("clip.fc1", n, L.fc1, f, Act{});
-            ops.back().g.act = 1;                                // quick-GELU
+            cur.ops.back().g.act = 1;                                // quick-GELU
             op_gemm("clip.fc2", f, L.fc2, x, x);                 // x += mlp(ln2(x))
             if (l == inter) {                                    // intermediate = x.clone(); final LN applied to it
                 op_ln("clip.final_ln.inter", x, xi, clip_final_ln);
-                Op o{}; o.kind = OP_CVT_OUT; o.name = "clip.out_inter"; o.p0 = ptr(xi); o.i0 = M * E; o.i3 = 1; ops.push_back(o);
+                Op o{}; o.kind = OP_CVT_OUT; o.name = "clip.out_inter"; o.p0 = ptr(xi); o.i0 = M * E; o.i3 = 1; cur.ops.push_back(o);
             }
         }
         op_ln("clip.final_ln", x, n, clip_final_ln);
-        { Op o{}; o.kind = OP_CVT_OUT; o.name = "clip.out_last"; o.p0 = ptr(n); o.i0 = M * E; o.i3 = 0; ops.push_back(o); }
-        if (pass == 0) { arena_peak_dry = arena_peak; arena = saved; }
-    }
-    pB2 = B; ph = T; pw = 0; pM = 0; clip_inter_planned = inter;
-    return LDX_OK;
+        { Op o{}; o.kind = OP_CVT_OUT; o.name = "clip.out_last"; o.p0 = ptr(n); o.i0 = M * E; o.i3 = 0; cur.ops.push_back(o); }
+        return LDX_OK;
+    });
 }
 
 // Textual-inversion vectors for the next ldx_clip_encode calls: the reference extends the token table by one row per vector
@@ -491,9 +450,7 @@ int Engine::clip_pooled(const float* last, const int* ids, int B, int T, int eos
     if (!last || !ids || !out || B <= 0 || T <= 0) { set_error("ldx_clip_pooled: bad argument"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
     launch_clip_pooled(last, ids, B, T, ccfg.hidden_size, eos_id, clip_proj, out, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return LDX_EHIP; }
-    return LDX_OK;
+    return launch_status();
 }
 
 int Engine::run_clip(const int* ids, int B, int T, int inter_layer, float* out_last, float* out_inter, hipStream_t st) {
@@ -505,17 +462,10 @@ int Engine::run_clip(const int* ids, int B, int T, int inter_layer, float* out_l
         inter = inter_layer < 0 ? ccfg.num_layers + inter_layer : inter_layer;
         if (inter < 0 || inter >= ccfg.num_layers) { set_error("ldx_clip_encode: inter_layer out of range"); return LDX_EINVAL; }
     }
-    if (B != pB2 || T != ph || inter != clip_inter_planned) {
-        HIP_OK(hipStreamSynchronize(st));
-        int rc = plan_clip(B, T, inter);
-        if (rc) return rc;
-    }
-    b_ids = ids; b_out = out_last; b_out2 = out_inter; prof_graph = false;
-    int rc = exec_ops(st);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return LDX_EHIP; }
-    return LDX_OK;
+    if (int rc = select_plan(PlanKey{B, T, 0, inter}, st, [&] { return plan_clip(B, T, inter); })) return rc;
+    bind = Bindings{}; bind.ids = ids; bind.out = out_last; bind.out2 = out_inter; prof_graph = false;
+    if (int rc = exec_ops(st)) return rc;
+    return launch_status();
 }
 
 }  // namespace ldx

@@ -86,20 +86,13 @@ int Engine::plan_t5(int B, int L) {
     const ldx_t5_config& c = tcfg;
     const int E = c.d_model, F = c.d_ff, M = B * L, heads = c.num_heads, D = E / heads;
     const int Lp = ((L + 63) / 64) * 64;
-    for (int pass = 0; pass < 2; ++pass) {
-        ops.clear(); flops = 0; free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0;
-        if (pass == 1) {
-            if (arena && arena_cap < arena_peak_dry) { HIP_OK(hipFree(arena)); arena = nullptr; }
-            if (!arena) { HIP_OK(hipMalloc(&arena, arena_peak_dry)); arena_cap = arena_peak_dry; }
-        }
-        void* saved = arena;
-        if (pass == 0) arena = nullptr;
+    return build_plan(PlanKey{B, L}, [&]() -> int {
         Act x = new_act(M, E);
-        { Op o{}; o.kind = OP_EMBED; o.name = "t5.embed"; o.p1 = ptr(x); o.i0 = B; o.i1 = L; o.i2 = E; o.i3 = c.vocab_size; ops.push_back(o); }
+        { Op o{}; o.kind = OP_EMBED; o.name = "t5.embed"; o.p1 = ptr(x); o.i0 = B; o.i1 = L; o.i2 = E; o.i3 = c.vocab_size; cur.ops.push_back(o); }
         Act n = new_act(M, E), qkv = new_act(M, 3 * E), a = new_act(M, E), f = new_act(M, F);
         auto rms = [&](const char* name, Act X, Act Y, const NormW& w) {
             op_ln(name, X, Y, w);
-            ops.back().ln.eps = 1e-6f; ops.back().ln.rms = 1;
+            cur.ops.back().ln.eps = 1e-6f; cur.ops.back().ln.rms = 1;
         };
         for (int l = 0; l < c.num_layers; ++l) {
             const T5LayerW& W = t5_layers[l];
@@ -107,36 +100,27 @@ int Engine::plan_t5(int B, int L) {
             op_gemm("t5.qkv", n, W.qkv, qkv, Act{});
             const char* base = (const char*)ptr(qkv);
             op_attn("t5.attn", base, 3 * E, base + (size_t)E * 2, 3 * E, base + (size_t)2 * E * 2, 3 * E, a, B, heads, L, L, D);
-            { Op& o = ops.back(); o.at.scale = 1.0f; o.at.bias_ld = Lp; o.at.bias_hs = (long)L * Lp; o.i3 = 1; }
+            { Op& o = cur.ops.back(); o.at.scale = 1.0f; o.at.bias_ld = Lp; o.at.bias_hs = (long)L * Lp; o.i3 = 1; }
             op_gemm("t5.o", a, W.o, x, x);                        // x += attention output
             rms("t5.ln2", x, n, W.ln2);
             op_gemm("t5.wi", n, W.wi, f, Act{}, true);            // gelu_tanh(wi_0 n) * (wi_1 n)
-            ops.back().g.geglu = 2;
+            cur.ops.back().g.geglu = 2;
             op_gemm("t5.wo", f, W.wo, x, x);                      // x += FF output
         }
         rms("t5.final_ln", x, n, t5_final_ln);
-        { Op o{}; o.kind = OP_CVT_OUT; o.name = "t5.out"; o.p0 = ptr(n); o.i0 = M * E; o.i3 = 0; ops.push_back(o); }
-        if (pass == 0) { arena_peak_dry = arena_peak; arena = saved; }
-    }
-    pB2 = B; ph = L; pw = 0; pM = 0;
-    return LDX_OK;
+        { Op o{}; o.kind = OP_CVT_OUT; o.name = "t5.out"; o.p0 = ptr(n); o.i0 = M * E; o.i3 = 0; cur.ops.push_back(o); }
+        return LDX_OK;
+    });
 }
 
 int Engine::run_t5(const int* ids, int B, int L, const float* bias, float* out, hipStream_t st) {
     if (!finalized || kind != KIND_T5) { set_error("ldx_t5_encode: not a finalized T5 engine"); return LDX_ESTATE; }
     if (!ids || !bias || !out || B <= 0 || L <= 0) { set_error("ldx_t5_encode: bad argument"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
-    if (B != pB2 || L != ph) {
-        HIP_OK(hipStreamSynchronize(st));
-        int rc = plan_t5(B, L);
-        if (rc) return rc;
-    }
-    b_ids = ids; b_bias = bias; b_out = out; b_out2 = nullptr; prof_graph = false;
-    int rc = exec_ops(st);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return LDX_EHIP; }
-    return LDX_OK;
+    if (int rc = select_plan(PlanKey{B, L}, st, [&] { return plan_t5(B, L); })) return rc;
+    bind = Bindings{}; bind.ids = ids; bind.bias = bias; bind.out = out; prof_graph = false;
+    if (int rc = exec_ops(st)) return rc;
+    return launch_status();
 }
 
 }  // namespace ldx

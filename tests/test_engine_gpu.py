@@ -217,6 +217,10 @@ def test_denoise_cfg_equals_denoise_on_the_concatenated_batch(setup, ldx, dt):
                 r = _rel(shared, ref.cpu().numpy())
                 print(f"[{dt}] B {B} sigma {sigma}: shared prefix vs full batch rel-L2 {r:.3e}; executed {info['flops_executed'] / 1e9:.2f} of {info['flops'] / 1e9:.2f} GFLOP")
                 assert r <= tol and info["flops_shared"] > 0 and abs(info["flops_executed"] + info["flops_shared"] - info["flops"]) <= 1e-6 * info["flops"]
+                e.set_cfg_share(False)                       # back and forth: each share mode keeps its own plan, bit-identical on the revisit
+                assert torch.equal(e.denoise_cfg(x, sigma, ctx), got)
+                e.set_cfg_share(2)
+                assert torch.equal(e.denoise_cfg(x, sigma, ctx), shared)
         x = torch.randn([1, 4, 16, 16], generator=gen).cuda()
         ctx = torch.randn([2, 77, cfg.context_dim], generator=gen).cuda()
         xx = torch.cat([x, x]).contiguous()

@@ -74,6 +74,8 @@ def test_vae_encode_vs_reference_golden(ldx, ldx_lib, g, dt, tol):
         with torch.no_grad():
             ref = O.vae_decode(sd, cfg, z)
         assert float(((img.cpu() - ref) ** 2).mean()) < 1e-3
+        # and back to each mode: the re-planned encode / decode are bit-identical to the first ones
+        assert torch.equal(eng.encode_moments(px), mom) and torch.equal(eng.decode(z.cuda()), img)
 
 
 def test_vae_encode_requires_encoder_weights(ldx, ldx_lib):

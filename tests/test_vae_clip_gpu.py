@@ -58,16 +58,20 @@ def test_clip_vs_reference_golden(ldx, ldx_lib, golden_dir, dt, tol):
     cfg = ldx.CLIPConfig.tiny()
     sd = ldx.weights.synth_state_dict(ldx.weights.clip_state_dict_spec(cfg), seed=777)
     eng = ldx.CLIPTextEngine(cfg, sd, device=0, dtype=dt)
+    first = {}
     for skip in (None, -2):
         for i in range(5):
             pairs = [list(zip(g[f"ids_{i}"][c].tolist(), g[f"wts_{i}"][c].tolist())) for c in range(g[f"ids_{i}"].shape[0])]
             cond, pooled = eng.encode_token_weights(pairs, layer_idx=skip)
+            first.setdefault(skip, (pairs, cond.clone()))
             want = g[f"cond_tiny_skip{skip}_{i}"]
             assert cond.shape == want.shape
             r = _rel(cond, want)
             print(f"[{dt}] CLIP skip={skip} prompt {i}: rel-L2 {r:.3e}")
             assert r <= tol
             assert _rel(pooled, g[f"pooled_tiny_skip{skip}_{i}"]) <= tol
+    for skip, (pairs, cond) in first.items():          # back to each intermediate-layer mode: the re-planned encode is bit-identical
+        assert torch.equal(eng.encode_token_weights(pairs, layer_idx=skip)[0], cond)
 
 
 def test_clip_full_size_vs_oracle(ldx, ldx_lib, golden_dir):
