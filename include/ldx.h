@@ -366,6 +366,17 @@ int ldx_op_gemm2_mx(const void* A1, int lda1, const void* SA1, int sa_ld1, const
                     const float* bias1, void* C1, int ldc1,
                     const void* A2, int lda2, const void* SA2, int sa_ld2, const void* W2, const void* SW2, int sw_ld2, int M2, int N2, int K2,
                     const float* bias2, void* C2, int ldc2, int dtype, void* stream);
+/* Read-only probe: which kernel ldx_op_gemm / ldx_op_gemm_mx / ldx_op_conv3x3[_skip] (M2 > 0: ldx_op_gemm2[_mx] with the second problem M2, N2, K2) and the engines'
+ * plans would launch for a problem described by plain integers.  Launches nothing and touches no device.  mode 0 plain / 1 conv3x3 (Cin .. stride: the conv
+ * geometry, K = 9 * Cin + the channels of a fused 1x1 skip); geglu as GemmArgs::geglu; splitk = K splits, -1: the planner's own choice; f8: MX fp8 operands,
+ * c8: MX fp8 output, ln_fold: LayerNorm folded in.  gn_hw > 0 (one problem only): the output feeds a GroupNorm of gn_groups groups over images of gn_hw rows
+ * whose statistics workspace holds gn_max_chunks chunks per image — the launch is the one the planner would make after asking for the fused statistics.
+ * out[0 .. 9] = kernel family (0 register-staged tile, 1 the same for two problems, 2 ping-pong, 3 ping-pong for two problems, 4 ring, 5 patch-resident conv,
+ * 6 .. 9 = 0 .. 3 with MX fp8 operands), tile rows BM, tile columns BN (as instantiated), WM (register-staged tiles: threads / 128), f8, ln_fold, K splits in effect,
+ * reduce (0 none, 1 reduce launch, 2 reduce launch + GroupNorm statistics, 3 inside the kernel), kernel launches, GroupNorm chunks per image (0: statistics not fused). */
+int ldx_op_gemm_pick(int M, int N, int K, int mode, int geglu, int splitk, int f8, int c8, int ln_fold,
+                     int Cin, int Hin, int Win, int Hout, int Wout, int stride, int M2, int N2, int K2,
+                     int gn_hw, int gn_groups, int gn_max_chunks, int32_t* out);
 int ldx_op_conv3x3(const void* X, int ldx, const void* W, int B, int Hin, int Win, int Cin, int Cout,
                    int stride, int Hout, int Wout, int resize_to_out, const float* bias,
                    const float* rowvec, int rowvec_ld, const void* R, int ldr, void* Y, int ldy,

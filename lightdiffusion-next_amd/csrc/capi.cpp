@@ -486,6 +486,35 @@ int ldx_op_gemm2_mx(const void* A1, int lda1, const void* SA1, int sa_ld1, const
     launch_gemm2(a, b, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_gemm2_mx");
 }
+int ldx_op_gemm_pick(int M, int N, int K, int mode, int geglu, int splitk, int f8, int c8, int ln_fold,
+                     int Cin, int Hin, int Win, int Hout, int Wout, int stride, int M2, int N2, int K2,
+                     int gn_hw, int gn_groups, int gn_max_chunks, int32_t* out) {
+    if (!out || M <= 0 || N <= 0 || K <= 0 || (mode != 0 && mode != 1) || (mode == 1 && (Cin <= 0 || Hout <= 0 || Wout <= 0 || (M2 > 0)))) {
+        set_error("ldx_op_gemm_pick: bad argument"); return LDX_EINVAL; }
+    static char buf[16];                       // operands are only ever tested for being there
+    void* const P = buf;
+    GemmArgs g{};
+    g.A = P; g.W = P; g.M = M; g.N = N; g.K = K; g.mode = mode; g.lda = mode ? Cin : K; g.geglu = geglu; g.rows_per_batch = mode ? Hout * Wout : 1;
+    if (mode) {
+        g.Cin = Cin; g.Hin = Hin; g.Win = Win; g.Hout = Hout; g.Wout = Wout; g.stride = stride;
+        if (stride == 1) { g.Hv = Hout; g.Wv = Wout; } else { g.Hv = Hin; g.Wv = Win; }
+        g.resize = (g.Hv != Hin || g.Wv != Win) ? 1 : 0;
+        if (K > 9 * Cin) { g.A2 = P; g.lda2 = g.Cin2 = K - 9 * Cin; }
+    }
+    if (f8) { g.f8 = 1; g.SA = g.SW = (const uint32_t*)P; g.sa_ld = M; g.sw_ld = N; }
+    if (c8) { g.C8 = P; g.ldc8 = N; g.SC = (uint32_t*)P; g.sc_ld = M; } else { g.C = P; g.ldc = N; }
+    if (ln_fold) g.ln_c1 = (const float*)P;
+    g.splitk = splitk >= 0 ? splitk : (c8 ? 1 : gemm_choose_splitk(M, N, f8 ? K / 2 : K, geglu != 0));
+    if (g.splitk > 1) { g.ws = (float*)P; g.sk_count = (unsigned*)P; }
+    GemmArgs b{};
+    b.A = P; b.W = P; b.M = M2; b.N = N2; b.K = K2; b.lda = K2; b.C = P; b.ldc = N2; b.rows_per_batch = 1; b.f8 = g.f8;
+    int gn = 0;
+    if (gn_hw > 0 && M2 <= 0 && (gn = gemm_gn_fuse(g, gn_hw, gn_groups, gn_max_chunks)) != 0) g.gn_partial = (float*)P;
+    const GemmPick p = gemm_pick(g, M2 > 0 ? &b : nullptr);
+    const int32_t r[10] = {p.family, p.bm, p.bn, p.wm, p.f8, p.lnf, p.S, p.reduce, p.launches, gn};
+    for (int i = 0; i < 10; ++i) out[i] = r[i];
+    return LDX_OK;
+}
 int ldx_op_conv3x3(const void* X, int ldx_, const void* W, int B, int Hin, int Win, int Cin, int Cout, int stride, int Hout, int Wout,
                    int resize_to_out, const float* bias, const float* rowvec, int rowvec_ld, const void* R, int ldr, void* Y, int ldy,
                    int dtype, void* stream) {

@@ -86,6 +86,7 @@ static __device__ __forceinline__ void cp_load_residuals(const GemmArgs& p, cons
 }
 
 constexpr int CP_TH = 16, CP_TW = 32, CP_PW = CP_TW + 2, CP_PIX = (CP_TH + 2) * CP_PW;     // 612 patch pixels
+static_assert(CP_TH * CP_TW == CONV_PATCH_BM, "GemmPick::bm of the patch kernel");
 constexpr int CP_PP = (CP_PIX * 4 + 63) / 64;                                             // 39 pieces of 64 slots per channel chunk
 constexpr int CP_PATCH = CP_PP * 1024;
 constexpr int CP_RED = 8 * 32 * 2 * 4;                                                    // GroupNorm partials of the 8 waves

@@ -606,8 +606,7 @@ void Engine::fuse_gn_stats() {
             RowGemmArgs& r = cur.ops[i - 1].rg;
             GroupNormArgs& n = cur.ops[i].gn;
             const int bm = 128 * 320 / r.K;
-            static const bool off = getenv("LDX_GN_FUSE") && atoi(getenv("LDX_GN_FUSE")) == 0;
-            if (off || r.pro == 2 || r.Y != n.X || r.ldy != n.ldx || r.N != n.C || r.N != r.K || n.G != 32 || (long)r.M != (long)n.B * n.HW || n.HW % bm || n.HW / bm > gn_ws_rows ||
+            if (!gemm_gn_fuse_enabled() || r.pro == 2 || r.Y != n.X || r.ldy != n.ldx || r.N != n.C || r.N != r.K || n.G != 32 || (long)r.M != (long)n.B * n.HW || n.HW % bm || n.HW / bm > gn_ws_rows ||
                 gn_uses_small_kernel(n.B, n.HW, n.C, n.G)) continue;      // last term: the one-launch small GroupNorm kernel takes it (norm.hip)
             r.gn_out = n.partial; r.gn_nchunk = n.HW / bm; r.HW = n.HW;
             n.stats_chunks = n.HW / bm;
@@ -1368,7 +1367,9 @@ int64_t Engine::n_launches() const {
         if (ctx_cache && o.ctx_only) continue;            // steady state of a sampling run: the context's projections are cached
         if (o.kind == OP_ATTN && o.at.nsplit > 1) { n += 2; continue; }      // split keys + merge launch (attn512.hip)
         if (o.kind == OP_GN) n += o.gn.stats_chunks > GN_NCHUNK ? 2 : (o.gn.stats_chunks > 0 ? 1 : 2);      // fold + apply / apply / statistics + apply
-        else n += (o.kind == OP_GEMM && o.g.splitk > 1 && !gemm_sk_fixup(o.g)) ? 2 : 1;
+        else if (o.kind == OP_GEMM) n += gemm_pick(o.g).launches;          // with its split-K reduce launch, if it has one
+        else if (o.kind == OP_GEMM2) n += gemm_pick(o.g, &o.g2).launches;
+        else n += 1;
     }
     return n;
 }

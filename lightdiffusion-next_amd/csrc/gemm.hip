@@ -549,6 +549,24 @@ __global__ __launch_bounds__(1024) void splitk_reduce_gn_kernel(const GemmArgs p
     }
 }
 
+// ---- dispatch: which kernel a GEMM / convolution runs -------------------------------------------------------------------------------
+// Every LDX_* switch this file reads, read once when the library loads; "set at all" stays apart from "non-zero" where the two differ.  Deliberately NOT re-read by
+// reload_dispatch_env(): plans bake these decisions into their op arguments (splitk, gn_nchunk), and a reload between planning and launching would make the two disagree.
+static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+static double env_rate(const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; }
+static bool env_unless_0(const char* name) { const char* v = getenv(name); return !(v && atoi(v) == 0); }
+static const struct GemmSwitches {
+    int pp = env_int("LDX_PP", 1), pp_mink = env_int("LDX_PP_MINK", 1024), pp_mink_mx = env_int("LDX_PP_MINK_MX", 2048);      // ping-pong kernel: 0 off, 1 cost model, 2 whenever a candidate fills >= 3/4 of the CUs; its shortest K
+    double pp_r224 = env_rate("LDX_PP224_RATE", 1.33), pp_r192 = env_rate("LDX_PP192_RATE", 1.29);                              // cost-model rates of the 224 / 192 wide tiles (0: never)
+    double mx_r224 = env_rate("LDX_MX224_RATE", 2.08), mx_r192 = env_rate("LDX_MX192_RATE", 2.1);
+    int tile = env_int("LDX_GEMM_TILE", 0);                                                                                       // experiment switch: BM * 1000 + BN for every launch
+    bool no_tile160 = getenv("LDX_NO_TILE160") != nullptr, no_split2 = getenv("LDX_NO_SPLIT2") != nullptr;                       // set at all, even to nothing
+    int splitk = env_int("LDX_SPLITK", 0);                                                                                        // experiment switch: K splits wherever K allows
+    int skgn_chunks = env_int("LDX_SKGN_CHUNKS", GN_NCHUNK);                                                                      // experiment switch: chunks per image of the reduce + GroupNorm launch (fewer = fatter workgroups)
+    bool gn_fuse = env_unless_0("LDX_GN_FUSE"), gn_fuse_splitk = env_unless_0("LDX_GN_FUSE_SPLITK"), gn_fuse_wide = env_unless_0("LDX_GN_FUSE_WIDE");
+    bool sk_fixup = env_int("LDX_SK_FIXUP", 0) != 0; int sk_fixup_max = env_int("LDX_SK_FIXUP_MAX", SK_FIXUP_MAX_S);
+    int ep_general = env_int("LDX_EP_GENERAL", 0);                                                                                // -> GemmArgs::ep_general
+} g_sw;
 // geometry of that launch: R row lanes of N / 4 threads (<= 1024 threads, >= 2 * G), chunks of RB rows; 0 = not applicable
 static int splitk_gn_geom(const GemmArgs& a, int HW, int G, int max_chunks, int* R_out) {
     if (a.N % 4 || !a.C || a.N % G || HW <= 0 || a.M % HW) return 0;
@@ -557,9 +575,7 @@ static int splitk_gn_geom(const GemmArgs& a, int HW, int G, int max_chunks, int*
     int R = nq <= 128 ? 8 : (nq <= 256 ? 4 : 2);        // a power of two (chunks of R rows must tile the image); up to 1024 threads: the kernel is latency-bound
     if (nq * R < 2 * G) return 0;
     if (gn_uses_small_kernel(a.M / HW, HW, a.N, G)) return 0;      // the one-launch small GroupNorm kernel takes this one (norm.hip): faster than apply-only
-
-    static const int lim_env = getenv("LDX_SKGN_CHUNKS") ? atoi(getenv("LDX_SKGN_CHUNKS")) : GN_NCHUNK;      // experiment switch: chunks per image (fewer = fatter workgroups)
-    int lim = max_chunks < lim_env ? max_chunks : lim_env;
+    const int lim = max_chunks < g_sw.skgn_chunks ? max_chunks : g_sw.skgn_chunks;
     // rows per chunk: a multiple of R dividing HW, as small as keeps nchunk <= lim (more workgroups), at least R
     int RB = 0;
     for (int cand = R; cand <= HW; cand += R) if (HW % cand == 0 && HW / cand <= lim) { RB = cand; break; }
@@ -568,12 +584,27 @@ static int splitk_gn_geom(const GemmArgs& a, int HW, int G, int max_chunks, int*
     return HW / RB;
 }
 
-// tile selection: {BM, BN}
+// tile selection: the {BM, BN} the heuristics ask for; gemm_pick maps it to the instantiation that exists for the launch's mode and flags
 struct TileSel { int bm, bn; };
-static const double pp_r224 = getenv("LDX_PP224_RATE") ? atof(getenv("LDX_PP224_RATE")) : 1.33, pp_r192 = getenv("LDX_PP192_RATE") ? atof(getenv("LDX_PP192_RATE")) : 1.29;   // 0: never
+// The ping-pong cost model, shared by the single launch (gemm_tile), the MX fp8 one (mx_pp_bn) and the two-problem one (gemm2_pp_bn), which differ in how they
+// count tiles and in their constants: of the candidate widths (rate 0 or a tile count of 0: not a candidate) that give at least 192 workgroups — fewer would
+// leave a quarter of the CUs idle — the one with the lowest cost = rounds x slots x tile area / rate, if that beats the 128-row kernel's cost_old by 5 %
+// (LDX_PP=2: always).  Returns its width, 0 = keep the 128-row kernel.
+template <int NC, typename TileCount>
+static int pp_cost_model(const int (&cand)[NC], const double (&rate)[NC], TileCount tiles, double cost_old) {
+    double best = 1e30; int best_bn = 0;
+    for (int c = 0; c < NC; ++c) {
+        if (rate[c] <= 0) continue;
+        const long t = tiles(cand[c]);
+        if (t < 192) continue;
+        const double cost = (double)((t + 255) / 256) * 256.0 * 256.0 * cand[c] / rate[c];
+        if (cost < best) { best = cost; best_bn = cand[c]; }
+    }
+    return best_bn && (g_sw.pp >= 2 || best < 0.95 * cost_old) ? best_bn : 0;
+}
+
 static inline TileSel gemm_tile(int M, int N, int K, bool geglu, int splitk, bool allow_pp = true, bool plain = false) {      // plain: a GEMM (224 / 192 wide ping-pong tiles exist), not a conv
-    static const int force = getenv("LDX_GEMM_TILE") ? atoi(getenv("LDX_GEMM_TILE")) : 0;      // experiment switch: BM*1000+BN
-    if (force) return {force / 1000, force % 1000};
+    if (g_sw.tile) return {g_sw.tile / 1000, g_sw.tile % 1000};
     if (!geglu && N <= 32 && splitk <= 1) return {128, 32};          // ESRGAN dense-block convs (growth 32), 3-channel output convs
     if (!geglu && N <= 64 && splitk <= 1 && (long)((M + 127) / 128) >= 400) return {128, 64};
     // Large problems: the 256-row ping-pong kernel (gemm_pp.inc; one 8-wave workgroup per CU, LDS-DMA ring) when a simple cost model
@@ -581,38 +612,26 @@ static inline TileSel gemm_tile(int M, int N, int K, bool geglu, int splitk, boo
     // ~1.0 on long K, against 0.72-0.96 for the register-staged 128-row kernel; short-K problems (a handful of K-tiles) are bound by
     // per-launch fixed costs and the output write instead and gain nothing, and N = 128 (VAE 1024^2 level) loses.
     // cost = rounds x slots x tile area / rate; LDX_PP: 0 off, 1 model (default), 2 whenever a candidate fills >= 3/4 of the CUs.
-    static const int pp_policy = getenv("LDX_PP") ? atoi(getenv("LDX_PP")) : 1;
-    static const int pp_mink = getenv("LDX_PP_MINK") ? atoi(getenv("LDX_PP_MINK")) : 1024;
     // GEGLU up-projections (N = 8 C, an erf per output pair in the output stage) gain from the 256-wide tiles already at K = 640: M 8192 N 5120 K 640 105 us on
     // 128 x 128, 97 on 256 x 128, 84 on 256 x 256 (profiles/r06/geglu_tiles.txt)
-    if (allow_pp && pp_policy && M >= 1024 && N >= 256 && (K >= pp_mink || (geglu && K >= 640))) {
+    if (allow_pp && g_sw.pp && M >= 1024 && N >= 256 && (K >= g_sw.pp_mink || (geglu && K >= 640))) {
         const long S = splitk > 1 ? splitk : 1, mt = (M + 255) / 256;
-        double best = 1e30; int best_bn = 0;
         const int cand[5] = {256, 224, 192, 160, 128};
-        const double rate[5] = {1.35, plain ? pp_r224 : 0, plain ? pp_r192 : 0, 1.15, 0.92};
-        for (int c = 0; c < 5; ++c) {
-            if ((geglu && cand[c] != 128 && cand[c] != 256) || rate[c] <= 0) continue;      // GEGLU pairs value / gate columns inside 64-column slabs: wave tiles of 64 or 128 columns
-            const long t = mt * ((N + cand[c] - 1) / cand[c]) * S;
-            if (t < 192) continue;                                   // would leave a quarter of the CUs idle
-            const double cost = (double)((t + 255) / 256) * 256.0 * 256.0 * cand[c] / rate[c];
-            if (cost < best) { best = cost; best_bn = cand[c]; }
-        }
-        if (best_bn) {
-            const int bo = geglu ? 128 : ((N % 160 == 0 && N % 128 != 0) ? 160 : 128);
-            const long to = (long)((M + 127) / 128) * ((N + bo - 1) / bo) * S;
-            const double cost_old = (double)((to + 511) / 512) * 512.0 * 128.0 * bo / 0.84;
-            // (round 6) a ragged 128-wide ping-pong tiling (N = 320: 3 column tiles for 2.5) against 160-wide register-staged tiles that fit one per CU: measured equal
-            // (M 16384 N 320 K 2880: 61.4 vs 60.0 us, profiles/r06/conv_tiles.txt), and only the exact tiling can feed the consumer GroupNorm's statistics
-            const bool ragged_tie = best_bn == 128 && N % 128 != 0 && N % bo == 0 && to <= 256;
-            if (pp_policy >= 2 || (best < 0.95 * cost_old && !ragged_tie)) return {256, best_bn};
-        }
+        const double rate[5] = {1.35, plain ? g_sw.pp_r224 : 0, plain ? g_sw.pp_r192 : 0, 1.15, 0.92};
+        const int bo = geglu ? 128 : ((N % 160 == 0 && N % 128 != 0) ? 160 : 128);
+        const long to = (long)((M + 127) / 128) * ((N + bo - 1) / bo) * S;
+        const auto tiles = [&](int c) -> long { return (geglu && c != 128 && c != 256) ? 0 : mt * ((N + c - 1) / c) * S; };      // GEGLU pairs value / gate columns inside 64-column slabs: wave tiles of 64 or 128 columns
+        const int bn = pp_cost_model(cand, rate, tiles, (double)((to + 511) / 512) * 512.0 * 128.0 * bo / 0.84);
+        // (round 6) a ragged 128-wide ping-pong tiling (N = 320: 3 column tiles for 2.5) against 160-wide register-staged tiles that fit one per CU: measured equal
+        // (M 16384 N 320 K 2880: 61.4 vs 60.0 us, profiles/r06/conv_tiles.txt), and only the exact tiling can feed the consumer GroupNorm's statistics
+        const bool ragged_tie = bn == 128 && N % 128 != 0 && N % bo == 0 && to <= 256;
+        if (bn && (g_sw.pp >= 2 || !ragged_tie)) return {256, bn};
     }
     if (geglu) return {128, 128};
     int bn = (N % 160 == 0 && N % 128 != 0) ? 160 : 128;
     // wave quantisation: 257..511 tiles of 128x128 put two workgroups on some CUs and one on the rest (the launch takes as
     // long as the doubly-loaded CUs); if 128x160 tiles fit one per CU, every CU runs a single, 1.25x larger tile instead
-    static const bool no160 = getenv("LDX_NO_TILE160") != nullptr;
-    if (bn == 128 && N % 160 == 0 && splitk <= 2 && !no160) {
+    if (bn == 128 && N % 160 == 0 && splitk <= 2 && !g_sw.no_tile160) {
         const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128), t160 = (long)((M + 127) / 128) * (N / 160);
         if (t128 > 256 && t128 < 512 && t160 <= 256) bn = 160;      // with splitk == 2 (gemm_choose_splitk's one-per-CU rule): 2 x t160 <= 512 workgroups
     }
@@ -630,96 +649,26 @@ static inline TileSel gemm_tile(int M, int N, int K, bool geglu, int splitk, boo
     return {128, bn};
 }
 
-template <typename T, int MODE, int BM, int BN, int WM = 2, bool F8 = false, bool LNF = false>
-static void launch_gemm_inst(const GemmArgs& a, int S, hipStream_t s) {
-    gemm_gn_tile_check(a, BM, BN, S);
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * S;
-    const size_t lds = 2 * stage_bytes<BM, BN>();
-    static DevOnce once;
-    set_dyn_lds(once, (const void*)gemm_kernel<T, MODE, BM, BN, WM, F8, LNF>, (int)lds);
-    hipLaunchKernelGGL((gemm_kernel<T, MODE, BM, BN, WM, F8, LNF>), dim3(tiles), dim3(WM * 128), lds, s, a);
-}
-
-// MX fp8 operands: 256-row ping-pong tile width (160 / 128) or 0 = keep the 128-row kernel.  Same cost model as gemm_tile with the MX
+// MX fp8 operands: 256-row ping-pong tile width (160 / 128) or 0 = keep the 128-row kernel.  The cost model with the MX
 // rates (isolated Flux shapes, profiles/mx_probe.py); the quantised-output epilogue needs 64-column wave tiles (BN = 128).
 static int mx_pp_bn(long tiles_m256, long tiles_m128, int N, int K, int S, bool c8, long ym256 = 0, long ym128 = 0, int yN = 0) {      // y*: the second problem of a two-problem launch
-    static const int pp_policy = getenv("LDX_PP") ? atoi(getenv("LDX_PP")) : 1;
-    static const int pp_mink = getenv("LDX_PP_MINK_MX") ? atoi(getenv("LDX_PP_MINK_MX")) : 2048;
-    if (!pp_policy || N < 256 || K < pp_mink) return 0;
-    double best = 1e30; int best_bn = 0;
+    if (!g_sw.pp || N < 256 || K < g_sw.pp_mink_mx) return 0;
     // per-round rates from the 8192^3 sweep (profiles/ubench/README.md): wider tiles move fewer operand bytes per flop, and N = 3072 fits one round of 224s
-    static const double r224 = getenv("LDX_MX224_RATE") ? atof(getenv("LDX_MX224_RATE")) : 2.08;      // 0: never
-    static const double r192 = getenv("LDX_MX192_RATE") ? atof(getenv("LDX_MX192_RATE")) : 2.1;
     const int cand[4] = {224, 192, 160, 128};
-    const double rate[4] = {r224, r192, 1.93, 1.75};
-    for (int c = 0; c < 4; ++c) {
-        if ((c8 && cand[c] != 128 && cand[c] != 192) || rate[c] <= 0) continue;
-        const long t = tiles_m256 * ((N + cand[c] - 1) / cand[c]) * S + ym256 * ((yN + cand[c] - 1) / cand[c]);
-        if (t < 192) continue;
-        const double cost = (double)((t + 255) / 256) * 256.0 * 256.0 * cand[c] / rate[c];
-        if (cost < best) { best = cost; best_bn = cand[c]; }
-    }
-    if (!best_bn) return 0;
+    const double rate[4] = {g_sw.mx_r224, g_sw.mx_r192, 1.93, 1.75};
     const long to = tiles_m128 * ((N + 127) / 128) * S + ym128 * ((yN + 127) / 128);
-    const double cost_old = (double)((to + 511) / 512) * 512.0 * 128.0 * 128.0 / 1.2;
-    return (pp_policy >= 2 || best < 0.95 * cost_old) ? best_bn : 0;
+    const auto tiles = [&](int c) -> long { return (c8 && c != 128 && c != 192) ? 0 : tiles_m256 * ((N + c - 1) / c) * S + ym256 * ((yN + c - 1) / c); };
+    return pp_cost_model(cand, rate, tiles, (double)((to + 511) / 512) * 512.0 * 128.0 * 128.0 / 1.2);
 }
 
-template <typename T, int MODE>
-static void launch_gemm_mode(const GemmArgs& a, int S, hipStream_t s) {
-    if (MODE == 0 && a.f8) {        // MX fp8 operands: a K-tile holds 128 elements, so the tile heuristics see K / 2
-        if constexpr (MODE == 0) {
-            static const int force = getenv("LDX_GEMM_TILE") ? atoi(getenv("LDX_GEMM_TILE")) : 0;
-            const int bn = force ? (force / 1000 == 256 ? (force % 1000 == 192 ? 192 : a.C8 ? 128 : (force % 1000 == 224 ? 224 : force % 1000 == 160 ? 160 : 128)) : 0)
-                                 : (a.M >= 1024 ? mx_pp_bn((a.M + 255) / 256, (a.M + 127) / 128, a.N, a.K, S, a.C8 != nullptr) : 0);
-            if (bn) { launch_gemm_pp(a, bn, false, S, DTypeOf<T>::v, s); return; }
-        }
-        const TileSel t = gemm_tile(a.M, a.N, a.K / 2, a.geglu != 0, S, false);      // no MX ping-pong kernel yet (256 x 128 only when forced)
-        if (t.bm == 256 && t.bn == 128) launch_gemm_inst<T, 0, 256, 128, 4, true>(a, S, s);      // opt-in (LDX_TILE256)
-        else if (t.bm == 64) launch_gemm_inst<T, 0, 64, 64, 2, true>(a, S, s);
-        else if (t.bn == 160 && !a.C8) launch_gemm_inst<T, 0, 128, 160, 2, true>(a, S, s);
-        else launch_gemm_inst<T, 0, 128, 128, 2, true>(a, S, s);
-        return;
-    }
-    const TileSel t = gemm_tile(a.M, a.N, a.K, a.geglu != 0, S, true, MODE == 0 && !a.ln_c1);
-    if constexpr (MODE == 0) {
-        if (a.ln_c1) {       // LayerNorm folded in (no split-K): the tile shapes a transformer block's q|k|v / q / GEGLU projections take
-            if (t.bm == 256 && t.bn != 128 && !a.geglu) launch_gemm_pp(a, 160, true, 1, DTypeOf<T>::v, s);
-            else if (t.bm == 256) launch_gemm_pp(a, 128, true, 1, DTypeOf<T>::v, s);
-            else if (t.bm == 64) launch_gemm_inst<T, 0, 64, 64, 2, false, true>(a, 1, s);
-            else if (t.bn == 160 && !a.geglu) launch_gemm_inst<T, 0, 128, 160, 2, false, true>(a, 1, s);
-            else launch_gemm_inst<T, 0, 128, 128, 2, false, true>(a, 1, s);
-            return;
-        }
-    }
-    if (t.bm == 256 && t.bn > 128 && (!a.geglu || t.bn == 256)) launch_gemm_pp(a, t.bn, false, S, DTypeOf<T>::v, s);
-    else if (t.bm == 256) launch_gemm_pp(a, 128, false, S, DTypeOf<T>::v, s);
-    else if (t.bn == 32) launch_gemm_inst<T, MODE, 128, 32>(a, S, s);
-    else if (t.bm == 128 && t.bn == 64) launch_gemm_inst<T, MODE, 128, 64>(a, S, s);
-    else if (a.geglu && t.bm == 64) launch_gemm_inst<T, MODE, 128, 128>(a, S, s);      // (forced tiles only) the GEGLU pairing needs 64-column wave tiles
-    else if (MODE == 0 && t.bm == 64 && t.bn == 160 && S == 1 && a.K % BK == 0) launch_gemm_ring(a, DTypeOf<T>::v, s);      // gemm_ring.hip
-    else if (t.bm == 64) launch_gemm_inst<T, MODE, 64, 64>(a, S, s);
-    else if (t.bn == 160) launch_gemm_inst<T, MODE, 128, 160>(a, S, s);
-    else launch_gemm_inst<T, MODE, 128, 128>(a, S, s);
-}
-
-template <typename T>
-static void launch_gemm_t(const GemmArgs& a0, hipStream_t s) {
-    GemmArgs a = a0;
-    if (!gemm_sk_fixup(a)) a.sk_count = nullptr;        // the kernels reduce in place iff sk_count is set
-    const int S = (a.splitk > 1 && a.ws && !a.geglu) ? a.splitk : 1;
-    if (a.mode == 0) launch_gemm_mode<T, 0>(a, S, s); else launch_gemm_mode<T, 1>(a, S, s);
-    if (S > 1 && a.sk_count) return;                    // reduced by the last workgroup of every tile
-    if (S > 1 && a.gn_partial) {       // reduce + GroupNorm statistics (gemm_gn_fuse set the geometry)
-        int R = 1;
-        const int nchunk = splitk_gn_geom(a, a.gn_hw, a.gn_G, a.gn_nchunk, &R);
-        if (nchunk != a.gn_nchunk) { fprintf(stderr, "ldx: split-K GroupNorm geometry mismatch (%d vs %d)\n", nchunk, a.gn_nchunk); abort(); }
-        hipLaunchKernelGGL((splitk_reduce_gn_kernel<T>), dim3(nchunk, a.M / a.gn_hw), dim3((a.N / 4) * R), (size_t)R * a.N * 2 * sizeof(float), s, a, R);
-    } else if (S > 1) {
-        long total = (long)a.M * ((a.N + 3) / 4);
-        int grid = (int)((total + 255) / 256); if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(grid), dim3(256), 0, s, a);
-    }
+// 256-row ping-pong tiles for a two-problem launch: the cost model over the combined tile count; 0 = keep 128 x 128
+static int gemm2_pp_bn(const GemmArgs& a, const GemmArgs& b) {
+    if (!g_sw.pp || a.f8 || b.f8 || a.K < g_sw.pp_mink || b.K < g_sw.pp_mink || a.N < 256 || b.N < 256 || a.M + b.M < 1024) return 0;
+    const int cand[5] = {256, 224, 192, 160, 128};
+    const double rate[5] = {1.35, g_sw.pp_r224, g_sw.pp_r192, 1.15, 0.92};
+    const long to = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) + (long)((b.M + 127) / 128) * ((b.N + 127) / 128);
+    const auto tiles = [&](int c) -> long { return (long)((a.M + 255) / 256) * ((a.N + c - 1) / c) + (long)((b.M + 255) / 256) * ((b.N + c - 1) / c); };
+    return pp_cost_model(cand, rate, tiles, (double)((to + 511) / 512) * 512.0 * 128.0 * 128.0 / 0.84);
 }
 
 bool gemm_sk_fixup(const GemmArgs& a) {
@@ -729,77 +678,100 @@ bool gemm_sk_fixup(const GemmArgs& a) {
 #ifndef LDX_SK_FIXUP_BUILD
     return false;      // the in-kernel path is not compiled in (gemm_common.h): it costs every instantiation registers
 #else
-    static const bool off = !(getenv("LDX_SK_FIXUP") && atoi(getenv("LDX_SK_FIXUP")) != 0);
-    static const int max_s = getenv("LDX_SK_FIXUP_MAX") ? atoi(getenv("LDX_SK_FIXUP_MAX")) : SK_FIXUP_MAX_S;
-    if (off || !a.sk_count || !a.ws || a.splitk < 2 || a.splitk > max_s || a.geglu) return false;
+    if (!g_sw.sk_fixup || !a.sk_count || !a.ws || a.splitk < 2 || a.splitk > g_sw.sk_fixup_max || a.geglu) return false;
     return (long)((a.M + 63) / 64) * ((a.N + 31) / 32) <= SK_COUNTERS;      // an upper bound on the tile count of any tile shape
 #endif
 }
 
-void gemm_gn_tile_check(const GemmArgs& a, int BM, int BN, int S) {
-    if (!a.gn_partial || S > 1 || a.gn_cpg <= 0) return;       // split-K: the reduce launch owns the statistics and checks its own geometry
-    if (a.gn_hw % BM || a.gn_nchunk != a.gn_hw / BM || BN % a.gn_cpg || (BN > 160 && !(BM == 256 && BN <= 256 && a.N % BN == 0 && a.M % BM == 0))) {      // > 160: the ping-pong tiles' column-major stage
-        fprintf(stderr, "ldx: GroupNorm-statistics geometry mismatch: planned for %d chunks of an image of %d rows, %d channels per group; launching %d x %d tiles\n",
-                a.gn_nchunk, a.gn_hw, a.gn_cpg, BM, BN);
-        abort();
+// The one place that decides which kernel a launch runs (ldx_kernels.h): pure arithmetic over the arguments and g_sw.
+GemmPick gemm_pick(const GemmArgs& a, const GemmArgs* b) {
+    GemmPick p{GF_TILE, 0, 0, 0, false, false, 1, RED_NONE, 1};
+    const auto tile = [&p](GemmFamily f, int bm, int bn, int wm = 2) { p.family = f; p.bm = bm; p.bn = bn; p.wm = wm; return p; };
+    if (b && (a.M <= 0 || a.N <= 0)) return gemm_pick(*b);
+    if (b && (b->M <= 0 || b->N <= 0)) return gemm_pick(a);
+    if (b) {        // two problems: both plain mode, no split-K, no GEGLU, same operand kind (16-bit or MX); 128 x 128 tiles, or 256-row ping-pong tiles
+        int bn = 0;
+        if (a.f8 && b->f8 && a.M + b->M >= 1024 && b->N >= 256)       // MX: the two streams of a Flux double block / the two halves of linear1
+            bn = mx_pp_bn((a.M + 255) / 256, (a.M + 127) / 128, a.N, a.K < b->K ? a.K : b->K, 1, a.C8 || b->C8, (b->M + 255) / 256, (b->M + 127) / 128, b->N);
+        if (!bn) bn = gemm2_pp_bn(a, *b);
+        p.f8 = a.f8 != 0;
+        return bn ? tile(p.f8 ? GF_PP2_MX : GF_PP2, 256, bn, 0) : tile(p.f8 ? GF_TILE2_MX : GF_TILE2, 128, 128);
     }
+    if (a.M <= 0 || a.N <= 0) { p.launches = 0; return p; }
+    if (a.mode == 1 && conv_patch_ok(a)) return tile(GF_CONV_PATCH, CONV_PATCH_BM, a.N <= 16 ? 16 : a.N, 0);      // conv_patch.hip: narrow 3x3 convs with the input patch resident in LDS
+    p.f8 = a.mode == 0 && a.f8;
+    p.lnf = a.mode == 0 && !p.f8 && a.ln_c1;      // LayerNorm folded in (no split-K): the tile shapes a transformer block's q|k|v / q / GEGLU projections take
+    if (a.splitk > 1 && a.ws && !a.geglu && !p.lnf) {
+        p.S = a.splitk; p.reduce = gemm_sk_fixup(a) ? RED_IN_KERNEL : a.gn_partial ? RED_LAUNCH_GN : RED_LAUNCH;      // in-kernel: by the last workgroup of every tile
+        p.launches = p.reduce == RED_IN_KERNEL ? 1 : 2;
+    }
+    if (p.f8) {        // MX fp8 operands: a K-tile holds 128 elements, so the tile heuristics see K / 2
+        const int fw = g_sw.tile % 1000;
+        const int bn = g_sw.tile ? (g_sw.tile / 1000 == 256 ? (fw == 192 ? 192 : a.C8 ? 128 : (fw == 224 ? 224 : fw == 160 ? 160 : 128)) : 0)
+                                 : (a.M >= 1024 ? mx_pp_bn((a.M + 255) / 256, (a.M + 127) / 128, a.N, a.K, p.S, a.C8 != nullptr) : 0);
+        if (bn) return tile(GF_PP_MX, 256, bn, 0);
+        const TileSel t = gemm_tile(a.M, a.N, a.K / 2, a.geglu != 0, p.S, false);      // (256 x 128 register-staged only when forced)
+        if (t.bm == 256 && t.bn == 128) return tile(GF_TILE_MX, 256, 128, 4);
+        return t.bm == 64 ? tile(GF_TILE_MX, 64, 64) : tile(GF_TILE_MX, 128, t.bn == 160 && !a.C8 ? 160 : 128);
+    }
+    const TileSel t = gemm_tile(a.M, a.N, a.K, a.geglu != 0, p.S, true, a.mode == 0 && !a.ln_c1);
+    if (t.bm == 256) {        // ping-pong: the widths that exist — LayerNorm fold 160 / 128, GEGLU 256 / 128 (two or one 64-column slabs per wave), convs 256 / 160 / 128, plain GEMMs all five
+        const int w = t.bn;
+        if (p.lnf) return tile(GF_PP, 256, w != 128 && !a.geglu ? 160 : 128, 0);
+        if (a.geglu) return tile(GF_PP, 256, w == 256 ? 256 : 128, 0);
+        if (a.mode == 1) return tile(GF_PP, 256, w == 256 || w == 160 ? w : 128, 0);
+        return tile(GF_PP, 256, w == 256 || w == 224 || w == 192 || w == 160 ? w : 128, 0);
+    }
+    if (p.lnf) return t.bm == 64 ? tile(GF_TILE, 64, 64) : tile(GF_TILE, 128, t.bn == 160 && !a.geglu ? 160 : 128);
+    if (t.bn == 32) return tile(GF_TILE, 128, 32);
+    if (t.bm == 128 && t.bn == 64) return tile(GF_TILE, 128, 64);
+    if (a.geglu && t.bm == 64) return tile(GF_TILE, 128, 128);      // (forced tiles only) the GEGLU pairing needs 64-column wave tiles
+    if (a.mode == 0 && t.bm == 64 && t.bn == 160 && p.S == 1 && a.K % BK == 0) return tile(GF_RING, 64, 160, 0);      // gemm_ring.hip
+    return t.bm == 64 ? tile(GF_TILE, 64, 64) : tile(GF_TILE, 128, t.bn == 160 ? 160 : 128);
 }
 
-// Planner query (GemmArgs::gn_partial): which tile will launch_gemm_mode pick for `a`, and can that tile's epilogue produce the consumer
-// GroupNorm's statistics?  Mirrors launch_gemm_mode's mapping from gemm_tile() to an instantiation.  LDX_GN_FUSE=0 switches the fusion off.
+// Planner query (GemmArgs::gn_partial): can the epilogue of the kernel gemm_pick gives `a` — or its split-K reduce launch — produce the consumer GroupNorm's
+// statistics?  LDX_GN_FUSE=0 switches the fusion off.
 int gemm_gn_fuse(GemmArgs& a, int HW, int G, int max_chunks) {
-    static const bool off = getenv("LDX_GN_FUSE") && atoi(getenv("LDX_GN_FUSE")) == 0;
-    if (off || a.f8 || a.C8 || a.geglu || a.ln_c1 || !a.C || G <= 0 || a.N % G || a.N % 4 || HW <= 0 || a.M % HW) return 0;
-    if (a.mode == 1) {                        // conv_patch.hip takes it: one chunk per 32 x 16-pixel tile (N = 128 only), or no fusion
-        GemmArgs t = a; t.gn_partial = nullptr;
-        if (conv_patch_ok(t)) {
-            const int nc = conv_patch_gn_chunks(a, HW, G);
-            if (!nc || nc > max_chunks) return 0;
-            a.gn_cpg = a.N / G; a.gn_G = G; a.gn_hw = HW; a.gn_nchunk = nc;
-            return nc;
-        }
-    }
-    const bool fix = gemm_sk_fixup(a);        // in-kernel split-K reduction: the last workgroup of a tile runs the ordinary epilogue, statistics included
-    if (a.splitk > 1 && a.ws && !fix) {        // split-K with a reduce launch: that launch produces the statistics (splitk_reduce_gn_kernel)
-        static const bool sk_off = getenv("LDX_GN_FUSE_SPLITK") && atoi(getenv("LDX_GN_FUSE_SPLITK")) == 0;
-        int R = 1;
-        const int nchunk = sk_off ? 0 : splitk_gn_geom(a, HW, G, max_chunks, &R);
-        if (!nchunk) return 0;
-        a.gn_cpg = a.N / G; a.gn_G = G; a.gn_hw = HW; a.gn_nchunk = nchunk;
-        return nchunk;
-    }
+    if (!g_sw.gn_fuse || a.f8 || a.C8 || a.geglu || a.ln_c1 || !a.C || G <= 0 || a.N % G || a.N % 4 || HW <= 0 || a.M % HW) return 0;
+    GemmArgs t = a; t.gn_partial = nullptr;
+    const GemmPick p = gemm_pick(t);
     const int cpg = a.N / G;
-    const TileSel t = gemm_tile(a.M, a.N, a.K, false, fix ? a.splitk : 1, true, a.mode == 0);
-    int bm, bn;
-    if (t.bm == 256 && t.bn > 128) { bm = 256; bn = t.bn; }
-    else if (t.bm == 256) { bm = 256; bn = 128; }
-    else if (t.bn == 32) { bm = 128; bn = 32; }
-    else if (t.bm == 128 && t.bn == 64) { bm = 128; bn = 64; }
-    else if (t.bm == 64) { bm = 64; bn = t.bn == 160 ? 160 : 64; }
-    else if (t.bn == 160) { bm = 128; bn = 160; }
-    else { bm = 128; bn = 128; }
-    static const bool wide_off = getenv("LDX_GN_FUSE_WIDE") && atoi(getenv("LDX_GN_FUSE_WIDE")) == 0;
-    const bool wide_ok = bm == 256 && bn > 160 && bn <= 256 && !wide_off && a.N % bn == 0 && a.M % bm == 0 && !a.geglu;      // the column-major output stage of the ping-pong tiles (gemm_common.h GNW): whole tiles only
-    if ((bn > 160 && !wide_ok) || bn % cpg || HW % bm || (bn / cpg) * 2 > 256) return 0;          // epilogue support (gemm_common.h GNS / GNW); groups must not straddle tile columns, tiles must not straddle images
-    const int nchunk = HW / bm;
-    if (nchunk > max_chunks) return 0;
+    int nchunk = 0;
+    if (p.family == GF_CONV_PATCH) nchunk = conv_patch_gn_chunks(a, HW, G);        // one chunk per 32 x 16-pixel tile (N = 128 only), or no fusion
+    else if (p.reduce == RED_LAUNCH) { int R = 1; nchunk = g_sw.gn_fuse_splitk ? splitk_gn_geom(a, HW, G, max_chunks, &R) : 0; }      // split-K: the reduce launch produces the statistics (splitk_reduce_gn_kernel)
+    else {        // the tile's own epilogue (with the in-kernel split-K reduction: run by the last workgroup of a tile)
+        const bool wide_ok = p.bm == 256 && p.bn > 160 && g_sw.gn_fuse_wide && a.N % p.bn == 0 && a.M % p.bm == 0;      // the column-major output stage of the ping-pong tiles (gemm_common.h GNW): whole tiles only
+        if ((p.bn > 160 && !wide_ok) || p.bn % cpg || HW % p.bm || (p.bn / cpg) * 2 > 256) return 0;          // epilogue support (gemm_common.h GNS / GNW); groups must not straddle tile columns, tiles must not straddle images
+        nchunk = HW / p.bm;
+    }
+    if (!nchunk || nchunk > max_chunks) return 0;
     a.gn_cpg = cpg; a.gn_G = G; a.gn_hw = HW; a.gn_nchunk = nchunk;
     return nchunk;
+}
+bool gemm_gn_fuse_enabled() { return g_sw.gn_fuse; }
+
+// Last defence for GemmArgs::gn_partial: the geometry the plan carries must be what gemm_gn_fuse says about this very launch.  Planner and launcher ask the same
+// gemm_pick, so this fires only on a bug inside that one function or on arguments changed after planning — and then aborts instead of feeding the GroupNorm stale rows.
+static void gemm_gn_check(const GemmArgs& a) {
+    GemmArgs t = a;
+    const int nchunk = a.gn_partial ? gemm_gn_fuse(t, a.gn_hw, a.gn_G, a.gn_nchunk) : 0;
+    if (!a.gn_partial || (nchunk == a.gn_nchunk && t.gn_cpg == a.gn_cpg)) return;
+    fprintf(stderr, "ldx: GroupNorm-statistics geometry mismatch: planned for %d chunks of an image of %d rows, %d channels per group; this launch gives %d chunks\n", a.gn_nchunk, a.gn_hw, a.gn_cpg, nchunk);
+    abort();
 }
 
 // heuristic shared with the planner: how many K splits for an (M, N, K) problem
 int gemm_choose_splitk(int M, int N, int K, bool geglu) {
     if (geglu) return 1;
-    static const int force_sk = getenv("LDX_SPLITK") ? atoi(getenv("LDX_SPLITK")) : 0;      // experiment switch
-    if (force_sk && K % BK == 0 && K / BK >= force_sk * 2) return force_sk;
+    if (g_sw.splitk && K % BK == 0 && K / BK >= g_sw.splitk * 2) return g_sw.splitk;
     const int bn = (N % 160 == 0 && N % 128 != 0) ? 160 : 128;
     const int tiles = ((M + 127) / 128) * ((N + bn - 1) / bn);
     const int nk = K / BK;
     // one workgroup per CU (193..256 tiles, or that many 160-wide ones) runs a long K loop alone: a CU advances two co-resident
     // workgroups by one K-tile each in about the time a lone one needs for its own, so halving K for twice the workgroups nearly
     // halves the launch; the fp32 partials + reduce pass cost ~15 us (64^2-level 3x3 convs 640 -> 640: 122 -> ~80 us)
-    static const bool split2 = !getenv("LDX_NO_SPLIT2");
-    if (split2 && K % BK == 0 && nk >= 60) {
+    if (!g_sw.no_split2 && K % BK == 0 && nk >= 60) {
         const long mt = (M + 127) / 128;
         const long t160 = (N % 160 == 0) ? mt * (N / 160) : 0;
         if ((tiles > 192 && tiles <= 256) || (tiles > 256 && tiles < 512 && t160 > 192 && t160 <= 256)) return 2;
@@ -812,6 +784,65 @@ int gemm_choose_splitk(int M, int N, int K, bool geglu) {
     return s < 2 ? 1 : s;
 }
 
+template <typename T, int MODE, int BM, int BN, int WM = 2, bool F8 = false, bool LNF = false>
+static void launch_gemm_inst(const GemmArgs& a, int S, hipStream_t s) {
+    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * S;
+    const size_t lds = 2 * stage_bytes<BM, BN>();
+    static DevOnce once;
+    set_dyn_lds(once, (const void*)gemm_kernel<T, MODE, BM, BN, WM, F8, LNF>, (int)lds);
+    hipLaunchKernelGGL((gemm_kernel<T, MODE, BM, BN, WM, F8, LNF>), dim3(tiles), dim3(WM * 128), lds, s, a);
+}
+
+// the register-staged instantiations (GF_TILE, GF_TILE_MX) by the pick's tile
+template <typename T, int MODE>
+static void launch_gemm_tile(const GemmArgs& a, const GemmPick& p, hipStream_t s) {
+    const int tile = p.bm * 1000 + p.bn;
+    if constexpr (MODE == 0) {
+        if (p.f8 && tile == 256128) return launch_gemm_inst<T, 0, 256, 128, 4, true>(a, p.S, s);      // opt-in (LDX_GEMM_TILE)
+        if (p.f8 && tile == 64064) return launch_gemm_inst<T, 0, 64, 64, 2, true>(a, p.S, s);
+        if (p.f8 && tile == 128160) return launch_gemm_inst<T, 0, 128, 160, 2, true>(a, p.S, s);
+        if (p.f8 && tile == 128128) return launch_gemm_inst<T, 0, 128, 128, 2, true>(a, p.S, s);
+        if (p.lnf && tile == 64064) return launch_gemm_inst<T, 0, 64, 64, 2, false, true>(a, 1, s);
+        if (p.lnf && tile == 128160) return launch_gemm_inst<T, 0, 128, 160, 2, false, true>(a, 1, s);
+        if (p.lnf && tile == 128128) return launch_gemm_inst<T, 0, 128, 128, 2, false, true>(a, 1, s);
+    }
+    const bool lean = !p.f8 && !p.lnf;
+    if (lean && tile == 128032) return launch_gemm_inst<T, MODE, 128, 32>(a, p.S, s);
+    if (lean && tile == 128064) return launch_gemm_inst<T, MODE, 128, 64>(a, p.S, s);
+    if (lean && tile == 64064) return launch_gemm_inst<T, MODE, 64, 64>(a, p.S, s);
+    if (lean && tile == 128160) return launch_gemm_inst<T, MODE, 128, 160>(a, p.S, s);
+    if (lean && tile == 128128) return launch_gemm_inst<T, MODE, 128, 128>(a, p.S, s);
+    fprintf(stderr, "ldx: gemm_pick chose a %d x %d tile (mode %d, f8 %d, ln-fold %d) that has no instantiation\n", p.bm, p.bn, MODE, (int)p.f8, (int)p.lnf);
+    abort();
+}
+
+template <typename T>
+static void launch_gemm_t(const GemmArgs& a, const GemmPick& p, hipStream_t s) {
+    if (p.family == GF_RING) launch_gemm_ring(a, DTypeOf<T>::v, s);
+    else if (p.family == GF_PP || p.family == GF_PP_MX) launch_gemm_pp(a, p.bn, p.lnf, p.S, DTypeOf<T>::v, s);
+    else if (a.mode == 0) launch_gemm_tile<T, 0>(a, p, s);
+    else launch_gemm_tile<T, 1>(a, p, s);
+    if (p.reduce == RED_LAUNCH_GN) {       // reduce + GroupNorm statistics (gemm_gn_fuse set the geometry, gemm_gn_check held it to this launch)
+        int R = 1;
+        const int nchunk = splitk_gn_geom(a, a.gn_hw, a.gn_G, a.gn_nchunk, &R);
+        hipLaunchKernelGGL((splitk_reduce_gn_kernel<T>), dim3(nchunk, a.M / a.gn_hw), dim3((a.N / 4) * R), (size_t)R * a.N * 2 * sizeof(float), s, a, R);
+    } else if (p.reduce == RED_LAUNCH) {
+        long total = (long)a.M * ((a.N + 3) / 4);
+        int grid = (int)((total + 255) / 256); if (grid > 2048) grid = 2048;
+        hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(grid), dim3(256), 0, s, a);
+    }
+}
+
+void launch_gemm(const GemmArgs& a0, DType dt, hipStream_t s) {
+    GemmArgs a = a0; a.ep_general = g_sw.ep_general;
+    const GemmPick p = gemm_pick(a);
+    if (!p.launches) return;
+    gemm_gn_check(a);
+    if (p.family == GF_CONV_PATCH) { launch_conv_patch(a, dt, s); return; }
+    if (p.reduce != RED_IN_KERNEL) a.sk_count = nullptr;        // the kernels reduce in place iff sk_count is set
+    if (dt == DT_BF16) launch_gemm_t<__bf16>(a, p, s); else launch_gemm_t<_Float16>(a, p, s);
+}
+
 template <typename T, bool F8>
 static void launch_gemm2_t(const GemmArgs& a, const GemmArgs& b, hipStream_t s) {
     const int ta = ((a.M + 127) / 128) * ((a.N + 127) / 128), tb = ((b.M + 127) / 128) * ((b.N + 127) / 128);
@@ -820,50 +851,14 @@ static void launch_gemm2_t(const GemmArgs& a, const GemmArgs& b, hipStream_t s) 
     set_dyn_lds(once, (const void*)gemm2_kernel<T, 128, 128, F8>, (int)lds);
     hipLaunchKernelGGL((gemm2_kernel<T, 128, 128, F8>), dim3(ta + tb), dim3(256), lds, s, a, b, ta);
 }
-// 256-row ping-pong tiles for a two-problem launch: same cost model as gemm_tile over the combined tile count; 0 = keep 128 x 128
-static int gemm2_pp_bn(const GemmArgs& a, const GemmArgs& b) {
-    static const int pp_policy = getenv("LDX_PP") ? atoi(getenv("LDX_PP")) : 1;
-    static const int pp_mink = getenv("LDX_PP_MINK") ? atoi(getenv("LDX_PP_MINK")) : 1024;
-    if (!pp_policy || a.f8 || b.f8 || a.K < pp_mink || b.K < pp_mink || a.N < 256 || b.N < 256 || a.M + b.M < 1024) return 0;
-    double best = 1e30; int best_bn = 0;
-    const int cand[5] = {256, 224, 192, 160, 128};
-    const double rate[5] = {1.35, pp_r224, pp_r192, 1.15, 0.92};
-    for (int c = 0; c < 5; ++c) {
-        if (rate[c] <= 0) continue;
-        const long t = (long)((a.M + 255) / 256) * ((a.N + cand[c] - 1) / cand[c]) + (long)((b.M + 255) / 256) * ((b.N + cand[c] - 1) / cand[c]);
-        if (t < 192) continue;
-        const double cost = (double)((t + 255) / 256) * 256.0 * 256.0 * cand[c] / rate[c];
-        if (cost < best) { best = cost; best_bn = cand[c]; }
-    }
-    if (!best_bn) return 0;
-    const long to = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) + (long)((b.M + 127) / 128) * ((b.N + 127) / 128);
-    const double cost_old = (double)((to + 511) / 512) * 512.0 * 128.0 * 128.0 / 0.84;
-    return (pp_policy >= 2 || best < 0.95 * cost_old) ? best_bn : 0;
-}
-// both plain mode, no split-K, no GEGLU, same operand kind (16-bit or MX); 128x128 tiles, or 256-row ping-pong tiles (16-bit)
 void launch_gemm2(const GemmArgs& a, const GemmArgs& b, DType dt, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) { launch_gemm(b, dt, s); return; }
     if (b.M <= 0 || b.N <= 0) { launch_gemm(a, dt, s); return; }
-    GemmArgs x = a, y = b; x.splitk = y.splitk = 1; { static const int epg = getenv("LDX_EP_GENERAL") ? atoi(getenv("LDX_EP_GENERAL")) : 0; x.ep_general = y.ep_general = epg; }
-    if (x.f8 && y.f8 && x.M + y.M >= 1024 && y.N >= 256) {       // MX: the two streams of a Flux double block / the two halves of linear1
-        const bool c8 = x.C8 || y.C8;
-        const int bn = mx_pp_bn((x.M + 255) / 256, (x.M + 127) / 128, x.N, x.K < y.K ? x.K : y.K, 1, c8, (y.M + 255) / 256, (y.M + 127) / 128, y.N);
-        if (bn) { launch_gemm_pp2(x, y, bn, dt, s); return; }
-    }
-    if (const int bn = gemm2_pp_bn(x, y)) {
-        launch_gemm_pp2(x, y, bn, dt, s);
-        return;
-    }
-    if (dt == DT_BF16) { if (a.f8) launch_gemm2_t<__bf16, true>(x, y, s); else launch_gemm2_t<__bf16, false>(x, y, s); }
-    else { if (a.f8) launch_gemm2_t<_Float16, true>(x, y, s); else launch_gemm2_t<_Float16, false>(x, y, s); }
-}
-
-static const int ep_general_env = getenv("LDX_EP_GENERAL") ? atoi(getenv("LDX_EP_GENERAL")) : 0;
-void launch_gemm(const GemmArgs& a0, DType dt, hipStream_t s) {
-    if (a0.M <= 0 || a0.N <= 0) return;
-    GemmArgs a = a0; a.ep_general = ep_general_env;
-    if (a.mode == 1 && conv_patch_ok(a)) { launch_conv_patch(a, dt, s); return; }      // conv_patch.hip: narrow 3x3 convs with the input patch resident in LDS
-    if (dt == DT_BF16) launch_gemm_t<__bf16>(a, s); else launch_gemm_t<_Float16>(a, s);
+    const GemmPick p = gemm_pick(a, &b);
+    GemmArgs x = a, y = b; x.splitk = y.splitk = 1; x.ep_general = y.ep_general = g_sw.ep_general;
+    if (p.family == GF_PP2 || p.family == GF_PP2_MX) launch_gemm_pp2(x, y, p.bn, dt, s);
+    else if (dt == DT_BF16) { if (p.f8) launch_gemm2_t<__bf16, true>(x, y, s); else launch_gemm2_t<__bf16, false>(x, y, s); }
+    else { if (p.f8) launch_gemm2_t<_Float16, true>(x, y, s); else launch_gemm2_t<_Float16, false>(x, y, s); }
 }
 
 // ------------------------------------------------------------------------------------------

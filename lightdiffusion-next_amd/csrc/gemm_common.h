@@ -18,7 +18,8 @@ constexpr int BK = 64;
 // gemm_ring.hip: 64 x 160 LDS-DMA ring tiles for mid-size plain GEMMs; gemm_tile (gemm.hip) asks gemm_ring_ok
 bool gemm_ring_ok(int M, int N, int K, bool plain, int splitk);
 void launch_gemm_ring(const GemmArgs& a, DType dt, hipStream_t s);
-// conv_patch.hip: patch-resident 3x3 conv for N = 32 / 64 / 128 (ESRGAN, VAE last level); launch_gemm asks conv_patch_ok
+// conv_patch.hip: patch-resident 3x3 conv for N = 32 / 64 / 128 (ESRGAN, VAE last level); gemm_pick asks conv_patch_ok
+constexpr int CONV_PATCH_BM = 512;      // output rows per tile: 16 x 32 pixels
 bool conv_patch_ok(const GemmArgs& a);
 int conv_patch_gn_chunks(const GemmArgs& a, int HW, int G);
 void launch_conv_patch(const GemmArgs& a, DType dt, hipStream_t s);

@@ -16,7 +16,6 @@ LDX_PP_DECL(f16)
 #undef LDX_PP_DECL
 
 void launch_gemm_pp(const GemmArgs& a, int bn, bool lnf, int S, DType dt, hipStream_t s) {
-    gemm_gn_tile_check(a, 256, (lnf || (a.geglu && bn != 256)) && bn != 160 ? 128 : bn, S);
     if (a.mode == 0 && a.f8) { launch_gemm_pp_mx(a, bn, S, dt, s); return; }      // MX fp8 operands
     if (a.mode == 0) { if (dt == DT_BF16) launch_pp_plain_bf16(a, bn, lnf, S, s); else launch_pp_plain_f16(a, bn, lnf, S, s); }
     else { if (dt == DT_BF16) launch_pp_conv_bf16(a, bn, S, s); else launch_pp_conv_f16(a, bn, S, s); }

@@ -150,7 +150,6 @@ bool gemm_ring_ok(int M, int N, int K, bool plain, int splitk) {
 }
 
 void launch_gemm_ring(const GemmArgs& a, DType dt, hipStream_t s) {
-    gemm_gn_tile_check(a, GR_BM, GR_BN, 1);
     const unsigned tiles = (unsigned)(((a.M + GR_BM - 1) / GR_BM) * ((a.N + GR_BN - 1) / GR_BN));
     if (dt == DT_BF16) {
         static DevOnce once;

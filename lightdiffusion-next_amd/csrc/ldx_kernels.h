@@ -88,14 +88,27 @@ struct GemmArgs {
 };
 // Can launch_gemm(a) produce GroupNorm statistics for a consumer GroupNorm(G groups) over [B][HW][a.N]?  If yes, returns the number of
 // tile rows per batch image (the consumer's chunk count) and fills a.gn_* except gn_partial; 0 = not fusable (the GroupNorm runs its own pass).
-// Launch-side guard for GemmArgs::gn_partial without split-K: the tile the launcher instantiates must be the one gemm_gn_fuse() planned the partial
-// layout for (chunk = one BM-row tile of an image, whole groups inside a BN-column tile); aborts otherwise instead of feeding the GroupNorm stale rows.
-void gemm_gn_tile_check(const GemmArgs& a, int BM, int BN, int S);
+// It asks gemm_pick() below for the kernel and applies that kernel's epilogue conditions; launch_gemm() holds a set gn_partial to the same answer and aborts otherwise.
 int gemm_gn_fuse(GemmArgs& a, int HW, int G, int max_chunks);
+bool gemm_gn_fuse_enabled();                                // LDX_GN_FUSE != 0 (the engine's row-block producers ask)
 void launch_gemm(const GemmArgs& a, DType dt, hipStream_t s);
 // two independent plain GEMMs (mode 0, no split-K / GEGLU, both 16-bit or both MX) as one launch of 128x128 tiles
 void launch_gemm2(const GemmArgs& a, const GemmArgs& b, DType dt, hipStream_t s);
 int gemm_choose_splitk(int M, int N, int K, bool geglu);   // 1 = no split
+// Which kernel launch_gemm(a) — launch_gemm2(a, *b) with a second problem — runs: pure host arithmetic over the arguments and the LDX_* dispatch switches, which are
+// read once when the library loads.  The launchers switch on it, the planner asks it (gemm_gn_fuse, Engine::n_launches), ldx_op_gemm_pick shows it to tests.
+enum GemmFamily : int { GF_TILE = 0, GF_TILE2, GF_PP, GF_PP2, GF_RING, GF_CONV_PATCH, GF_TILE_MX, GF_TILE2_MX, GF_PP_MX, GF_PP2_MX };      // register-staged tile (gemm.hip), ping-pong (gemm_pp.inc), ring, patch-resident conv; 2: two problems; MX: fp8 operands
+enum GemmReduce : int { RED_NONE = 0, RED_LAUNCH, RED_LAUNCH_GN, RED_IN_KERNEL };      // split-K partials: no split / reduce launch / reduce launch that also writes the GroupNorm statistics / last workgroup of a tile
+struct GemmPick {
+    GemmFamily family;
+    int bm, bn;                    // the tile as the instantiation has it (not as the heuristics asked for it)
+    int wm;                        // register-staged tiles: workgroup threads / 128; 0 elsewhere
+    bool f8, lnf;                  // MX fp8 operands; LayerNorm folded in
+    int S;                         // K splits in effect (1: none)
+    GemmReduce reduce;
+    int launches;                  // kernel launches in all (0: empty problem)
+};
+GemmPick gemm_pick(const GemmArgs& a, const GemmArgs* b = nullptr);
 constexpr int SK_FIXUP_MAX_S = 4;                          // in-kernel fix-up up to this many splits (the last arriver reads S slabs back to back); above: reduce launch
 constexpr int SK_COUNTERS = 8192;                          // per-tile counters a caller keeps for it
 #ifdef LDX_SK_FIXUP_BUILD
@@ -104,7 +117,7 @@ inline size_t gemm_sk_ws_floats(int M, int N, int S) { return (size_t)S * ((size
 inline size_t gemm_sk_ws_floats(int M, int N, int S) { return (size_t)S * (size_t)M * (size_t)N; }      // [S][M][N] fp32 partials for the reduce launch (the slab layout only exists in fix-up builds)
 #endif
 bool gemm_sk_fixup(const GemmArgs& a);                     // will launch_gemm(a) reduce inside the kernel?  (opt-in: LDX_SK_FIXUP=1; measured slower than the reduce launch)
-// 256-row ping-pong tiles (gemm_pp.hip; chosen by launch_gemm's cost model): bn = 128 / 160 / 256 tile width, lnf = GemmArgs::ln_c1 fold, S = K splits
+// 256-row ping-pong tiles (gemm_pp.hip; GemmPick family GF_PP* ): bn = the tile width as gemm_pick gives it, lnf = GemmArgs::ln_c1 fold, S = K splits
 void launch_gemm_pp(const GemmArgs& a, int bn, bool lnf, int S, DType dt, hipStream_t s);
 void launch_gemm_pp2(const GemmArgs& a, const GemmArgs& b, int bn, DType dt, hipStream_t s);
 

@@ -37,6 +37,14 @@ def test_op_tests_on_the_forced_ring_tile(ldx_lib):
     assert r.returncode == 0 and " passed" in tail and "failed" not in tail, tail
 
 
+def _pick_family(L, M, N, K, conv=None):
+    """The kernel family the dispatcher gives ldx_op_gemm (conv = (Cin, Hin, Win, Hout, Wout, stride): ldx_op_conv3x3) for this shape: ldx_op_gemm_pick, out[0]."""
+    import ctypes as C
+    out = (C.c_int32 * 10)()
+    assert L.ldx_op_gemm_pick(M, N, K, 1 if conv else 0, 0, -1, 0, 0, 0, *(conv or (0,) * 6), 0, 0, 0, 0, 0, 0, out) == 0
+    return ("tile", "tile2", "pingpong", "pingpong2", "ring", "conv_patch", "tile_mx", "tile2_mx", "pingpong_mx", "pingpong2_mx")[out[0]]
+
+
 @pytest.mark.parametrize("shape", [(2048, 1280, 1280), (2048, 3840, 1280), (2000, 1280, 640), (8192, 640, 2560)])
 def test_ring_gemm_shapes_match_torch(ldx_lib, shape):
     """Un-forced: shapes the planner sends to the ring kernel (M 2048, N = K = 1280: the SD1.5 32^2 level's proj_in / to_out / to_q / proj_out) and, with
@@ -48,6 +56,8 @@ def test_ring_gemm_shapes_match_torch(ldx_lib, shape):
     p = lambda t: C.c_void_p(t.data_ptr())
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     M, N, K = shape
+    if shape == (2048, 1280, 1280):
+        assert _pick_family(L, M, N, K) == "ring"
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     A = torch.randn(M, K, device="cuda", generator=g).bfloat16(); W = (torch.randn(N, K, device="cuda", generator=g) / K ** 0.5).bfloat16()
     bias = torch.randn(N, device="cuda", generator=g); R = torch.randn(M, N, device="cuda", generator=g).bfloat16()
@@ -81,21 +91,25 @@ def test_ring_gemm_short_k(ldx_lib, K):
 
 def test_large_shapes_pick_the_pingpong_kernel_and_match_torch(ldx, ldx_lib):
     """Un-forced: shapes the cost model sends to the ping-pong kernel (plain GEMM with long K, 3x3 conv at the level-0 size), against
-    torch fp32 on the same 16-bit operands."""
+    torch fp32 on the same 16-bit operands.  The probe (ldx_op_gemm_pick) says which kernel a shape gets: M 4096 N 1280 K 2048, this test's GEMM since it
+    was written, never reached the ping-pong kernel (80 tiles of 256 x 256 at most: below the cost model's 192) and runs on 128 x 160 register-staged
+    tiles; it keeps its comparison, and M 8192 is the plain GEMM that is held to the ping-pong family."""
     import ctypes as C
     import torch
     L = ldx_lib
     p = lambda t: C.c_void_p(t.data_ptr())
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     g = torch.Generator(device="cuda").manual_seed(5)
-    M, N, K = 4096, 1280, 2048
-    A = torch.randn(M, K, device="cuda", generator=g).bfloat16(); W = (torch.randn(N, K, device="cuda", generator=g) / K ** 0.5).bfloat16()
-    bias = torch.randn(N, device="cuda", generator=g); R = torch.randn(M, N, device="cuda", generator=g).bfloat16()
-    Cc = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-    assert L.ldx_op_gemm(p(A), K, p(W), M, N, K, p(bias), None, 0, 1, 0, p(R), N, p(Cc), N, None, 0, 0, st) == 0
-    ref = A.float() @ W.float().t() + bias + R.float()
-    assert float((Cc.float() - ref).norm() / ref.norm()) < 4e-3
+    for (M, N, K), family in (((4096, 1280, 2048), "tile"), ((8192, 1280, 2048), "pingpong")):
+        assert _pick_family(L, M, N, K) == family
+        A = torch.randn(M, K, device="cuda", generator=g).bfloat16(); W = (torch.randn(N, K, device="cuda", generator=g) / K ** 0.5).bfloat16()
+        bias = torch.randn(N, device="cuda", generator=g); R = torch.randn(M, N, device="cuda", generator=g).bfloat16()
+        Cc = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+        assert L.ldx_op_gemm(p(A), K, p(W), M, N, K, p(bias), None, 0, 1, 0, p(R), N, p(Cc), N, None, 0, 0, st) == 0
+        ref = A.float() @ W.float().t() + bias + R.float()
+        assert float((Cc.float() - ref).norm() / ref.norm()) < 4e-3
     B, H, Cin, Cout = 2, 64, 320, 320
+    assert _pick_family(L, B * H * H, Cout, 9 * Cin, conv=(Cin, H, H, H, H, 1)) == "pingpong"
     X = torch.randn(B, H, H, Cin, device="cuda", generator=g).bfloat16()
     Wc = (torch.randn(Cout, Cin, 3, 3, device="cuda", generator=g) / (9 * Cin) ** 0.5)
     Wp = Wc.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).contiguous().bfloat16()
