@@ -377,6 +377,14 @@ int ldx_op_gemm2_mx(const void* A1, int lda1, const void* SA1, int sa_ld1, const
 int ldx_op_gemm_pick(int M, int N, int K, int mode, int geglu, int splitk, int f8, int c8, int ln_fold,
                      int Cin, int Hin, int Win, int Hout, int Wout, int stride, int M2, int N2, int K2,
                      int gn_hw, int gn_groups, int gn_max_chunks, int32_t* out);
+/* Read-only probe: which kernel ldx_op_attention / ldx_op_attention_bias / ldx_op_attention_mx and the engines' plans would launch for a problem described by plain
+ * integers.  Launches nothing and touches no device.  causal / bias / o8 (MX fp8 output, D = 128 only) / knorm_ws (the key-norm workspace of the pipelined kernels) say
+ * what is present; ldq .. ldo are the row strides in elements (ldo also the byte stride of an MX fp8 output); operands count as 16-byte aligned.
+ * out[0 .. 12] = kernel family (0 attn_kernel on 16x16 MFMAs, 1 attn32_kernel, 2 attn32ap_kernel, 3 attn32g_kernel, 4 attn40p_kernel, 5 attn128p_kernel, 6 attn512_kernel),
+ * three template arguments as instantiated (attn_kernel KS, DT, QT; attn32g_kernel NKS, NDT, ONES; attn32_kernel KVB, VAR; attn32ap_kernel VAR; else 0), attn32g's K prefetch
+ * ring on / off, queries per workgroup, threads per workgroup, workgroups, dynamic LDS bytes, key-norm launch first (0 / 1), key splits in effect (attn512, with the
+ * workspace the planner gives it; > 1: a merge launch follows), MX fp8 output allowed for the shape (0 / 1), kernel launches. */
+int ldx_op_attn_pick(int B, int H, int Nq, int Mk, int D, int causal, int bias, int o8, int ldq, int ldk, int ldv, int ldo, int knorm_ws, int32_t* out);
 int ldx_op_conv3x3(const void* X, int ldx, const void* W, int B, int Hin, int Win, int Cin, int Cout,
                    int stride, int Hout, int Wout, int resize_to_out, const float* bias,
                    const float* rowvec, int rowvec_ld, const void* R, int ldr, void* Y, int ldy,

@@ -22,6 +22,7 @@
 // Workgroup = 4 waves x 32 queries; K and V^T tiles of 64 keys double-buffered in LDS, global
 // loads register-staged one block ahead.  Head dims D in {8..160}, D % 8 == 0: the QK^T
 // contraction is padded to 32*KS, the PV output to 16*DT rows (zero-filled in LDS/registers).
+#include <stdio.h>
 #include <stdlib.h>
 #include "ldx_device.h"
 #include "ldx_kernels.h"
@@ -578,45 +579,7 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(const AttnArgs p) {
     }
 }
 
-template <typename T, int KVB, int KROWB, int VROWB, int VAR = 0>
-static void launch_attn32_k(const AttnArgs& a, hipStream_t s) {
-    const size_t lds = 2 * KVB * (KROWB + VROWB);
-    static DevOnce once;
-    set_dyn_lds(once, (const void*)attn32_kernel<T, KVB, KROWB, VROWB, VAR>, (int)lds);
-    dim3 grid(((a.Nq + 255) / 256) * a.H * a.B);
-    hipLaunchKernelGGL((attn32_kernel<T, KVB, KROWB, VROWB, VAR>), grid, dim3(256), lds, s, a);
-}
 #include "attn32ap.inc"
-template <typename T>
-static void launch_attn32(const AttnArgs& a, hipStream_t s) {
-    // 8-wave two-group kernel (round 3, attn32ap.inc) when its 512-query workgroups still fill the chip.  LDX_ATTN32_AP: 0 off, 1 (default) phases
-    // separated by the barriers only (hipcc interleaves the next PV MFMAs with the softmax), 2 strict phases, 3 strict + s_setprio around the MFMAs.
-    // Same box, B2 H8 N16384 D40: attn32_kernel 1.197 ms, strict 1.14-1.21, default 1.12-1.15; step 60.02 -> 61.18 it/s.
-    static const int ap = getenv("LDX_ATTN32_AP") ? atoi(getenv("LDX_ATTN32_AP")) : 1;
-    static const long ap_minwg = getenv("LDX_ATTN32_AP_MINWG") ? atol(getenv("LDX_ATTN32_AP_MINWG")) : 256;
-    if (ap && a.Mk >= 64 && (long)((a.Nq + 511) / 512) * a.H * a.B >= ap_minwg) {
-        switch (ap) {
-            case 2: launch_attn32ap<T, 0>(a, s); break;
-            case 3: launch_attn32ap<T, 1>(a, s); break;
-#ifdef LDX_ATTN_ABLATE                                    // measured-and-not-adopted variants (6, 7: correct, bit-identical) and timing ablations
-            case 6: launch_attn32ap<T, 66>(a, s); break;      // (wrong results) of profiles/ubench/README.md round 3.  6: split softmax (VAR & 64), +6 %
-            case 7: launch_attn32ap<T, 130>(a, s); break;     // 7: K fragments read a phase early (VAR & 128), +-0.5 %
-            case 4: launch_attn32ap<T, 4>(a, s); break;       // no MFMAs
-            case 8: launch_attn32ap<T, 8>(a, s); break;       // no softmax
-            case 12: launch_attn32ap<T, 12>(a, s); break;     // neither: staging + barriers + fragment reads
-            case 34: launch_attn32ap<T, 34>(a, s); break;     // default schedule without the 64 fma of exp2(s * c - m * c)
-#endif
-            default: launch_attn32ap<T, 2>(a, s); break;
-        }
-        return;
-    }
-    static const int kvb = getenv("LDX_ATTN32_KVB") ? atoi(getenv("LDX_ATTN32_KVB")) : 64;       // experiment switch
-    // strides 160 / 160 had 2-way conflicts on every fragment read (SQ_LDS_BANK_CONFLICT 88.1 M -> 21.0 M cycles per launch with 144 / 192;
-    // same time at D = 40, which is VALU / MFMA bound)
-    static const int var = getenv("LDX_ATTN32_VAR") ? atoi(getenv("LDX_ATTN32_VAR")) : 1;               // 1: V^T fragments prefetched before the softmax (1.219 -> 1.206 ms at B2 H8 N16384, twice on one box); 0: read at the PV MFMAs
-    if (var == 1) { launch_attn32_k<T, 64, 144, 192, 1>(a, s); return; }
-    if (kvb == 128 && a.Mk >= 1024) launch_attn32_k<T, 128, 144, 192>(a, s); else launch_attn32_k<T, 64, 144, 192>(a, s);
-}
 
 
 // Generalisation of attn32_kernel to the other head dims of the path (D = 64 CLIP/T5-sized, 80 and 160 for SD1.5 levels 1-3,
@@ -915,142 +878,185 @@ __global__ __launch_bounds__(256, 2) void attn32g_kernel(const AttnArgs p) {
     }
 }
 
-template <typename T, int NKS, int NDT, int QT, bool ONES>
-static void launch_attn32g(const AttnArgs& a, hipStream_t s) {
-    constexpr int KROW = G32_KROW(NKS), VROW = G32_VROW(NDT);
-    const size_t lds = 2 * AT_KV * (KROW + VROW);
-    constexpr int QB = 128 * QT;
-    dim3 grid(((a.Nq + QB - 1) / QB) * a.H * a.B);
-    static const bool kpf = !(getenv("LDX_ATTN_KPF") && atoi(getenv("LDX_ATTN_KPF")) == 0);      // K fragment prefetch ring (round 3); 0: hipcc's just-in-time reads
-    if (kpf) {
-        static DevOnce once;
-        set_dyn_lds(once, (const void*)attn32g_kernel<T, NKS, NDT, QT, ONES, true>, (int)lds);
-        hipLaunchKernelGGL((attn32g_kernel<T, NKS, NDT, QT, ONES, true>), grid, dim3(256), lds, s, a);
-    } else {
-        static DevOnce once;
-        set_dyn_lds(once, (const void*)attn32g_kernel<T, NKS, NDT, QT, ONES, false>, (int)lds);
-        hipLaunchKernelGGL((attn32g_kernel<T, NKS, NDT, QT, ONES, false>), grid, dim3(256), lds, s, a);
-    }
-}
-// head dims served by the generic 32x32x16 kernel (LDX_ATTN32G bit mask 1: D=80, 2: D=160, 4: D=128, 8: D=64).  Default 7: same-box
-// step A/B 54.76 -> 55.34 it/s with D = 80 and 160; D = 128 (Flux, VALU denominator instead of a fifth d tile) 19.6 -> 18.4 ms of
-// attention per forward; D = 64 only appears with a causal mask or a bias on this path.
-static int attn32g_variant(const AttnArgs& a) {      // 0: not taken, else the head dim handled by a 32x32 instantiation
-    static const int mask = getenv("LDX_ATTN32G") ? atoi(getenv("LDX_ATTN32G")) : 7;
-    if (!mask || a.causal || a.bias) return 0;
-    const long wg = (long)((a.Nq + 127) / 128) * a.H * a.B;
-    static const long min_wg = getenv("LDX_ATTN32G_MINWG") ? atol(getenv("LDX_ATTN32G_MINWG")) : 16;      // 64 -> 16: +0.9 % on the 512^2 step (the 16x16 D = 160 instantiation spills)
-    if (wg < min_wg) return 0;
-    if ((mask & 1) && a.D == 80) return 80;
-    if ((mask & 2) && a.D == 160) return 160;
-    if ((mask & 4) && a.D == 128) return 128;
-    if ((mask & 8) && a.D == 64) return 64;
-    return 0;
-}
-bool attention_mx_out_ok(const AttnArgs& a) { return attn32g_variant(a) == 128; }
-template <typename T>
-static bool try_attn32g(const AttnArgs& a, hipStream_t s) {
-    switch (attn32g_variant(a)) {
-        case 80: launch_attn32g<T, 5, 3, 1, true>(a, s); return true;
-        case 160: launch_attn32g<T, 10, 6, 1, true>(a, s); return true;
-        case 128: launch_attn32g<T, 8, 4, 1, false>(a, s); return true;
-        case 64: launch_attn32g<T, 4, 2, 1, false>(a, s); return true;
-        default: return false;
-    }
-}
-
-template <typename T, int KS, int DT, int QT>
-static void launch_attn_q(const AttnArgs& a, hipStream_t s) {
-    constexpr int STAGE = AT_KV * (AttnCfg<KS, DT>::KROWB + AttnCfg<KS, DT>::VROWB);
-    constexpr int QB = 64 * QT;
-    const size_t lds = 2 * STAGE;
-    static DevOnce once;
-    set_dyn_lds(once, (const void*)attn_kernel<T, KS, DT, QT>, (int)lds);
-    dim3 grid(((a.Nq + QB - 1) / QB) * a.H * a.B);
-    hipLaunchKernelGGL((attn_kernel<T, KS, DT, QT>), grid, dim3(256), lds, s, a);
-}
-template <typename T, int KS, int DT>
-static void launch_attn_t(const AttnArgs& a, hipStream_t s) {
-    // 64 queries per wave when the accumulators fit (DT <= 3) and the grid still fills the chip
-    if constexpr (KS == 2 && DT == 3) {
-        // D = 40 (SD1.5 level 0) on 32x32x16 MFMAs: +4.6 % in isolation, +2.2 % on the whole step; LDX_ATTN32=0 falls back
-        static const int v32 = getenv("LDX_ATTN32") ? atoi(getenv("LDX_ATTN32")) : 1;
-        if (v32 && !a.causal && !a.bias && a.D > 32 && a.D % 8 == 0 && (long)((a.Nq + 255) / 256) * a.H * a.B >= 512) { launch_attn32<T>(a, s); return; }
-    }
-    if constexpr (DT <= 3) {
-        if ((long)((a.Nq + 255) / 256) * a.H * a.B >= 512 && !a.causal) { launch_attn_q<T, KS, DT, 4>(a, s); return; }
-    }
-    // D >= 144 (DT >= 10): two 16-query tiles per wave need 12 more VGPRs than the file has (40 B of scratch per lane, hipcc
-    // -Rpass-analysis): one tile per wave there.  Only small grids / masked calls get here (attn32g takes the rest).
-    if constexpr (DT >= 10) launch_attn_q<T, KS, DT, 1>(a, s);
-    else launch_attn_q<T, KS, DT, 2>(a, s);
-}
-
-template <typename T>
-static void launch_attn_d(const AttnArgs& a, hipStream_t s) {
-    const int D = a.D;
-    if (try_attn32g<T>(a, s)) return;
-    // KS = ceil(D/32) contraction steps, DT = floor(D/16) + 1 output tiles (room for the ones column at d = D)
-    if (D < 16) launch_attn_t<T, 1, 1>(a, s);
-    else if (D < 32) launch_attn_t<T, 1, 2>(a, s);
-    else if (D == 32) launch_attn_t<T, 1, 3>(a, s);
-    else if (D < 48) launch_attn_t<T, 2, 3>(a, s);
-    else if (D < 64) launch_attn_t<T, 2, 4>(a, s);
-    else if (D == 64) launch_attn_t<T, 2, 5>(a, s);
-    else if (D < 80) launch_attn_t<T, 3, 5>(a, s);
-    else if (D < 96) launch_attn_t<T, 3, 6>(a, s);
-    else if (D == 96) launch_attn_t<T, 3, 7>(a, s);
-    else if (D < 128) launch_attn_t<T, 4, 8>(a, s);
-    else if (D == 128) launch_attn_t<T, 4, 9>(a, s);
-    else if (D < 160) launch_attn_t<T, 5, 10>(a, s);
-    else launch_attn_t<T, 5, 11>(a, s);
-}
-
-// Dispatch switches of launch_attention, read ONCE (static initialisation) — the launch path itself never calls getenv.
-// Experiments and tests that flip a switch inside one process call reload_dispatch_env() (C ABI: ldx_reload_env) after changing the environment.
-struct AttnSwitches { bool pipe40, pipe128; long minwg40, minwg128; float thr; };
+// ---------------------------------------------------------------------------------------------
+// Which kernel launch_attention takes: attn_pick() below, pure host arithmetic over the arguments and these switches.
+// Every runtime LDX_ATTN* switch of the launch path, read ONCE when the library loads — the launch path itself never calls getenv.  Experiments and tests that
+// flip a switch inside one process call reload_dispatch_env() (C ABI: ldx_reload_env) after changing the environment.
+struct AttnSwitches {
+    bool pipe, pipe128;            // LDX_ATTN_PIPE / LDX_ATTN_PIPE128 = 0: the pipelined D = 40 / D = 128 kernels off (attn32ap / attn32, attn32g instead)
+    long pipe_minwg40, pipe_minwg128;      // LDX_ATTN_PIPE_MINWG: fewest 256-query workgroups they take (256: the chip; 192: three quarters of the CUs in one round)
+    float pipe_thr;                // LDX_ATTN_PIPE_THR: their rescale threshold (tests force the rare path with small values); NaN = the type's own
+    bool pipe_kb;                  // LDX_ATTN_PIPE_KB = 0 (experiment): the exact maximum on every key block even with AttnArgs::knorm_ws
+    int attn32;                    // LDX_ATTN32 = 0: D = 40 back on the 16x16 kernel.  On 32x32x16 MFMAs: +4.6 % in isolation, +2.2 % on the whole step
+    // LDX_ATTN32_AP, the 8-wave two-group kernel (round 3, attn32ap.inc) when its 512-query workgroups still fill the chip (LDX_ATTN32_AP_MINWG): 0 off, 1 (default) phases
+    // separated by the barriers only (hipcc interleaves the next PV MFMAs with the softmax), 2 strict phases, 3 strict + s_setprio around the MFMAs.
+    // Same box, B2 H8 N16384 D40: attn32_kernel 1.197 ms, strict 1.14-1.21, default 1.12-1.15; step 60.02 -> 61.18 it/s.
+    int ap; long ap_minwg;
+    // attn32_kernel: LDX_ATTN32_VAR 1: V^T fragments prefetched before the softmax (1.219 -> 1.206 ms at B2 H8 N16384, twice on one box); 0: read at the PV MFMAs, and then
+    // LDX_ATTN32_KVB = 128 (experiment) stages 128 keys per block from Mk = 1024 on
+    int kvb, var;
+    bool kpf;                      // LDX_ATTN_KPF = 0: attn32g without its K fragment prefetch ring (round 3): hipcc's just-in-time reads
+    // head dims served by the generic 32x32x16 kernel (LDX_ATTN32G bit mask 1: D=80, 2: D=160, 4: D=128, 8: D=64).  Default 7: same-box step A/B 54.76 -> 55.34 it/s with
+    // D = 80 and 160; D = 128 (Flux, VALU denominator instead of a fifth d tile) 19.6 -> 18.4 ms of attention per forward; D = 64 only appears with a causal mask or a
+    // bias on this path.  LDX_ATTN32G_MINWG 64 -> 16: +0.9 % on the 512^2 step (the 16x16 D = 160 instantiation spills)
+    int g32_mask; long g32_minwg;
+    bool a512; int a512_splits;    // LDX_ATTN512 = 0: no D = 512 kernel (the VAE falls back to GEMMs and a row softmax); LDX_ATTN512_SPLITS > 0 forces its key-split count
+};
 static AttnSwitches read_attn_switches() {
+    auto num = [](const char* name, long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; };
+    auto unless0 = [](const char* name) { const char* v = getenv(name); return !(v && atoi(v) == 0); };
     AttnSwitches w;
-    const char* e = getenv("LDX_ATTN_PIPE");
-    const char* e128 = getenv("LDX_ATTN_PIPE128");
-    const char* m = getenv("LDX_ATTN_PIPE_MINWG");
     const char* t = getenv("LDX_ATTN_PIPE_THR");
-    w.pipe40 = !e || atoi(e) != 0;
-    w.pipe128 = !e128 || atoi(e128) != 0;
-    w.minwg40 = m ? atol(m) : 256;
-    w.minwg128 = m ? atol(m) : 192;
-    w.thr = t ? (float)atof(t) : __builtin_nanf("");          // NaN = the type's own rescale threshold
+    w.pipe = unless0("LDX_ATTN_PIPE"); w.pipe128 = unless0("LDX_ATTN_PIPE128"); w.pipe_kb = unless0("LDX_ATTN_PIPE_KB"); w.pipe_thr = t ? (float)atof(t) : __builtin_nanf("");
+    w.pipe_minwg40 = num("LDX_ATTN_PIPE_MINWG", 256); w.pipe_minwg128 = num("LDX_ATTN_PIPE_MINWG", 192);
+    w.attn32 = (int)num("LDX_ATTN32", 1); w.ap = (int)num("LDX_ATTN32_AP", 1); w.ap_minwg = num("LDX_ATTN32_AP_MINWG", 256);
+    w.kvb = (int)num("LDX_ATTN32_KVB", 64); w.var = (int)num("LDX_ATTN32_VAR", 1);
+    w.kpf = unless0("LDX_ATTN_KPF"); w.g32_mask = (int)num("LDX_ATTN32G", 7); w.g32_minwg = num("LDX_ATTN32G_MINWG", 16);
+    w.a512 = unless0("LDX_ATTN512"); w.a512_splits = (int)num("LDX_ATTN512_SPLITS", 0);
     return w;
 }
 static AttnSwitches g_attn_sw = read_attn_switches();
 void reload_dispatch_env() { g_attn_sw = read_attn_switches(); }
 
-// which kernel family launch_attention() takes for `a` (planner / profile labels): 3 attn512, 1 attn40p, 2 attn128p, 0 the generic dispatch (attn32g / attn32 / attn)
-int attention_dispatch_class(const AttnArgs& a) {
+// Shapes the special-purpose kernels take.  attn512.hip: one head of D = 512 (VAE mid-block attention)
+static bool attn512_ok(const AttnArgs& a) {
+    return a.D == 512 && !a.causal && !a.bias && !a.O8 && a.Nq > 0 && a.Mk > 0 && a.B > 0 && a.H > 0 && a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 4 == 0;
+}
+// its key splits: enough workgroups for the chip (>= 224 of 256 CUs), never more than 8, each split at least 16 key blocks
+static int attn512_splits(const AttnArgs& a, int force) {
+    const long wgs = (long)((a.Nq + ATTN512_QB - 1) / ATTN512_QB) * a.H * a.B;
+    const int nblk = (a.Mk + ATTN512_KV - 1) / ATTN512_KV;
+    int s = force > 0 ? force : (int)((255 + wgs) / wgs);
+    if (s > 8) s = 8;
+    while (s > 1 && nblk / s < 16) --s;
+    if (force > 0 && s > nblk) s = nblk;
+    return s < 1 ? 1 : s;
+}
+// attn_pipe.hip (D = 40, 16-bit output) and attn_pipe128.hip (D = 128, 16-bit or MX fp8 output): whole 256-query workgroups, whole pairs of key blocks, 16-byte rows
+bool attn_pipe_ok(const AttnArgs& a) {
+    if ((a.D != 40 && a.D != 128) || a.causal || a.bias || a.Nq % 256 || a.Mk % 128 || a.Mk < 256 || a.ldq % 8 || a.ldk % 8 || a.ldv % 8) return false;
+    if (a.D == 40) return !a.O8 && a.ldo % 4 == 0;
+    return a.O8 ? (a.ldo8 % 16 == 0 && ((uintptr_t)a.O8 & 15) == 0) : (a.ldo % 8 == 0 && ((uintptr_t)a.O & 15) == 0);
+}
+// the head dim the generic 32x32x16 kernel takes `a` at, 0: not taken
+static int attn32g_dim(const AttnArgs& a, const AttnSwitches& w) {
+    if (!w.g32_mask || a.causal || a.bias || (long)((a.Nq + 127) / 128) * a.H * a.B < w.g32_minwg) return 0;
+    const int bit = a.D == 80 ? 1 : a.D == 160 ? 2 : a.D == 128 ? 4 : a.D == 64 ? 8 : 0;
+    return (w.g32_mask & bit) ? a.D : 0;
+}
+
+AttnPick attn_pick(const AttnArgs& a) {
     const AttnSwitches& w = g_attn_sw;
-    if (attn512_ok(a)) return 3;
-    if (w.pipe40 && attn_pipe_ok(a) && (long)(a.Nq / 256) * a.H * a.B >= w.minwg40) return 1;
-    if (w.pipe128 && attn_pipe128_ok(a) && (long)(a.Nq / 256) * a.H * a.B >= w.minwg128) return 2;
-    return 0;
+    AttnPick p{};
+    p.thr = w.pipe_thr;
+    p.mx_out = attn32g_dim(a, w) == 128;
+    if (a.Nq <= 0 || a.B <= 0) return p;
+    auto take = [&](AttnFamily f, int t0, int t1, int t2, int qb, int block, int lds) {
+        p.family = f; p.targ[0] = t0; p.targ[1] = t1; p.targ[2] = t2; p.qb = qb; p.block = block; p.lds = lds;
+        p.grid = (unsigned)(((a.Nq + qb - 1) / qb) * a.H * a.B);
+        p.nsplit = p.launches = 1;
+    };
+    const long wg256 = (long)((a.Nq + 255) / 256) * a.H * a.B;      // 256-query workgroups
+    if (w.a512 && attn512_ok(a)) {
+        take(AF_ATTN512, 0, 0, 0, ATTN512_QB, 256, ATTN512_LDS);
+        p.nsplit_want = attn512_splits(a, w.a512_splits);
+        p.nsplit = a.nsplit > 1 && a.split_ws ? a.nsplit : 1;        // no workspace: one workgroup walks all keys of its query block
+        p.grid *= (unsigned)p.nsplit;
+        p.launches = p.nsplit > 1 ? 2 : 1;
+        return p;
+    }
+    // D = 40 self-attention of the large levels: the software-pipelined one-wave-per-SIMD kernel when its 256-query workgroups fill the chip;
+    // D = 128 (Flux): the same pipeline when one round of them covers at least three quarters of the CUs
+    if (attn_pipe_ok(a) && (a.D == 40 ? w.pipe && wg256 >= w.pipe_minwg40 : w.pipe128 && wg256 >= w.pipe_minwg128)) {
+        if (a.D == 40) take(AF_ATTN40P, 0, 0, 0, 256, 256, ATTN40P_LDS); else take(AF_ATTN128P, 0, 0, 0, 256, 256, ATTN128P_LDS);
+        p.knorm = a.knorm_ws && w.pipe_kb;
+        p.launches = p.knorm ? 2 : 1;
+        return p;
+    }
+    if (const int d = attn32g_dim(a, w)) {
+        const bool ones = d == 80 || d == 160;                        // the denominator from a ones row of V (one d tile more at 160); 128, 64: summed on the VALU
+        const int nks = d / 16, ndt = d / 32 + (ones ? 1 : 0);        // k-steps of 16, d tiles of 32
+        take(AF_ATTN32G, nks, ndt, ones, 128, 256, 2 * AT_KV * (G32_KROW(nks) + G32_VROW(ndt)));
+        p.kpf = w.kpf;
+        return p;
+    }
+    // 16x16 kernel: KS = ceil(D/32) contraction steps, DT output tiles with room for the ones column at d = D (the instantiations that exist, by largest D)
+    static const struct { int dmax, ks, dt; } ladder[] = {{15, 1, 1}, {31, 1, 2}, {32, 1, 3}, {47, 2, 3}, {63, 2, 4}, {64, 2, 5}, {79, 3, 5}, {95, 3, 6}, {96, 3, 7},
+                                                          {127, 4, 8}, {128, 4, 9}, {159, 5, 10}, {1 << 30, 5, 11}};
+    int i = 0;
+    while (a.D > ladder[i].dmax) ++i;
+    const int ks = ladder[i].ks, dt = ladder[i].dt;
+    if (ks == 2 && dt == 3 && w.attn32 && !a.causal && !a.bias && a.D > 32 && a.D % 8 == 0 && wg256 >= 512) {      // D = 40 (SD1.5 level 0) on 32x32x16 MFMAs
+        if (w.ap && a.Mk >= 64 && (long)((a.Nq + 511) / 512) * a.H * a.B >= w.ap_minwg) {
+            int var = w.ap == 2 ? 0 : w.ap == 3 ? 1 : 2;      // the kernel's VAR: 2 = phases separated by the barriers only
+#ifdef LDX_ATTN_ABLATE      // profiles/ubench/README.md round 3, measured and not adopted (correct, bit-identical): 6 split softmax (VAR & 64), +6 %; 7 K fragments read a phase early (VAR & 128), +-0.5 %;
+            // timing ablations (wrong results): 4 no MFMAs, 8 no softmax, 12 neither (staging + barriers + fragment reads), 34 the default schedule without the 64 fma of exp2(s * c - m * c)
+            var = w.ap == 6 ? 66 : w.ap == 7 ? 130 : w.ap == 4 || w.ap == 8 || w.ap == 12 || w.ap == 34 ? w.ap : var;
+#endif
+            take(AF_ATTN32AP, var, 0, 0, 512, 512, 2 * 64 * (144 + 192));
+            return p;
+        }
+        // K / V row strides 144 / 192 B: 160 / 160 had 2-way conflicts on every fragment read (SQ_LDS_BANK_CONFLICT 88.1 M -> 21.0 M cycles per launch;
+        // same time at D = 40, which is VALU / MFMA bound)
+        const int kvb = w.var != 1 && w.kvb == 128 && a.Mk >= 1024 ? 128 : 64;
+        take(AF_ATTN32, kvb, w.var == 1, 0, 256, 256, 2 * kvb * (144 + 192));
+        return p;
+    }
+    // 64 queries per wave (QT = 4) when the accumulators fit (DT <= 3) and the grid still fills the chip.  D >= 144 (DT >= 10): two 16-query tiles per wave need 12 more
+    // VGPRs than the file has (40 B of scratch per lane, hipcc -Rpass-analysis): one tile per wave there.  Only small grids / masked calls get here (attn32g takes the rest).
+    const int qt = dt <= 3 && wg256 >= 512 && !a.causal ? 4 : dt >= 10 ? 1 : 2;
+    take(AF_ATTN, ks, dt, qt, 64 * qt, 256, 2 * AT_KV * (ks * 64 + 32 + ((dt * 32) % 64 == 0 ? dt * 32 + 32 : dt * 32)));
+    return p;
+}
+
+// every instantiation behind launch_attention, as attn_pick names them in AttnPick::targ
+#define ATTN_KERNEL_INSTANCES(X) X(1, 1, 2) X(1, 1, 4) X(1, 2, 2) X(1, 2, 4) X(1, 3, 2) X(1, 3, 4) X(2, 3, 2) X(2, 3, 4) X(2, 4, 2) X(2, 5, 2) X(3, 5, 2) X(3, 6, 2) X(3, 7, 2) \
+                                 X(4, 8, 2) X(4, 9, 2) X(5, 10, 1) X(5, 11, 1)                                             /* KS, DT, QT */
+#define ATTN32G_INSTANCES(X) X(5, 3, true) X(10, 6, true) X(8, 4, false) X(4, 2, false)                                    /* NKS, NDT, ONES: D = 80, 160, 128, 64 */
+#define ATTN32_INSTANCES(X) X(64, 1) X(128, 0) X(64, 0)                                                                     /* KVB, VAR */
+#ifdef LDX_ATTN_ABLATE
+#define ATTN32AP_INSTANCES(X) X(0) X(1) X(2) X(66) X(130) X(4) X(8) X(12) X(34)                                             /* VAR */
+#else
+#define ATTN32AP_INSTANCES(X) X(0) X(1) X(2)
+#endif
+#define ATTN_LAUNCH(...) { static DevOnce once; set_dyn_lds(once, (const void*)__VA_ARGS__, p.lds); hipLaunchKernelGGL((__VA_ARGS__), dim3(p.grid), dim3(p.block), p.lds, s, a); return; }
+template <typename T>
+static void launch_picked(const AttnPick& p, const AttnArgs& a, hipStream_t s) {
+    const int t0 = p.targ[0], t1 = p.targ[1], t2 = p.targ[2];
+    switch (p.family) {
+#define X(KS, DT, QT) if (t0 == KS && t1 == DT && t2 == QT) ATTN_LAUNCH(attn_kernel<T, KS, DT, QT>)
+        case AF_ATTN: ATTN_KERNEL_INSTANCES(X) break;
+#undef X
+#define X(KVB, VAR) if (t0 == KVB && t1 == VAR) ATTN_LAUNCH(attn32_kernel<T, KVB, 144, 192, VAR>)
+        case AF_ATTN32: ATTN32_INSTANCES(X) break;
+#undef X
+#define X(VAR) if (t0 == VAR) ATTN_LAUNCH(attn32ap_kernel<T, 144, 192, VAR>)
+        case AF_ATTN32AP: ATTN32AP_INSTANCES(X) break;
+#undef X
+#define X(NKS, NDT, ONES) if (t0 == NKS && t1 == NDT && p.kpf) ATTN_LAUNCH(attn32g_kernel<T, NKS, NDT, 1, ONES, true>) if (t0 == NKS && t1 == NDT) ATTN_LAUNCH(attn32g_kernel<T, NKS, NDT, 1, ONES, false>)
+        case AF_ATTN32G: ATTN32G_INSTANCES(X) break;
+#undef X
+        default: break;
+    }
+    fprintf(stderr, "ldx: attn_pick chose family %d <%d, %d, %d>, which has no instantiation\n", (int)p.family, t0, t1, t2);
+    abort();
 }
 
 void launch_attention(const AttnArgs& a, DType dt, hipStream_t s) {
     if (a.Nq <= 0 || a.B <= 0) return;
-    const AttnSwitches& w = g_attn_sw;
-    if (attn512_ok(a)) { launch_attn512(a, dt, s); return; }      // one head of D = 512 (VAE mid-block attention): attn512.hip
-    // D = 40 self-attention of the large levels: the software-pipelined one-wave-per-SIMD kernel (attn_pipe.hip) when its 256-query workgroups
-    // fill the chip.  LDX_ATTN_PIPE=0 restores attn32ap / attn32; LDX_ATTN_PIPE_THR=<x> overrides the rescale threshold (tests).
-    if (w.pipe40 && attn_pipe_ok(a) && (long)(a.Nq / 256) * a.H * a.B >= w.minwg40) {
-        launch_attn_pipe(a, dt, s, w.thr);
-        return;
+    const AttnPick p = attn_pick(a);
+    // MX fp8 output: callers set O8 only where AttnPick::mx_out allows it, and then one of the two kernels that write it takes the launch — anything else is a bug
+    // in attn_pick or arguments changed after planning, and would leave the consumer GEMM stale bytes
+    if (a.O8 && p.family != AF_ATTN128P && !(p.family == AF_ATTN32G && a.D == 128)) {
+        fprintf(stderr, "ldx: attention with MX fp8 output (B %d H %d Nq %d Mk %d D %d) picked kernel family %d, which does not write it\n", a.B, a.H, a.Nq, a.Mk, a.D, (int)p.family);
+        abort();
     }
-    // D = 128 (Flux): the same pipeline (attn_pipe128.hip) when one round of its 256-query workgroups covers at least three quarters of the CUs.
-    // O8 (MX fp8 output) needs attention_mx_out_ok(), i.e. the attn32g D = 128 variant enabled: the callers' test, unchanged.
-    if (w.pipe128 && attn_pipe128_ok(a) && (long)(a.Nq / 256) * a.H * a.B >= w.minwg128) {
-        launch_attn_pipe128(a, dt, s, w.thr);
-        return;
+    switch (p.family) {
+        case AF_ATTN512: launch_attn512(a, p, dt, s); break;
+        case AF_ATTN40P: launch_attn_pipe(a, p, dt, s); break;
+        case AF_ATTN128P: launch_attn_pipe128(a, p, dt, s); break;
+        default: if (dt == DT_BF16) launch_picked<__bf16>(p, a, s); else launch_picked<_Float16>(p, a, s);
     }
-    if (dt == DT_BF16) launch_attn_d<__bf16>(a, s); else launch_attn_d<_Float16>(a, s);
 }
 
 }  // namespace ldx

@@ -315,12 +315,3 @@ __global__ __launch_bounds__(512, 1) void attn32ap_kernel(const AttnArgs p) {
             }
     }
 }
-template <typename T, int VAR>
-static void launch_attn32ap(const AttnArgs& a, hipStream_t s) {
-    constexpr int KROWB = 144, VROWB = 192;
-    const size_t lds = 2 * 64 * (KROWB + VROWB);
-    static DevOnce once;
-    set_dyn_lds(once, (const void*)attn32ap_kernel<T, KROWB, VROWB, VAR>, (int)lds);
-    dim3 grid(((a.Nq + 511) / 512) * a.H * a.B);
-    hipLaunchKernelGGL((attn32ap_kernel<T, KROWB, VROWB, VAR>), grid, dim3(512), lds, s, a);
-}

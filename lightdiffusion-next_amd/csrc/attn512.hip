@@ -72,6 +72,7 @@ template <int R0> static __device__ __forceinline__ void a5_get8(const f32x16& t
 constexpr int A5_D = 512, A5_KV = 32, A5_QB = 128;
 constexpr int A5_KROW = A5_D * 2 + 16, A5_VROW = A5_D * 2 + 64;               // 1040 = 65 x 16 B, 1088 = 17 x 64 B
 constexpr int A5_KB = A5_KV * A5_KROW, A5_VB = A5_KV * A5_VROW, A5_STAGE = A5_KB + A5_VB, A5_LDS = 2 * A5_STAGE;      // 136 192 B
+static_assert(A5_QB == ATTN512_QB && A5_KV == ATTN512_KV && A5_LDS == ATTN512_LDS, "attn_pick (attention.hip) plans with these");
 constexpr int A5_WS_ROW = A5_D + 4;                                            // floats per (split, query) row of the split workspace: O[512], m, l, pad
 
 // ABL (timing-only builds, wrong results; LDX_ATTN512_ABL, read once): 1 = no LDS-DMA inside the key loop (the two stages keep blocks 0 / 1), 2 = no V^T fragment
@@ -286,28 +287,13 @@ __global__ __launch_bounds__(256) void attn512_merge_kernel(const AttnArgs p) {
     *(uint2*)(Op + d) = pack4<T>(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
 }
 
-bool attn512_ok(const AttnArgs& a) {
-    static const bool off = getenv("LDX_ATTN512") && atoi(getenv("LDX_ATTN512")) == 0;
-    return !off && a.D == A5_D && !a.causal && !a.bias && !a.O8 && a.Nq > 0 && a.Mk > 0 && a.B > 0 && a.H > 0 && a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 4 == 0;
-}
-// key splits for a launch: enough workgroups for the chip (>= 224 of 256 CUs), never more than 8, each split at least 16 key blocks
-int attn512_splits(const AttnArgs& a) {
-    static const int force = getenv("LDX_ATTN512_SPLITS") ? atoi(getenv("LDX_ATTN512_SPLITS")) : 0;
-    const long wgs = (long)((a.Nq + A5_QB - 1) / A5_QB) * a.H * a.B;
-    const int nblk = (a.Mk + A5_KV - 1) / A5_KV;
-    int s = force > 0 ? force : (int)((255 + wgs) / wgs);
-    if (s > 8) s = 8;
-    while (s > 1 && nblk / s < 16) --s;
-    if (force > 0 && s > nblk) s = nblk;
-    return s < 1 ? 1 : s;
-}
 size_t attn512_ws_floats(const AttnArgs& a, int nsplit) { return nsplit > 1 ? (size_t)nsplit * a.B * a.H * a.Nq * A5_WS_ROW : 0; }
 
-void launch_attn512(const AttnArgs& a0, DType dt, hipStream_t s) {
+// p: the pick that chose this kernel (attn_pick: the grid, and the key splits in effect — AttnArgs::nsplit where its workspace is there, else 1)
+void launch_attn512(const AttnArgs& a0, const AttnPick& p, DType dt, hipStream_t s) {
     AttnArgs a = a0;
-    if (a.nsplit > 1 && !a.split_ws) a.nsplit = 1;           // no workspace: one workgroup walks all keys of its query block
-    if (a.nsplit < 1) a.nsplit = 1;
-    const unsigned grid = (unsigned)(((a.Nq + A5_QB - 1) / A5_QB) * a.nsplit * a.H * a.B);
+    a.nsplit = p.nsplit;
+    const unsigned grid = p.grid;
     const long mrows = (long)a.B * a.H * a.Nq;
     static const int abl = getenv("LDX_ATTN512_ABL") ? atoi(getenv("LDX_ATTN512_ABL")) : 0;
     if (abl && dt == DT_BF16) {

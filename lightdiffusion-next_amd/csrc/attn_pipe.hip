@@ -405,47 +405,39 @@ void launch_attn_knorm(const AttnArgs& a, DType dt, hipStream_t s) {
     else hipLaunchKernelGGL((attn_knorm_kernel<_Float16>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a);
 }
 
-bool attn_pipe_ok(const AttnArgs& a) {
-    return a.D == 40 && !a.causal && !a.bias && !a.O8 && a.Nq % 256 == 0 && a.Mk % 128 == 0 && a.Mk >= 256 &&
-           a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 4 == 0;
-}
-
 template <typename T, int ABL = 0>
-static void launch_attn40p(const AttnArgs& a, hipStream_t s, float thr) {
-    const size_t lds = 2 * 64 * (144 + 192);
-    dim3 grid((a.Nq / 256) * a.H * a.B);
-    static const bool kb_off = getenv("LDX_ATTN_PIPE_KB") && atoi(getenv("LDX_ATTN_PIPE_KB")) == 0;      // experiment switch: exact maximum on every block
-    if (a.knorm_ws && !kb_off && ABL == 0) {
+static void launch_attn40p(const AttnArgs& a, const AttnPick& p, hipStream_t s, float thr) {
+    if (p.knorm && ABL == 0) {
         const long waves = (long)a.B * a.H * ((a.Mk + 63) / 64);
         hipLaunchKernelGGL((attn_knorm_kernel<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a);
-        hipLaunchKernelGGL((attn40p_kernel<T, ABL, true>), grid, dim3(256), lds, s, a, thr);
+        hipLaunchKernelGGL((attn40p_kernel<T, ABL, true>), dim3(p.grid), dim3(p.block), p.lds, s, a, thr);
     } else {
-        hipLaunchKernelGGL((attn40p_kernel<T, ABL, false>), grid, dim3(256), lds, s, a, thr);
+        hipLaunchKernelGGL((attn40p_kernel<T, ABL, false>), dim3(p.grid), dim3(p.block), p.lds, s, a, thr);
     }
 }
 
-// thr_override: NaN = the type's default (tests force the rare path with small values)
-void launch_attn_pipe(const AttnArgs& a, DType dt, hipStream_t s, float thr_override) {
-    const bool ov = thr_override == thr_override;
+// p: the pick that chose this kernel (grid, LDS bytes, the key-norm launch; thr: NaN = the type's default, tests force the rare path with small values)
+void launch_attn_pipe(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s) {
+    const bool ov = p.thr == p.thr;
 #ifdef LDX_ATTN_ABLATE
     if (const char* e = getenv("LDX_ATTN_PIPE_ABL")) {
         const float thr = ApT<__bf16>::thr;
         switch (atoi(e)) {
-            case 1: launch_attn40p<__bf16, 1>(a, s, thr); return;
-            case 2: launch_attn40p<__bf16, 2>(a, s, thr); return;
-            case 8: launch_attn40p<__bf16, 8>(a, s, thr); return;
-            case 16: launch_attn40p<__bf16, 16>(a, s, thr); return;
-            case 32: launch_attn40p<__bf16, 32>(a, s, thr); return;
-            case 9: launch_attn40p<__bf16, 9>(a, s, thr); return;
-            case 25: launch_attn40p<__bf16, 25>(a, s, thr); return;
-            case 27: launch_attn40p<__bf16, 27>(a, s, thr); return;
-            case 59: launch_attn40p<__bf16, 59>(a, s, thr); return;
+            case 1: launch_attn40p<__bf16, 1>(a, p, s, thr); return;
+            case 2: launch_attn40p<__bf16, 2>(a, p, s, thr); return;
+            case 8: launch_attn40p<__bf16, 8>(a, p, s, thr); return;
+            case 16: launch_attn40p<__bf16, 16>(a, p, s, thr); return;
+            case 32: launch_attn40p<__bf16, 32>(a, p, s, thr); return;
+            case 9: launch_attn40p<__bf16, 9>(a, p, s, thr); return;
+            case 25: launch_attn40p<__bf16, 25>(a, p, s, thr); return;
+            case 27: launch_attn40p<__bf16, 27>(a, p, s, thr); return;
+            case 59: launch_attn40p<__bf16, 59>(a, p, s, thr); return;
             default: break;
         }
     }
 #endif
-    if (dt == DT_BF16) launch_attn40p<__bf16>(a, s, ov ? thr_override : ApT<__bf16>::thr);
-    else launch_attn40p<_Float16>(a, s, ov ? fminf(thr_override, ApT<_Float16>::thr) : ApT<_Float16>::thr);
+    if (dt == DT_BF16) launch_attn40p<__bf16>(a, p, s, ov ? p.thr : ApT<__bf16>::thr);
+    else launch_attn40p<_Float16>(a, p, s, ov ? fminf(p.thr, ApT<_Float16>::thr) : ApT<_Float16>::thr);
 }
 
 }  // namespace ldx

@@ -401,50 +401,42 @@ __global__ __launch_bounds__(256, 1) void attn128p_kernel(const AttnArgs p, cons
     }
 }
 
-bool attn_pipe128_ok(const AttnArgs& a) {
-    return a.D == 128 && !a.causal && !a.bias && a.Nq % 256 == 0 && a.Mk % 128 == 0 && a.Mk >= 256 &&
-           a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && (a.O8 ? (a.ldo8 % 16 == 0 && ((uintptr_t)a.O8 & 15) == 0) : (a.ldo % 8 == 0 && ((uintptr_t)a.O & 15) == 0));
-}
-
 template <typename T, int ABL = 0>
-static void launch_attn128p(const AttnArgs& a, hipStream_t s, float thr) {
-    const size_t lds = 3 * 64 * (272 + 320);
-    const dim3 grid((a.Nq / 256) * a.H * a.B);
-    static const bool kb_off = getenv("LDX_ATTN_PIPE_KB") && atoi(getenv("LDX_ATTN_PIPE_KB")) == 0;      // experiment switch: exact maximum on every half-slot
-    if (a.knorm_ws && !kb_off && ABL == 0) {
+static void launch_attn128p(const AttnArgs& a, const AttnPick& p, hipStream_t s, float thr) {
+    if (p.knorm && ABL == 0) {
         launch_attn_knorm(a, std::is_same<T, __bf16>::value ? DT_BF16 : DT_F16, s);
         static DevOnce once;
-        set_dyn_lds(once, (const void*)attn128p_kernel<T, ABL, true>, (int)lds);
-        hipLaunchKernelGGL((attn128p_kernel<T, ABL, true>), grid, dim3(256), lds, s, a, thr);
+        set_dyn_lds(once, (const void*)attn128p_kernel<T, ABL, true>, p.lds);
+        hipLaunchKernelGGL((attn128p_kernel<T, ABL, true>), dim3(p.grid), dim3(p.block), p.lds, s, a, thr);
     } else {
         static DevOnce once;
-        set_dyn_lds(once, (const void*)attn128p_kernel<T, ABL, false>, (int)lds);
-        hipLaunchKernelGGL((attn128p_kernel<T, ABL, false>), grid, dim3(256), lds, s, a, thr);
+        set_dyn_lds(once, (const void*)attn128p_kernel<T, ABL, false>, p.lds);
+        hipLaunchKernelGGL((attn128p_kernel<T, ABL, false>), dim3(p.grid), dim3(p.block), p.lds, s, a, thr);
     }
 }
 
-void launch_attn_pipe128(const AttnArgs& a, DType dt, hipStream_t s, float thr_override) {
-    const bool ov = thr_override == thr_override;
+void launch_attn_pipe128(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s) {
+    const bool ov = p.thr == p.thr;
 #ifdef LDX_ATTN_ABLATE
     if (const char* e = getenv("LDX_ATTN_PIPE_ABL")) {
         const float thr = ApT<__bf16>::thr;
         switch (atoi(e)) {
-            case 1: launch_attn128p<__bf16, 1>(a, s, thr); return;
-            case 2: launch_attn128p<__bf16, 2>(a, s, thr); return;
-            case 4: launch_attn128p<__bf16, 4>(a, s, thr); return;
-            case 8: launch_attn128p<__bf16, 8>(a, s, thr); return;
-            case 16: launch_attn128p<__bf16, 16>(a, s, thr); return;
-            case 32: launch_attn128p<__bf16, 32>(a, s, thr); return;
-            case 34: launch_attn128p<__bf16, 34>(a, s, thr); return;
-            case 24: launch_attn128p<__bf16, 24>(a, s, thr); return;
-            case 58: launch_attn128p<__bf16, 58>(a, s, thr); return;
-            case 62: launch_attn128p<__bf16, 62>(a, s, thr); return;
+            case 1: launch_attn128p<__bf16, 1>(a, p, s, thr); return;
+            case 2: launch_attn128p<__bf16, 2>(a, p, s, thr); return;
+            case 4: launch_attn128p<__bf16, 4>(a, p, s, thr); return;
+            case 8: launch_attn128p<__bf16, 8>(a, p, s, thr); return;
+            case 16: launch_attn128p<__bf16, 16>(a, p, s, thr); return;
+            case 32: launch_attn128p<__bf16, 32>(a, p, s, thr); return;
+            case 34: launch_attn128p<__bf16, 34>(a, p, s, thr); return;
+            case 24: launch_attn128p<__bf16, 24>(a, p, s, thr); return;
+            case 58: launch_attn128p<__bf16, 58>(a, p, s, thr); return;
+            case 62: launch_attn128p<__bf16, 62>(a, p, s, thr); return;
             default: break;
         }
     }
 #endif
-    if (dt == DT_BF16) launch_attn128p<__bf16>(a, s, ov ? thr_override : ApT<__bf16>::thr);
-    else launch_attn128p<_Float16>(a, s, ov ? fminf(thr_override, ApT<_Float16>::thr) : ApT<_Float16>::thr);
+    if (dt == DT_BF16) launch_attn128p<__bf16>(a, p, s, ov ? p.thr : ApT<__bf16>::thr);
+    else launch_attn128p<_Float16>(a, p, s, ov ? fminf(p.thr, ApT<_Float16>::thr) : ApT<_Float16>::thr);
 }
 
 }  // namespace ldx

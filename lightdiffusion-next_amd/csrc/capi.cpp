@@ -402,8 +402,8 @@ int ldx_op_attention_mx(const void* Q, int ldq, const void* K, int ldk, const vo
     a.O8 = O8; a.ldo8 = ldo8; a.SO = (uint32_t*)SO; a.so_ld = so_ld;
     if (!Q || !K || !V || !O8 || !SO || B <= 0 || H <= 0 || Nq <= 0 || Mk <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo8 % 16 || ldo8 < H * 128 || so_ld < B * Nq) {
         set_error("ldx_op_attention_mx: bad argument"); return LDX_EINVAL; }
-    if (attn_pipe128_ok(a)) a.knorm_ws = op_workspace((size_t)B * H * ((Mk + 63) / 64));
-    if (!attention_mx_out_ok(a)) { set_error("ldx_op_attention_mx: needs head dim 128 and at least 16 query blocks of 128 (B * H * ceil(Nq / 128))"); return LDX_EINVAL; }
+    if (attn_pipe_ok(a)) a.knorm_ws = op_workspace((size_t)B * H * ((Mk + 63) / 64));
+    if (!attn_pick(a).mx_out) { set_error("ldx_op_attention_mx: needs head dim 128 and at least 16 query blocks of 128 (B * H * ceil(Nq / 128))"); return LDX_EINVAL; }
     launch_attention(a, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_attention_mx");
 }
@@ -515,6 +515,23 @@ int ldx_op_gemm_pick(int M, int N, int K, int mode, int geglu, int splitk, int f
     for (int i = 0; i < 10; ++i) out[i] = r[i];
     return LDX_OK;
 }
+int ldx_op_attn_pick(int B, int H, int Nq, int Mk, int D, int causal, int bias, int o8, int ldq, int ldk, int ldv, int ldo, int knorm_ws, int32_t* out) {
+    if (!out || B <= 0 || H <= 0 || Nq <= 0 || Mk <= 0 || D <= 0 || D % 8 || (D > 160 && D != 512) || ldq <= 0 || ldk <= 0 || ldv <= 0 || ldo <= 0 || (o8 && D != 128)) {
+        set_error("ldx_op_attn_pick: bad argument (D % 8, D <= 160 or D == 512; MX fp8 output: D == 128)"); return LDX_EINVAL; }
+    alignas(16) static char buf[16];           // operands are only ever tested for being there and for their alignment
+    void* const P = buf;
+    AttnArgs a{};
+    a.Q = a.K = a.V = P; a.O = P; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.B = B; a.H = H; a.Nq = Nq; a.Mk = Mk; a.D = D; a.scale = 1.f; a.causal = causal;
+    if (bias) { a.bias = (const float*)P; a.bias_ld = (Mk + 63) / 64 * 64; }
+    if (o8) { a.O8 = P; a.ldo8 = ldo; a.SO = (uint32_t*)P; a.so_ld = B * Nq; }
+    if (knorm_ws) a.knorm_ws = (float*)P;
+    AttnPick p = attn_pick(a);
+    if (p.nsplit_want > 1) { a.nsplit = p.nsplit_want; a.split_ws = (float*)P; p = attn_pick(a); }      // as the planner and ldx_op_attention launch it
+    const int32_t r[13] = {p.family, p.targ[0], p.targ[1], p.targ[2], p.kpf, p.qb, p.block, (int32_t)p.grid, p.lds, p.knorm, p.nsplit, p.mx_out, p.launches};
+    for (int i = 0; i < 13; ++i) out[i] = r[i];
+    return LDX_OK;
+}
 int ldx_op_conv3x3(const void* X, int ldx_, const void* W, int B, int Hin, int Win, int Cin, int Cout, int stride, int Hout, int Wout,
                    int resize_to_out, const float* bias, const float* rowvec, int rowvec_ld, const void* R, int ldr, void* Y, int ldy,
                    int dtype, void* stream) {
@@ -561,12 +578,14 @@ int ldx_op_attention(const void* Q, int ldq, const void* K, int ldk, const void*
                      float scale, int causal, int dtype, void* stream) {
     if (!Q || !K || !V || !O || D % 8 || (D > 160 && D != 512) || D <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || Mk <= 0) { set_error("ldx_op_attention: bad argument (D % 8, D <= 160 or D == 512)"); return LDX_EINVAL; }
     AttnArgs a{Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Nq, Mk, D, scale, causal, nullptr, 0, 0};
-    if (D == 512) {
-        if (!attn512_ok(a)) { set_error("ldx_op_attention: D = 512 without a mask only (attn512.hip)"); return LDX_EINVAL; }
-        a.nsplit = attn512_splits(a);
-        if (a.nsplit > 1) { a.split_ws = op_workspace(attn512_ws_floats(a, a.nsplit)); if (!a.split_ws) { set_error("attention split workspace allocation failed"); return LDX_EHIP; } }
+    const AttnPick p = attn_pick(a);
+    if (D == 512 && p.family != AF_ATTN512) { set_error("ldx_op_attention: D = 512 without a mask only (attn512.hip)"); return LDX_EINVAL; }
+    if (p.nsplit_want > 1) {
+        a.nsplit = p.nsplit_want;
+        a.split_ws = op_workspace(attn512_ws_floats(a, a.nsplit));
+        if (!a.split_ws) { set_error("attention split workspace allocation failed"); return LDX_EHIP; }
     }
-    if (attn_pipe_ok(a) || attn_pipe128_ok(a)) a.knorm_ws = op_workspace((size_t)B * H * ((Mk + 63) / 64));      // (shared single-op scratch: one stream per device, include/ldx.h)
+    if (attn_pipe_ok(a)) a.knorm_ws = op_workspace((size_t)B * H * ((Mk + 63) / 64));      // (shared single-op scratch: one stream per device, include/ldx.h)
     launch_attention(a, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_attention");
 }

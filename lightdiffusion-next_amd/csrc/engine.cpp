@@ -693,22 +693,23 @@ void Engine::op_attn(const char* name, const void* Q, int ldq, const void* K, in
     AttnArgs& a = o.at;
     a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = ptr(O); a.ldo = O.ld;
     a.B = B; a.H = H; a.Nq = Nq; a.Mk = Mk; a.D = D; a.scale = 1.0f / std::sqrt((float)D); a.causal = 0;
-    if (attn_pipe_ok(a) || attn_pipe128_ok(a)) {       // key-block norms for the pipelined kernels' score bound (attn_pipe.hip): a few KiB, live for this op only
+    if (attn_pipe_ok(a)) {       // key-block norms for the pipelined kernels' score bound (attn_pipe.hip): a few KiB, live for this op only
         const size_t off = a_alloc((size_t)B * H * ((Mk + 63) / 64) * 4); a.knorm_ws = (float*)((uintptr_t)cur.arena + off); a_free(off);
     }
-    if (attn512_ok(a)) {              // D = 512 (VAE): key splits when the query blocks alone leave CUs idle; fp32 partials live for this op only
-        a.nsplit = attn512_splits(a);
-        if (a.nsplit > 1) { const size_t off = a_alloc(attn512_ws_floats(a, a.nsplit) * 4); a.split_ws = (float*)((uintptr_t)cur.arena + off); a_free(off); }
+    const AttnPick p = attn_pick(a);
+    if (p.nsplit_want > 1) {          // D = 512 (VAE): key splits when the query blocks alone leave CUs idle; fp32 partials live for this op only
+        a.nsplit = p.nsplit_want;
+        const size_t off = a_alloc(attn512_ws_floats(a, a.nsplit) * 4); a.split_ws = (float*)((uintptr_t)cur.arena + off); a_free(off);
     }
     o.flops = 4.0 * B * H * (double)Nq * Mk * D;
     o.bytes = 2.0 * (double)B * H * D * (2.0 * Nq + 2.0 * Mk);
     {
-        const int ks = D <= 32 ? 1 : D <= 64 ? 2 : D <= 96 ? 3 : D <= 128 ? 4 : 5;
-        const int dtl = D / 16 + 1;
-        const int cls = attention_dispatch_class(a);         // the device kernel's own name where one family takes the launch (rocprofv3 reports the same)
-        if (attn512_ok(a)) snprintf(o.klabel, sizeof(o.klabel), "attn512_kernel<%s>x%d", dt == DT_BF16 ? "bf16" : "f16", a.nsplit);
-        else if (cls == 1 || cls == 2) snprintf(o.klabel, sizeof(o.klabel), "%s<%s>%s", cls == 1 ? "attn40p_kernel" : "attn128p_kernel", dt == DT_BF16 ? "bf16" : "f16", Nq == Mk ? "self" : "cross");
-        else snprintf(o.klabel, sizeof(o.klabel), "attn_kernel<%s,%d,%d>%s", dt == DT_BF16 ? "bf16" : "f16", ks, dtl, Nq == Mk ? "self" : "cross");
+        // the device kernel's own name with its template arguments (rocprofv3 reports the same), then self / cross or attn512's key splits
+        static const char* const fmt[] = {"attn_kernel<%s,%d,%d,%d>", "attn32_kernel<%s,%d,144,192,%d>", "attn32ap_kernel<%s,144,192,%d>", "attn32g_kernel<%s,%d,%d,1,%d,%d>",
+                                          "attn40p_kernel<%s>", "attn128p_kernel<%s>", "attn512_kernel<%s>"};      // by AttnFamily
+        const int n = snprintf(o.klabel, sizeof(o.klabel), fmt[p.family], dt == DT_BF16 ? "bf16" : "f16", p.targ[0], p.targ[1], p.targ[2], (int)p.kpf);
+        if (p.family == AF_ATTN512) snprintf(o.klabel + n, sizeof(o.klabel) - n, "x%d", a.nsplit);
+        else snprintf(o.klabel + n, sizeof(o.klabel) - n, "%s", Nq == Mk ? "self" : "cross");
     }
     cur.ops.push_back(o);
     cur.flops += o.flops;
@@ -1365,10 +1366,10 @@ int64_t Engine::n_launches() const {
     int64_t n = 0;
     for (const Op& o : cur.ops) {
         if (ctx_cache && o.ctx_only) continue;            // steady state of a sampling run: the context's projections are cached
-        if (o.kind == OP_ATTN && o.at.nsplit > 1) { n += 2; continue; }      // split keys + merge launch (attn512.hip)
         if (o.kind == OP_GN) n += o.gn.stats_chunks > GN_NCHUNK ? 2 : (o.gn.stats_chunks > 0 ? 1 : 2);      // fold + apply / apply / statistics + apply
         else if (o.kind == OP_GEMM) n += gemm_pick(o.g).launches;          // with its split-K reduce launch, if it has one
         else if (o.kind == OP_GEMM2) n += gemm_pick(o.g, &o.g2).launches;
+        else if (o.kind == OP_ATTN) n += attn_pick(o.at).launches;      // with the pipelined kernels' key-norm launch / attn512's merge launch
         else n += 1;
     }
     return n;

@@ -295,7 +295,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
             const char* base = (const char*)ptr(QKV);
             op_attn(name, base, QKV.ld, base + (size_t)C * 2, QKV.ld, base + (size_t)2 * C * 2, QKV.ld, O, 1, H, QKV.rows, QKV.rows, D);
             AttnArgs& a = cur.ops.back().at;
-            if (!fx_fp8 || !qo || !(fuse_mask & 2) || !attention_mx_out_ok(a)) return false;
+            if (!fx_fp8 || !qo || !(fuse_mask & 2) || !attn_pick(a).mx_out) return false;
             const int ro = row_of(*obase, O);
             a.O8 = qo->y + (size_t)ro * qo->K; a.ldo8 = qo->K; a.SO = qo->s + ro; a.so_ld = RT;
             return true;

@@ -176,7 +176,7 @@ void Engine::emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int 
         // C = 512 (every SD VAE): flash attention, one head of D = 512 (attn512.hip) — q | k | v in one projection, the scores stay in the CUs.
         // Before round 5 (and still for other widths / LDX_ATTN512=0): q k^T GEMM -> row softmax -> p v GEMM through HBM, below.
         AttnArgs probe{}; probe.D = C; probe.B = B; probe.H = 1; probe.Nq = N; probe.Mk = N; probe.ldq = probe.ldk = probe.ldv = 3 * C; probe.ldo = C;
-        if (a.qkv.w && attn512_ok(probe)) {
+        if (a.qkv.w && attn_pick(probe).family == AF_ATTN512) {
             Act qkv = new_act(M, 3 * C);
             op_gemm("vae.attn.qkv", hn, a.qkv, qkv, Act{});
             release(hn);

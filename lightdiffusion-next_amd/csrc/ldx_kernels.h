@@ -150,7 +150,7 @@ struct AttnArgs {
     // optional additive score bias (T5 relative-position bias): fp32 [H][>= Nq][bias_ld], bias_ld = Mk rounded up to 64,
     // shared by the batch, added to q.k BEFORE the scale (pass bias / scale); padded entries are ignored
     const float* bias; int bias_ld; long bias_hs;
-    // O8 != null (only when attention_mx_out_ok(a)): the output is written as MX fp8 instead of 16-bit O — bytes
+    // O8 != null (only when attn_pick(a).mx_out): the output is written as MX fp8 instead of 16-bit O — bytes
     // O8[b*Nq + n][h*D + d] (row stride ldo8) and, D being 128, one scale dword per (row, head): SO[h][b*Nq + n] (row stride so_ld)
     void* O8; int ldo8; uint32_t* SO; int so_ld;
     // optional workspace of B * H * ceil(Mk / 64) floats (attn_pipe.hip, attn_pipe128.hip): with it the pipelined kernels prove most key blocks safe from the
@@ -162,25 +162,37 @@ struct AttnArgs {
     float* split_ws; int nsplit;
 };
 void launch_attention(const AttnArgs& a, DType dt, hipStream_t s);
-int attention_dispatch_class(const AttnArgs& a);       // 3 attn512_kernel, 1 attn40p_kernel, 2 attn128p_kernel, 0 generic (attn32g / attn32 / attn)
-// launch_attention's dispatch switches (LDX_ATTN_PIPE, LDX_ATTN_PIPE128, LDX_ATTN_PIPE_MINWG, LDX_ATTN_PIPE_THR) are read once at load;
-// this re-reads them (tests / same-process A/B runs only — never on the launch path)
+// Which kernel launch_attention(a) runs: pure host arithmetic over the arguments and the LDX_ATTN* dispatch switches, which are read once when the library loads.
+// launch_attention switches on it, the planner asks it (Engine::op_attn, Engine::n_launches, the single-op C ABI), ldx_op_attn_pick shows it to tests.
+enum AttnFamily : int { AF_ATTN = 0, AF_ATTN32, AF_ATTN32AP, AF_ATTN32G, AF_ATTN40P, AF_ATTN128P, AF_ATTN512 };      // attn_kernel (16x16 MFMAs), attn32_kernel, attn32ap_kernel, attn32g_kernel (attention.hip, attn32ap.inc); attn40p_kernel (attn_pipe.hip), attn128p_kernel (attn_pipe128.hip), attn512_kernel (attn512.hip)
+struct AttnPick {
+    AttnFamily family;
+    int targ[3];                   // the template arguments after the type, as instantiated: attn_kernel KS, DT, QT; attn32g_kernel NKS, NDT, ONES; attn32_kernel KVB, VAR; attn32ap_kernel VAR; 0 elsewhere
+    bool kpf;                      // attn32g_kernel: with the K fragment prefetch ring (its KPFON argument)
+    int qb, block;                 // queries per workgroup, threads per workgroup
+    unsigned grid; int lds;        // workgroups, dynamic LDS bytes
+    bool knorm;                    // pipelined kernels: a key-norm launch runs first (AttnArgs::knorm_ws given and LDX_ATTN_PIPE_KB != 0)
+    float thr;                     // pipelined kernels: rescale threshold override (LDX_ATTN_PIPE_THR), NaN = the type's own
+    int nsplit;                    // key splits in effect: 1, or attn512 with AttnArgs::nsplit and its workspace; > 1: a merge launch follows
+    int nsplit_want;               // attn512: the splits a caller should ask for, with attn512_ws_floats() floats in AttnArgs::split_ws
+    bool mx_out;                   // a caller may set AttnArgs::O8: the generic D = 128 gate holds, so attn128p_kernel or attn32g_kernel<8, 4> takes the launch
+    int launches;                  // kernel launches in all (0: empty problem)
+};
+AttnPick attn_pick(const AttnArgs& a);
+bool attn_pipe_ok(const AttnArgs& a);      // the shape rule of the two pipelined kernels, grid-fill gates aside: the planner provides AttnArgs::knorm_ws for these
+// the LDX_ATTN* switches are read once at load; this re-reads all of them (tests / same-process A/B runs only — never on the launch path)
 void reload_dispatch_env();
 
-// Software-pipelined D = 40 kernel (attn_pipe.hip, round 4): attn_pipe_ok() says whether it takes the shape (D = 40, Nq % 256 == 0, Mk % 128 == 0,
-// Mk >= 256, no mask / bias); thr_override = NaN keeps the type's rescale threshold (tests force the rare path with small values).
-bool attn_pipe_ok(const AttnArgs& a);
-void launch_attn_pipe(const AttnArgs& a, DType dt, hipStream_t s, float thr_override);
-// The same pipeline for D = 128 (attn_pipe128.hip: Flux joint attention), 16-bit or MX fp8 output (AttnArgs::O8)
-bool attn_pipe128_ok(const AttnArgs& a);
-// Flash attention for D = 512 heads (attn512.hip): attn512_ok() says whether launch_attention takes the shape; the planner asks attn512_splits() for the
-// key split and provides attn512_ws_floats() floats of workspace in AttnArgs::split_ws
-bool attn512_ok(const AttnArgs& a);
-int attn512_splits(const AttnArgs& a);
+// The kernels of the other files, launched by launch_attention with the pick that chose them (grid, LDS size; threshold and key-norm launch; key splits).
+// attn_pipe.hip: software-pipelined D = 40 kernel (round 4); attn_pipe128.hip: the same pipeline for D = 128 (Flux joint attention), 16-bit or MX fp8 output (AttnArgs::O8);
+// attn512.hip: flash attention for D = 512 heads, keys split over AttnPick::nsplit workgroups per query block
+constexpr int ATTN40P_LDS = 2 * 64 * (144 + 192), ATTN128P_LDS = 3 * 64 * (272 + 320);
+constexpr int ATTN512_QB = 128, ATTN512_KV = 32, ATTN512_LDS = 2 * ATTN512_KV * ((512 * 2 + 16) + (512 * 2 + 64));      // queries per workgroup, keys per block, two stages of K and V rows
+void launch_attn_pipe(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s);
+void launch_attn_pipe128(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s);
+void launch_attn512(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s);
 size_t attn512_ws_floats(const AttnArgs& a, int nsplit);
-void launch_attn512(const AttnArgs& a, DType dt, hipStream_t s);
 void launch_attn_knorm(const AttnArgs& a, DType dt, hipStream_t s);      // key-block norms for either pipelined kernel (AttnArgs::knorm_ws)
-void launch_attn_pipe128(const AttnArgs& a, DType dt, hipStream_t s, float thr_override);
 
 // Cross-attention sub-block as one kernel (xattn_block.hip): H[m][:] += to_out(softmax(to_q(LayerNorm(H[m][:])) . K_b^T) . V_b) + bo, in place,
 // for m in [0, M), image b = m / N.  Wq / Wo: [C][C] 16-bit, row = output feature.  K / V: the projected context, rows b * Mk + key, head h at
@@ -219,7 +231,6 @@ bool rowgemm_ok(const RowGemmArgs& a);
 void launch_rowgemm(const RowGemmArgs& a, DType dt, hipStream_t s);
 bool xattn_block_ok(const XAttnArgs& a);
 void launch_xattn_block(const XAttnArgs& a, DType dt, hipStream_t s);
-bool attention_mx_out_ok(const AttnArgs& a);      // true if launch_attention will take a kernel that implements O8 / SO
 
 // ---------------------------------------------------------------------------------------------
 // GroupNorm(32 groups) over NHWC + optional SiLU.  Two launches: partial statistics, then apply.

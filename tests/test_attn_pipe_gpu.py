@@ -70,11 +70,25 @@ class _Env:
         self._reload()
 
 
-def _attn(L, ldx, q, k, v, H, scale, code, pipe, thr=None):
+FAMILIES = ("attn", "attn32", "attn32ap", "attn32g", "attn40p", "attn128p", "attn512")      # ldx_op_attn_pick, out[0]
+
+
+def _family(L, q, k, v, H, ldo, o8=0):
+    """The kernel family the dispatcher gives this attention under the switches in effect (ldx_op_attn_pick: host arithmetic, launches nothing)."""
+    B, N, Cc = q.shape
+    out = (C.c_int32 * 13)()
+    assert L.ldx_op_attn_pick(B, H, N, k.shape[1], Cc // H, 0, 0, o8, q.stride(1), k.stride(1), v.stride(1), ldo, 1, out) == 0
+    return FAMILIES[out[0]]
+
+
+def _attn(L, ldx, q, k, v, H, scale, code, pipe, thr=None, taken=None):
+    """taken: whether the pipelined kernel takes the launch — by default it does with pipe = 1 and never with pipe = 0; asserted before launching."""
     B, N, Cc = q.shape
     D = Cc // H
     out = torch.full_like(q, float("nan"))
     with _Env(LDX_ATTN_PIPE=pipe, LDX_ATTN_PIPE128=pipe, LDX_ATTN_PIPE_MINWG=1, LDX_ATTN_PIPE_THR=thr):
+        fam = _family(L, q, k, v, H, Cc)
+        assert (fam == {40: "attn40p", 128: "attn128p"}[D]) == (bool(pipe) if taken is None else taken), (fam, pipe, taken)
         ldx.lib.check(L.ldx_op_attention(_p(q), q.stride(1), _p(k), k.stride(1), _p(v), v.stride(1), _p(out), Cc, B, H, N, k.shape[1], D, scale, 0, code, _st()), "attn")
     torch.cuda.synchronize()
     return out
@@ -221,7 +235,7 @@ def test_shapes_the_dispatcher_declines_or_takes_with_other_key_counts(L, ldx, B
     k = torch.randn(B, M, H * D, device="cuda", generator=g).to(td)
     v = torch.randn(B, M, H * D, device="cuda", generator=g).to(td)
     scale = 1.0 / math.sqrt(D)
-    got = _attn(L, ldx, q, k, v, H, scale, code, pipe=1)
+    got = _attn(L, ldx, q, k, v, H, scale, code, pipe=1, taken=(N, M) == (768, 640))
     _check(got, _ref(q, k, v, H, scale), "bf16", f"fallback N{N} M{M}")
 
 
@@ -308,6 +322,7 @@ def test_pipe128_flux_shape_rows_and_mx_output(L, ldx):
         Y = torch.zeros(B * N, Cn + 16, device="cuda", dtype=torch.uint8)
         S = torch.zeros(Cn // 128, B * N + 9, 4, device="cuda", dtype=torch.uint8)
         with _Env(LDX_ATTN_PIPE128=pipe):
+            assert _family(L, q, k, v, H, Cn + 16, o8=1) == ("attn128p" if pipe else "attn32g")
             ldx.lib.check(L.ldx_op_attention_mx(_p(q), q.stride(1), _p(k), k.stride(1), _p(v), v.stride(1), _p(Y), Cn + 16, _p(S), B * N + 9, B, H, N, N, scale, code, _st()), "attention_mx")
         torch.cuda.synchronize()
         return Y.cpu()[:, :Cn].clone(), S.cpu()[:, :B * N].clone()
@@ -334,5 +349,5 @@ def test_pipe128_declined_shapes_stay_correct(L, ldx, B, H, N, M):
     k = torch.randn(B, M, H * D, device="cuda", generator=g).to(td)
     v = torch.randn(B, M, H * D, device="cuda", generator=g).to(td)
     scale = 1.0 / math.sqrt(D)
-    got = _attn(L, ldx, q, k, v, H, scale, code, pipe=1)
+    got = _attn(L, ldx, q, k, v, H, scale, code, pipe=1, taken=(N, M) == (768, 640))
     _check(got, _ref(q, k, v, H, scale), "bf16", f"D128 N{N} M{M}")

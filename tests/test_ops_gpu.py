@@ -7,6 +7,7 @@ and on max-abs relative to the output scale (<= 2e-2 bf16 / 4e-3 fp16); attentio
 """
 import ctypes as C
 import math
+import os
 
 import pytest
 import torch
@@ -272,17 +273,29 @@ def test_layernorm(L, ldx, dt, rows, C):
     _check(Y, F.layer_norm(X.float(), (C,), gamma, beta, 1e-5), dt, what="layernorm")
 
 
+ATTN_FAMILIES = ("attn", "attn32", "attn32ap", "attn32g", "attn40p", "attn128p", "attn512")      # ldx_op_attn_pick, out[0]
+# the D = 40 kernel behind the pipelined one: the 8-wave attn32ap_kernel, or the 4-wave attn32_kernel where test_pingpong_gpu.py reruns these tests with LDX_ATTN32_AP=0
+D40_KERNEL = "attn32" if os.environ.get("LDX_ATTN32_AP") == "0" else "attn32ap"
+
+
+def _attn_family(L, B, H, Nq, Mk, D, causal, ldq, ldk, ldv, ldo):
+    """The kernel family the dispatcher gives this attention (ldx_op_attn_pick: host arithmetic, launches nothing)."""
+    out = (C.c_int32 * 13)()
+    assert L.ldx_op_attn_pick(B, H, Nq, Mk, D, causal, 0, 0, ldq, ldk, ldv, ldo, 1, out) == 0
+    return ATTN_FAMILIES[out[0]]
+
+
+# B, H, Nq, Mk, D, causal, fused_qkv
+ATTN_D40_CASES = [       # 512 workgroups of 256 queries, 256 of 512 queries, and a shape the pipelined kernel refuses (ragged keys / queries, 64 keys): D40_KERNEL
+    (4, 16, 2048, 333, 40, 0, 0), (8, 8, 2000, 2048, 40, 0, 0), (2, 32, 2048, 64, 40, 0, 0)]
+ATTN_G32_CASES = [       # >= 16 workgroups of 128 queries at D = 80 / 160 / 128, ragged or too small for the pipelined D = 128 kernel: the generic 32x32x16 kernel (attn32g_kernel)
+    (2, 8, 1024, 1024, 160, 0, 1), (2, 8, 4096, 77, 80, 0, 0), (2, 16, 1000, 333, 80, 0, 0), (4, 8, 513, 1024, 160, 0, 0), (2, 8, 4096, 4096, 80, 0, 1),
+    (1, 24, 1100, 1100, 128, 0, 1), (2, 12, 700, 130, 128, 0, 0)]       # D = 128 (Flux): VALU-denominator variant
 ATTN_CASES = [
-    # B, H, Nq, Mk, D, causal, fused_qkv
     (2, 8, 256, 256, 8, 0, 1), (2, 8, 200, 200, 16, 0, 1), (1, 8, 1024, 1024, 32, 0, 1), (2, 8, 1024, 1024, 40, 0, 1),
     (2, 8, 4096, 77, 40, 0, 0), (1, 8, 300, 154, 80, 0, 0), (2, 8, 256, 256, 160, 0, 1), (2, 12, 77, 77, 64, 1, 1),
     (1, 8, 4096, 4096, 40, 0, 1), (1, 2, 130, 231, 64, 0, 0), (1, 4, 200, 200, 64, 1, 1),
-    # >= 512 workgroups of 256 queries at D = 40: the 32x32x16 kernel (attn32_kernel), ragged key and query tails
-    (4, 16, 2048, 333, 40, 0, 0), (8, 8, 2000, 2048, 40, 0, 0), (2, 32, 2048, 64, 40, 0, 0),
-    # >= 64 workgroups of 128 queries at D = 80 / 160: the generic 32x32x16 kernel (attn32g_kernel)
-    (2, 8, 1024, 1024, 160, 0, 1), (2, 8, 4096, 77, 80, 0, 0), (2, 16, 1000, 333, 80, 0, 0), (4, 8, 513, 1024, 160, 0, 0), (2, 8, 4096, 4096, 80, 0, 1),
-    (1, 24, 1100, 1100, 128, 0, 1), (2, 12, 700, 130, 128, 0, 0),       # D = 128 (Flux): VALU-denominator variant
-]
+] + ATTN_D40_CASES + ATTN_G32_CASES
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
@@ -303,6 +316,8 @@ def test_attention(L, ldx, dt, case):
         ldq, ldk, ldv = C_, 2 * C_, 2 * C_
     O_ = torch.zeros(B, Nq, C_, device="cuda", dtype=td)
     scale = 1.0 / math.sqrt(D)
+    want = D40_KERNEL if case in ATTN_D40_CASES else "attn32g" if case in ATTN_G32_CASES else None
+    assert want is None or _attn_family(L, B, H, Nq, Mk, D, causal, ldq, ldk, ldv, C_) == want
     ldx.lib.check(L.ldx_op_attention(_p(q), ldq, _p(k), ldk, _p(v), ldv, _p(O_), C_, B, H, Nq, Mk, D, scale, causal, code, _st()), "attn")
     torch.cuda.synchronize()
     qf, kf, vf = (t.float().reshape(B, -1, H, D).transpose(1, 2) for t in (q, k, v))
@@ -313,11 +328,17 @@ def test_attention(L, ldx, dt, case):
     _check(O_, ref, dt, scale=2.0, what=f"attention {case}")
 
 
-@pytest.mark.parametrize("shape", [(1, 2, 512, 40), (4, 16, 2048, 40)])      # second shape: 256 workgroups of 512 queries -> attn32ap_kernel (round 3)
+# the 16x16 kernel; 256 workgroups of 256 queries: the pipelined kernel; the same grid with a ragged last query block, which that kernel refuses: 256 workgroups of 512
+# queries, the smallest grid attn32ap_kernel takes by default
+RESCALE_KERNELS = {(1, 2, 512, 40): "attn", (4, 16, 2048, 40): "attn40p", (4, 16, 2000, 40): D40_KERNEL}
+
+
+@pytest.mark.parametrize("shape", list(RESCALE_KERNELS))
 def test_attention_online_softmax_rescale(L, ldx, shape):
     """Force the running-max rescale: one key late in the sequence dominates every row (cdna guide rule 26)."""
     td, code = DT["bf16"]
     B, H, N, D = shape
+    assert _attn_family(L, B, H, N, N, D, 0, H * D, H * D, H * D, H * D) == RESCALE_KERNELS[shape]
     g = torch.Generator(device="cuda").manual_seed(9)
     q = torch.randn(B, N, H * D, device="cuda", generator=g)
     k = torch.randn(B, N, H * D, device="cuda", generator=g)

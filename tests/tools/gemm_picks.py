@@ -13,17 +13,14 @@ a narrower tile (and mostly aborted on the mismatch); the table holds the answer
     python tests/tools/gemm_picks.py --rows     # the rows themselves, one per line (the probe's integer arguments)
     python tests/tools/gemm_picks.py --show     # the committed table, readable: every row of every environment with its pick
 """
-import array
-import base64
 import ctypes as C
-import hashlib
-import json
 import os
-import subprocess
 import sys
-import zlib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from pick_table import ROOT, decode, env_key, load_lib, rows_digest  # noqa: E402,F401  (the test asks this module for them)
+import pick_table  # noqa: E402
+
 TABLE = os.path.join(ROOT, "tests", "golden", "gemm_picks.json")
 
 FAMILIES = ("tile", "tile2", "pingpong", "pingpong2", "ring", "conv_patch", "tile_mx", "tile2_mx", "pingpong_mx", "pingpong2_mx")      # GemmFamily (ldx_kernels.h)
@@ -32,10 +29,6 @@ OUT = ("family", "bm", "bn", "wm", "f8", "lnf", "S", "reduce", "launches", "gn_c
 FIELDS = ("family", "bm", "bn", "S", "reduce", "launches", "gn_chunks")                          # what the table holds
 ENVS = [{}] + [{"LDX_GEMM_TILE": t} for t in ("256128", "256160", "256192", "256224", "256256", "64160")] + [{"LDX_PP": "0"}, {"LDX_PP": "2"}, {"LDX_GN_FUSE": "0"}]
 GN_MAX = 256      # chunks per image the engine's GroupNorm workspace holds
-
-
-def env_key(env):
-    return ",".join(f"{k}={v}" for k, v in sorted(env.items())) or "default"
 
 
 # ---- rows: the probe's arguments (M, N, K, mode, geglu, splitk, f8, c8, ln_fold, Cin, Hin, Win, Hout, Wout, stride, M2, N2, K2, gn_hw, gn_groups, gn_max_chunks)
@@ -151,16 +144,10 @@ def all_rows():
     return rows
 
 
-def rows_digest(rows):
-    return hashlib.sha256("\n".join(" ".join(map(str, r)) for r in rows).encode()).hexdigest()
-
-
 # ---- asking the library
 def picks_of_current_env(rows):
     """[(family, bm, bn, S, reduce, launches, gn_chunks)] of this process's environment (the switches are read once, when the library loads)."""
-    sys.path.insert(0, ROOT)
-    import ldx_amd
-    L = ldx_amd.lib.load()
+    L = load_lib()
     out = (C.c_int32 * len(OUT))()
     keep = [OUT.index(f) for f in FIELDS]
     res = []
@@ -172,38 +159,15 @@ def picks_of_current_env(rows):
 
 
 def picks_of_env(env):
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("LDX_")}
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--dump"], env=dict(clean, **env), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return [tuple(p) for p in json.loads(r.stdout)]
-
-
-# ---- the table: the distinct picks once, then per environment one 16-bit index per row, deflated and base64-coded (ten environments x 14 244 rows repeat
-# themselves enough to shrink from 430 KB of digits to about 30 KB); `--show` prints it row by row
-def encode(per_env):
-    uniq = sorted({p for picks in per_env.values() for p in picks})
-    idx = {p: i for i, p in enumerate(uniq)}
-    return uniq, {k: base64.b64encode(zlib.compress(array.array("H", [idx[p] for p in picks]).tobytes(), 9)).decode() for k, picks in per_env.items()}
-
-
-def decode(table, key):
-    a = array.array("H")
-    a.frombytes(zlib.decompress(base64.b64decode(table["envs"][key])))
-    return [tuple(table["picks"][i]) for i in a]
+    return pick_table.picks_of_env(__file__, env)
 
 
 def load_table():
-    with open(TABLE) as f:
-        return json.load(f)
+    return pick_table.load_table(TABLE)
 
 
 def write_table(per_env, rows, path=TABLE):
-    uniq, envs = encode(per_env)
-    t = {"fields": list(FIELDS), "families": list(FAMILIES), "reduce": list(REDUCE), "n_rows": len(rows), "rows_sha256": rows_digest(rows),
-         "picks": [list(p) for p in uniq], "envs": envs}
-    with open(path, "w") as f:          # one key per line
-        f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(t[k], sort_keys=True, separators=(',', ':'))}" for k in sorted(t)) + "\n}\n")
-    return t
+    return pick_table.write_table(path, per_env, rows, fields=list(FIELDS), families=list(FAMILIES), reduce=list(REDUCE))
 
 
 def describe(row, pick):
@@ -212,26 +176,4 @@ def describe(row, pick):
 
 
 if __name__ == "__main__":
-    rows = all_rows()
-    if "--rows" in sys.argv:
-        print("\n".join(" ".join(map(str, r)) for r in rows))
-    elif "--show" in sys.argv:
-        t = load_table()
-        for k in t["envs"]:
-            for r, p in zip(rows, decode(t, k)):
-                print(k, describe(r, p))
-    elif "--dump" in sys.argv:
-        print(json.dumps(picks_of_current_env(rows)))
-    else:
-        per_env = {env_key(e): picks_of_env(e) for e in ENVS}
-        if "--write" in sys.argv:
-            write_table(per_env, rows)
-            print(f"wrote {len(rows)} rows x {len(ENVS)} environments to {TABLE}")
-        else:
-            t = load_table()
-            for k, picks in per_env.items():
-                old = decode(t, k)
-                moved = [i for i in range(len(rows)) if i >= len(old) or old[i] != picks[i]]
-                print(f"{k}: {len(rows)} rows, {len(moved)} differ from the table")
-                for i in moved[:20]:
-                    print("   ", describe(rows[i], picks[i]), " (table:", old[i] if i < len(old) else None, ")")
+    pick_table.cli(sys.modules[__name__])
