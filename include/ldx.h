@@ -385,6 +385,15 @@ int ldx_op_gemm_pick(int M, int N, int K, int mode, int geglu, int splitk, int f
  * ring on / off, queries per workgroup, threads per workgroup, workgroups, dynamic LDS bytes, key-norm launch first (0 / 1), key splits in effect (attn512, with the
  * workspace the planner gives it; > 1: a merge launch follows), MX fp8 output allowed for the shape (0 / 1), kernel launches. */
 int ldx_op_attn_pick(int B, int H, int Nq, int Mk, int D, int causal, int bias, int o8, int ldq, int ldk, int ldv, int ldo, int knorm_ws, int32_t* out);
+/* Read-only probe: the stage choice of one SpatialTransformer of a UNet plan (xf_pick).  Launches nothing and touches no device.  C level width, B evaluation
+ * batch, HW pixels per image, Mc context tokens, share the batch of the shared CFG prefix (0 = none), ln_fold whether folded LayerNorm weights were loaded,
+ * gn_stats_chunks the statistics rows per image the producer of the transformer's input wrote (0 = none).
+ * out[0 .. 19] = LayerNorms folded (0 / 1), norm + proj_in as one rowgemm launch (0 / 1), proj_out stage; then for the first block and for every later block eight
+ * values each: norm1 + q|k|v stage, to_out 1 stage, cross-attention as one xattn_block launch (0 / 1), norm2 + q stage, to_out 2 stage, feed-forward as one ff_block
+ * launch (0 / 1), norm3 + GEGLU projection stage, ops of the block; last the ops of norm + proj_in and proj_out together.  Stages: 0 tile GEMM, 1 row-block launch
+ * (rowgemm), 2 one GEMM on folded weights, 3 LayerNorm + GEMM, 4 affine-free LayerNorm + GEMM on folded weights.  norm2 / to_out 2 / norm3 stages say what runs when
+ * the one-launch sub-block does not.  An op is one launch unless gemm_pick / attn_pick say more (split-K reduce, key norms). */
+int ldx_op_xf_pick(int C, int heads, int B, int HW, int Mc, int share, int ln_fold, int gn_stats_chunks, int32_t* out);
 int ldx_op_conv3x3(const void* X, int ldx, const void* W, int B, int Hin, int Win, int Cin, int Cout,
                    int stride, int Hout, int Wout, int resize_to_out, const float* bias,
                    const float* rowvec, int rowvec_ld, const void* R, int ldr, void* Y, int ldy,

@@ -532,6 +532,17 @@ int ldx_op_attn_pick(int B, int H, int Nq, int Mk, int D, int causal, int bias, 
     for (int i = 0; i < 13; ++i) out[i] = r[i];
     return LDX_OK;
 }
+int ldx_op_xf_pick(int C, int heads, int B, int HW, int Mc, int share, int ln_fold, int gn_stats_chunks, int32_t* out) {
+    if (!out || C <= 0 || heads <= 0 || C % heads || B <= 0 || HW <= 0 || Mc <= 0 || share < 0 || share > B || gn_stats_chunks < 0) {
+        set_error("ldx_op_xf_pick: bad argument (positive sizes, C % heads == 0, 0 <= share <= B)"); return LDX_EINVAL; }
+    const XfPick p = xf_pick(XfShape{C, heads, B, HW, Mc, share, ln_fold != 0, gn_stats_chunks});
+    int n = 0;
+    out[n++] = p.fold; out[n++] = p.proj_in_rowgemm; out[n++] = p.proj_out;
+    for (const XfBlockPick* b : {&p.first, &p.rest})
+        for (int v : {(int)b->qkv, (int)b->o1, (int)b->xattn, (int)b->q2, (int)b->o2, (int)b->ffblock, (int)b->ff1, b->ops}) out[n++] = v;
+    out[n++] = p.ops_outer;
+    return LDX_OK;
+}
 int ldx_op_conv3x3(const void* X, int ldx_, const void* W, int B, int Hin, int Win, int Cin, int Cout, int stride, int Hout, int Wout,
                    int resize_to_out, const float* bias, const float* rowvec, int rowvec_ld, const void* R, int ldr, void* Y, int ldy,
                    int dtype, void* stream) {

@@ -317,9 +317,6 @@ bool Engine::mk_res(const std::string& pre, int Cin, int Cout, ResW& r) {
     return true;
 }
 
-#ifndef LDX_LNFOLD_MAXROWS_DEFAULT
-#define LDX_LNFOLD_MAXROWS_DEFAULT 8192      // rows of a transformer level up to which its LayerNorms are folded into the consuming GEMMs (emit_xf)
-#endif
 static inline bool q_prescale() { static const bool on = getenv("LDX_NO_QPRESCALE") == nullptr; return on; }
 
 bool Engine::mk_xf(const std::string& pre, int C, int depth, XfW& x) {
@@ -586,13 +583,18 @@ void Engine::op_conv(const char* name, Act X, int B, int Hin, int Win, int Cin, 
     cur.ops.push_back(o);
     cur.flops += o.flops;
 }
+// the kernels launch_groupnorm runs for the op as it stands (fuse_gn_stats asks again once the statistics come from the producer)
+static void gn_label(Op& o) {
+    static const char* const names[] = {"gn_small", "gn_stats+gn_apply", "gn_apply(fused stats)", "gn_fold+gn_apply(fused stats)"};      // by GnKind
+    snprintf(o.klabel, sizeof(o.klabel), "%s", names[gn_pick(o.gn).kind]);
+}
 void Engine::op_gn(const char* name, Act X, Act Y, int B, int HW, const NormW& n, float eps, bool silu) {
     Op o{}; o.kind = OP_GN; o.name = name;
     GroupNormArgs& g = o.gn;
     g.X = ptr(X); g.ldx = X.ld; g.Y = ptr(Y); g.ldy = Y.ld; g.B = B; g.HW = HW; g.C = n.C; g.G = 32; g.eps = eps; g.silu = silu;
     g.gamma = n.g; g.beta = n.b; g.partial = (float*)(cur.arena ? (char*)cur.arena + cur.gn_ws_off : nullptr);
     o.bytes = 2.0 * 3.0 * (double)B * HW * n.C;       // read (stats) + read + write (apply)
-    snprintf(o.klabel, sizeof(o.klabel), "gn_stats+gn_apply");
+    gn_label(o);
     cur.ops.push_back(o);
 }
 // SURVEY §8 a10-a11 / VERDICT r2 item 1c: GroupNorm statistics from the producing conv / GEMM epilogue.  A GroupNorm whose input tensor was written by
@@ -605,13 +607,13 @@ void Engine::fuse_gn_stats() {
         if (cur.ops[i].kind == OP_GN && cur.ops[i - 1].kind == OP_ROWGEMM) {          // row-block producer (proj_out + residual): statistics from its output stage
             RowGemmArgs& r = cur.ops[i - 1].rg;
             GroupNormArgs& n = cur.ops[i].gn;
-            const int bm = 128 * 320 / r.K;
+            const int bm = rowblock_rows(r.K);
             if (!gemm_gn_fuse_enabled() || r.pro == 2 || r.Y != n.X || r.ldy != n.ldx || r.N != n.C || r.N != r.K || n.G != 32 || (long)r.M != (long)n.B * n.HW || n.HW % bm || n.HW / bm > gn_ws_rows ||
                 gn_uses_small_kernel(n.B, n.HW, n.C, n.G)) continue;      // last term: the one-launch small GroupNorm kernel takes it (norm.hip)
             r.gn_out = n.partial; r.gn_nchunk = n.HW / bm; r.HW = n.HW;
             n.stats_chunks = n.HW / bm;
             cur.ops[i].bytes = 2.0 * 2.0 * (double)n.B * n.HW * n.C;
-            snprintf(cur.ops[i].klabel, sizeof(cur.ops[i].klabel), "gn_apply(fused stats)");
+            gn_label(cur.ops[i]);
             continue;
         }
         if (cur.ops[i].kind != OP_GN || cur.ops[i - 1].kind != OP_GEMM) continue;
@@ -623,62 +625,41 @@ void Engine::fuse_gn_stats() {
         g.gn_partial = n.partial;
         n.stats_chunks = nchunk;
         cur.ops[i].bytes = 2.0 * 2.0 * (double)n.B * n.HW * n.C;       // read + write (apply only)
-        snprintf(cur.ops[i].klabel, sizeof(cur.ops[i].klabel), "gn_apply(fused stats)");
+        gn_label(cur.ops[i]);
     }
 }
-// Planner rule for the row-block kernels (rowgemm / xattn_block / ff_block): one workgroup per row block and one workgroup per CU, so below ~3/4 of the
-// CUs the tile GEMMs win (SD1.5 512^2 has 64 row blocks per launch: step 6.14 -> 6.83 ms with the row-block kernels) and smaller problems stay on the
-// separate launches.  LDX_ROWBLOCK_MINWG moves the limit (0: always).
-// In a shared CFG prefix (half the batch: 128 row blocks at 1024^2, bs = 1) the limit is lower: the alternative there is the SAME number of rows on LayerNorm +
-// tile-GEMM launches, which measured slower (LN 12.1 + GEMM 46.3 us against 40.6 for the row-block launch of the full batch; profiles/r06/share_*.txt).
-// rowblock_prefix is set by emit_xf / fuse_gn_rowgemm while they emit prefix ops.
-bool Engine::rowblock_fills_chip(long workgroups) const {
-    static const long min_wg = getenv("LDX_ROWBLOCK_MINWG") ? atol(getenv("LDX_ROWBLOCK_MINWG")) : 192;
-    static const long min_wg_prefix = getenv("LDX_ROWBLOCK_MINWG_PREFIX") ? atol(getenv("LDX_ROWBLOCK_MINWG_PREFIX")) : 96;
-    return workgroups >= (rowblock_prefix ? (min_wg_prefix < min_wg ? min_wg_prefix : min_wg) : min_wg);
-}
-// Row-block GEMM (rowgemm.hip) in place of [LayerNorm +] an N = 320 k, K = 320 projection; false (nothing emitted) when the kernel does not take it
-bool Engine::op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R, int pro, const NormW* nw) {
-    RowGemmArgs a{};
+// Row-block GEMM (rowgemm.hip) in place of [LayerNorm +] an N = k K, K = 320 / 640 projection, where xf_pick says so
+void Engine::op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R, int pro, const NormW* nw) {
+    Op o{}; o.kind = OP_ROWGEMM; o.name = name;
+    RowGemmArgs& a = o.rg;
     a.X = ptr(X); a.ldx = X.ld; a.Y = ptr(Y); a.ldy = Y.ld; a.M = X.rows; a.N = w.N; a.K = w.K; a.W = w.w; a.bias = w.b;
     a.R = R.valid ? ptr(R) : nullptr; a.ldr = R.ld; a.pro = pro; a.eps = 1e-5f;
     if (nw) { a.g = nw->g; a.b = nw->b; }
-    // Round 6: with nothing to fuse in front (pro = 0: to_out / proj_out + residual) the kernel only competes with the plain tile GEMM, whose output stage went
-    // lean: at K = 640 and many rows (CFG batch 16: M = 65 536) the tile GEMM wins (92 against 156 us per launch); at bs = 1 (M = 8192) the two are level in the
-    // step (13.27 against 13.28 ms) and the row block stays.
-    static const long plain640_maxm = getenv("LDX_ROWGEMM_PLAIN640_MAXM") ? atol(getenv("LDX_ROWGEMM_PLAIN640_MAXM")) : 16384;
-    if (pro == 0 && a.K == 640 && a.M > plain640_maxm) return false;
-    if (!w.w || !rowgemm_ok(a) || !rowblock_fills_chip((a.M + 128 * 320 / a.K - 1) / (128 * 320 / a.K) * (a.K / 320))) return false;
-    Op o{}; o.kind = OP_ROWGEMM; o.name = name; o.rg = a;
     o.flops = 2.0 * a.M * (double)a.N * a.K;
     o.bytes = 2.0 * ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N * (R.valid ? 2 : 1));
     snprintf(o.klabel, sizeof(o.klabel), "rowgemm<%s,%d>", dt == DT_BF16 ? "bf16" : "f16", pro);
     cur.ops.push_back(o);
     cur.flops += o.flops;
-    return true;
 }
-// GroupNorm (no SiLU, C = 320, statistics already written by its producer) directly followed by the N = K = 320 GEMM that reads its output
-// (SpatialTransformer norm + proj_in): the pair becomes one rowgemm launch with the GroupNorm apply as its prologue.  Runs after fuse_gn_stats().
+// SpatialTransformer norm + proj_in, as emit_xf emitted them, become one rowgemm launch with the GroupNorm apply as its prologue where xf_proj_in_rowgemm says so.
+// Runs after fuse_gn_stats() (the statistics must come from norm's producer) and after the hand-over of a shared prefix (a proj_in that also stores the second
+// half's rows stays a GEMM).
 void Engine::fuse_gn_rowgemm() {
     for (size_t i = 0; i + 1 < cur.ops.size(); ++i) {
-        rowblock_prefix = i < cur.prefix_end;
-        if (cur.ops[i].kind != OP_GN || cur.ops[i + 1].kind != OP_GEMM) continue;
+        if (cur.ops[i].kind != OP_GN || cur.ops[i + 1].kind != OP_GEMM || strcmp(cur.ops[i].name, "xf.norm") || strcmp(cur.ops[i + 1].name, "xf.proj_in")) continue;
         const GroupNormArgs& n = cur.ops[i].gn;
         const GemmArgs& g = cur.ops[i + 1].g;
-        if (n.silu || n.stats_chunks <= 0 || n.stats_chunks > GN_NCHUNK || n.G != 32 || g.A != n.Y || g.lda != n.ldy || g.mode != 0 || g.K != n.C || g.geglu || g.ln_c1 ||
-            g.f8 || g.C8 || g.Cf || g.rowvec || g.splitk > 1 || g.gate || g.R2 || g.act || g.oscale != 0.f || g.gn_partial || g.dup_rows || (long)g.M != (long)n.B * n.HW || !g.C) continue;
-        RowGemmArgs a{};
+        if (n.silu || g.dup_rows || !xf_proj_in_rowgemm(n.C, g.M, n.HW, i < cur.prefix_end, n.stats_chunks)) continue;
+        Op o{}; o.kind = OP_ROWGEMM; o.name = cur.ops[i + 1].name;
+        RowGemmArgs& a = o.rg;
         a.X = n.X; a.ldx = n.ldx; a.Y = g.C; a.ldy = g.ldc; a.M = g.M; a.N = g.N; a.K = g.K; a.W = g.W; a.bias = g.bias; a.R = g.R; a.ldr = g.ldr;
         a.pro = 2; a.g = n.gamma; a.b = n.beta; a.eps = n.eps; a.partial = n.partial; a.nchunk = n.stats_chunks; a.HW = n.HW; a.G = n.G;
-        if (!rowgemm_ok(a) || !rowblock_fills_chip((a.M + 128 * 320 / a.K - 1) / (128 * 320 / a.K) * (a.K / 320))) continue;
-        Op o{}; o.kind = OP_ROWGEMM; o.name = cur.ops[i + 1].name; o.rg = a;
         o.flops = cur.ops[i + 1].flops; o.bytes = cur.ops[i + 1].bytes;
         snprintf(o.klabel, sizeof(o.klabel), "rowgemm<%s,2>", dt == DT_BF16 ? "bf16" : "f16");
         cur.ops[i] = o;
         cur.ops.erase(cur.ops.begin() + (long)i + 1);
         if (i + 1 < cur.prefix_end) --cur.prefix_end;
     }
-    rowblock_prefix = false;
 }
 void Engine::op_ln(const char* name, Act X, Act Y, const NormW& n) {
     Op o{}; o.kind = OP_LN; o.name = name;
@@ -777,90 +758,81 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
     // Shared CFG prefix (plan(): share): up to the first cross-attention both halves of the batch hold the same values, so norm / proj_in / norm1 / q|k|v /
     // self-attention / to_out of the FIRST transformer block run on the first Bq samples (rows [0, Mq)) only
     int Bq = Bshare > 0 ? Bshare : B, Mq = Bq * H * W;
-    rowblock_prefix = Bq != B;
+    // which launches the level's stages run as; norm + proj_in become one rowgemm launch in fuse_gn_rowgemm, once norm's statistics come from its producer
+    const XfPick pick = xf_pick(XfShape{C, heads, B, H * W, Mc, Bshare, x.blocks[0].ln_fold, 0});
     auto head = [&](const Act& a) { Act v = a; v.rows = Mq; v.owned = false; return v; };      // the first Mq rows of a buffer
     Act t1 = new_act(M, C);
     op_gn("xf.norm", X, t1, Bq, H * W, x.gn, 1e-6f, false);
     Act h = new_act(M, C);
     op_gemm("xf.proj_in", head(t1), x.proj_in, head(h), Act{});
     release(t1);
-    // Folded LayerNorms (XfBlockW::ln_fold): the q|k|v / q / GEGLU GEMM reads h itself, accumulates each row's statistics from its own A
-    // fragments and normalises in its epilogue (GemmArgs::ln_c1): no LayerNorm launch, no normalised copy of h.  A split-K consumer keeps a
-    // plain (affine-free) LayerNorm launch in front of the folded weights.
-    // Per level: folded where the row-block kernels do not take the level's projections (fewer than ~192 row blocks) and the level is small (measured,
-    // same box: 512^2 step 6.00 -> 5.88 ms with all three levels folded, 430 -> 382 launches; 1024^2 14.23 -> 14.25 with only the 32^2 level folded
-    // (neutral), 14.29 when the 64^2 level's rowgemm launches are replaced too; 8192 rows at C = 1280 (latent 256^2: HiresFix) lose 8 % of an evaluation:
-    // the folded GEGLU projection runs on the 128-row tiles instead of the ping-pong ones).  The limit is on rows x C; LDX_LNFOLD_MAXROWS moves it
-    // (rows at C = 320; 0: never).
-    static const long fold_maxrows = getenv("LDX_LNFOLD_MAXROWS") ? atol(getenv("LDX_LNFOLD_MAXROWS")) : LDX_LNFOLD_MAXROWS_DEFAULT;
-    const bool rowblocks = (C == 320 || C == 640) && rowblock_fills_chip(((long)M + 128 * 320 / C - 1) / (128 * 320 / C) * (C / 320));
-    const bool fold = x.depth > 0 && x.blocks[0].ln_fold && !rowblocks && (long)M * C <= fold_maxrows * 320;      // 8192 rows at C = 320, 2048 at C = 1280
     Act n{};
-    auto ln_gemm = [&](const char* ln_name, const char* name, const NormW& ln, const LinearW& w, const float* c1, Act Cc, bool geglu) {
-        if (fold && gemm_choose_splitk(Mq, w.N, w.K, geglu) == 1) {
-            op_gemm(name, head(h), w, head(Cc), Act{}, geglu);
+    // LayerNorm + projection of the first Mq rows of h, by stage: `w` behind a LayerNorm (its own launch or rowgemm's prologue), the folded copy `wf` otherwise
+    auto norm_gemm = [&](XfStage st, const char* rowgemm_name, const char* ln_name, const char* name, const NormW& ln, const LinearW& w, const LinearW& wf, const float* c1, Act Cc, bool geglu) {
+        if (st == XS_ROWBLOCK) { op_rowgemm(rowgemm_name, head(h), w, head(Cc), Act{}, 1, &ln); return; }
+        if (st == XS_FOLDED) {
+            op_gemm(name, head(h), wf, head(Cc), Act{}, geglu);
             GemmArgs& g = cur.ops.back().g;
             g.ln_c1 = c1; g.ln_eps = 1e-5f;
             return;
         }
         if (!n.valid) n = new_act(M, C);
         NormW plain = ln;
-        if (fold) { plain.g = nullptr; plain.b = nullptr; }     // gamma / beta already live in the folded weights / bias
+        if (st == XS_LN_FOLDED) { plain.g = nullptr; plain.b = nullptr; }     // gamma / beta already live in the folded weights / bias
         op_ln(ln_name, head(h), head(n), plain);
-        op_gemm(name, head(n), w, head(Cc), Act{}, geglu);
+        op_gemm(name, head(n), st == XS_LN_FOLDED ? wf : w, head(Cc), Act{}, geglu);
+    };
+    // projection + residual into h, in place: x += W . a + b
+    auto out_gemm = [&](XfStage st, const char* name, Act a, const LinearW& w) {
+        if (st == XS_ROWBLOCK) op_rowgemm(name, a, w, head(h), head(h), 0, nullptr); else op_gemm(name, a, w, head(h), head(h));
     };
     for (int d = 0; d < x.depth; ++d) {
         const XfBlockW& b = x.blocks[d];
+        const XfBlockPick& bp = d == 0 ? pick.first : pick.rest;
         Act qkv = new_act(M, 3 * C);
-        if (fold || b.qkv.b || !op_rowgemm("xf.ln1+qkv", head(h), b.qkv, head(qkv), Act{}, 1, &b.ln1))        // LayerNorm + q|k|v projection as one launch (C = 320)
-            ln_gemm("xf.ln1", "xf.qkv", b.ln1, fold ? b.qkv_f : b.qkv, b.c1_qkv, qkv, false);
+        norm_gemm(bp.qkv, "xf.ln1+qkv", "xf.ln1", "xf.qkv", b.ln1, b.qkv, b.qkv_f, b.c1_qkv, qkv, false);
         Act a = new_act(M, C);
         const char* base = (const char*)ptr(qkv);
         op_attn("xf.attn1", base, 3 * C, base + (size_t)C * 2, 3 * C, base + (size_t)2 * C * 2, 3 * C, a, Bq, heads, H * W, H * W, D);
         if (q_prescale()) cur.ops.back().at.scale = 1.0f / 1.44269504088896340736f;       // the q rows of the projection already carry scale * log2(e)
         release(qkv);
-        if (!op_rowgemm("xf.o1", head(a), b.o1, head(h), head(h), 0, nullptr))
-            op_gemm("xf.o1", head(a), b.o1, head(h), head(h));                   // x += attn1(norm1(x))   (in place)
+        out_gemm(bp.o1, "xf.o1", head(a), b.o1);                   // x += attn1(norm1(x))
         if (Bq != B) {
             // the context enters here: from now on the halves differ.  The second half's rows take over the shared results that full-batch ops still read.
             cur.prefix_end = cur.ops.size();                               // every op so far ran on one half of the batch
             if (dups) for (const DupReq& dq : *dups) dup_second_half(dq);
             dup_second_half(DupReq{h, Mq, cur.ops.size() - 1});       // the op just emitted (to_out + residual) wrote h
-            Bq = B; Mq = M; rowblock_prefix = false;
+            Bq = B; Mq = M;
         }
         // k|v of the context come from the one batched projection emitted at the start of the forward
         const char* kvb = (const char*)((uintptr_t)cur.arena + cur.kv_all_off) + (size_t)b.kv_off * 2;
-        XAttnArgs xa{};
-        xa.H = ptr(h); xa.ldh = h.ld; xa.M = M; xa.N = H * W; xa.C = C; xa.heads = heads; xa.ln_g = b.ln2.g; xa.ln_b = b.ln2.b; xa.eps = 1e-5f;
-        xa.Wq = b.q2.w; xa.Wo = b.o2.w; xa.bo = b.o2.b; xa.K = kvb; xa.ldk = kv_total; xa.V = kvb + (size_t)C * 2; xa.ldv = kv_total; xa.Mk = Mc;
-        xa.scale = q_prescale() ? 1.0f / 1.44269504088896340736f : 1.0f / std::sqrt((float)D);
-        if (!fold && !b.q2.b && xattn_block_ok(xa) && rowblock_fills_chip((M + 127) / 128)) {
+        if (bp.xattn) {
             // LayerNorm + q projection + attention over the context + out projection + residual as ONE launch (xattn_block.hip)
-            Op o{}; o.kind = OP_XATTN; o.name = "xf.xattn2"; o.xa = xa;
+            Op o{}; o.kind = OP_XATTN; o.name = "xf.xattn2";
+            XAttnArgs& xa = o.xa;
+            xa.H = ptr(h); xa.ldh = h.ld; xa.M = M; xa.N = H * W; xa.C = C; xa.heads = heads; xa.ln_g = b.ln2.g; xa.ln_b = b.ln2.b; xa.eps = 1e-5f;
+            xa.Wq = b.q2.w; xa.Wo = b.o2.w; xa.bo = b.o2.b; xa.K = kvb; xa.ldk = kv_total; xa.V = kvb + (size_t)C * 2; xa.ldv = kv_total; xa.Mk = Mc;
+            xa.scale = q_prescale() ? 1.0f / 1.44269504088896340736f : 1.0f / std::sqrt((float)D);
             o.flops = 2.0 * 2.0 * M * (double)C * C + 4.0 * B * heads * (double)(H * W) * Mc * D;
             o.bytes = 2.0 * 2.0 * (double)M * C;
             snprintf(o.klabel, sizeof(o.klabel), "xattn_block<%s>", dt == DT_BF16 ? "bf16" : "f16");
             cur.ops.push_back(o);
             cur.flops += o.flops;
-            release(a);
         } else {
             Act q = new_act(M, C);
-            static const bool x2 = !(getenv("LDX_ROWGEMM_X2") && atoi(getenv("LDX_ROWGEMM_X2")) == 0);      // A/B switch for the two uses below
-            if (!x2 || fold || b.q2.b || !op_rowgemm("xf.ln2+q2", h, b.q2, q, Act{}, 1, &b.ln2))          // C = 640: LayerNorm + q projection as one row-block launch
-                ln_gemm("xf.ln2", "xf.q2", b.ln2, fold ? b.q2_f : b.q2, b.c1_q2, q, false);
+            norm_gemm(bp.q2, "xf.ln2+q2", "xf.ln2", "xf.q2", b.ln2, b.q2, b.q2_f, b.c1_q2, q, false);
             op_attn("xf.attn2", ptr(q), C, kvb, kv_total, kvb + (size_t)C * 2, kv_total, a, B, heads, H * W, Mc, D);
             if (q_prescale()) cur.ops.back().at.scale = 1.0f / 1.44269504088896340736f;       // the q rows of the projection already carry scale * log2(e)
             release(q);
-            if (!x2 || !op_rowgemm("xf.o2", a, b.o2, h, h, 0, nullptr))
-                op_gemm("xf.o2", a, b.o2, h, h);                   // x += attn2(norm2(x), ctx)
-            release(a);
+            out_gemm(bp.o2, "xf.o2", a, b.o2);                     // x += attn2(norm2(x), ctx)
         }
-        FFBlockArgs fa{};
-        fa.H = ptr(h); fa.ldh = h.ld; fa.M = M; fa.C = C; fa.inner = 4 * C; fa.ln_g = b.ln3.g; fa.ln_b = b.ln3.b; fa.eps = 1e-5f;
-        fa.W1 = b.ff1.w; fa.b1 = b.ff1.b; fa.W2 = b.ff2.w; fa.b2 = b.ff2.b;
-        if (!fold && ff_block_ok(fa) && rowblock_fills_chip((M + 127) / 128)) {
+        release(a);
+        if (bp.ffblock) {
             // LayerNorm + GEGLU projection + down projection + residual as ONE launch (ff_block.hip): the [M][4C] activation never leaves the CUs
-            Op o{}; o.kind = OP_FFBLOCK; o.name = "xf.ffblock"; o.fb = fa;
+            Op o{}; o.kind = OP_FFBLOCK; o.name = "xf.ffblock";
+            FFBlockArgs& fa = o.fb;
+            fa.H = ptr(h); fa.ldh = h.ld; fa.M = M; fa.C = C; fa.inner = 4 * C; fa.ln_g = b.ln3.g; fa.ln_b = b.ln3.b; fa.eps = 1e-5f;
+            fa.W1 = b.ff1.w; fa.b1 = b.ff1.b; fa.W2 = b.ff2.w; fa.b2 = b.ff2.b;
             o.flops = 2.0 * M * (double)C * (8.0 * C) + 2.0 * M * (double)C * (4.0 * C);
             o.bytes = 2.0 * 2.0 * (double)M * C;
             snprintf(o.klabel, sizeof(o.klabel), "ff_block<%s>", dt == DT_BF16 ? "bf16" : "f16");
@@ -868,15 +840,14 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
             cur.flops += o.flops;
         } else {
             Act f = new_act(M, 4 * C);
-            ln_gemm("xf.ln3", "xf.ff1", b.ln3, fold ? b.ff1_f : b.ff1, b.c1_ff1, f, true);        // GEGLU
+            norm_gemm(bp.ff1, "", "xf.ln3", "xf.ff1", b.ln3, b.ff1, b.ff1_f, b.c1_ff1, f, true);        // GEGLU
             op_gemm("xf.ff2", f, b.ff2, h, h);                     // x = ff(norm3(x)) + x
             release(f);
         }
     }
     if (n.valid) release(n);
-    static const bool po = !(getenv("LDX_ROWGEMM_PO") && atoi(getenv("LDX_ROWGEMM_PO")) == 0);      // A/B switch
-    if (!po || !op_rowgemm("xf.proj_out", h, x.proj_out, OUT, X, 0, nullptr))
-        op_gemm("xf.proj_out", h, x.proj_out, OUT, X);         // + x_in
+    if (pick.proj_out == XS_ROWBLOCK) op_rowgemm("xf.proj_out", h, x.proj_out, OUT, X, 0, nullptr);
+    else op_gemm("xf.proj_out", h, x.proj_out, OUT, X);         // + x_in
     release(h);
 }
 
@@ -1093,7 +1064,7 @@ void Plan::release() {
 
 int Engine::build_plan(const PlanKey& key, const std::function<int()>& emit, bool zero_arena) {
     auto reset = [&] {
-        free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0; rowblock_prefix = false;
+        free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0;
         cur.ops.clear(); cur.flops = 0; cur.flops_shared = 0; cur.prefix_end = 0;
     };
     cur.key = PlanKey{};                  // no plan until the bound pass has completed
@@ -1366,7 +1337,7 @@ int64_t Engine::n_launches() const {
     int64_t n = 0;
     for (const Op& o : cur.ops) {
         if (ctx_cache && o.ctx_only) continue;            // steady state of a sampling run: the context's projections are cached
-        if (o.kind == OP_GN) n += o.gn.stats_chunks > GN_NCHUNK ? 2 : (o.gn.stats_chunks > 0 ? 1 : 2);      // fold + apply / apply / statistics + apply
+        if (o.kind == OP_GN) n += gn_pick(o.gn).launches;          // one for the small kernel and for apply-only, two with a statistics or fold launch
         else if (o.kind == OP_GEMM) n += gemm_pick(o.g).launches;          // with its split-K reduce launch, if it has one
         else if (o.kind == OP_GEMM2) n += gemm_pick(o.g, &o.g2).launches;
         else if (o.kind == OP_ATTN) n += attn_pick(o.at).launches;      // with the pipelined kernels' key-norm launch / attn512's merge launch

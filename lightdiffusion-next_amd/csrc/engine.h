@@ -230,9 +230,9 @@ private:
     int gn_ws_rows = 256;
     size_t gn_ws_bytes(int B, long HWmax) { gn_ws_rows = (int)gn_workspace_rows(HWmax); return (size_t)B * (gn_ws_rows + GN_FOLD) * 32 * 2 * 4; }
     size_t ws_alloc(size_t bytes);                        // split-K workspace of one op (engine.cpp)
-    void fuse_gn_stats();
-    void fuse_gn_rowgemm();                               // GroupNorm (producer statistics) + proj_in -> one rowgemm launch
-    bool op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R, int pro, const NormW* nw);          // post-pass over ops: GroupNorms whose input was just written by a fusable GEMM / conv get their statistics from its epilogue
+    void fuse_gn_stats();                                 // post-pass over ops: GroupNorms whose input was just written by a fusable GEMM / conv get their statistics from its epilogue
+    void fuse_gn_rowgemm();                               // post-pass: xf.norm (producer statistics) + xf.proj_in -> one rowgemm launch where xf_proj_in_rowgemm says so
+    void op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R, int pro, const NormW* nw);
     Bindings bind;                                        // this call's
     // VAE
     std::vector<std::vector<ResW>> vae_up; std::vector<LinearW> vae_upconv; std::vector<bool> vae_has_up;
@@ -268,8 +268,6 @@ private:
     std::vector<std::pair<size_t, size_t>> free_list;
     std::map<size_t, size_t> live;
     size_t arena_top = 0, arena_peak = 0;
-    bool rowblock_prefix = false;                         // emitting ops of the shared CFG prefix (rowblock_fills_chip)
-    bool rowblock_fills_chip(long workgroups) const;
     // Two passes of `emit` into cur: a dry one (arena == nullptr) measures the peak, the second binds real pointers into an arena of that
     // size (the current plan's when it is large enough; zero_arena: zero-filled).  cur.key = key on success.
     int build_plan(const PlanKey& key, const std::function<int()>& emit, bool zero_arena = false);

@@ -198,8 +198,7 @@ __global__ __launch_bounds__(512, 1) void ff_block_kernel(const FFBlockArgs p) {
 }
 
 bool ff_block_ok(const FFBlockArgs& a) {
-    static const bool off = getenv("LDX_FF_FUSE") && atoi(getenv("LDX_FF_FUSE")) == 0;
-    return !off && a.C == FB_C && a.inner == FB_I && a.M > 0 && a.ldh % 8 == 0 && a.b1 != nullptr;
+    return g_plan_sw.ff_fuse && a.C == FB_C && a.inner == FB_I && a.M > 0 && a.ldh % 8 == 0 && a.b1 != nullptr;
 }
 template <typename T>
 static void launch_ff_t(const FFBlockArgs& a, hipStream_t s) {

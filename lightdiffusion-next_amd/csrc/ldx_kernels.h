@@ -232,6 +232,50 @@ void launch_rowgemm(const RowGemmArgs& a, DType dt, hipStream_t s);
 bool xattn_block_ok(const XAttnArgs& a);
 void launch_xattn_block(const XAttnArgs& a, DType dt, hipStream_t s);
 
+// Every LDX_* switch behind the stage choice of a SpatialTransformer and the one-launch GroupNorm, read once when the library loads (xf_pick.cpp, next to the pick).
+// Deliberately NOT re-read by reload_dispatch_env(): plans bake these decisions into their op lists, and a reload between planning and launching would make the two disagree.
+struct PlanSwitches {
+    long rowblock_minwg, rowblock_minwg_prefix;      // LDX_ROWBLOCK_MINWG / _PREFIX: fewest workgroups a row-block launch may have (rowblock_fills_chip)
+    long plain640_maxm;                              // LDX_ROWGEMM_PLAIN640_MAXM: most rows of a K = 640 rowgemm without a prologue
+    long lnfold_maxrows;                             // LDX_LNFOLD_MAXROWS: rows at C = 320 up to which a level folds its LayerNorms (0: never)
+    long gn_small_max;                               // LDX_GN_SMALL_MAX: elements per (image, group) the one-launch GroupNorm kernel takes
+    bool rowgemm, rowgemm640, rowgemm_x2, rowgemm_po, xattn_fuse, ff_fuse;      // LDX_ROWGEMM, LDX_ROWGEMM640, LDX_ROWGEMM_X2, LDX_ROWGEMM_PO, LDX_XATTN_FUSE, LDX_FF_FUSE: 0 switches the kernel (or that use of it) off
+    PlanSwitches();
+};
+extern const PlanSwitches g_plan_sw;
+
+// The stage choice of one SpatialTransformer: pure host arithmetic over the level's shape, the switches above and the kernels' own shape rules (rowgemm_ok,
+// xattn_block_ok, ff_block_ok).  Engine::emit_xf emits what it says, Engine::fuse_gn_rowgemm asks xf_proj_in_rowgemm again once the producer's statistics are known,
+// ldx_op_xf_pick shows it to tests (xf_pick.cpp).
+struct XfShape {
+    int C, heads, B, HW, Mc;       // level width, heads, evaluation batch, pixels per image, context tokens
+    int Bshare;                    // batch of the shared CFG prefix (0 = none): norm / proj_in and the self-attention half of the FIRST block run on Bshare images
+    bool ln_fold;                  // folded LayerNorm copies of the weights were loaded (XfBlockW::ln_fold)
+    int gn_chunks;                 // statistics rows per image the producer of the input wrote for norm (0 = none)
+};
+enum XfStage : int { XS_TILE = 0,          // to_out / proj_out: the tile GEMM
+                     XS_ROWBLOCK,          // one row-block launch (rowgemm, prologue 1 in front of a projection, 0 for to_out / proj_out)
+                     XS_FOLDED,            // one GEMM on the folded weights (GemmArgs::ln_c1)
+                     XS_LN_GEMM,           // affine LayerNorm + GEMM
+                     XS_LN_FOLDED };       // affine-free LayerNorm + GEMM on the folded weights (the folded GEMM would be split-K)
+struct XfBlockPick {
+    XfStage qkv, o1, q2, o2, ff1;  // norm1 + q|k|v, to_out 1, norm2 + q, to_out 2, norm3 + GEGLU projection (q2 / o2 / ff1 unused inside xattn / ffblock)
+    bool xattn, ffblock;           // the cross-attention / feed-forward sub-block as one launch (xattn_block / ff_block)
+    int ops;                       // ops of the block; Engine::n_launches adds what gemm_pick / attn_pick say an op launches beyond one (split-K reduce, key norms)
+};
+struct XfPick {
+    bool fold;                     // the level runs its LayerNorms folded into the consuming GEMMs
+    bool proj_in_rowgemm;          // norm + proj_in as one rowgemm launch (GroupNorm prologue) instead of GroupNorm + GEMM
+    XfStage proj_out;
+    XfBlockPick first, rest;       // the first block and every later one (they differ under a shared prefix)
+    int ops_outer;                 // ops of norm + proj_in and proj_out; the transformer has ops_outer + first.ops + (depth - 1) * rest.ops
+};
+XfPick xf_pick(const XfShape& s);
+static inline int rowblock_rows(int K) { return 128 * 320 / K; }      // rows of one row block at width K = 320 / 640
+long rowblock_count(long M, int K);                          // workgroups of a row-block launch over M rows at width K (128 rows x 320 columns each)
+bool rowblock_fills_chip(long workgroups, bool prefix);      // the planner's chip-fill rule for them; prefix: the launch belongs to a shared CFG prefix
+bool xf_proj_in_rowgemm(int C, long M, int HW, bool prefix, int gn_chunks);      // XfPick::proj_in_rowgemm for M rows
+
 // ---------------------------------------------------------------------------------------------
 // GroupNorm(32 groups) over NHWC + optional SiLU.  Two launches: partial statistics, then apply.
 struct GroupNormArgs {
@@ -252,6 +296,17 @@ void launch_groupnorm(const GroupNormArgs& a, DType dt, hipStream_t s);
 // the dispatch rule of launch_groupnorm for its one-launch kernel (statistics + apply in one workgroup per (image, group)); the planner asks it too:
 // such a GroupNorm does not take producer-written statistics (LDX_GN_SMALL_MAX overrides the element bound)
 bool gn_uses_small_kernel(int B, long HW, int C, int G);
+// What launch_groupnorm(a) launches: pure host arithmetic.  The launcher switches on it, Engine::n_launches and the profile labels ask it.
+enum GnKind : int { GN_SMALL = 0, GN_STATS_APPLY, GN_APPLY, GN_FOLD_APPLY };      // gn_small_kernel / gn_stats_kernel + gn_apply_kernel / gn_apply_kernel on the producer's statistics / gn_fold_kernel first
+struct GnPick {
+    GnKind kind;
+    int CH, TX, RY;                // gn_stats_kernel / gn_apply_kernel: chunks per thread (the template argument), threads per pixel, pixel rows per workgroup
+    int nchunk;                    // statistics rows per image that gn_apply_kernel reads (GroupNormArgs::nchunk)
+    unsigned grid1[2], grid2[2];   // workgroups (x, y) of the first launch (small, statistics or fold; 0 = none) and of gn_apply_kernel (0 = none)
+    int lds;                       // dynamic LDS bytes of gn_stats_kernel
+    int launches;
+};
+GnPick gn_pick(const GroupNormArgs& a);
 
 // LayerNorm over the last dim C of [rows][ldx] -> [rows][ldy]
 // gamma/beta may be null (elementwise_affine=False); optional adaLN modulation (Flux):

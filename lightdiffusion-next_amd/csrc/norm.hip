@@ -357,63 +357,65 @@ __global__ __launch_bounds__(64) void gn_fold_kernel(const float* in, float* out
 }
 
 bool gn_uses_small_kernel(int B, long HW, int C, int G) {
-    static const long small_max = getenv("LDX_GN_SMALL_MAX") ? atol(getenv("LDX_GN_SMALL_MAX")) : 256 * 80;      // elements per (batch, group) the one-launch kernel takes
-    return G > 0 && (C / G) % 8 == 0 && HW * (C / G) <= small_max && (long)G * B >= 32;
+    return G > 0 && (C / G) % 8 == 0 && HW * (C / G) <= g_plan_sw.gn_small_max && (long)G * B >= 32;
+}
+
+GnPick gn_pick(const GroupNormArgs& a) {
+    GnPick p{};
+    if (a.stats_chunks <= 0 && gn_uses_small_kernel(a.B, a.HW, a.C, a.G)) {
+        p.kind = GN_SMALL; p.grid1[0] = a.G; p.grid1[1] = a.B; p.launches = 1;
+        return p;
+    }
+    const GnGeom g = gn_geom(a.C);
+    p.CH = g.CH; p.TX = g.TX; p.RY = g.RY;
+    if (a.stats_chunks > 0) {           // statistics came with the producer's epilogue: apply only, behind a fold of more rows than gn_apply wants
+        p.kind = a.stats_chunks > GN_NCHUNK ? GN_FOLD_APPLY : GN_APPLY;
+        p.nchunk = p.kind == GN_FOLD_APPLY ? GN_FOLD : a.stats_chunks;
+        if (p.kind == GN_FOLD_APPLY) { p.grid1[0] = GN_FOLD; p.grid1[1] = a.B; }
+    } else {
+        p.kind = GN_STATS_APPLY;
+        // enough pixel chunks to fill the chip (~1024 workgroups), but >= 4 pixels per thread row
+        int nchunk = (1024 + a.B - 1) / a.B;
+        const int maxc = (a.HW + g.RY * 4 - 1) / (g.RY * 4);
+        if (nchunk > maxc) nchunk = maxc;
+        if (nchunk > GN_NCHUNK) nchunk = GN_NCHUNK;
+        if (nchunk < 1) nchunk = 1;
+        p.nchunk = nchunk; p.grid1[0] = nchunk; p.grid1[1] = a.B;
+        p.lds = (int)((size_t)g.RY * a.C * 2 * sizeof(float));
+    }
+    int nblk = (a.HW + g.RY * 8 - 1) / (g.RY * 8);
+    if (nblk > 512) nblk = 512;
+    if (nblk < 1) nblk = 1;
+    p.grid2[0] = nblk; p.grid2[1] = a.B;
+    p.launches = p.kind == GN_APPLY ? 1 : 2;
+    return p;
 }
 
 template <typename T>
 static void launch_gn_t(const GroupNormArgs& a_in, hipStream_t s) {
+    const GnPick p = gn_pick(a_in);
     GroupNormArgs a = a_in;
-    if (a.stats_chunks > 0) {           // statistics came with the producer's epilogue: apply only
-        const GnGeom g = gn_geom(a.C);
-        a.nchunk = a.stats_chunks;
-        if (a.stats_chunks > GN_NCHUNK) {
-            float* folded = a.partial + (size_t)a.B * a.stats_chunks * a.G * 2;
-            hipLaunchKernelGGL(gn_fold_kernel, dim3(GN_FOLD, a.B), dim3(64), 0, s, a.partial, folded, a.stats_chunks, a.G);
-            a.partial = folded; a.nchunk = GN_FOLD;
-        }
-        int nblk = (a.HW + g.RY * 8 - 1) / (g.RY * 8);
-        if (nblk > 512) nblk = 512;
-        if (nblk < 1) nblk = 1;
-        dim3 grid2(nblk, a.B);
-        switch (g.CH) {
-            case 1: hipLaunchKernelGGL((gn_apply_kernel<T, 1>), grid2, dim3(256), 0, s, a, g.TX, g.RY, nblk); break;
-            case 2: hipLaunchKernelGGL((gn_apply_kernel<T, 2>), grid2, dim3(256), 0, s, a, g.TX, g.RY, nblk); break;
-            default: hipLaunchKernelGGL((gn_apply_kernel<T, 4>), grid2, dim3(256), 0, s, a, g.TX, g.RY, nblk); break;
-        }
+    const dim3 grid1(p.grid1[0], p.grid1[1]), grid2(p.grid2[0], p.grid2[1]);
+    if (p.kind == GN_SMALL) {
+        hipLaunchKernelGGL((gn_small_kernel<T>), grid1, dim3(256), 0, s, a);
         return;
     }
-    if (gn_uses_small_kernel(a.B, a.HW, a.C, a.G)) {
-        hipLaunchKernelGGL((gn_small_kernel<T>), dim3(a.G, a.B), dim3(256), 0, s, a);
-        return;
+    a.nchunk = p.nchunk;
+    if (p.kind == GN_FOLD_APPLY) {
+        float* folded = a.partial + (size_t)a.B * a.stats_chunks * a.G * 2;
+        hipLaunchKernelGGL(gn_fold_kernel, grid1, dim3(64), 0, s, a.partial, folded, a.stats_chunks, a.G);
+        a.partial = folded;
+    } else if (p.kind == GN_STATS_APPLY) {
+        switch (p.CH) {
+            case 1: hipLaunchKernelGGL((gn_stats_kernel<T, 1>), grid1, dim3(256), p.lds, s, a, p.TX, p.RY); break;
+            case 2: hipLaunchKernelGGL((gn_stats_kernel<T, 2>), grid1, dim3(256), p.lds, s, a, p.TX, p.RY); break;
+            default: hipLaunchKernelGGL((gn_stats_kernel<T, 4>), grid1, dim3(256), p.lds, s, a, p.TX, p.RY); break;
+        }
     }
-    const GnGeom g = gn_geom(a.C);
-    // enough pixel chunks to fill the chip (~1024 workgroups), but >= 4 pixels per thread row
-    int nchunk = (1024 + a.B - 1) / a.B;
-    const int maxc = (a.HW + g.RY * 4 - 1) / (g.RY * 4);
-    if (nchunk > maxc) nchunk = maxc;
-    if (nchunk > GN_NCHUNK) nchunk = GN_NCHUNK;
-    if (nchunk < 1) nchunk = 1;
-    a.nchunk = nchunk;
-    dim3 grid1(nchunk, a.B);
-    const size_t lds = (size_t)g.RY * a.C * 2 * sizeof(float);
-    int nblk = (a.HW + g.RY * 8 - 1) / (g.RY * 8);
-    if (nblk > 512) nblk = 512;
-    if (nblk < 1) nblk = 1;
-    dim3 grid2(nblk, a.B);
-    switch (g.CH) {
-        case 1:
-            hipLaunchKernelGGL((gn_stats_kernel<T, 1>), grid1, dim3(256), lds, s, a, g.TX, g.RY);
-            hipLaunchKernelGGL((gn_apply_kernel<T, 1>), grid2, dim3(256), 0, s, a, g.TX, g.RY, nblk);
-            break;
-        case 2:
-            hipLaunchKernelGGL((gn_stats_kernel<T, 2>), grid1, dim3(256), lds, s, a, g.TX, g.RY);
-            hipLaunchKernelGGL((gn_apply_kernel<T, 2>), grid2, dim3(256), 0, s, a, g.TX, g.RY, nblk);
-            break;
-        default:
-            hipLaunchKernelGGL((gn_stats_kernel<T, 4>), grid1, dim3(256), lds, s, a, g.TX, g.RY);
-            hipLaunchKernelGGL((gn_apply_kernel<T, 4>), grid2, dim3(256), 0, s, a, g.TX, g.RY, nblk);
-            break;
+    switch (p.CH) {
+        case 1: hipLaunchKernelGGL((gn_apply_kernel<T, 1>), grid2, dim3(256), 0, s, a, p.TX, p.RY, (int)p.grid2[0]); break;
+        case 2: hipLaunchKernelGGL((gn_apply_kernel<T, 2>), grid2, dim3(256), 0, s, a, p.TX, p.RY, (int)p.grid2[0]); break;
+        default: hipLaunchKernelGGL((gn_apply_kernel<T, 4>), grid2, dim3(256), 0, s, a, p.TX, p.RY, (int)p.grid2[0]); break;
     }
 }
 

@@ -234,9 +234,7 @@ __global__ __launch_bounds__(512, 1) void rowgemm_kernel(const RowGemmArgs p) {
 }
 
 bool rowgemm_ok(const RowGemmArgs& a) {
-    static const bool off = getenv("LDX_ROWGEMM") && atoi(getenv("LDX_ROWGEMM")) == 0;
-    static const bool off640 = getenv("LDX_ROWGEMM640") && atoi(getenv("LDX_ROWGEMM640")) == 0;
-    if (off || (a.K != 320 && a.K != 640) || (a.K == 640 && off640) || a.N <= 0 || a.N % a.K || a.M <= 0 || a.ldx % 8 || a.ldy % 8 || (a.R && a.ldr % 4) || a.pro < 0 || a.pro > 2) return false;
+    if (!g_plan_sw.rowgemm || (a.K != 320 && a.K != 640) || (a.K == 640 && !g_plan_sw.rowgemm640) || a.N <= 0 || a.N % a.K || a.M <= 0 || a.ldx % 8 || a.ldy % 8 || (a.R && a.ldr % 4) || a.pro < 0 || a.pro > 2) return false;
     const int bm = 128 * 320 / a.K;
     if (a.pro >= 1 && (!a.g || !a.b)) return false;
     if (a.pro == 2 && (!a.partial || a.G != 32 || a.HW % bm || a.M % a.HW || a.nchunk < 1 || a.nchunk > GN_NCHUNK)) return false;

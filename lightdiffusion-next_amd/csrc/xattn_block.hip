@@ -284,8 +284,7 @@ __global__ __launch_bounds__(512, 1) void xattn_block_kernel(const XAttnArgs p) 
 }
 
 bool xattn_block_ok(const XAttnArgs& a) {
-    static const bool off = getenv("LDX_XATTN_FUSE") && atoi(getenv("LDX_XATTN_FUSE")) == 0;
-    return !off && a.C == XA_C && a.heads == XA_H && a.Mk >= 1 && a.Mk <= XA_MK && a.N % XA_BM == 0 && a.M % a.N == 0 && a.ldh % 8 == 0 && a.ldk % 4 == 0 && a.ldv % 8 == 0;
+    return g_plan_sw.xattn_fuse && a.C == XA_C && a.heads == XA_H && a.Mk >= 1 && a.Mk <= XA_MK && a.N % XA_BM == 0 && a.M % a.N == 0 && a.ldh % 8 == 0 && a.ldk % 4 == 0 && a.ldv % 8 == 0;
 }
 
 template <typename T>

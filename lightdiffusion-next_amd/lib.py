@@ -121,6 +121,7 @@ _SIGS = {
     "ldx_op_gemm2_mx": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "ldx_op_gemm_pick": (_i, [_i] * 21 + [C.POINTER(C.c_int32)]),
     "ldx_op_attn_pick": (_i, [_i] * 13 + [C.POINTER(C.c_int32)]),
+    "ldx_op_xf_pick": (_i, [_i] * 8 + [C.POINTER(C.c_int32)]),
     "ldx_op_gemm_mx": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
     "ldx_op_layernorm": (_i, [_vp, _i, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     "ldx_op_attention": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
