@@ -41,26 +41,6 @@ template <int KS, int DT> struct AttnCfg {
     static constexpr int VROWB = (DT * 32) % 64 == 0 ? DT * 32 + 32 : DT * 32;
 };
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-__device__ __forceinline__ uint2 lds_read_tr16(const char* p) {
-    const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-    union { s16x4 v; uint2 u; } x; x.v = v; return x.u;
-}
-// value of lane^16 / lane^32 combined with own value; v_permlane*_swap with both operands = v leaves
-// {own, partner} in the two results (order depends on the lane), so a commutative op needs no select.
-__device__ __forceinline__ float quad_max(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float quad_sum(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
 template <typename T, int KS, int DT, int QT>
 __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnArgs p) {
     constexpr int AT_QW = 16 * QT, AT_QB = 64 * QT;
@@ -130,8 +110,8 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnArgs p) {
     // keys >= Mk (and staging slots beyond the 64 x D/8 tile) fall outside num_records and load as zeros —
     // no exec-mask branches or 64-bit address math in the loop.
     constexpr int OOB = (int)0x80000000;
-    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)(((long)(p.Mk - 1) * p.ldk + D) * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)(((long)(p.Mk - 1) * p.ldv + D) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)(((long)(p.Mk - 1) * p.ldk + D) * 2), RSRC_RAW_WORD3);
+    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)(((long)(p.Mk - 1) * p.ldv + D) * 2), RSRC_RAW_WORD3);
     uint4 rk[NLD], rv[NLD];
     int ko[NLD], vo[NLD], lk[NLD], lv[NLD];
 #pragma unroll
@@ -397,8 +377,8 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(const AttnArgs p) {
     const int nblk = (p.Mk + KVB - 1) / KVB;
 
     constexpr int OOB = (int)0x80000000;
-    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)(((long)(p.Mk - 1) * p.ldk + D) * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)(((long)(p.Mk - 1) * p.ldv + D) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)(((long)(p.Mk - 1) * p.ldk + D) * 2), RSRC_RAW_WORD3);
+    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)(((long)(p.Mk - 1) * p.ldv + D) * 2), RSRC_RAW_WORD3);
     constexpr int NLD = (KVB * 6 + 255) / 256;       // up to 6 chunks per row (D <= 48)
     uint4 rk[NLD], rv[NLD];
     int ko[NLD], vo[NLD], lk[NLD], lv[NLD];
@@ -647,8 +627,8 @@ __global__ __launch_bounds__(256, 2) void attn32g_kernel(const AttnArgs p) {
     const int nblk = (p.Mk + AT_KV - 1) / AT_KV;
 
     constexpr int OOB = (int)0x80000000;
-    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)(((long)(p.Mk - 1) * p.ldk + D) * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)(((long)(p.Mk - 1) * p.ldv + D) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)(((long)(p.Mk - 1) * p.ldk + D) * 2), RSRC_RAW_WORD3);
+    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)(((long)(p.Mk - 1) * p.ldv + D) * 2), RSRC_RAW_WORD3);
     constexpr int NLD = (AT_KV * NKS * 2 + 255) / 256;       // up to 2*NKS chunks per row
     uint4 rk[NLD], rv[NLD];
     int ko[NLD], vo[NLD], lk[NLD], lv[NLD];

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(512, 1) void attn32ap_kernel(const AttnArgs p) {
     constexpr bool KPRE = (VAR & 128) != 0;
     const bool gk = KPRE ? (g == 0) : (g != 0);                     // this group stages K (else V)
     const int ld_g = gk ? p.ldk : p.ldv;
-    const __amdgpu_buffer_rsrc_t rG = __builtin_amdgcn_make_buffer_rsrc((void*)(gk ? Kp : Vp), 0, (int)(((long)(p.Mk - 1) * ld_g + D) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rG = __builtin_amdgcn_make_buffer_rsrc((void*)(gk ? Kp : Vp), 0, (int)(((long)(p.Mk - 1) * ld_g + D) * 2), RSRC_RAW_WORD3);
     char* const ringG = smem + (gk ? 0 : 2 * KBYTES);
     const int rowb_g = gk ? KROWB : VROWB, tileb_g = gk ? KBYTES : VBYTES;
     uint4 rs[2];

@@ -25,44 +25,6 @@
 
 namespace ldx {
 
-typedef __attribute__((ext_vector_type(4))) int a5_i32x4;
-typedef __attribute__((ext_vector_type(4))) short a5_s16x4;
-static __device__ __forceinline__ a5_i32x4 a5_srd(const void* base, long bytes) {
-    const unsigned long long q = (unsigned long long)base;
-    const int n = (int)(bytes > 0x7fffffffL ? 0x7fffffffL : (bytes > 0 ? bytes : 0));
-    return (a5_i32x4){(int)(unsigned)q, (int)((unsigned)(q >> 32) & 0xffffu), n, 0x00020000};
-}
-// lane l lands at lds + 16 l; M0 is written without being declared (see the note in gemm_pp.inc: nothing else in this kernel lives in M0)
-static __device__ __forceinline__ void a5_dma16(const a5_i32x4 rsrc, int voff, int soff, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-static __device__ __forceinline__ uint2 a5_read_tr16(const char* p) {
-    const a5_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) a5_s16x4*)p);
-    union { a5_s16x4 v; uint2 u; } x; x.v = v; return x.u;
-}
-
-// S^T MFMAs with the accumulator in ARCH VGPRs (inline asm, every operand "v"): as builtins hipcc gives S two of the 16 accumulator-file tiles and swaps the
-// displaced O tiles through VGPRs around every block (690 v_accvgpr copies per block in the first build).  The softmax reads S on the VALU, O never leaves
-// the accumulator file.  An asm MFMA is opaque to hipcc's hazard recogniser: a5_settle() supplies the wait states between the last MFMA and the first VALU read.
-template <typename T> static __device__ __forceinline__ void a5_sacc0(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
-    if constexpr (std::is_same<T, __bf16>::value) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
-    else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
-}
-template <typename T> static __device__ __forceinline__ void a5_sacc(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
-    if constexpr (std::is_same<T, __bf16>::value) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
-    else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
-}
-static __device__ __forceinline__ void a5_settle(f32x16& a, f32x16& b) { if (&a == &b) asm volatile("s_nop 15\n\ts_nop 7" : "+v"(a)); else asm volatile("s_nop 15\n\ts_nop 7" : "+v"(a), "+v"(b)); }      // 16-pass MFMA result -> VALU read
-
-// eight registers of an O tile out of the accumulator file, as asm with "a" inputs: read by plain C++ after the key loop, hipcc decides at the loop exit
-// which parts of O to move to VGPRs and spills what does not fit
-template <int R0> static __device__ __forceinline__ void a5_get8(const f32x16& t, float (&v)[8]) {
-    asm volatile("v_accvgpr_read_b32 %0, %8\n\tv_accvgpr_read_b32 %1, %9\n\tv_accvgpr_read_b32 %2, %10\n\tv_accvgpr_read_b32 %3, %11\n\t"
-                 "v_accvgpr_read_b32 %4, %12\n\tv_accvgpr_read_b32 %5, %13\n\tv_accvgpr_read_b32 %6, %14\n\tv_accvgpr_read_b32 %7, %15\n\ts_nop 1"
-                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-                 : "a"(t[R0]), "a"(t[R0 + 1]), "a"(t[R0 + 2]), "a"(t[R0 + 3]), "a"(t[R0 + 4]), "a"(t[R0 + 5]), "a"(t[R0 + 6]), "a"(t[R0 + 7]));
-}
-
 #ifndef A5_KPF
 #define A5_KPF 8
 #endif
@@ -119,8 +81,8 @@ __global__ __launch_bounds__(256, 1) void attn512_kernel(const AttnArgs p) {
 
     // ---- staging: wave w moves rows 8 w .. 8 w + 7 of the K block and of the V block, one 1-KiB LDS-DMA instruction per row ----
     constexpr int OOB = (int)0x80000000;
-    const a5_i32x4 rK = a5_srd(Kp, ((long)(p.Mk - 1) * p.ldk + A5_D) * 2);
-    const a5_i32x4 rV = a5_srd(Vp, ((long)(p.Mk - 1) * p.ldv + A5_D) * 2);
+    const i32x4 rK = make_srd(Kp, ((long)(p.Mk - 1) * p.ldk + A5_D) * 2);
+    const i32x4 rV = make_srd(Vp, ((long)(p.Mk - 1) * p.ldv + A5_D) * 2);
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
     auto issue = [&](int blk, int stage) __attribute__((always_inline)) {
         const int key0 = (kb0 + blk) * A5_KV + wave * 8;
@@ -130,8 +92,8 @@ __global__ __launch_bounds__(256, 1) void attn512_kernel(const AttnArgs p) {
             const int voff = key < p.Mk ? lane * 16 : OOB;
             const unsigned dst = lds_base + stage * A5_STAGE + (wave * 8 + j) * A5_KROW;
             const unsigned dsv = lds_base + stage * A5_STAGE + A5_KB + (wave * 8 + j) * A5_VROW;
-            a5_dma16(rK, voff, key < p.Mk ? key * p.ldk * 2 : 0, dst);
-            a5_dma16(rV, voff, key < p.Mk ? key * p.ldv * 2 : 0, dsv);
+            lds_dma16(rK, voff, key < p.Mk ? key * p.ldk * 2 : 0, dst);
+            lds_dma16(rV, voff, key < p.Mk ? key * p.ldv * 2 : 0, dsv);
         }
     };
     if (nblk > 0) issue(0, 0);
@@ -155,14 +117,14 @@ __global__ __launch_bounds__(256, 1) void attn512_kernel(const AttnArgs p) {
 #pragma unroll
             for (int ks = 0; ks < 32; ++ks) {
                 const ap_i32x4 qb = ap_bits(qf[ks]);
-                if (ks == 0) a5_sacc0<T>(s0, kfr[0], qb);
-                else if (NCH == 2 && ks == 1) a5_sacc0<T>(s1, kfr[1 % KPF], qb);
-                else if (NCH == 2 && (ks & 1)) a5_sacc<T>(s1, kfr[ks % KPF], qb);
-                else a5_sacc<T>(s0, kfr[ks % KPF], qb);
+                if (ks == 0) ap_sacc0_vv<T>(s0, kfr[0], qb);
+                else if (NCH == 2 && ks == 1) ap_sacc0_vv<T>(s1, kfr[1 % KPF], qb);
+                else if (NCH == 2 && (ks & 1)) ap_sacc_vv<T>(s1, kfr[ks % KPF], qb);
+                else ap_sacc_vv<T>(s0, kfr[ks % KPF], qb);
                 if (ks + KPF < 32) kfr[ks % KPF] = __builtin_bit_cast(ap_i32x4, *(const uint4*)(sK + l31 * A5_KROW + (2 * (ks + KPF) + h2) * 16));
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (NCH == 2) a5_settle(s0, s1); else a5_settle(s0, s0);
+            if constexpr (NCH == 2) mfma_settle(s0, s1); else mfma_settle(s0);
         }
         float sv[16];
 #pragma unroll
@@ -217,8 +179,8 @@ __global__ __launch_bounds__(256, 1) void attn512_kernel(const AttnArgs p) {
             for (int dt = 0; dt < 16; ++dt) {
                 const char* vp = sV + (16 * st + 4 * (g16 >> 1) + (l15 >> 2)) * A5_VROW + (dt * 32 + 16 * (g16 & 1) + (l15 & 3) * 4) * 2;
                 U128 vf;
-                vf.d[0] = a5_read_tr16(vp);
-                vf.d[1] = a5_read_tr16(vp + 8 * A5_VROW);
+                vf.d[0] = lds_read_tr16(vp);
+                vf.d[1] = lds_read_tr16(vp + 8 * A5_VROW);
                 o[dt] = mfma32(as_v8<T>(vf.u), pf[st], o[dt]);
             }
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
@@ -226,7 +188,7 @@ __global__ __launch_bounds__(256, 1) void attn512_kernel(const AttnArgs p) {
 
     // ---- finalize ----  (lane ids re-derived from an opaque copy: left alone, hipcc computes the output addresses ahead of the key loop and spills them)
     int lane_e = lane;
-    asm volatile("s_nop 15\n\ts_nop 7" : "+v"(lane_e));          // also the wait states between the last PV MFMA and the accumulator reads below
+    mfma_settle(lane_e);                                         // also the wait states between the last PV MFMA and the accumulator reads below
     const int l31e = lane_e & 31, h2e = lane_e >> 5;
     const float l = xrow32_sum(lsum);
     const int q = q0 + l31e;
@@ -237,7 +199,7 @@ __global__ __launch_bounds__(256, 1) void attn512_kernel(const AttnArgs p) {
 #pragma unroll
         for (int dt = 0; dt < 16; ++dt) {
             float lo[8], hi[8];
-            a5_get8<0>(o[dt], lo); a5_get8<8>(o[dt], hi);
+            acc_get8<0>(o[dt], lo); acc_get8<8>(o[dt], hi);
             *(uint2*)(Op + dt * 32 + 4 * h2e) = pack4<T>(lo[0] * inv, lo[1] * inv, lo[2] * inv, lo[3] * inv);
             *(uint2*)(Op + dt * 32 + 8 + 4 * h2e) = pack4<T>(lo[4] * inv, lo[5] * inv, lo[6] * inv, lo[7] * inv);
             *(uint2*)(Op + dt * 32 + 16 + 4 * h2e) = pack4<T>(hi[0] * inv, hi[1] * inv, hi[2] * inv, hi[3] * inv);
@@ -248,7 +210,7 @@ __global__ __launch_bounds__(256, 1) void attn512_kernel(const AttnArgs p) {
 #pragma unroll
         for (int dt = 0; dt < 16; ++dt) {
             float lo[8], hi[8];
-            a5_get8<0>(o[dt], lo); a5_get8<8>(o[dt], hi);
+            acc_get8<0>(o[dt], lo); acc_get8<8>(o[dt], hi);
             *(float4*)(w + dt * 32 + 4 * h2e) = make_float4(lo[0], lo[1], lo[2], lo[3]);
             *(float4*)(w + dt * 32 + 8 + 4 * h2e) = make_float4(lo[4], lo[5], lo[6], lo[7]);
             *(float4*)(w + dt * 32 + 16 + 4 * h2e) = make_float4(hi[0], hi[1], hi[2], hi[3]);

@@ -26,23 +26,11 @@
 
 namespace ldx {
 
-typedef __attribute__((ext_vector_type(4))) int am_i32x4;
-static __device__ __forceinline__ am_i32x4 am_srd(const void* base, long bytes) {
-    const unsigned long long q = (unsigned long long)base;
-    const int n = (int)(bytes > 0x7fffffffL ? 0x7fffffffL : (bytes > 0 ? bytes : 0));
-    return (am_i32x4){(int)(unsigned)q, (int)((unsigned)(q >> 32) & 0xffffu), n, 0x00020000};
-}
-static __device__ __forceinline__ void am_dma16(const am_i32x4 rsrc, int voff, int soff, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-static __device__ __forceinline__ void am_dma4(const am_i32x4 rsrc, int voff, int soff, unsigned lds) {       // lane l lands at lds + 4 l
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds" :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
 static __device__ __forceinline__ f32x16 mfma32_mx(i32x8 a, i32x8 b, f32x16 c, int sa, int sb) {
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, sa, 0, sb);
 }
 
-// S^T MFMAs with the accumulator in ARCH VGPRs (inline asm; see attn512.hip: as builtins hipcc puts S into the accumulator file next to O and moves
+// S^T MFMAs with the accumulator in ARCH VGPRs (inline asm; see ap_sacc_vv in attn_pipe_common.h: as builtins hipcc puts S into the accumulator file next to O and moves
 // it — and the operand fragments — back and forth: 1152 v_accvgpr copies and 48 scratch accesses per key block in the first build).  The softmax reads S on the
 // VALU; O stays in the accumulator file (PV MFMAs are builtins; the rare rescale and the epilogue touch it through asm with "a" operands).
 // The scale VGPRs are written by a VALU shift right before: s_nop 1 covers the VALU-write -> MFMA-read wait states hipcc cannot see inside asm.
@@ -51,13 +39,6 @@ static __device__ __forceinline__ void am_sacc0(f32x16& d, i32x8 a, i32x8 b, int
 }
 static __device__ __forceinline__ void am_sacc(f32x16& d, i32x8 a, i32x8 b, int sa, int sb) {
     asm volatile("s_nop 1\n\tv_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]" : "+v"(d) : "v"(a), "v"(b), "v"(sa), "v"(sb));
-}
-static __device__ __forceinline__ void am_settle2(f32x16& a, f32x16& b) { asm volatile("s_nop 15\n\ts_nop 7" : "+v"(a), "+v"(b)); }
-template <int R0> static __device__ __forceinline__ void am_get8(const f32x16& t, float (&v)[8]) {
-    asm volatile("v_accvgpr_read_b32 %0, %8\n\tv_accvgpr_read_b32 %1, %9\n\tv_accvgpr_read_b32 %2, %10\n\tv_accvgpr_read_b32 %3, %11\n\t"
-                 "v_accvgpr_read_b32 %4, %12\n\tv_accvgpr_read_b32 %5, %13\n\tv_accvgpr_read_b32 %6, %14\n\tv_accvgpr_read_b32 %7, %15\n\ts_nop 1"
-                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-                 : "a"(t[R0]), "a"(t[R0 + 1]), "a"(t[R0 + 2]), "a"(t[R0 + 3]), "a"(t[R0 + 4]), "a"(t[R0 + 5]), "a"(t[R0 + 6]), "a"(t[R0 + 7]));
 }
 
 constexpr int AM_D = 128, AM_KB = 128, AM_QB = 256;
@@ -115,10 +96,10 @@ __global__ __launch_bounds__(512 / QT, QT == 2 ? 1 : 2) void attn_mx_kernel(cons
     }
 
     // ---- staging ----
-    const am_i32x4 rK = am_srd((const char*)p.K8 + (long)b * p.Mk * p.ldk8 + h * AM_D, ((long)(p.Mk - 1) * p.ldk8 + AM_D));
-    const am_i32x4 rV = am_srd((const char*)p.V8T + ((long)b * p.H + h) * AM_D * p.Lp, (long)AM_D * p.Lp);
-    const am_i32x4 rSK = am_srd(p.SK + (long)h * p.sk_ld + (long)b * p.Mk, (long)p.Mk * 4);
-    const am_i32x4 rSV = am_srd(p.SV + ((long)b * p.H + h) * (p.Lp / AM_KB) * AM_D, (long)(p.Lp / AM_KB) * AM_D * 4);
+    const i32x4 rK = make_srd((const char*)p.K8 + (long)b * p.Mk * p.ldk8 + h * AM_D, ((long)(p.Mk - 1) * p.ldk8 + AM_D));
+    const i32x4 rV = make_srd((const char*)p.V8T + ((long)b * p.H + h) * AM_D * p.Lp, (long)AM_D * p.Lp);
+    const i32x4 rSK = make_srd(p.SK + (long)h * p.sk_ld + (long)b * p.Mk, (long)p.Mk * 4);
+    const i32x4 rSV = make_srd(p.SV + ((long)b * p.H + h) * (p.Lp / AM_KB) * AM_D, (long)(p.Lp / AM_KB) * AM_D * 4);
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
     // a piece = 8 rows: lane -> row 8 piece + prow, LDS position lane & 7 <- source chunk (lane & 7) ^ swz(row), swz(row) = (row >> 1) & 7: the 16 rows one
     // ds_read_b128 lane group of a 32-row operand touches hold 8 even and 8 odd rows (128-B rows: two rows per 64 banks), and rows of equal parity must sit at
@@ -131,15 +112,15 @@ __global__ __launch_bounds__(512 / QT, QT == 2 ? 1 : 2) void attn_mx_kernel(cons
         for (int i = 0; i < 16 / NW; ++i) {
             const int pc = wave + NW * i;
             const int key = blk * AM_KB + 8 * pc + prow;
-            am_dma16(rK, key < p.Mk ? key * p.ldk8 + gch : OOB, 0, dst + pc * 1024);
-            am_dma16(rV, (8 * pc + prow) * p.Lp + blk * AM_KB + gch, 0, dst + AM_TILE + pc * 1024);
+            lds_dma16(rK, key < p.Mk ? key * p.ldk8 + gch : OOB, 0, dst + pc * 1024);
+            lds_dma16(rV, (8 * pc + prow) * p.Lp + blk * AM_KB + gch, 0, dst + AM_TILE + pc * 1024);
         }
         if (wave == 0) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) { const int key = blk * AM_KB + 64 * i + lane; am_dma4(rSK, key < p.Mk ? key * 4 : OOB, 0, dst + 2 * AM_TILE + i * 256); }
+            for (int i = 0; i < 2; ++i) { const int key = blk * AM_KB + 64 * i + lane; lds_dma4(rSK, key < p.Mk ? key * 4 : OOB, 0, dst + 2 * AM_TILE + i * 256); }
         } else if (wave == 1) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) am_dma4(rSV, (blk * AM_KB + 64 * i + lane) * 4, 0, dst + 2 * AM_TILE + 512 + i * 256);
+            for (int i = 0; i < 2; ++i) lds_dma4(rSV, (blk * AM_KB + 64 * i + lane) * 4, 0, dst + 2 * AM_TILE + 512 + i * 256);
         }
     };
     if (nblk > 0) issue(0, 0);
@@ -264,13 +245,13 @@ __global__ __launch_bounds__(512 / QT, QT == 2 ? 1 : 2) void attn_mx_kernel(cons
                 // ---- A ----
 #pragma unroll
                 for (int i = 0; i < 4; ++i) qk(0, i);
-                am_settle2(S[0][0], S[0][1]);
+                mfma_settle(S[0][0], S[0][1]);
                 __builtin_amdgcn_sched_barrier(0);
                 // ---- B ----
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { qk(QT - 1, i); vload(i); sm(0, i); __builtin_amdgcn_sched_barrier(0); }
                 const i32x8 pb0 = pk;
-                am_settle2(S[QT - 1][0], S[QT - 1][1]);
+                mfma_settle(S[QT - 1][0], S[QT - 1][1]);
                 __builtin_amdgcn_sched_barrier(0);
                 // ---- C ----
 #pragma unroll
@@ -284,7 +265,7 @@ __global__ __launch_bounds__(512 / QT, QT == 2 ? 1 : 2) void attn_mx_kernel(cons
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { qk(0, i); vload(i); }
-                am_settle2(S[0][0], S[0][1]);
+                mfma_settle(S[0][0], S[0][1]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) sm(0, i);
@@ -303,12 +284,12 @@ __global__ __launch_bounds__(512 / QT, QT == 2 ? 1 : 2) void attn_mx_kernel(cons
 
     // ---- finalize: O / l, 16-bit rows or MX fp8 rows + one scale dword per (row, head) (the d tile dt IS the head's 32-d block dt) ----
     int lane_e = lane;
-    asm volatile("s_nop 15\n\ts_nop 7" : "+v"(lane_e));           // wait states between the last PV MFMA and the accumulator reads; opaque lane id (attn512.hip)
+    mfma_settle(lane_e);                                          // wait states between the last PV MFMA and the accumulator reads; opaque lane id (attn512.hip)
     const int l31e = lane_e & 31, h2e = lane_e >> 5;
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         float l;
-        { float lo[8]; am_get8<0>(osum[qt], lo); l = lo[0]; }        // every row of the ones tile holds the row sum of the rounded P (scale 2^-6 applied by the MFMA)
+        { float lo[8]; acc_get8<0>(osum[qt], lo); l = lo[0]; }        // every row of the ones tile holds the row sum of the rounded P (scale 2^-6 applied by the MFMA)
         const float inv = (l > 0.f) ? 1.0f / l : 0.f;
         const int q = q0 + 32 * qt + l31e;
         const long row = (long)b * p.Nq + q;
@@ -318,7 +299,7 @@ __global__ __launch_bounds__(512 / QT, QT == 2 ? 1 : 2) void attn_mx_kernel(cons
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
             float v[16];
-            { float lo[8], hi[8]; am_get8<0>(o[qt][dt], lo); am_get8<8>(o[qt][dt], hi);
+            { float lo[8], hi[8]; acc_get8<0>(o[qt][dt], lo); acc_get8<8>(o[qt][dt], hi);
 #pragma unroll
               for (int r = 0; r < 8; ++r) { v[r] = lo[r] * inv; v[8 + r] = hi[r] * inv; } }
             if (p.O8) {

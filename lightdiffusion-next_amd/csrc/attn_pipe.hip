@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256, 1) void attn40p_kernel(const AttnArgs p, const
             qn[qt] = sqrtf(__uint_as_float(sw[0]) + __uint_as_float(sw[1])) * 1.002f;
         }
     }
-    const __amdgpu_buffer_rsrc_t rN = __builtin_amdgcn_make_buffer_rsrc((void*)(KB ? p.knorm_ws + (long)hb * nblk : nullptr), 0, KB ? nblk * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rN = __builtin_amdgcn_make_buffer_rsrc((void*)(KB ? p.knorm_ws + (long)hb * nblk : nullptr), 0, KB ? nblk * 4 : 0, RSRC_RAW_WORD3);
 
     // ---- staging: 640 16-byte chunks per slot (K tile 320 + V tile 320) over 256 threads in three rounds; the tile a round moves is wave-uniform
     //   round 0: K chunk tid;  round 1: wave 0: K chunk 256 + lane, waves 1-3: V chunk tid - 64;  round 2: waves 0, 1: V chunk tid + 192
@@ -161,8 +161,8 @@ __global__ __launch_bounds__(256, 1) void attn40p_kernel(const AttnArgs p, const
     uint4 rsA[3], rsB[3];                            // two staging sets (named, statically indexed): the loads of slot t are stored in slot t + 1
     // tile indices are clamped to the last block: the tail slots re-stage it into ring slots nobody reads any more.  Buffer loads: the per-lane
     // chunk offset in voffset, the tile's byte offset in soffset (SALU only)
-    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)(((long)(p.Mk - 1) * p.ldk + D) * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)(((long)(p.Mk - 1) * p.ldv + D) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)(((long)(p.Mk - 1) * p.ldk + D) * 2), RSRC_RAW_WORD3);
+    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)(((long)(p.Mk - 1) * p.ldv + D) * 2), RSRC_RAW_WORD3);
     const __amdgpu_buffer_rsrc_t r1 = r1k ? rK : rV;
     const unsigned step1 = r1k ? kstep : vstep;
     auto gload1 = [&](uint4 (&rs)[3], int i, int kblk, int vblk) __attribute__((always_inline)) {
@@ -217,9 +217,9 @@ __global__ __launch_bounds__(256, 1) void attn40p_kernel(const AttnArgs p, const
     // matrix work of a slot, one MFMA per call: QK^T i in [0, 12): (ks, kt, qt) = (i >> 2, (i >> 1) & 1, i & 1); PV j in [0, 16): (st, dt, qt)
     auto qk1 = [&](auto I, f32x16 (&s)[2][2]) __attribute__((always_inline)) {
         constexpr int i = decltype(I)::value, ks = i >> 2, kt = (i >> 1) & 1, qt = i & 1;
-        if constexpr (ks == 0) ap_sacc0<T>(s[kt][qt], ap_bits(kf[0][kt]), qf[qt][0]);
-        else if constexpr (ks == 1) ap_sacc<T>(s[kt][qt], ap_bits(kf[1][kt]), qf[qt][1]);
-        else ap_sacc<T>(s[kt][qt], ap_bits(kf[2][kt]), qf[qt][2]);
+        if constexpr (ks == 0) ap_sacc0_aa<T>(s[kt][qt], ap_bits(kf[0][kt]), qf[qt][0]);
+        else if constexpr (ks == 1) ap_sacc_aa<T>(s[kt][qt], ap_bits(kf[1][kt]), qf[qt][1]);
+        else ap_sacc_aa<T>(s[kt][qt], ap_bits(kf[2][kt]), qf[qt][2]);
     };
     auto pv1 = [&](auto J, ap_i32x4 (&pf)[2][4], V8 (&vf)[4][2]) __attribute__((always_inline)) {
         constexpr int j = decltype(J)::value, st = j >> 2, dt = (j >> 1) & 1, qt = j & 1;
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256, 1) void attn40p_kernel(const AttnArgs p, const
     ap_for(ap_range<0, 12>(), [&](auto I) __attribute__((always_inline)) { qk1(I, sA); });
     kread(1);
     gload(rsA, 2, 0);
-    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");      // the asm MFMAs' results settle before the VALU reads them
+    mfma_settle_all<3>();      // the asm MFMAs' results settle before the VALU reads them
     __syncthreads();                                 // every wave has read K(0) from ring slot 0
     lstore(rsA, 0);
     gload(rsB, 3, 1);                                // what slot 0 stores (K(3), V(1)): every slot stores the tiles loaded a slot earlier
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256, 1) void attn40p_kernel(const AttnArgs p, const
         pc[1][3][3] = ap_pack<T>(ex[31 % (LAG + 1)], ey[31 % (LAG + 1)]);
         // rare path: some query's S'(t+1) exceeds thr: raise its reference by the integer dl BEFORE the exponentials of block t + 1 are taken
         auto raise_reference = [&]() __attribute__((always_inline)) {
-            asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");      // PV(t-1) has landed in O
+            mfma_settle_all<3>();      // PV(t-1) has landed in O
             ap_for(ap_range<0, 2>(), [&](auto QT) __attribute__((always_inline)) {
                 constexpr int qt = decltype(QT)::value;
                 const float mnew = fminf(mref[qt] + fmaxf(ceilf(qt ? bm1 : bm0), 0.f), 60000.f);
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256, 1) void attn40p_kernel(const AttnArgs p, const
             // variant does in every slot), and only inside that the threshold test proper.  (As two consecutive branches hipcc hoisted the rare path's
             // AGPR -> VGPR copies of O in front of the first one: 64 v_accvgpr_read per slot.)
             if (__builtin_amdgcn_ballot_w64(ap_max2(bm0, bm1) > thr) != 0) {
-                asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+                mfma_settle_all<2>();
                 ap_for(ap_range<0, 8>(), [&](auto M) __attribute__((always_inline)) { maxblk(M, sn); });
                 bm0 = bmax(0); bm1 = bmax(1);
                 if (__builtin_amdgcn_ballot_w64(ap_max2(bm0, bm1) > thr) != 0) raise_reference();
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256, 1) void attn40p_kernel(const AttnArgs p, const
         kofs = min(kofs + kstep, klast); vofs = min(vofs + vstep, vlast);
     }
     ap_for(ap_range<0, 16>(), [&](auto J) __attribute__((always_inline)) { pv1(J, pA, vfA); });      // P(nblk-1) (nblk even: written by the odd slot into pA) x V(nblk-1)
-    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+    mfma_settle_all<3>();
 
     // ---- finalize: l from row D of O^T (ones column), normalise, store
 #pragma unroll
@@ -408,8 +408,7 @@ void launch_attn_knorm(const AttnArgs& a, DType dt, hipStream_t s) {
 template <typename T, int ABL = 0>
 static void launch_attn40p(const AttnArgs& a, const AttnPick& p, hipStream_t s, float thr) {
     if (p.knorm && ABL == 0) {
-        const long waves = (long)a.B * a.H * ((a.Mk + 63) / 64);
-        hipLaunchKernelGGL((attn_knorm_kernel<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a);
+        launch_attn_knorm(a, std::is_same<T, __bf16>::value ? DT_BF16 : DT_F16, s);
         hipLaunchKernelGGL((attn40p_kernel<T, ABL, true>), dim3(p.grid), dim3(p.block), p.lds, s, a, thr);
     } else {
         hipLaunchKernelGGL((attn40p_kernel<T, ABL, false>), dim3(p.grid), dim3(p.block), p.lds, s, a, thr);

@@ -42,16 +42,6 @@ template <typename T> __device__ __forceinline__ void ap128_half_b(float sb, flo
 __device__ __forceinline__ void ap128_exp1(float s, float c, float nm, float& x) {
     asm("v_fma_f32 %0, %1, %2, %3\n\tv_exp_f32 %0, %0" : "=&v"(x) : "v"(s), "s"(c), "v"(nm));
 }
-// QK^T MFMAs of this kernel: K fragment (A operand) in arch VGPRs, Q fragment in AGPRs, S in arch VGPRs.  (With the K fragments in AGPRs as in attn_pipe.hip
-// hipcc overlapped them with an O tile and saved / restored that tile around every block: 16 + 16 v_accvgpr copies.)
-template <typename T> __device__ __forceinline__ void ap128_sacc0(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
-    if constexpr (std::is_same<T, __bf16>::value) asm volatile(AP_BF16 " %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
-    else asm volatile(AP_F16 " %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
-}
-template <typename T> __device__ __forceinline__ void ap128_sacc(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
-    if constexpr (std::is_same<T, __bf16>::value) asm volatile(AP_BF16 " %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-    else asm volatile(AP_F16 " %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-}
 // The dot product is opaque to hipcc's hazard recogniser inside an asm: it pads ONE wait state between this and a plain VALU read of l, and that is not
 // enough on gfx950 — in the KB variant the copy of l for the loop exit sat right behind the last of these and read the OLD value: the last dword of P of
 // the last half-slot was missing from the denominator of every query of q tile 1 (found as a probability mass of 0.12 on key 507 of 512).  Callers
@@ -118,7 +108,7 @@ __global__ __launch_bounds__(256, 1) void attn128p_kernel(const AttnArgs p, cons
             }
         }
     }
-    const __amdgpu_buffer_rsrc_t rN = __builtin_amdgcn_make_buffer_rsrc((void*)(KB ? p.knorm_ws + (long)hb * nblk : nullptr), 0, KB ? nblk * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rN = __builtin_amdgcn_make_buffer_rsrc((void*)(KB ? p.knorm_ws + (long)hb * nblk : nullptr), 0, KB ? nblk * 4 : 0, RSRC_RAW_WORD3);
 
     // ---- staging: a 64 x 256 B tile is 1024 16-byte chunks = four per thread (rows srow + 16 i, chunk sch); chunks 0-3 K, 4-7 V
     const int srow = tid >> 4, sch = tid & 15;
@@ -127,8 +117,8 @@ __global__ __launch_bounds__(256, 1) void attn128p_kernel(const AttnArgs p, cons
     const unsigned kstep = (unsigned)(KVB * p.ldk * 2), vstep = (unsigned)(KVB * p.ldv * 2);
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
     const unsigned lK = lds_base + (unsigned)(srow * KROWB + sch * 16), lV = lds_base + (unsigned)(VBASE + srow * VROWB + sch * 16);
-    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)(((long)(p.Mk - 1) * p.ldk + D) * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)(((long)(p.Mk - 1) * p.ldv + D) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)(((long)(p.Mk - 1) * p.ldk + D) * 2), RSRC_RAW_WORD3);
+    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)(((long)(p.Mk - 1) * p.ldv + D) * 2), RSRC_RAW_WORD3);
     uint4 rs[8];
     auto gload1 = [&](auto I, int kblk, int vblk) __attribute__((always_inline)) {      // tile indices clamp to the last block (the tail re-stages it into ring slots nobody reads)
         constexpr int i = decltype(I)::value;
@@ -183,8 +173,8 @@ __global__ __launch_bounds__(256, 1) void attn128p_kernel(const AttnArgs p, cons
     // (16-key step (j >> 3) of the half, d tile (j >> 1) & 3), q tile j & 1
     auto qk1 = [&](auto I, f32x16 (&s)[2]) __attribute__((always_inline)) {
         constexpr int i = decltype(I)::value, ks = i >> 1, qt = i & 1;
-        if constexpr (ks == 0) ap128_sacc0<T>(s[qt], ap_bits(kfr[0]), qf[qt][0]);
-        else ap128_sacc<T>(s[qt], ap_bits(kfr[ks & 3]), qf[qt][ks]);
+        if constexpr (ks == 0) ap_sacc0_va<T>(s[qt], ap_bits(kfr[0]), qf[qt][0]);
+        else ap_sacc_va<T>(s[qt], ap_bits(kfr[ks & 3]), qf[qt][ks]);
     };
     auto pv1 = [&](auto J, ap_i32x4 (&pf)[2][2]) __attribute__((always_inline)) {
         constexpr int j = decltype(J)::value, f = j >> 1, st = f >> 2, dt = f & 3, qt = j & 1;
@@ -235,7 +225,7 @@ __global__ __launch_bounds__(256, 1) void attn128p_kernel(const AttnArgs p, cons
             kfr[f & 3] = as_v8<T>(*(const uint4*)(kp + f * 32));
             qk1(ap_ic<2 * f>{}, sX); qk1(ap_ic<2 * f + 1>{}, sX);
         });
-        asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");      // the asm MFMAs' results settle before the VALU reads them
+        mfma_settle_all<3>();      // the asm MFMAs' results settle before the VALU reads them
         ap_for(ap_range<0, 2>(), [&](auto QT) __attribute__((always_inline)) {
             constexpr int qt = decltype(QT)::value;
             float m = sX[qt][0];
@@ -296,7 +286,7 @@ __global__ __launch_bounds__(256, 1) void attn128p_kernel(const AttnArgs p, cons
         asm volatile("s_nop 7" ::: "memory");          // the dot2 results land before anything reads lsum (see ap128_rowsum)
         // rare path: some query's score in sn exceeds 2^thr over the reference: raise it by the integer dl
         auto raise_reference = [&]() __attribute__((always_inline)) {
-            asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");      // the PV MFMAs have landed in O
+            mfma_settle_all<3>();      // the PV MFMAs have landed in O
             ap_for(ap_range<0, 2>(), [&](auto QT) __attribute__((always_inline)) {
                 constexpr int qt = decltype(QT)::value;
                 const float dl = fminf(fmaxf(ceilf(qt ? bm1 : bm0), 0.f), 1e30f);      // integer >= 0
@@ -317,7 +307,7 @@ __global__ __launch_bounds__(256, 1) void attn128p_kernel(const AttnArgs p, cons
             // ONE branch on the common path: the bound does not prove this half safe for some query of the wave -> the exact maximum (what the other
             // variant does in every half-slot), and only inside that the threshold test proper (see attn_pipe.hip)
             if (__builtin_amdgcn_ballot_w64(ap_max2(bm0, bm1) > thr) != 0) {
-                asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+                mfma_settle_all<2>();
                 ap_for(ap_range<0, 4>(), [&](auto M) __attribute__((always_inline)) { maxblk(M, sn); });
                 bm0 = bmax(0); bm1 = bmax(1);
                 if (__builtin_amdgcn_ballot_w64(ap_max2(bm0, bm1) > thr) != 0) raise_reference();
@@ -344,7 +334,7 @@ __global__ __launch_bounds__(256, 1) void attn128p_kernel(const AttnArgs p, cons
             pv1(ap_ic<2 * f>{}, pR); pv1(ap_ic<2 * f + 1>{}, pR);
         });
     }
-    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+    mfma_settle_all<3>();
 
     // ---- finalize: l = both half-waves' row sums, normalise, store (16-bit, or MX fp8 + E8M0 scales: the four d tiles are the head's four blocks of 32).
     // The O^T accumulator layout gives a lane 8 bytes (4 as fp8) of 32 different rows per store; the wave transposes its 64 x 128 tile through the

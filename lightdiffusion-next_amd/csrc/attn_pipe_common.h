@@ -7,27 +7,51 @@
 
 namespace ldx {
 
-typedef __attribute__((ext_vector_type(4))) short ap_s16x4;
 typedef __attribute__((ext_vector_type(4))) int ap_i32x4;
 typedef __attribute__((ext_vector_type(2))) int ap_i32x2;
-__device__ __forceinline__ ap_i32x2 ap_lds_read_tr16(const char* p) {
-    return __builtin_bit_cast(ap_i32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ap_s16x4*)p));
-}
+__device__ __forceinline__ ap_i32x2 ap_lds_read_tr16(const char* p) { return __builtin_bit_cast(ap_i32x2, lds_read_tr16(p)); }
 template <typename V> __device__ __forceinline__ ap_i32x4 ap_bits(const V& v) { return __builtin_bit_cast(ap_i32x4, v); }
 template <typename T> struct ApT;
 template <> struct ApT<__bf16>   { static constexpr int split = 256, expsh = 7, maxdl = 255; static constexpr float thr = 64.0f; };      // P <= 2^64: N * 2^64 * |v| stays far inside fp32
 template <> struct ApT<_Float16> { static constexpr int split = 2048, expsh = 10, maxdl = 31; static constexpr float thr = 15.0f; };
 
-// ---- QK^T MFMAs (32x32x16) with explicit register classes: S' in arch VGPRs, K / Q fragments in AGPRs.  First MFMA of a chain: C = 0.
+// ---- QK^T MFMAs (32x32x16) as inline asm with explicit register classes: S in arch VGPRs (the softmax reads it on the VALU), O never leaves the
+// accumulator file.  First MFMA of a chain (ap_sacc0_*): C = 0.  One function per operand class, named <A operand><B operand>, because the constraints
+// are string literals:
+//   _aa  attn_pipe.hip (D = 40): K / Q fragments in AGPRs.  A 512-register wave has 256 arch VGPRs and 256 AGPRs; hipcc puts every MFMA result into
+//        AGPRs at this budget and copies S' back and forth (1358 v_accvgpr moves per two slots in the first build); LDS reads and staging loads land
+//        in AGPRs directly.
+//   _va  attn_pipe128.hip (D = 128): K fragment (A operand) in arch VGPRs, Q fragment in AGPRs.  (With the K fragments in AGPRs as in attn_pipe.hip
+//        hipcc overlapped them with an O tile and saved / restored that tile around every block: 16 + 16 v_accvgpr copies.)
+//   _vv  attn512.hip (D = 512): every operand "v": as builtins hipcc gives S two of the 16 accumulator-file tiles and swaps the displaced O tiles
+//        through VGPRs around every block (690 v_accvgpr copies per block in the first build).
+// An asm MFMA is opaque to hipcc's hazard recogniser: mfma_settle / mfma_settle_all (ldx_device.h) supply the wait states between the last MFMA and
+// the first VALU read of S.
 #define AP_BF16 "v_mfma_f32_32x32x16_bf16"
 #define AP_F16 "v_mfma_f32_32x32x16_f16"
-template <typename T> __device__ __forceinline__ void ap_sacc0(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
+template <typename T> __device__ __forceinline__ void ap_sacc0_aa(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
     if constexpr (std::is_same<T, __bf16>::value) asm volatile(AP_BF16 " %0, %1, %2, 0" : "=&v"(d) : "a"(a), "a"(b));
     else asm volatile(AP_F16 " %0, %1, %2, 0" : "=&v"(d) : "a"(a), "a"(b));
 }
-template <typename T> __device__ __forceinline__ void ap_sacc(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
+template <typename T> __device__ __forceinline__ void ap_sacc_aa(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
     if constexpr (std::is_same<T, __bf16>::value) asm volatile(AP_BF16 " %0, %1, %2, %0" : "+v"(d) : "a"(a), "a"(b));
     else asm volatile(AP_F16 " %0, %1, %2, %0" : "+v"(d) : "a"(a), "a"(b));
+}
+template <typename T> __device__ __forceinline__ void ap_sacc0_va(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
+    if constexpr (std::is_same<T, __bf16>::value) asm volatile(AP_BF16 " %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
+    else asm volatile(AP_F16 " %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
+}
+template <typename T> __device__ __forceinline__ void ap_sacc_va(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
+    if constexpr (std::is_same<T, __bf16>::value) asm volatile(AP_BF16 " %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
+    else asm volatile(AP_F16 " %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
+}
+template <typename T> __device__ __forceinline__ void ap_sacc0_vv(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
+    if constexpr (std::is_same<T, __bf16>::value) asm volatile(AP_BF16 " %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
+    else asm volatile(AP_F16 " %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
+}
+template <typename T> __device__ __forceinline__ void ap_sacc_vv(f32x16& d, ap_i32x4 a, ap_i32x4 b) {
+    if constexpr (std::is_same<T, __bf16>::value) asm volatile(AP_BF16 " %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
+    else asm volatile(AP_F16 " %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
 }
 // ---- softmax pieces.  Piece k: exp2 of element a, the pack of piece k - 2's results (px, py -> one dword of P), exp2 of element b.  A VALU read of a
 // fresh transcendental result needs a wait state; hipcc cannot see the order inside an asm block and pads every block whose inputs were written by

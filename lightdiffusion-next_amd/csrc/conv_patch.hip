@@ -35,19 +35,6 @@
 
 namespace ldx {
 
-typedef __attribute__((ext_vector_type(4))) int cp_i32x4;
-static __device__ __forceinline__ cp_i32x4 cp_srd(const void* base, long bytes) {
-    const unsigned long long q = (unsigned long long)base;
-    const int n = (int)(bytes > 0x7fffffffL ? 0x7fffffffL : (bytes > 0 ? bytes : 0));
-    return (cp_i32x4){(int)(unsigned)q, (int)((unsigned)(q >> 32) & 0xffffu), n, 0x00020000};
-}
-// M0 is written without being declared (gemm_pp.inc explains why that is safe in these kernels)
-static __device__ __forceinline__ void cp_dma16(const cp_i32x4 rsrc, int voff, int soff, unsigned lds) {
-    // both are wave-uniform; under SGPR pressure the compiler keeps such values in vector registers and would hand those to the asm
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    lds = (unsigned)__builtin_amdgcn_readfirstlane((int)lds);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n in [0, 23] (larger: 23 — a smaller count than allowed only waits longer): a computed jump into
 // a table of (s_waitcnt, s_branch) pairs.  A 20-way switch compiled to ~40 compare-and-branch instructions per step.
 static __device__ __forceinline__ void cp_wait_n(int n) {
@@ -108,8 +95,8 @@ __global__ __launch_bounds__(512, 1) void conv_patch_kernel(const GemmArgs p, co
     const int Cin = p.Cin, nkc = Cin >> 5, nsteps = 3 * nkc;
     const int ntl = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;       // tiles of this workgroup
 
-    const cp_i32x4 rA = cp_srd(p.A, (((long)nimg * p.Hin * p.Win - 1) * p.lda + Cin) * 2);
-    const cp_i32x4 rW = cp_srd(p.W, (long)p.N * p.K * 2);
+    const i32x4 rA = make_srd(p.A, (((long)nimg * p.Hin * p.Win - 1) * p.lda + Cin) * 2);
+    const i32x4 rW = make_srd(p.W, (long)p.N * p.K * 2);
     const float rs_y = p.resize ? (float)p.Hin / (float)p.Hv : 1.f, rs_x = p.resize ? (float)p.Win / (float)p.Wv : 1.f;
 
     // tile it of this workgroup -> (image, y0, x0); an XCD's workgroups walk one contiguous range of tiles, neighbours at the same time (shared halos in its L2)
@@ -165,7 +152,7 @@ __global__ __launch_bounds__(512, 1) void conv_patch_kernel(const GemmArgs p, co
         const unsigned dst = lds_base + pslot_in * CP_PATCH;
 #pragma unroll
         for (int i = 0; i < NPP; ++i)
-            if (wave + 8 * i < CP_PP && !(abl & 1)) cp_dma16(rA, pv[i], kc * 64, dst + (wave + 8 * i) * 1024);
+            if (wave + 8 * i < CP_PP && !(abl & 1)) lds_dma16_uniform(rA, pv[i], kc * 64, dst + (wave + 8 * i) * 1024);
         issued += nP;
         pslot_in = pslot_in + 1 == PR ? 0 : pslot_in + 1;
     };
@@ -175,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void conv_patch_kernel(const GemmArgs p, co
         const int soff = (kx * Cin + kc * 32) * 2;
 #pragma unroll
         for (int i = 0; i < NWP; ++i)
-            if (wave + 8 * i < WP && !(abl & 2)) cp_dma16(rW, wv[i], soff, dst + (wave + 8 * i) * 1024);
+            if (wave + 8 * i < WP && !(abl & 2)) lds_dma16_uniform(rW, wv[i], soff, dst + (wave + 8 * i) * 1024);
         issued += nW;
     };
 
@@ -385,7 +372,7 @@ __global__ __launch_bounds__(640, 1) void conv_patch_ws_kernel(const GemmArgs p,
 
     if (wave == 8) {
         // ---- patch loader: chunk stream (tile, kc) in order, PR - 1 chunks ahead of the consumers; all 39 pieces of a chunk from this wave
-        const cp_i32x4 rA = cp_srd(p.A, (((long)nimg * p.Hin * p.Win - 1) * p.lda + Cin) * 2);
+        const i32x4 rA = make_srd(p.A, (((long)nimg * p.Hin * p.Win - 1) * p.lda + Cin) * 2);
         const float rs_y = p.resize ? (float)p.Hin / (float)p.Hv : 1.f, rs_x = p.resize ? (float)p.Win / (float)p.Wv : 1.f;
         // Per-lane source offsets (slot q = 64 piece + lane -> pixel q >> 2 = 34 Y + X, position q & 3).  Without a resize they are the sum of a part that does
         // not depend on the tile — pv[i] = (Y Win + X) lda 2 + 16 octet, computed ONCE — and the patch origin (a scalar, passed as the DMA's scalar offset); only tiles on the image
@@ -443,14 +430,14 @@ __global__ __launch_bounds__(640, 1) void conv_patch_ws_kernel(const GemmArgs p,
             if (!(abl & 1)) {
                 if (p.resize) {
 #pragma unroll
-                    for (int i = 0; i < CP_PP; ++i) cp_dma16(rA, pv[i], kc_in * 64, dst + i * 1024);
+                    for (int i = 0; i < CP_PP; ++i) lds_dma16_uniform(rA, pv[i], kc_in * 64, dst + i * 1024);
                 } else {
                     if (!border) {                           // two loops, not a test per piece: hipcc if-converted the per-piece form and every tile paid the masks
 #pragma unroll
-                        for (int i = 0; i < CP_PP; ++i) cp_dma16(rA, pv[i], sbase + kc_in * 64, dst + i * 1024);
+                        for (int i = 0; i < CP_PP; ++i) lds_dma16_uniform(rA, pv[i], sbase + kc_in * 64, dst + i * 1024);
                     } else {
 #pragma unroll
-                        for (int i = 0; i < CP_PP; ++i) cp_dma16(rA, pv[i], kc_in * 64, dst + i * 1024);
+                        for (int i = 0; i < CP_PP; ++i) lds_dma16_uniform(rA, pv[i], kc_in * 64, dst + i * 1024);
                     }
                 }
             }
@@ -480,7 +467,7 @@ __global__ __launch_bounds__(640, 1) void conv_patch_ws_kernel(const GemmArgs p,
     }
     if (wave == 9) {
         // ---- weight loader: stage stream (tile, step) in order, RW - 1 steps ahead; piece pw = ky * NJ + j, lane -> row 16 j + (lane >> 2), position lane & 3
-        const cp_i32x4 rW = cp_srd(p.W, (long)p.N * p.K * 2);
+        const i32x4 rW = make_srd(p.W, (long)p.N * p.K * 2);
         int wv[WP];
 #pragma unroll
         for (int pw = 0; pw < WP; ++pw) {
@@ -497,7 +484,7 @@ __global__ __launch_bounds__(640, 1) void conv_patch_ws_kernel(const GemmArgs p,
             const int soff = (kx * Cin + kc * 32) * 2;
             if (!(abl & 2)) {
 #pragma unroll
-                for (int pw = 0; pw < WP; ++pw) cp_dma16(rW, wv[pw], soff, dst + pw * 1024);
+                for (int pw = 0; pw < WP; ++pw) lds_dma16_uniform(rW, wv[pw], soff, dst + pw * 1024);
             }
             issued += WP;
             if (++s_in == nsteps) { s_in = 0; ++itw_in; }

@@ -26,6 +26,7 @@ constexpr int FB_AROW = FB_C * 2 + 16;            // 656 B
 constexpr int FB_GROW = FB_CH * 2 + 16;           // 272 B
 constexpr int FB_ABYTES = FB_BM * FB_AROW, FB_GBYTES = FB_BM * FB_GROW;
 constexpr int FB_LDS = FB_ABYTES + 2 * FB_GBYTES + 2 * FB_C * 4;
+static_assert(FB_C == RB_C && FB_BM == RB_BM && FB_AROW == RB_AROW, "rb_layernorm_rows writes this A tile");
 
 template <typename T>
 __global__ __launch_bounds__(512, 1) void ff_block_kernel(const FFBlockArgs p) {
@@ -45,43 +46,7 @@ __global__ __launch_bounds__(512, 1) void ff_block_kernel(const FFBlockArgs p) {
 
     // ---- LayerNorm of 128 rows -> A (4 lanes per row, row in registers, two-pass statistics) ----
     for (int i = tid; i < FB_C; i += 512) { sG[i] = p.ln_g[i]; sBt[i] = p.ln_b[i]; }
-    {
-        const int row = tid >> 2, part = tid & 3;
-        const long m = m0 + row;
-        float x[80];
-        if (m < p.M) {
-#pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const uint4 u = *(const uint4*)(Hp + m * p.ldh + (part + 4 * j) * 8);
-                float f[8];
-                unpack8<T>(u, f);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[8 * j + e] = f[e];
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 80; ++e) x[e] = 0.f;
-        }
-        float su = 0.f;
-#pragma unroll
-        for (int e = 0; e < 80; ++e) su += x[e];
-        su += dpp_f<0xB1>(su); su += dpp_f<0x4E>(su);
-        const float mean = su * (1.0f / FB_C);
-        float sq = 0.f;
-#pragma unroll
-        for (int e = 0; e < 80; ++e) { const float d = x[e] - mean; sq = fmaf(d, d, sq); }
-        sq += dpp_f<0xB1>(sq); sq += dpp_f<0x4E>(sq);
-        const float rstd = rsqrtf(sq * (1.0f / FB_C) + p.eps);
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 10; ++j) {
-            const int c0 = (part + 4 * j) * 8;
-            float f[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = fmaf((x[8 * j + e] - mean) * rstd, sG[c0 + e], sBt[c0 + e]);
-            *(uint4*)(sA + row * FB_AROW + c0 * 2) = pack8<T>(f);
-        }
-    }
+    rb_layernorm_rows<T>(Hp, p.ldh, m0, p.M, p.eps, sG, sBt, sA, tid, false);
     __syncthreads();
 
     f32x4 y[3][8];

@@ -85,8 +85,8 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& p, const int bloc
     const long a_total = (MODE == 0) ? (long)(p.M - 1) * p.lda + p.K : ((long)(p.M / hw) * p.Hin * p.Win - 1) * p.lda + p.Cin;
     const long a_rem = (a_total - a_base) * ES;
     const long w_rem = ((long)p.N * p.K - (long)n0 * p.K) * ES;
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)(Ap + a_base * ES), 0, (int)(a_rem > 0x7fffffffL ? 0x7fffffffL : a_rem), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)(Wp + (long)n0 * p.K * ES), 0, (int)(w_rem > 0x7fffffffL ? 0x7fffffffL : w_rem), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)(Ap + a_base * ES), 0, (int)(a_rem > 0x7fffffffL ? 0x7fffffffL : a_rem), RSRC_RAW_WORD3);
+    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)(Wp + (long)n0 * p.K * ES), 0, (int)(w_rem > 0x7fffffffL ? 0x7fffffffL : w_rem), RSRC_RAW_WORD3);
 
     int a_voff[LA];                   // plain: final byte offset ; conv: per-tap byte offset (recomputed per tap)
     int a_pix[LA];                    // conv: byte offset of this row's batch image + chunk
@@ -112,7 +112,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& p, const int bloc
     const bool has_a2 = (MODE == 1) && p.A2 != nullptr;
     const long rem2 = has_a2 ? ((long)(p.M - m0 - 1) * p.lda2 + p.Cin2) * 2 : 0;
     const __amdgpu_buffer_rsrc_t rA2 = __builtin_amdgcn_make_buffer_rsrc(
-        has_a2 ? (void*)((const char*)p.A2 + (long)m0 * p.lda2 * 2) : (void*)p.A, 0, (int)(rem2 > 0x7fffffffL ? 0x7fffffffL : (rem2 > 0 ? rem2 : 0)), 0x00020000);
+        has_a2 ? (void*)((const char*)p.A2 + (long)m0 * p.lda2 * 2) : (void*)p.A, 0, (int)(rem2 > 0x7fffffffL ? 0x7fffffffL : (rem2 > 0 ? rem2 : 0)), RSRC_RAW_WORD3);
     int a2_voff[(MODE == 1) ? LA : 1];
 #pragma unroll
     for (int j = 0; j < ((MODE == 1) ? LA : 1); ++j)
@@ -133,8 +133,8 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& p, const int bloc
     __amdgpu_buffer_rsrc_t rSA, rSW;
     if (F8) {
         const long sa_rem = ((long)nk_all * p.sa_ld - m0) * 4, sw_rem = ((long)nk_all * p.sw_ld - n0) * 4;
-        rSA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.SA + m0), 0, (int)(sa_rem > 0x7fffffffL ? 0x7fffffffL : sa_rem), 0x00020000);
-        rSW = __builtin_amdgcn_make_buffer_rsrc((void*)(p.SW + n0), 0, (int)(sw_rem > 0x7fffffffL ? 0x7fffffffL : sw_rem), 0x00020000);
+        rSA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.SA + m0), 0, (int)(sa_rem > 0x7fffffffL ? 0x7fffffffL : sa_rem), RSRC_RAW_WORD3);
+        rSW = __builtin_amdgcn_make_buffer_rsrc((void*)(p.SW + n0), 0, (int)(sw_rem > 0x7fffffffL ? 0x7fffffffL : sw_rem), RSRC_RAW_WORD3);
 #pragma unroll
         for (int i = 0; i < MI; ++i) { const int r = wm * (BM / WM) + i * 16 + l15; sa_voff[i] = (m0 + r < p.M) ? r * 4 : OOB; }
 #pragma unroll

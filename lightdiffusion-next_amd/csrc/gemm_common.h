@@ -198,7 +198,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p_in, f32x4 (&acc)
         constexpr int SLAB = BM * BN;                                   // floats
         const int lane_off = (((wm * 2 + wn) * MI * NJ) * 64 + (g4 * 16 + l15)) * 16;      // bytes; + (i * NJ + j) * 1024
         {
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ws + ((size_t)tile * S + split) * SLAB), 0, SLAB * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ws + ((size_t)tile * S + split) * SLAB), 0, SLAB * 4, RSRC_RAW_WORD3);
 #pragma unroll
             for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -221,7 +221,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p_in, f32x4 (&acc)
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int sp = 0; sp < S; ++sp) {
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ws + ((size_t)tile * S + sp) * SLAB), 0, SLAB * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ws + ((size_t)tile * S + sp) * SLAB), 0, SLAB * 4, RSRC_RAW_WORD3);
             f32x4 t[MI][NJ];
 #pragma unroll
             for (int i = 0; i < MI; ++i)

@@ -17,22 +17,7 @@
 //       in mem(p + 1), which group 0 starts after b_2p+1;
 //  WAR  the slot of half-tile p - 1 is refilled in mem(p); its last reads (mem(p - 1), completed by lgkmcnt(0) before the
 //       barrier that ends that part) precede b_2p-1 for both groups, and group 0 issues the refill after b_2p-1.
-// The DMA is inline asm so that hipcc does not put a vmcnt(0) in front of every ds_read (it does for the builtin).
-// The asm writes M0 without declaring it: hipcc rejects "m0" in a clobber list as a reserved register ("may lead to undefined behaviour",
-// -Winline-asm), and on gfx950 nothing else in these kernels lives in M0 (DS instructions do not need it; no movrel / sendmsg / LDS-direct
-// users — `grep -c m0` over the kernels' ISA finds only these s_mov_b32).  A kernel that adds such a user must re-materialise M0 itself.
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-__device__ __forceinline__ i32x4 make_srd(const void* base, long bytes) {
-    const unsigned long long q = (unsigned long long)base;
-    const int n = (int)(bytes > 0x7fffffffL ? 0x7fffffffL : (bytes > 0 ? bytes : 0));
-    return (i32x4){(int)(unsigned)q, (int)((unsigned)(q >> 32) & 0xffffu), n, 0x00020000};
-}
-__device__ __forceinline__ void lds_dma16(const i32x4 rsrc, int voff, int soff, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void lds_dma4(const i32x4 rsrc, int voff, int soff, unsigned lds) {       // lane l lands at lds + 4 l
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds" :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
+// Descriptors, the DMA itself and the counted wait are make_srd / lds_dma16 / lds_dma4 / vm_wait of ldx_device.h.
 constexpr int PP_HALF = 256 * 128, PP_NSLOT = 5, PP_GM = 4;
 constexpr int PP_LDS = PP_NSLOT * PP_HALF;
 
@@ -204,9 +189,9 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int block)
     issue_a(0, 0); issue_w(0, 1);
     if (nk > 1) {
         issue_a(1, 2); issue_w(1, 3);
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 + LW) : "memory");
+        vm_wait<4 + LW>();
     } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vm_wait<0>();
     }
     asm volatile("s_barrier" ::: "memory");
     LDX_PP_STAMP(2);
@@ -255,8 +240,8 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int block)
                 for (int j = 0; j < NJ0; ++j)
                     if (j < nj) csb[j] = (int)(*(const uint32_t*)(sb + SC_OFF + 1024 + (wn * (BN / 2) + (j0 + j) * 16 + l15) * 4) >> (8 * g4));
             }
-            if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 + LW) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (more) vm_wait<4 + LW>();
+            else vm_wait<0>();
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
             // ---------------- compute part: registers only ----------------

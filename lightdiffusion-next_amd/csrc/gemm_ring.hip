@@ -24,28 +24,16 @@
 
 namespace ldx {
 
-typedef __attribute__((ext_vector_type(4))) int gr_i32x4;
-static __device__ __forceinline__ gr_i32x4 gr_srd(const void* base, long bytes) {
-    const unsigned long long q = (unsigned long long)base;
-    const int n = (int)(bytes > 0x7fffffffL ? 0x7fffffffL : (bytes > 0 ? bytes : 0));
-    return (gr_i32x4){(int)(unsigned)q, (int)((unsigned)(q >> 32) & 0xffffu), n, 0x00020000};
-}
-// M0 is written without being declared (gemm_pp.inc explains why that is safe in these kernels)
-static __device__ __forceinline__ void gr_dma16(const gr_i32x4 rsrc, int voff, int soff, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-
 constexpr int GR_BM = 64, GR_BN = 160, GR_NS = 5;
 constexpr int GR_STAGE = (GR_BM + GR_BN) * 128;          // 28 672 B
 constexpr int GR_LDS = GR_NS * GR_STAGE;                 // 143 360 B
 
-template <int N> static __device__ __forceinline__ void gr_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 // wait until at most `tiles` later K-tiles of this wave (P pieces each) are still in flight
 template <int P> static __device__ __forceinline__ void gr_wait_tiles(int tiles) {
-    if (tiles >= 3) gr_wait<3 * P>();
-    else if (tiles == 2) gr_wait<2 * P>();
-    else if (tiles == 1) gr_wait<P>();
-    else gr_wait<0>();
+    if (tiles >= 3) vm_wait<3 * P>();
+    else if (tiles == 2) vm_wait<2 * P>();
+    else if (tiles == 1) vm_wait<P>();
+    else vm_wait<0>();
 }
 
 template <typename T>
@@ -64,8 +52,8 @@ __global__ __launch_bounds__(512, 1) void gemm_ring_kernel(const GemmArgs p) {
     const int m0 = tm * GR_BM, n0 = tn * GR_BN;
     const int nk = p.K / BK;
 
-    const gr_i32x4 rA = gr_srd((const char*)p.A + (long)m0 * p.lda * 2, ((long)(p.M - m0 - 1) * p.lda + p.K) * 2);
-    const gr_i32x4 rW = gr_srd((const char*)p.W + (long)n0 * p.K * 2, ((long)(p.N - n0) * p.K) * 2);
+    const i32x4 rA = make_srd((const char*)p.A + (long)m0 * p.lda * 2, ((long)(p.M - m0 - 1) * p.lda + p.K) * 2);
+    const i32x4 rW = make_srd((const char*)p.W + (long)n0 * p.K * 2, ((long)(p.N - n0) * p.K) * 2);
     // this wave's DMA pieces: piece = 8 tile rows, lane l -> row 8 piece + (l >> 3), LDS position l & 7 <- source chunk (l & 7) ^ (row & 7)
     const int prow = lane >> 3, gchunk = (lane & 7) ^ prow;       // (8 piece + prow) & 7 == prow
     const int arow = 8 * wave + prow;
@@ -81,10 +69,10 @@ __global__ __launch_bounds__(512, 1) void gemm_ring_kernel(const GemmArgs p) {
     auto issue = [&](int kt, int slot) __attribute__((always_inline)) {
         const unsigned dst = lds_base + slot * GR_STAGE;
         const int soff = kt * (BK * 2);
-        gr_dma16(rA, a_voff, soff, dst + wave * 1024);
-        gr_dma16(rW, w_voff[0], soff, dst + (8 + wave) * 1024);
-        gr_dma16(rW, w_voff[1], soff, dst + (16 + wave) * 1024);
-        if (wave < 4) gr_dma16(rW, w_voff[2], soff, dst + (24 + wave) * 1024);
+        lds_dma16(rA, a_voff, soff, dst + wave * 1024);
+        lds_dma16(rW, w_voff[0], soff, dst + (8 + wave) * 1024);
+        lds_dma16(rW, w_voff[1], soff, dst + (16 + wave) * 1024);
+        if (wave < 4) lds_dma16(rW, w_voff[2], soff, dst + (24 + wave) * 1024);
     };
 
     f32x4 acc[MI][NJ];

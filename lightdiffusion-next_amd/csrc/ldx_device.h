@@ -143,6 +143,15 @@ __device__ __forceinline__ float xrow32_sum(float v) {    // + lane ^ 32
     auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return __uint_as_float(a[0]) + __uint_as_float(a[1]);
 }
+// value of lane^16 / lane^32 combined with own value; v_permlane*_swap with both operands = v leaves
+// {own, partner} in the two results (order depends on the lane), so a commutative op needs no select.
+__device__ __forceinline__ float quad_max(float v) {
+    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+}
+__device__ __forceinline__ float quad_sum(float v) { return xrow32_sum(xrow16_sum(v)); }
 // sum over groups of LPR consecutive lanes (16, 32 or 64); every lane of the group gets the total
 template <int LPR> __device__ __forceinline__ float group_sum(float v) {
     v = row16_sum(v);
@@ -152,11 +161,7 @@ template <int LPR> __device__ __forceinline__ float group_sum(float v) {
 }
 __device__ __forceinline__ float wave_sum(float v) { return group_sum<64>(v); }
 __device__ __forceinline__ float wave_max(float v) {
-    v = row16_max(v);
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+    return quad_max(row16_max(v));
 }
 
 // XCD-aware block remap (8 XCDs, block b is dispatched to XCD b % 8): give each XCD a contiguous
@@ -169,6 +174,71 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     const int xcd = bid % nx, idx = bid / nx;
     const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + idx;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Primitives that carry a hardware or compiler contract.  Each exists once, here, with its contract; the kernels only call them.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+
+// Word 3 of every buffer descriptor built here (gfx9 layout: only DATA_FORMAT = 32-bit set): a raw, unswizzled buffer of stride 0 whose offsets are
+// checked against num_records in bytes — out-of-range loads return zeros, which is what the kernels' OOB offsets rely on.
+constexpr int RSRC_RAW_WORD3 = 0x00020000;
+
+// Descriptor over `bytes` bytes from `base` (clamped to [0, 2^31 - 1]) as four SGPR dwords, for the inline-asm loads below.
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+__device__ __forceinline__ i32x4 make_srd(const void* base, long bytes) {
+    const unsigned long long q = (unsigned long long)base;
+    const int n = (int)(bytes > 0x7fffffffL ? 0x7fffffffL : (bytes > 0 ? bytes : 0));
+    return (i32x4){(int)(unsigned)q, (int)((unsigned)(q >> 32) & 0xffffu), n, RSRC_RAW_WORD3};
+}
+
+// LDS-DMA: global -> LDS without VGPR staging; lane l lands at lds + 16 l (lds_dma4: lds + 4 l).  rsrc, soff and lds are wave-uniform.
+// Inline asm so that hipcc does not put a vmcnt(0) in front of every ds_read (it does for the builtin); completion is the caller's counted vm_wait.
+// The asm writes M0 without declaring it: hipcc rejects "m0" in a clobber list as a reserved register ("may lead to undefined behaviour",
+// -Winline-asm), and on gfx950 nothing else in these kernels lives in M0 (DS instructions do not need it; no movrel / sendmsg / LDS-direct
+// users — `grep -c m0` over the kernels' ISA finds only these s_mov_b32).  A kernel that adds such a user must re-materialise M0 itself.
+__device__ __forceinline__ void lds_dma16(const i32x4 rsrc, int voff, int soff, unsigned lds) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
+__device__ __forceinline__ void lds_dma4(const i32x4 rsrc, int voff, int soff, unsigned lds) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds" :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
+// lds_dma16 with soff and lds forced through readfirstlane: both are wave-uniform, but under SGPR pressure the compiler keeps such values in vector
+// registers and would hand those to the asm.  conv_patch.hip uses this flavour; gemm_pp.inc, gemm_ring.hip, attn512.hip and attn_mx.hip use the
+// plain one: that split is how the kernels were written and was carried over, not decided.
+__device__ __forceinline__ void lds_dma16_uniform(const i32x4 rsrc, int voff, int soff, unsigned lds) {
+    soff = __builtin_amdgcn_readfirstlane(soff);
+    lds = (unsigned)__builtin_amdgcn_readfirstlane((int)lds);
+    lds_dma16(rsrc, voff, soff, lds);
+}
+// s_waitcnt vmcnt(N): at most N of this wave's vector-memory operations (LDS-DMA pieces retire in issue order) still in flight
+template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
+
+// ds_read_b64_tr_b16: the transposing LDS read that gathers a V^T fragment from row-major V
+__device__ __forceinline__ uint2 lds_read_tr16(const char* p) {
+    typedef __attribute__((ext_vector_type(4))) short s16x4;
+    const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
+    union { s16x4 v; uint2 u; } x; x.v = v; return x.u;
+}
+
+// Wait states behind asm MFMAs.  An MFMA written as inline asm (attn_pipe_common.h) is opaque to hipcc's hazard recogniser, and so is any asm that
+// reads a builtin MFMA's result: the s_nop runs below stand in for it between the last 16-pass MFMA and the first VALU read of its result.
+// mfma_settle(x) / (a, b): 24 wait states, tied to the registers read next ("+v") so that neither the read nor the nops move.
+// mfma_settle_all<RUNS>(): RUNS x 16 wait states behind a memory clobber, for the software-pipelined kernels whose results are many tiles.
+template <typename V> __device__ __forceinline__ void mfma_settle(V& x) { asm volatile("s_nop 15\n\ts_nop 7" : "+v"(x)); }
+template <typename V> __device__ __forceinline__ void mfma_settle(V& a, V& b) { asm volatile("s_nop 15\n\ts_nop 7" : "+v"(a), "+v"(b)); }
+template <int RUNS> __device__ __forceinline__ void mfma_settle_all() {
+    static_assert(RUNS == 2 || RUNS == 3, "the two nop runs the pipelined attention kernels use");
+    if constexpr (RUNS == 3) asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+    else asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+}
+// eight registers of an O tile out of the accumulator file, as asm with "a" inputs: read by plain C++ after the key loop, hipcc decides at the loop exit
+// which parts of O to move to VGPRs and spills what does not fit.  Call mfma_settle first when the tile's last writer was an MFMA.
+template <int R0> __device__ __forceinline__ void acc_get8(const f32x16& t, float (&v)[8]) {
+    asm volatile("v_accvgpr_read_b32 %0, %8\n\tv_accvgpr_read_b32 %1, %9\n\tv_accvgpr_read_b32 %2, %10\n\tv_accvgpr_read_b32 %3, %11\n\t"
+                 "v_accvgpr_read_b32 %4, %12\n\tv_accvgpr_read_b32 %5, %13\n\tv_accvgpr_read_b32 %6, %14\n\tv_accvgpr_read_b32 %7, %15\n\ts_nop 1"
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
+                 : "a"(t[R0]), "a"(t[R0 + 1]), "a"(t[R0 + 2]), "a"(t[R0 + 3]), "a"(t[R0 + 4]), "a"(t[R0 + 5]), "a"(t[R0 + 6]), "a"(t[R0 + 7]));
 }
 
 }  // namespace ldx

@@ -21,26 +21,6 @@
 
 namespace ldx {
 
-namespace {
-typedef __attribute__((ext_vector_type(4))) short xs16x4;
-__device__ __forceinline__ uint2 x_lds_read_tr16(const char* p) {
-    const xs16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) xs16x4*)p);
-    union { xs16x4 v; uint2 u; } x; x.v = v; return x.u;
-}
-__device__ __forceinline__ float x_quad_max(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float x_quad_sum(float v) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-}  // namespace
-
 #ifdef XA_ABLATE
 __device__ int xa_dbg = 0;       // timing ablations (wrong results): 1 no phase 1, 2 no phase 2, 4 no phase 3 MFMAs, 8 no epilogue, 16 no LN loads
 #define XA_DBG(bit) (xa_dbg & (bit))
@@ -52,6 +32,7 @@ constexpr int XA_AROW = XA_C * 2 + 16;            // 656 B: 16 consecutive rows 
 constexpr int XA_VROW = 96;                       // bytes per key row of a wave's V_h region (48 d; == 32 mod 64, see AttnCfg)
 constexpr int XA_ABYTES = XA_BM * XA_AROW, XA_VBYTES = XA_MK * XA_VROW;
 constexpr int XA_LDS = XA_ABYTES + XA_H * XA_VBYTES + 2 * XA_C * 4;       // + gamma / beta
+static_assert(XA_C == RB_C && XA_BM == RB_BM && XA_AROW == RB_AROW, "rb_layernorm_rows writes this A tile");
 
 // Q^T / Y^T projection of one wave: acc[t][qt] (lane: q = 16 qt + l15, row 16 t + 4 g4 + r of the wave's 40 weight rows) = W[rows][:] . A^T
 template <typename T>
@@ -115,43 +96,7 @@ __global__ __launch_bounds__(512, 1) void xattn_block_kernel(const XAttnArgs p) 
             *(uint4*)(sV + row * XA_VROW + ch * 16) = u;
         }
     }
-    {
-        const int row = tid >> 2, part = tid & 3;
-        const long m = m0 + row;
-        float x[80];
-        if (m < p.M && !XA_DBG(16)) {
-#pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const uint4 u = *(const uint4*)(Hp + m * p.ldh + (part + 4 * j) * 8);
-                float f[8];
-                unpack8<T>(u, f);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[8 * j + e] = f[e];
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 80; ++e) x[e] = 0.f;
-        }
-        float su = 0.f;
-#pragma unroll
-        for (int e = 0; e < 80; ++e) su += x[e];
-        su += dpp_f<0xB1>(su); su += dpp_f<0x4E>(su);
-        const float mean = su * (1.0f / XA_C);
-        float sq = 0.f;
-#pragma unroll
-        for (int e = 0; e < 80; ++e) { const float d = x[e] - mean; sq = fmaf(d, d, sq); }
-        sq += dpp_f<0xB1>(sq); sq += dpp_f<0x4E>(sq);
-        const float rstd = rsqrtf(sq * (1.0f / XA_C) + p.eps);
-        __syncthreads();                                 // gamma / beta in LDS
-#pragma unroll
-        for (int j = 0; j < 10; ++j) {
-            const int c0 = (part + 4 * j) * 8;
-            float f[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = fmaf((x[8 * j + e] - mean) * rstd, sG[c0 + e], sBt[c0 + e]);
-            *(uint4*)(sA + row * XA_AROW + c0 * 2) = pack8<T>(f);
-        }
-    }
+    rb_layernorm_rows<T>(Hp, p.ldh, m0, p.M, p.eps, sG, sBt, sA, tid, XA_DBG(16));
     __syncthreads();
 
     // ---- phase 1: Q^T of head `wave` ----
@@ -186,8 +131,8 @@ __global__ __launch_bounds__(512, 1) void xattn_block_kernel(const XAttnArgs p) 
         for (int j = 0; j < 3; ++j) {
             const char* vp = sV + (j * 32 + g4 * 4 + (l15 >> 2)) * XA_VROW + (dt * 16 + (l15 & 3) * 4) * 2;
             U128 u;
-            u.d[0] = x_lds_read_tr16(vp);
-            u.d[1] = (j < 2) ? x_lds_read_tr16(vp + 16 * XA_VROW) : make_uint2(0u, 0u);
+            u.d[0] = lds_read_tr16(vp);
+            u.d[1] = (j < 2) ? lds_read_tr16(vp + 16 * XA_VROW) : make_uint2(0u, 0u);
             vf[dt][j] = as_v8<T>(u.u);
         }
     __syncthreads();                                     // every wave is done with A: the attention output goes over it
@@ -217,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void xattn_block_kernel(const XAttnArgs p) 
                 if (16 * kt + 4 * g4 + r >= p.Mk) s[kt][r] = -INFINITY;
                 mx = fmaxf(mx, s[kt][r]);
             }
-        mx = x_quad_max(mx);
+        mx = quad_max(mx);
         const float mc = (mx == -INFINITY) ? 0.f : mx * c;
         float pv[6][4], l = 0.f;
 #pragma unroll
@@ -229,7 +174,7 @@ __global__ __launch_bounds__(512, 1) void xattn_block_kernel(const XAttnArgs p) 
             }
 #pragma unroll
         for (int r = 0; r < 4; ++r) pv[5][r] = 0.f;
-        l = x_quad_sum(l);
+        l = quad_sum(l);
         f32x4 o[3];
 #pragma unroll
         for (int dt = 0; dt < 3; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
