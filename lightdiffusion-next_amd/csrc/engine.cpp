@@ -29,15 +29,6 @@ int launch_status() {
     return LDX_EHIP;
 }
 
-#define HIP_OK(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) {                                                              \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                    \
-            return LDX_EHIP;                                                                 \
-        }                                                                                    \
-    } while (0)
-
 // ---------------------------------------------------------------------------------------------
 // 16-bit conversions on the host (round-to-nearest-even)
 static inline float half_to_float(uint16_t h) {
@@ -292,7 +283,7 @@ bool Engine::mk_res(const std::string& pre, int Cin, int Cout, ResW& r) {
     emb_srcs.push_back({ew, eb, Cout});
     if (!mk_norm(pre + ".out_layers.0", Cout, r.gn2)) return false;
     r.has_skip = Cin != Cout;
-    const bool try_fuse = r.has_skip && Cin % 64 == 0 && !getenv("LDX_NO_FUSED_SKIP");
+    const bool try_fuse = r.has_skip && Cin % 64 == 0 && g_plan_sw.fused_skip;
     if (!try_fuse && !mk_conv3(pre + ".out_layers.3", Cout, Cout, Cout, r.conv2)) return false;
     if (r.has_skip) {
         // out = conv2(h) + skip_connection(x): one implicit GEMM over K = 9*Cout + Cin (GemmArgs::A2), weights [Cout][ky][kx][Cout | Cin]
@@ -317,7 +308,7 @@ bool Engine::mk_res(const std::string& pre, int Cin, int Cout, ResW& r) {
     return true;
 }
 
-static inline bool q_prescale() { static const bool on = getenv("LDX_NO_QPRESCALE") == nullptr; return on; }
+static inline bool q_prescale() { return g_plan_sw.q_prescale; }
 
 bool Engine::mk_xf(const std::string& pre, int C, int depth, XfW& x) {
     x.C = C; x.depth = depth;
@@ -342,8 +333,7 @@ bool Engine::mk_xf(const std::string& pre, int C, int depth, XfW& x) {
         // Round 4: it does pay where the row-block kernels are not taken (512^2 step 6.01 -> 5.87 ms) and loses where they are (1024^2: 14.31 -> 15.04 with
         // the fold everywhere), so both copies of the three weights are kept (+0.3 GB for SD1.5) and the planner decides per input shape
         // (emit_xf: LDX_LNFOLD_MAXROWS); LDX_LNFOLD=0: plain weights only.
-        static const bool fold_env = !(getenv("LDX_LNFOLD") != nullptr && atoi(getenv("LDX_LNFOLD")) == 0);
-        b.ln_fold = fold_env;
+        b.ln_fold = g_plan_sw.lnfold;
         // softmax_scale * log2(e) folded into the q projections at load time (one rounding of c * Wq instead of rounding q and multiplying
         // every score): the attention ops then run with scale = 1 / log2(e), i.e. exp2(q.k - m) as before; LDX_NO_QPRESCALE=1 keeps the plain weights
         const float cq = q_prescale() ? (1.0f / std::sqrt((float)(C / cfg.num_heads))) * 1.44269504088896340736f : 1.0f;
@@ -548,8 +538,14 @@ unsigned* Engine::sk_counters() {
 size_t Engine::ws_alloc(size_t bytes) { const size_t off = a_alloc(bytes); a_free(off); return off; }
 
 // ---- op emitters ---------------------------------------------------------------------------------
+Op& Engine::emit(OpKind kind, const char* name) {
+    cur.ops.emplace_back();
+    Op& o = cur.ops.back();
+    memset(&o, 0, sizeof(o)); o.kind = kind; o.name = name;
+    return o;
+}
 void Engine::op_gemm(const char* name, Act A, const LinearW& w, Act C, Act R, bool geglu, const float* rowvec, int rv_ld, int rpb) {
-    Op o{}; o.kind = OP_GEMM; o.name = name;
+    Op& o = emit(OP_GEMM, name);
     GemmArgs& g = o.g;
     g.A = ptr(A); g.lda = A.ld; g.W = w.w; g.M = A.rows; g.N = w.N; g.K = w.K; g.mode = 0;
     g.bias = w.b; g.rowvec = rowvec; g.rowvec_ld = rv_ld; g.rows_per_batch = rpb > 0 ? rpb : 1;
@@ -561,12 +557,11 @@ void Engine::op_gemm(const char* name, Act A, const LinearW& w, Act C, Act R, bo
     o.flops = 2.0 * g.M * (double)g.N * g.K;
     o.bytes = 2.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * (geglu ? g.N / 2 : g.N) * (R.valid ? 2 : 1));
     snprintf(o.klabel, sizeof(o.klabel), "gemm_kernel<%s,0>", dt == DT_BF16 ? "bf16" : "f16");
-    cur.ops.push_back(o);
     cur.flops += o.flops;
 }
 void Engine::op_conv(const char* name, Act X, int B, int Hin, int Win, int Cin, const LinearW& w, int stride, int Hout, int Wout,
                      Act Y, Act R, const float* rowvec, int rv_ld, float* Cf, int ldcf) {
-    Op o{}; o.kind = OP_GEMM; o.name = name;
+    Op& o = emit(OP_GEMM, name);
     GemmArgs& g = o.g;
     g.A = ptr(X); g.lda = X.ld; g.W = w.w; g.M = B * Hout * Wout; g.N = w.N; g.K = w.K; g.mode = 1;
     g.Cin = Cin; g.Hin = Hin; g.Win = Win; g.Hout = Hout; g.Wout = Wout; g.stride = stride;
@@ -580,7 +575,6 @@ void Engine::op_conv(const char* name, Act X, int B, int Hin, int Win, int Cin, 
     o.flops = 2.0 * g.M * (double)g.N * g.K;
     o.bytes = 2.0 * ((double)B * Hin * Win * Cin + (double)g.N * g.K + (double)g.M * g.N * (R.valid ? 2 : 1));
     snprintf(o.klabel, sizeof(o.klabel), "gemm_kernel<%s,1>", dt == DT_BF16 ? "bf16" : "f16");
-    cur.ops.push_back(o);
     cur.flops += o.flops;
 }
 // the kernels launch_groupnorm runs for the op as it stands (fuse_gn_stats asks again once the statistics come from the producer)
@@ -589,13 +583,12 @@ static void gn_label(Op& o) {
     snprintf(o.klabel, sizeof(o.klabel), "%s", names[gn_pick(o.gn).kind]);
 }
 void Engine::op_gn(const char* name, Act X, Act Y, int B, int HW, const NormW& n, float eps, bool silu) {
-    Op o{}; o.kind = OP_GN; o.name = name;
+    Op& o = emit(OP_GN, name);
     GroupNormArgs& g = o.gn;
     g.X = ptr(X); g.ldx = X.ld; g.Y = ptr(Y); g.ldy = Y.ld; g.B = B; g.HW = HW; g.C = n.C; g.G = 32; g.eps = eps; g.silu = silu;
     g.gamma = n.g; g.beta = n.b; g.partial = (float*)(cur.arena ? (char*)cur.arena + cur.gn_ws_off : nullptr);
     o.bytes = 2.0 * 3.0 * (double)B * HW * n.C;       // read (stats) + read + write (apply)
     gn_label(o);
-    cur.ops.push_back(o);
 }
 // SURVEY §8 a10-a11 / VERDICT r2 item 1c: GroupNorm statistics from the producing conv / GEMM epilogue.  A GroupNorm whose input tensor was written by
 // the op right before it (so nothing else touches the shared statistics workspace in between) and whose producer launch can do it
@@ -630,7 +623,7 @@ void Engine::fuse_gn_stats() {
 }
 // Row-block GEMM (rowgemm.hip) in place of [LayerNorm +] an N = k K, K = 320 / 640 projection, where xf_pick says so
 void Engine::op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R, int pro, const NormW* nw) {
-    Op o{}; o.kind = OP_ROWGEMM; o.name = name;
+    Op& o = emit(OP_ROWGEMM, name);
     RowGemmArgs& a = o.rg;
     a.X = ptr(X); a.ldx = X.ld; a.Y = ptr(Y); a.ldy = Y.ld; a.M = X.rows; a.N = w.N; a.K = w.K; a.W = w.w; a.bias = w.b;
     a.R = R.valid ? ptr(R) : nullptr; a.ldr = R.ld; a.pro = pro; a.eps = 1e-5f;
@@ -638,7 +631,6 @@ void Engine::op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R,
     o.flops = 2.0 * a.M * (double)a.N * a.K;
     o.bytes = 2.0 * ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N * (R.valid ? 2 : 1));
     snprintf(o.klabel, sizeof(o.klabel), "rowgemm<%s,%d>", dt == DT_BF16 ? "bf16" : "f16", pro);
-    cur.ops.push_back(o);
     cur.flops += o.flops;
 }
 // SpatialTransformer norm + proj_in, as emit_xf emitted them, become one rowgemm launch with the GroupNorm apply as its prologue where xf_proj_in_rowgemm says so.
@@ -662,15 +654,14 @@ void Engine::fuse_gn_rowgemm() {
     }
 }
 void Engine::op_ln(const char* name, Act X, Act Y, const NormW& n) {
-    Op o{}; o.kind = OP_LN; o.name = name;
+    Op& o = emit(OP_LN, name);
     LayerNormArgs& l = o.ln;
     l.X = ptr(X); l.ldx = X.ld; l.Y = ptr(Y); l.ldy = Y.ld; l.rows = X.rows; l.C = n.C; l.eps = 1e-5f; l.gamma = n.g; l.beta = n.b;
     o.bytes = 2.0 * 2.0 * (double)X.rows * n.C;
     snprintf(o.klabel, sizeof(o.klabel), "ln_kernel");
-    cur.ops.push_back(o);
 }
 void Engine::op_attn(const char* name, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, Act O, int B, int H, int Nq, int Mk, int D) {
-    Op o{}; o.kind = OP_ATTN; o.name = name;
+    Op& o = emit(OP_ATTN, name);
     AttnArgs& a = o.at;
     a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = ptr(O); a.ldo = O.ld;
     a.B = B; a.H = H; a.Nq = Nq; a.Mk = Mk; a.D = D; a.scale = 1.0f / std::sqrt((float)D); a.causal = 0;
@@ -692,22 +683,19 @@ void Engine::op_attn(const char* name, const void* Q, int ldq, const void* K, in
         if (p.family == AF_ATTN512) snprintf(o.klabel + n, sizeof(o.klabel) - n, "x%d", a.nsplit);
         else snprintf(o.klabel + n, sizeof(o.klabel) - n, "%s", Nq == Mk ? "self" : "cross");
     }
-    cur.ops.push_back(o);
     cur.flops += o.flops;
 }
 
 // rows [0, rows) of the view -> rows [rows, 2 * rows): the second half of a CFG batch takes over what was computed once for both (plan(): share)
 void Engine::op_dup(const Act& a, int rows) {
-    Op o{}; o.kind = OP_DUP; o.name = "cfg.dup";
-    o.p0 = ptr(a); o.p1 = cur.arena ? (char*)ptr(a) + (size_t)rows * a.ld * 2 : nullptr; o.i0 = rows; o.i1 = a.C; o.i2 = a.ld;
+    Op& o = emit(OP_DUP, "cfg.dup");
+    o.dup = DupRowsArgs{ptr(a), cur.arena ? (char*)ptr(a) + (size_t)rows * a.ld * 2 : nullptr, rows, a.C, a.ld};
     o.bytes = 2.0 * 2.0 * (double)rows * a.C;
     snprintf(o.klabel, sizeof(o.klabel), "dup_rows");
-    cur.ops.push_back(o);
 }
 
 void Engine::dup_second_half(const DupReq& d) {
-    static const bool copy_only = getenv("LDX_CFG_SHARE_COPY") && atoi(getenv("LDX_CFG_SHARE_COPY")) != 0;      // A/B switch: always the copy launch
-    if (!copy_only && d.producer < cur.ops.size()) {
+    if (!g_plan_sw.cfg_share_copy && d.producer < cur.ops.size()) {
         Op& o = cur.ops[d.producer];
         if (o.kind == OP_GEMM && o.g.C == ptr(d.a) && o.g.ldc == d.a.ld && o.g.M == d.rows && !o.g.geglu && !o.g.C8) { o.g.dup_rows = d.rows; return; }
         if (o.kind == OP_ROWGEMM && o.rg.Y == ptr(d.a) && o.rg.ldy == d.a.ld && o.rg.M == d.rows) { o.rg.dup_rows = d.rows; return; }
@@ -808,7 +796,7 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
         const char* kvb = (const char*)((uintptr_t)cur.arena + cur.kv_all_off) + (size_t)b.kv_off * 2;
         if (bp.xattn) {
             // LayerNorm + q projection + attention over the context + out projection + residual as ONE launch (xattn_block.hip)
-            Op o{}; o.kind = OP_XATTN; o.name = "xf.xattn2";
+            Op& o = emit(OP_XATTN, "xf.xattn2");
             XAttnArgs& xa = o.xa;
             xa.H = ptr(h); xa.ldh = h.ld; xa.M = M; xa.N = H * W; xa.C = C; xa.heads = heads; xa.ln_g = b.ln2.g; xa.ln_b = b.ln2.b; xa.eps = 1e-5f;
             xa.Wq = b.q2.w; xa.Wo = b.o2.w; xa.bo = b.o2.b; xa.K = kvb; xa.ldk = kv_total; xa.V = kvb + (size_t)C * 2; xa.ldv = kv_total; xa.Mk = Mc;
@@ -816,7 +804,6 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
             o.flops = 2.0 * 2.0 * M * (double)C * C + 4.0 * B * heads * (double)(H * W) * Mc * D;
             o.bytes = 2.0 * 2.0 * (double)M * C;
             snprintf(o.klabel, sizeof(o.klabel), "xattn_block<%s>", dt == DT_BF16 ? "bf16" : "f16");
-            cur.ops.push_back(o);
             cur.flops += o.flops;
         } else {
             Act q = new_act(M, C);
@@ -829,14 +816,13 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
         release(a);
         if (bp.ffblock) {
             // LayerNorm + GEGLU projection + down projection + residual as ONE launch (ff_block.hip): the [M][4C] activation never leaves the CUs
-            Op o{}; o.kind = OP_FFBLOCK; o.name = "xf.ffblock";
+            Op& o = emit(OP_FFBLOCK, "xf.ffblock");
             FFBlockArgs& fa = o.fb;
             fa.H = ptr(h); fa.ldh = h.ld; fa.M = M; fa.C = C; fa.inner = 4 * C; fa.ln_g = b.ln3.g; fa.ln_b = b.ln3.b; fa.eps = 1e-5f;
             fa.W1 = b.ff1.w; fa.b1 = b.ff1.b; fa.W2 = b.ff2.w; fa.b2 = b.ff2.b;
             o.flops = 2.0 * M * (double)C * (8.0 * C) + 2.0 * M * (double)C * (4.0 * C);
             o.bytes = 2.0 * 2.0 * (double)M * C;
             snprintf(o.klabel, sizeof(o.klabel), "ff_block<%s>", dt == DT_BF16 ? "bf16" : "f16");
-            cur.ops.push_back(o);
             cur.flops += o.flops;
         } else {
             Act f = new_act(M, 4 * C);
@@ -855,7 +841,7 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
 // c_concat), a model with a cross-attention for the prefix to end at, and enough rows per half that the prefix ops still fill the chip — below
 // LDX_CFG_SHARE_MINROWS (default 8192: 512^2 at bs = 1 has 4096 and measured 5.73 against 5.69 ms per step shared) nothing is shared.
 int Engine::share_for(int B2, int h, int w, int xB, bool denoise, bool concat) const {
-    static const long share_minrows = getenv("LDX_CFG_SHARE_MINROWS") ? atol(getenv("LDX_CFG_SHARE_MINROWS")) : 8192;
+    const long share_minrows = g_plan_sw.cfg_share_minrows;
     if (!cfg_share || !denoise || concat || xB <= 0 || B2 != 2 * xB || (cfg_share == 1 && (long)xB * h * w < share_minrows)) return 0;
     for (auto& blk : in_blocks) if (blk.has_xf) return xB;
     return 0;
@@ -893,15 +879,20 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
         auto skip_view = [&](int s) { const int k = n_skips - 1 - s; return view(cat[k], out_hch[k], in_ch[s]); };
 
         // ---- ops ----
-        Op po{}; po.kind = OP_PREP; po.name = "prep"; cur.ops.push_back(po);          // pointers filled per call
         Act xin = new_act(B2 * h * w, 64);
         cur.prep_xc_off = xin.off;
+        {
+            PrepArgs& p = emit(OP_PREP, "prep").prep;          // x, sigma / timesteps and c_concat are the call's
+            p.B = B2; p.C = cfg.in_channels; p.H = h; p.W = w; p.Cpad = 64; p.xc = ptr(xin);
+            p.log_sigmas = d_log_sigmas; p.n_sigmas = n_sigmas; p.temb_table = d_temb; p.temb_dim = mc; p.temb_out = cur.d_temb_out;
+            if (d_emb_table) { p.emb_table = d_emb_table; p.emb_n = emb_total; p.emb_out = cur.d_emb_all; }
+        }
         Act ctx16 = new_act(B2 * Mc, cfg.context_dim);
-        { Op o{}; o.kind = OP_CVT; o.name = "ctx.cvt"; o.cvt_out = ptr(ctx16); o.cvt_n = (size_t)B2 * Mc * cfg.context_dim; o.ctx_only = true; cur.ops.push_back(o); }
+        { Op& o = emit(OP_CVT, "ctx.cvt"); o.cvt = CvtArgs{nullptr, ptr(ctx16), (size_t)B2 * Mc * cfg.context_dim}; o.ctx_only = true; }
         if (!d_emb_table) {       // per-step time-embedding MLP (LDX_EMB_TABLE=0); otherwise the prep kernel gathers the timestep's row of the table
-            { Op o{}; o.kind = OP_SKINNY; o.name = "time_embed.0"; o.sk = SkinnyArgs{cur.d_temb_out, mc, te0.w, te0.b, cur.d_e1, ted, B2, ted, mc, 0, 1}; cur.ops.push_back(o); }
-            { Op o{}; o.kind = OP_SKINNY; o.name = "time_embed.2"; o.sk = SkinnyArgs{cur.d_e1, ted, te2.w, te2.b, cur.d_e2, ted, B2, ted, ted, 0, 1}; cur.ops.push_back(o); }
-            { Op o{}; o.kind = OP_SKINNY; o.name = "emb_layers"; o.sk = SkinnyArgs{cur.d_e2, ted, emb_all.w, emb_all.b, cur.d_emb_all, emb_total, B2, emb_total, ted, 0, 0}; cur.ops.push_back(o); }
+            emit(OP_SKINNY, "time_embed.0").sk = skinny_args(cur.d_temb_out, mc, te0.w, te0.b, cur.d_e1, ted, B2, ted, mc, 0, 1);
+            emit(OP_SKINNY, "time_embed.2").sk = skinny_args(cur.d_e1, ted, te2.w, te2.b, cur.d_e2, ted, B2, ted, ted, 0, 1);
+            emit(OP_SKINNY, "emb_layers").sk = skinny_args(cur.d_e2, ted, emb_all.w, emb_all.b, cur.d_emb_all, emb_total, B2, emb_total, ted, 0, 0);
             cur.flops += 2.0 * B2 * ((double)ted * mc + (double)ted * ted + (double)emb_total * ted);
         }
         Act kvall = new_act(B2 * Mc, kv_total);
@@ -1005,7 +996,7 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
             op_conv("out.conv", t, B2, h, w, mc, conv_out, 1, h, w, Act{}, Act{}, nullptr, 0, cur.d_eps, cfg.out_channels);
             release(t);
         }
-        { Op o{}; o.kind = OP_FINISH; o.name = "finish"; cur.ops.push_back(o); }
+        { FinishArgs& f = emit(OP_FINISH, "finish").fin; f.eps = cur.d_eps; f.ld = cfg.out_channels; f.B = B2; f.C = cfg.out_channels; f.HW = h * w; }          // x, sigma and out are the call's
         release(ctx16); release(kvall);
         // what the shared prefix saves: every op in front of the first hand-over copy ran on half the batch (the context-only ops are not part of it)
         if (share > 0) {
@@ -1021,8 +1012,7 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
 // The 22 emb_layers outputs for EVERY timestep of the table (ldx_set_tables), by the same three skinny launches a forward would run on its B2 rows:
 // row t of d_emb_table is bit-identical to what those launches write for a sample whose timestep index is t (the skinny kernel's rows are independent).
 int Engine::build_emb_table() {
-    static const bool off = getenv("LDX_EMB_TABLE") && atoi(getenv("LDX_EMB_TABLE")) == 0;
-    if (off || d_emb_table || !d_temb || n_sigmas <= 0 || emb_total <= 0 || emb_total % 4) return LDX_OK;
+    if (!g_plan_sw.emb_table || d_emb_table || !d_temb || n_sigmas <= 0 || emb_total <= 0 || emb_total % 4) return LDX_OK;
     const int mc = cfg.model_channels, ted = 4 * mc, n = n_sigmas;
     float *e1 = nullptr, *e2 = nullptr, *tab = nullptr;
     auto fail = [&](hipError_t err, const char* what) {       // nothing of a half-built table survives an error
@@ -1036,9 +1026,9 @@ int Engine::build_emb_table() {
     if ((err = hipMalloc((void**)&e1, (size_t)n * ted * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
     if ((err = hipMalloc((void**)&e2, (size_t)n * ted * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
     if ((err = hipMalloc((void**)&tab, (size_t)n * emb_total * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
-    launch_skinny(SkinnyArgs{d_temb, mc, te0.w, te0.b, e1, ted, n, ted, mc, 0, 1}, dt, nullptr);
-    launch_skinny(SkinnyArgs{e1, ted, te2.w, te2.b, e2, ted, n, ted, ted, 0, 1}, dt, nullptr);
-    launch_skinny(SkinnyArgs{e2, ted, emb_all.w, emb_all.b, tab, emb_total, n, emb_total, ted, 0, 0}, dt, nullptr);
+    launch_skinny(skinny_args(d_temb, mc, te0.w, te0.b, e1, ted, n, ted, mc, 0, 1), dt, nullptr);
+    launch_skinny(skinny_args(e1, ted, te2.w, te2.b, e2, ted, n, ted, ted, 0, 1), dt, nullptr);
+    launch_skinny(skinny_args(e2, ted, emb_all.w, emb_all.b, tab, emb_total, n, emb_total, ted, 0, 0), dt, nullptr);
     if ((err = hipStreamSynchronize(nullptr)) != hipSuccess) return fail(err, "build_emb_table: hipStreamSynchronize");
     if ((err = hipGetLastError()) != hipSuccess) return fail(err, "build_emb_table: kernel launch");
     (void)hipFree(e1); (void)hipFree(e2);
@@ -1104,7 +1094,7 @@ void Engine::plan_stash() {
     cur = Plan{};
     // every cached plan keeps its own arena resident: bound the cache by count (4) AND by bytes (LDX_PLAN_CACHE_GIB, default 16 GiB of
     // stashed arenas — a Flux plan per prompt length, a 2048^2 VAE plan of several GiB ...); oldest first, the newest entry always stays
-    static const size_t cap_bytes = (size_t)((getenv("LDX_PLAN_CACHE_GIB") ? atof(getenv("LDX_PLAN_CACHE_GIB")) : 16.0) * (double)(1ull << 30));
+    const size_t cap_bytes = (size_t)(g_plan_sw.plan_cache_gib * (double)(1ull << 30));
     auto cached_bytes = [&]() { size_t n = 0; for (const Plan& p : plan_cache) n += p.arena_cap; return n; };
     while (plan_cache.size() > 4 || (plan_cache.size() > 1 && cached_bytes() > cap_bytes)) {
         plan_cache.front().release();
@@ -1121,117 +1111,119 @@ bool Engine::plan_restore(const PlanKey& key) {
     return false;
 }
 
+// The op's launcher on its argument struct.  A case at most copies the struct and fills in what belongs to the call (bind).
+int Engine::launch_op(const Op& o, hipStream_t ls) {
+    switch (o.kind) {
+        case OP_PREP: {
+            PrepArgs p = o.prep;
+            p.x = bind.x; p.sigma = bind.s; p.scale_input = bind.den ? 1 : 0; p.t_in = bind.den ? bind.t : bind.s; p.xB = bind.xB;      // bind.t: indices from the caller (null: looked up from sigma on the device)
+            p.cc = bind.cc; p.Cx = p.C - bind.ccn;
+            launch_prep(p, dt, ls);
+        } break;
+        case OP_FINISH: { FinishArgs f = o.fin; f.x = bind.den ? bind.x : nullptr; f.sigma = bind.s; f.out = bind.out; f.xB = bind.xB; launch_finish(f, ls); } break;
+        case OP_CVT: { CvtArgs a = o.cvt; a.in = bind.ctx; launch_f32_to_t(a, dt, ls); } break;
+        case OP_CVT_OUT: { CvtOutArgs a = o.out; a.out = o.second_output ? bind.out2 : bind.out; if (a.out) launch_t_to_f32(a, dt, ls); } break;
+        case OP_COPY_OUT: { CopyOutArgs a = o.copy; a.dst = bind.out; HIP_OK(launch_copy_out(a, ls)); } break;
+        case OP_SKINNY: launch_skinny(o.sk, dt, ls); break;
+        case OP_FX_SKINNY_Y: { SkinnyArgs a = o.sk; a.x = bind.y; launch_skinny(a, dt, ls); } break;
+        case OP_GEMM: launch_gemm(o.g, dt, ls); break;
+        case OP_GEMM2: launch_gemm2(o.g, o.g2, dt, ls); break;
+        case OP_MXQ: launch_mx_quant(o.mq, dt, ls); break;
+        case OP_ATTN_MX: launch_attn_mx(o.am, dt, ls); break;
+        case OP_MXVT: launch_mx_vt_quant(o.vt, dt, ls); break;
+        case OP_XATTN: launch_xattn_block(o.xa, dt, ls); break;
+        case OP_FFBLOCK: launch_ff_block(o.fb, dt, ls); break;
+        case OP_ROWGEMM: launch_rowgemm(o.rg, dt, ls); break;
+        case OP_GN: launch_groupnorm(o.gn, dt, ls); break;
+        case OP_LN: launch_layernorm(o.ln, dt, ls); break;
+        case OP_ATTN: { AttnArgs a = o.at; if (o.bias_from_call) a.bias = bind.bias; launch_attention(a, dt, ls); } break;      // T5's relative-position table is the call's
+        case OP_VAEPREP: { VaePrepArgs a = o.vprep; a.z = bind.x; launch_vae_prep(a, dt, ls); } break;
+        case OP_PIXPREP: { PixelsPrepArgs a = o.pix; a.px = bind.x; launch_pixels_prep(a, dt, ls); } break;
+        case OP_SOFTMAX: launch_softmax_rows(o.sm, dt, ls); break;
+        case OP_CLAMP: { ClampArgs a = o.clamp; a.out = bind.out; launch_clamp01(a, ls); } break;
+        case OP_MOMENTS: { MixArgs a = o.mix; a.out = bind.out; launch_mix_nhwc_to_nchw(a, ls); } break;
+        case OP_EMBED: { ClipEmbedArgs a = o.emb; a.ids = bind.ids; a.extra = clip_extra; a.n_extra = clip_extra_n; launch_clip_embed(a, dt, ls); } break;      // the textual-inversion rows change between calls
+        case OP_DUP: launch_dup_rows(o.dup, dt, ls); break;
+        case OP_FX_TEMB: { FluxTembArgs a = o.temb; a.t = o.of_guidance ? bind.guid : bind.s; launch_flux_temb(a, ls); } break;
+        case OP_FX_SILU: launch_silu_f32(o.silu, ls); break;
+        case OP_FX_PATCH: { FluxPatchArgs a = o.patch; a.x = bind.x; launch_flux_patchify(a, dt, ls); } break;
+        case OP_FX_ROPE: { QkRopeArgs a = o.rp; const int hp = a.D / 2; a.cosT = bind.pe_cos + (size_t)o.tok0 * hp; a.sinT = bind.pe_sin + (size_t)o.tok0 * hp;
+                           if (a.Q8) launch_qk_norm_rope_mx(a, dt, ls); else launch_qk_norm_rope(a, dt, ls); } break;
+        case OP_FX_UNPATCH: { FluxUnpatchArgs a = o.unpatch; a.x = bind.den ? bind.x : nullptr; a.sigma = bind.s; a.out = bind.out; launch_flux_unpatchify(a, ls); } break;
+    }
+    return LDX_OK;
+}
+
+// LDX_DEBUG_NAN: after every GEMM with a 16-bit output, scan it on the host and report NaN / Inf (synchronises: never inside a stream capture)
+static void debug_scan_nan(const Op& o, size_t oi, DType dt, hipStream_t ls) {
+    (void)hipStreamSynchronize(ls);
+    const int Nout = o.g.geglu ? o.g.N / 2 : o.g.N;
+    std::vector<uint16_t> hb((size_t)o.g.M * o.g.ldc);
+    (void)hipMemcpy(hb.data(), o.g.C, ((size_t)(o.g.M - 1) * o.g.ldc + Nout) * 2, hipMemcpyDeviceToHost);
+    long bad = 0, first = -1;
+    for (long m = 0; m < o.g.M; ++m) for (int n = 0; n < Nout; ++n) {
+        const uint16_t v = hb[(size_t)m * o.g.ldc + n];
+        const bool b = dt == DT_BF16 ? ((v & 0x7f80) == 0x7f80) : ((v & 0x7c00) == 0x7c00);
+        if (b) { ++bad; if (first < 0) first = m * (long)Nout + n; }
+    }
+    fprintf(stderr, "[nan] op %zu %-14s M%d N%d K%d sk%d ln%d rs%d: %ld bad%s\n", oi, o.name, o.g.M, o.g.N, o.g.K, o.g.splitk, o.g.ln_c1 ? 1 : 0,
+            0, bad, bad ? (std::string(" first at row ") + std::to_string(first / Nout) + " col " + std::to_string(first % Nout)).c_str() : "");
+}
+
+std::string Engine::prof_key(const Op& o) const {
+    std::string key = o.klabel[0] ? o.klabel : o.name;
+    if (!prof_detail) return key;
+    char sh[96] = "";
+    if (o.kind == OP_GEMM) snprintf(sh, sizeof(sh), " M%d N%d K%d sk%d%s", o.g.M, o.g.N, o.g.K, o.g.splitk, o.g.geglu ? " geglu" : "");
+    else if (o.kind == OP_ATTN) snprintf(sh, sizeof(sh), " B%d H%d N%d M%d D%d", o.at.B, o.at.H, o.at.Nq, o.at.Mk, o.at.D);
+    else if (o.kind == OP_ATTN_MX) snprintf(sh, sizeof(sh), " B%d H%d N%d M%d D128", o.am.B, o.am.H, o.am.Nq, o.am.Mk);
+    else if (o.kind == OP_GN) snprintf(sh, sizeof(sh), " B%d HW%d C%d", o.gn.B, o.gn.HW, o.gn.C);
+    else if (o.kind == OP_ROWGEMM) snprintf(sh, sizeof(sh), " M%ld N%d K%d", o.rg.M, o.rg.N, o.rg.K);
+    else if (o.kind == OP_XATTN) snprintf(sh, sizeof(sh), " M%ld C%d", (long)o.xa.M, o.xa.C);
+    else if (o.kind == OP_FFBLOCK) snprintf(sh, sizeof(sh), " M%ld C%d", (long)o.fb.M, o.fb.C);
+    else if (o.kind == OP_LN) snprintf(sh, sizeof(sh), " R%d C%d", o.ln.rows, o.ln.C);
+    else if (o.kind == OP_MXQ) snprintf(sh, sizeof(sh), " R%d K%d", o.mq.rows, o.mq.K);
+    else if (o.kind == OP_GEMM2) snprintf(sh, sizeof(sh), " M%d+%d N%d K%d", o.g.M, o.g2.M, o.g.N, o.g.K);
+    return key + sh;
+}
+
 int Engine::exec_ops(hipStream_t ls, size_t op_begin, size_t op_end, int ctx_sel) {
     if (op_end > cur.ops.size()) op_end = cur.ops.size();
+    static const bool dbg_nan = getenv("LDX_DEBUG_NAN") != nullptr;          // debug: first GEMM whose 16-bit output holds a NaN / Inf
     const bool prof_now = profiling && !prof_graph;
     if (prof_now && prof_events.size() < 2 * cur.ops.size()) {
         const size_t old = prof_events.size();
         prof_events.resize(2 * cur.ops.size());
         for (size_t i = old; i < prof_events.size(); ++i) HIP_OK(hipEventCreate(&prof_events[i]));
     }
+    auto skipped = [&](const Op& o) { return (ctx_sel == 1 && o.ctx_only) || (ctx_sel == 2 && !o.ctx_only); };
     for (size_t oi = op_begin; oi < op_end; ++oi) {
         const Op& o = cur.ops[oi];
-        if ((ctx_sel == 1 && o.ctx_only) || (ctx_sel == 2 && !o.ctx_only)) continue;
+        if (skipped(o)) continue;
         if (prof_now) HIP_OK(hipEventRecord(prof_events[2 * oi], ls));
-        switch (o.kind) {
-            case OP_PREP: {
-                PrepArgs p{};
-                p.x = bind.x; p.sigma = bind.s; p.B = cur.key.B; p.C = cfg.in_channels; p.H = cur.key.h; p.W = cur.key.w; p.Cpad = 64;
-                p.xc = (char*)cur.arena + cur.prep_xc_off; p.log_sigmas = d_log_sigmas; p.n_sigmas = n_sigmas;
-                p.temb_table = d_temb; p.temb_dim = cfg.model_channels; p.temb_out = cur.d_temb_out; p.t_out = nullptr;
-                p.scale_input = bind.den ? 1 : 0; p.t_in = bind.den ? bind.t : bind.s; p.xB = bind.xB;      // bind.t: indices from the caller (null: looked up from sigma on the device)
-                p.cc = bind.cc; p.Cx = cfg.in_channels - bind.ccn;
-                if (kind == KIND_UNET && d_emb_table) { p.emb_table = d_emb_table; p.emb_n = emb_total; p.emb_out = cur.d_emb_all; }
-                launch_prep(p, dt, ls);
-            } break;
-            case OP_CVT: launch_f32_to_t(bind.ctx, o.cvt_out, o.cvt_n, dt, ls); break;
-            case OP_SKINNY: launch_skinny(o.sk, dt, ls); break;
-            case OP_GEMM: {
-                launch_gemm(o.g, dt, ls);
-                static const bool dbg_nan = getenv("LDX_DEBUG_NAN") != nullptr;          // debug: first GEMM whose 16-bit output holds a NaN / Inf
-                if (dbg_nan && o.g.C && !prof_graph) {           // never inside a stream capture (the scan synchronises)
-                    (void)hipStreamSynchronize(ls);
-                    const int Nout = o.g.geglu ? o.g.N / 2 : o.g.N;
-                    std::vector<uint16_t> hb((size_t)o.g.M * o.g.ldc);
-                    (void)hipMemcpy(hb.data(), o.g.C, ((size_t)(o.g.M - 1) * o.g.ldc + Nout) * 2, hipMemcpyDeviceToHost);
-                    long bad = 0, first = -1;
-                    for (long m = 0; m < o.g.M; ++m) for (int n = 0; n < Nout; ++n) {
-                        const uint16_t v = hb[(size_t)m * o.g.ldc + n];
-                        const bool b = dt == DT_BF16 ? ((v & 0x7f80) == 0x7f80) : ((v & 0x7c00) == 0x7c00);
-                        if (b) { ++bad; if (first < 0) first = m * (long)Nout + n; }
-                    }
-                    fprintf(stderr, "[nan] op %zu %-14s M%d N%d K%d sk%d ln%d rs%d: %ld bad%s\n", oi, o.name, o.g.M, o.g.N, o.g.K, o.g.splitk, o.g.ln_c1 ? 1 : 0,
-                            0, bad, bad ? (std::string(" first at row ") + std::to_string(first / Nout) + " col " + std::to_string(first % Nout)).c_str() : "");
-                }
-            } break;
-            case OP_MXQ: launch_mx_quant(o.mq, dt, ls); break;
-            case OP_ATTN_MX: launch_attn_mx(o.am, dt, ls); break;
-            case OP_MXVT: launch_mx_vt_quant(o.vt, dt, ls); break;
-            case OP_GEMM2: launch_gemm2(o.g, o.g2, dt, ls); break;
-            case OP_XATTN: launch_xattn_block(o.xa, dt, ls); break;
-            case OP_FFBLOCK: launch_ff_block(o.fb, dt, ls); break;
-            case OP_ROWGEMM: launch_rowgemm(o.rg, dt, ls); break;
-            case OP_GN: launch_groupnorm(o.gn, dt, ls); break;
-            case OP_LN: launch_layernorm(o.ln, dt, ls); break;
-            case OP_ATTN:
-                if (o.i3 == 1) { AttnArgs a = o.at; a.bias = bind.bias; launch_attention(a, dt, ls); }      // per-call bias table (T5)
-                else launch_attention(o.at, dt, ls);
-                break;
-            case OP_FINISH: {
-                FinishArgs f{};
-                f.eps = cur.d_eps; f.ld = cfg.out_channels; f.x = bind.den ? bind.x : nullptr; f.sigma = bind.s; f.out = bind.out;
-                f.B = cur.key.B; f.C = cfg.out_channels; f.HW = cur.key.h * cur.key.w; f.xB = bind.xB;
-                launch_finish(f, ls);
-            } break;
-            case OP_VAEPREP: launch_vae_prep(bind.x, o.p1, o.i0, o.i1, o.i2, o.i3, vae_pq, vae_pq ? vae_pq + o.i1 * o.i1 : nullptr, dt, ls); break;
-            case OP_SOFTMAX: launch_softmax_rows(o.p1, o.i0, o.i1, o.i2, o.f0, dt, ls); break;
-            case OP_CLAMP: launch_clamp01((const float*)o.p0, bind.out, (size_t)o.i0, ls); break;
-            case OP_EMBED: launch_clip_embed(bind.ids, kind == KIND_T5 ? t5_tok : clip_tok, kind == KIND_T5 ? nullptr : clip_pos, o.p1, o.i0, o.i1, o.i2, o.i3,
-                                              kind == KIND_T5 ? nullptr : clip_extra, kind == KIND_T5 ? 0 : clip_extra_n, dt, ls); break;
-            case OP_CVT_OUT: if ((o.i3 ? bind.out2 : bind.out) != nullptr) launch_t_to_f32(o.p0, o.i3 ? bind.out2 : bind.out, (size_t)o.i0, dt, ls); break;
-            case OP_PIXPREP: launch_pixels_prep(bind.x, o.p1, o.i0, o.i1, o.i2, o.i3, o.f0, o.f1, dt, ls); break;
-            case OP_COPY_OUT: HIP_OK(hipMemcpyAsync(bind.out, o.p0, (size_t)o.cvt_n, hipMemcpyDeviceToDevice, ls)); break;
-            case OP_MOMENTS: launch_mix_nhwc_to_nchw((const float*)o.p0, o.i1, bind.out, o.i0, o.i1, o.i2, enc_qc, enc_qc ? enc_qc + o.i1 * o.i1 : nullptr, ls); break;
-            case OP_DUP: launch_dup_rows(o.p0, o.p1, o.i0, o.i1, o.i2, dt, ls); break;
-            case OP_FX_TEMB: launch_flux_temb(o.i0 ? bind.guid : bind.s, (float*)o.p1, cur.key.B, 256, 1000.0f, ls); break;
-            case OP_FX_SILU: launch_silu_f32((const float*)o.p0, (float*)o.p1, (size_t)o.i0, ls); break;
-            case OP_FX_PATCH: launch_flux_patchify(bind.x, o.p1, o.i0, o.i1, o.i2, o.i3, dt, ls); break;
-            case OP_FX_CVT_CTX: launch_f32_to_t(bind.ctx, o.cvt_out, o.cvt_n, dt, ls); break;
-            case OP_FX_SKINNY_Y: { SkinnyArgs a = o.sk; a.x = bind.y; launch_skinny(a, dt, ls); } break;
-            case OP_FX_SKINNY_G: break;
-            case OP_FX_ROPE: { QkRopeArgs a = o.rp; const int hp = a.D / 2; a.cosT = bind.pe_cos + (size_t)o.i0 * hp; a.sinT = bind.pe_sin + (size_t)o.i0 * hp;
-                               if (a.Q8) launch_qk_norm_rope_mx(a, dt, ls); else launch_qk_norm_rope(a, dt, ls); } break;
-            case OP_FX_UNPATCH: launch_flux_unpatchify(cur.fx_tok, 4 * o.i1, bind.den ? bind.x : nullptr, bind.s, bind.out, o.i0, o.i1, o.i2, o.i3, ls); break;
-        }
+        if (int rc = launch_op(o, ls)) return rc;
+        if (dbg_nan && o.kind == OP_GEMM && o.g.C && !prof_graph) debug_scan_nan(o, oi, dt, ls);
         if (prof_now) HIP_OK(hipEventRecord(prof_events[2 * oi + 1], ls));
     }
     if (prof_now) {
         HIP_OK(hipStreamSynchronize(ls));
         for (size_t i = op_begin; i < op_end; ++i) {
-            float ms = 0.f;
-            if ((ctx_sel == 1 && cur.ops[i].ctx_only) || (ctx_sel == 2 && !cur.ops[i].ctx_only)) continue;
-            HIP_OK(hipEventElapsedTime(&ms, prof_events[2 * i], prof_events[2 * i + 1]));
             const Op& o = cur.ops[i];
-            std::string key = o.klabel[0] ? o.klabel : o.name;
-            if (prof_detail) {
-                char sh[96] = "";
-                if (o.kind == OP_GEMM) snprintf(sh, sizeof(sh), " M%d N%d K%d sk%d%s", o.g.M, o.g.N, o.g.K, o.g.splitk, o.g.geglu ? " geglu" : "");
-                else if (o.kind == OP_ATTN) snprintf(sh, sizeof(sh), " B%d H%d N%d M%d D%d", o.at.B, o.at.H, o.at.Nq, o.at.Mk, o.at.D);
-                else if (o.kind == OP_ATTN_MX) snprintf(sh, sizeof(sh), " B%d H%d N%d M%d D128", o.am.B, o.am.H, o.am.Nq, o.am.Mk);
-                else if (o.kind == OP_GN) snprintf(sh, sizeof(sh), " B%d HW%d C%d", o.gn.B, o.gn.HW, o.gn.C);
-                else if (o.kind == OP_ROWGEMM) snprintf(sh, sizeof(sh), " M%ld N%d K%d", o.rg.M, o.rg.N, o.rg.K);
-                else if (o.kind == OP_XATTN) snprintf(sh, sizeof(sh), " M%ld C%d", (long)o.xa.M, o.xa.C);
-                else if (o.kind == OP_FFBLOCK) snprintf(sh, sizeof(sh), " M%ld C%d", (long)o.fb.M, o.fb.C);
-                else if (o.kind == OP_LN) snprintf(sh, sizeof(sh), " R%d C%d", o.ln.rows, o.ln.C);
-                else if (o.kind == OP_MXQ) snprintf(sh, sizeof(sh), " R%d K%d", o.mq.rows, o.mq.K);
-                else if (o.kind == OP_GEMM2) snprintf(sh, sizeof(sh), " M%d+%d N%d K%d", o.g.M, o.g2.M, o.g.N, o.g.K);
-                key += sh;
-            }
-            ProfEntry& pe = prof[key];
+            if (skipped(o)) continue;
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, prof_events[2 * i], prof_events[2 * i + 1]));
+            ProfEntry& pe = prof[prof_key(o)];
             pe.count += 1; pe.ms += ms; pe.flops += o.flops; pe.bytes += o.bytes;
         }
     }
     return LDX_OK;
+}
+
+int Engine::run_planned(const PlanKey& key, const std::function<int()>& replan, const Bindings& b, hipStream_t st) {
+    if (int rc = select_plan(key, st, replan)) return rc;
+    bind = b; prof_graph = false;
+    if (int rc = exec_ops(st)) return rc;
+    return launch_status();
 }
 
 int Engine::run_cfg(const float* x, float sigma, const float* ctx, int B, int h, int w, int Mc, float* out, hipStream_t st, int t_index) {

@@ -1,5 +1,6 @@
 // Internal declarations of the ldx UNet engine (see engine.cpp).
 #pragma once
+#include <cstring>
 #include <functional>
 #include <initializer_list>
 #include <map>
@@ -16,6 +17,15 @@ namespace ldx {
 extern thread_local std::string g_last_error;
 void set_error(const std::string& s);
 int launch_status();          // LDX_EHIP (and the error text) when a kernel launch since the last check failed
+// inside a function that returns an LDX_* code: leave with LDX_EHIP (and the error text) when a HIP call fails
+#define HIP_OK(expr)                                                                         \
+    do {                                                                                     \
+        hipError_t _e = (expr);                                                              \
+        if (_e != hipSuccess) {                                                              \
+            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                    \
+            return LDX_EHIP;                                                                 \
+        }                                                                                    \
+    } while (0)
 
 struct HostTensor {
     int dtype = LDX_F32;
@@ -44,15 +54,21 @@ struct Act { bool valid = false; bool owned = false; size_t off = 0; int rows = 
 enum OpKind { OP_PREP, OP_CVT, OP_SKINNY, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_FINISH,
               OP_VAEPREP, OP_SOFTMAX, OP_CLAMP, OP_EMBED, OP_CVT_OUT,
               OP_PIXPREP, OP_MOMENTS, OP_COPY_OUT,
-              OP_FX_PATCH, OP_FX_TEMB, OP_FX_SILU, OP_FX_ROPE, OP_FX_UNPATCH, OP_FX_CVT_CTX, OP_FX_SKINNY_Y, OP_FX_SKINNY_G, OP_MXQ, OP_GEMM2, OP_XATTN, OP_FFBLOCK, OP_ROWGEMM, OP_ATTN_MX, OP_MXVT, OP_DUP };
+              OP_FX_PATCH, OP_FX_TEMB, OP_FX_SILU, OP_FX_ROPE, OP_FX_UNPATCH, OP_FX_SKINNY_Y, OP_MXQ, OP_GEMM2, OP_XATTN, OP_FFBLOCK, OP_ROWGEMM, OP_ATTN_MX, OP_MXVT, OP_DUP };
 enum EngineKind { KIND_UNET = 0, KIND_VAE = 1, KIND_CLIP = 2, KIND_FLUX = 3, KIND_T5 = 4, KIND_ESRGAN = 5 };
+// One launch of a plan.  The rule: every kind has ONE argument struct (ldx_kernels.h, beside its launcher), filled by the planner, and Engine::launch_op hands it to
+// that launcher after filling in the pointers of the call (Bindings).  Nothing here has a meaning that depends on `kind`.
 struct Op {
     OpKind kind; const char* name;
     GemmArgs g; GemmArgs g2; GroupNormArgs gn; LayerNormArgs ln; AttnArgs at; SkinnyArgs sk; QkRopeArgs rp; MxQuantArgs mq; XAttnArgs xa; FFBlockArgs fb; RowGemmArgs rg; AttnMxArgs am; MxVtArgs vt;
-    void* cvt_out; size_t cvt_n;
-    bool ctx_only = false;         // depends on the context alone (16-bit copy of ctx, the batched k|v projection): skipped while Engine::ctx_cache holds
-    // generic slots for the small ops: src/dst pointers + dims
-    const void* p0; void* p1; int i0, i1, i2, i3; float f0, f1;
+    PrepArgs prep; FinishArgs fin; CvtArgs cvt; CvtOutArgs out; CopyOutArgs copy; VaePrepArgs vprep; PixelsPrepArgs pix; ClampArgs clamp; SoftmaxArgs sm; ClipEmbedArgs emb; MixArgs mix; DupRowsArgs dup;
+    FluxTembArgs temb; SiluArgs silu; FluxPatchArgs patch; FluxUnpatchArgs unpatch;
+    bool ctx_only;                 // depends on the context alone (16-bit copy of ctx, the batched k|v projection): skipped while Engine::ctx_cache holds
+    // which of the call's buffers (Bindings) launch_op binds, where the kind alone does not say
+    bool bias_from_call;           // the attention's score bias table is the call's (T5)
+    bool second_output;            // the converted result goes to the call's optional second output (CLIP's intermediate layer)
+    bool of_guidance;              // the embedded scalar is the call's guidance, not its sigma (Flux)
+    int tok0;                      // first token of the rope op's rows in the call's rotary tables
     double flops; double bytes; char klabel[48];
 };
 struct ProfEntry { long count = 0; double ms = 0, flops = 0, bytes = 0; };
@@ -104,6 +120,13 @@ struct Plan {
     int fb_B = 0, fb_L = 0, fb_Lt = 0, fb_C = 0; size_t fb_a_end = 0, fb_b_end = 0;
     void release();                        // the arena and the graph
 };
+
+// SkinnyArgs with every byte defined, the padding too (the plan recorder, tests/tools/plan_trace.py, compares launch arguments byte for byte)
+inline SkinnyArgs skinny_args(const float* x, int ldx, const void* W, const float* bias, float* out, int ldo, int M, int N, int K, int in_act, int out_act, int accum = 0) {
+    SkinnyArgs a; memset(&a, 0, sizeof(a));
+    a.x = x; a.ldx = ldx; a.W = W; a.bias = bias; a.out = out; a.ldo = ldo; a.M = M; a.N = N; a.K = K; a.in_act = in_act; a.out_act = out_act; a.accum = accum;
+    return a;
+}
 
 struct EmbSrc { const HostTensor* w; const HostTensor* b; int n; };
 
@@ -226,6 +249,11 @@ private:
     bool mk_xf(const std::string& pre, int C, int depth, XfW& x);
 
     int exec_ops(hipStream_t ls, size_t op_begin = 0, size_t op_end = (size_t)-1, int ctx_sel = 0);      // ctx_sel: 0 all ops, 1 skip ctx_only ops, 2 ONLY ctx_only ops
+    int launch_op(const Op& o, hipStream_t ls);           // the op's launcher on its argument struct, with this call's pointers (bind) filled in
+    std::string prof_key(const Op& o) const;              // profile label of an op (prof_detail: with its shape)
+    // the common tail of the calls that keep one plan and run it whole: make the plan of `key` current, bind the call's buffers, launch
+    int run_planned(const PlanKey& key, const std::function<int()>& replan, const Bindings& b, hipStream_t st);
+    Op& emit(OpKind kind, const char* name);              // appends a zeroed op to the plan being built; the reference holds until the next emit
     // GroupNorm workspace: gn_ws_rows producer rows per image + GN_FOLD folded rows, x 32 groups x 2 floats (ldx_kernels.h gn_workspace_rows)
     int gn_ws_rows = 256;
     size_t gn_ws_bytes(int B, long HWmax) { gn_ws_rows = (int)gn_workspace_rows(HWmax); return (size_t)B * (gn_ws_rows + GN_FOLD) * 32 * 2 * 4; }

@@ -11,15 +11,6 @@
 
 namespace ldx {
 
-#define HIP_OK(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) {                                                              \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                    \
-            return LDX_EHIP;                                                                 \
-        }                                                                                    \
-    } while (0)
-
 Engine::Engine(const ldx_esrgan_config& c, int dev) : cfg{}, device(dev) {
     kind = KIND_ESRGAN; ecfg = c;
     dt = (c.compute_dtype == LDX_F16) ? DT_F16 : DT_BF16;
@@ -71,7 +62,7 @@ int Engine::plan_esrgan(int B, int H, int W) {
             if (g.splitk > 1) g.splitk = 1;
         };
         Act x0 = new_act(M, 64);
-        { Op o{}; o.kind = OP_PIXPREP; o.name = "esrgan.prep"; o.p1 = ptr(x0); o.i0 = B; o.i1 = c.in_nc; o.i2 = H * W; o.i3 = 64; o.f0 = 1.0f; o.f1 = 0.0f; cur.ops.push_back(o); }
+        emit(OP_PIXPREP, "esrgan.prep").pix = PixelsPrepArgs{nullptr, ptr(x0), B, c.in_nc, H * W, 64, 1.0f, 0.0f};      // the pixels are the call's
         Act fea = new_act(M, nf);
         Act cat[3] = {new_act(M, CW), new_act(M, CW), new_act(M, CW)};
         conv("esrgan.conv_first", x0, 64, es_first, H, W, H, W, fea, Act{}, 0);
@@ -111,7 +102,7 @@ int Engine::plan_esrgan(int B, int H, int W) {
         float* pix = (float*)((uintptr_t)cur.arena + o_pix);
         op_conv("esrgan.conv_last", hr, B, h, w, nf, es_last, 1, h, w, Act{}, Act{}, nullptr, 0, pix, c.out_nc);
         release(hr);
-        { Op o{}; o.kind = OP_COPY_OUT; o.name = "esrgan.out"; o.p0 = pix; o.cvt_n = (size_t)B * h * w * c.out_nc * 4; cur.ops.push_back(o); }
+        emit(OP_COPY_OUT, "esrgan.out").copy = CopyOutArgs{pix, nullptr, (size_t)B * h * w * c.out_nc * 4};
         return LDX_OK;
     }, true);
 }
@@ -120,10 +111,8 @@ int Engine::run_esrgan(const float* px, int B, int H, int W, float* out, hipStre
     if (!finalized || kind != KIND_ESRGAN) { set_error("ldx_esrgan_forward: not a finalized ESRGAN engine"); return LDX_ESTATE; }
     if (!px || !out || B <= 0 || H <= 0 || W <= 0) { set_error("ldx_esrgan_forward: bad argument"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
-    if (int rc = select_plan(PlanKey{B, H, W}, st, [&] { return plan_esrgan(B, H, W); })) return rc;
-    bind = Bindings{}; bind.x = px; bind.out = out; prof_graph = false;
-    if (int rc = exec_ops(st)) return rc;
-    return launch_status();
+    Bindings b; b.x = px; b.out = out;
+    return run_planned(PlanKey{B, H, W}, [&] { return plan_esrgan(B, H, W); }, b, st);
 }
 
 }  // namespace ldx

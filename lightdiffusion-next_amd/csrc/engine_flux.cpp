@@ -18,15 +18,6 @@
 
 namespace ldx {
 
-#define HIP_OK(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) {                                                              \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                    \
-            return LDX_EHIP;                                                                 \
-        }                                                                                    \
-    } while (0)
-
 Engine::Engine(const ldx_flux_config& c, int dev) : cfg{}, device(dev) {
     kind = KIND_FLUX; fcfg = c;
     dt = (c.compute_dtype == LDX_F16) ? DT_F16 : DT_BF16;
@@ -120,8 +111,7 @@ int Engine::finalize_flux() {
         for (FluxDoubleW& d : fx_double)
             for (FluxStreamW* s : {&d.img, &d.txt}) q = q && mx_quantize_weight(s->qkv) && mx_quantize_weight(s->proj) && mx_quantize_weight(s->mlp0) && mx_quantize_weight(s->mlp2);
         for (FluxSingleW& s : fx_single) q = q && mx_quantize_weight(s.lin1_qkv) && mx_quantize_weight(s.lin1_mlp) && mx_quantize_weight(s.lin2);
-        static const bool mod8 = !(getenv("LDX_FLUX_MOD_FP8") && atoi(getenv("LDX_FLUX_MOD_FP8")) == 0);      // round 6: the batched adaLN modulation projections too (6.4 -> 3.2 GB streamed per forward)
-        if (mod8) q = q && mx_quantize_weight(fx_mod_all);
+        if (g_plan_sw.flux_mod_fp8) q = q && mx_quantize_weight(fx_mod_all);
         if (!q || hipDeviceSynchronize() != hipSuccess) { set_error(std::string("MX weight quantisation failed: ") + hipGetErrorString(hipGetLastError())); return LDX_EHIP; }
     }
     finalized = true;
@@ -136,7 +126,9 @@ bool Engine::mx_quantize_weight(LinearW& w) {
     if (hipMalloc(&sw, (size_t)(w.K / 128) * w.N * 4) != hipSuccess) return false;
     dev_allocs.push_back(sw);
     weight_bytes += (size_t)w.N * w.K + (size_t)(w.K / 128) * w.N * 4;
-    MxQuantArgs a{w.w, w.K, w.N, w.K, w8, w.K, (uint32_t*)sw, w.N};
+    MxQuantArgs a;
+    memset(&a, 0, sizeof(a));          // the padding too: the plan recorder compares launch arguments byte for byte
+    a.X = w.w; a.ldx = w.K; a.rows = w.N; a.K = w.K; a.Y = w8; a.ldy = w.K; a.S = (uint32_t*)sw; a.s_ld = w.N;
     launch_mx_quant(a, dt, nullptr);
     w.w8 = w8; w.sw = (uint32_t*)sw;
     return hipGetLastError() == hipSuccess;
@@ -155,30 +147,30 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
         cur.fb_first = f32buf((size_t)B * Li * C); cur.fb_res = f32buf((size_t)B * L * C); cur.fb_part = f32buf(2 * 1024 + 8);
         { const size_t o0 = a_alloc((size_t)B * L * C * 2), o1 = a_alloc((size_t)B * L * C * 2); cur.fb_s0 = (void*)((uintptr_t)cur.arena + o0); cur.fb_s1 = (void*)((uintptr_t)cur.arena + o1); }
         auto skinny = [&](const char* name, OpKind kind, const float* x, int ldx_, const LinearW& lw, float* out, int out_act, int accum) {
-            Op o{}; o.kind = kind; o.name = name; o.sk = SkinnyArgs{x, ldx_, lw.w, lw.b, out, lw.N, B, lw.N, lw.K, 0, out_act, accum}; cur.ops.push_back(o);
+            emit(kind, name).sk = skinny_args(x, ldx_, lw.w, lw.b, out, lw.N, B, lw.N, lw.K, 0, out_act, accum);
             cur.flops += 2.0 * B * (double)lw.N * lw.K;
         };
         // vec = time_in(temb(t)) + guidance_in(temb(g)) + vector_in(y)           (Flux.py:683-696)
-        { Op o{}; o.kind = OP_FX_TEMB; o.name = "fx.temb_t"; o.p1 = cur.fx_temb; o.i0 = 0; cur.ops.push_back(o); }
+        emit(OP_FX_TEMB, "fx.temb_t").temb = FluxTembArgs{nullptr, cur.fx_temb, B, 256, 1000.0f};
         skinny("fx.time_in.0", OP_SKINNY, cur.fx_temb, 256, fx_time0, cur.fx_h1, 1, 0);
         skinny("fx.time_in.1", OP_SKINNY, cur.fx_h1, C, fx_time1, cur.fx_vec, 0, 0);
         if (f.guidance_embed) {
-            { Op o{}; o.kind = OP_FX_TEMB; o.name = "fx.temb_g"; o.p1 = cur.fx_gemb; o.i0 = 1; cur.ops.push_back(o); }
+            { Op& o = emit(OP_FX_TEMB, "fx.temb_g"); o.temb = FluxTembArgs{nullptr, cur.fx_gemb, B, 256, 1000.0f}; o.of_guidance = true; }
             skinny("fx.guidance_in.0", OP_SKINNY, cur.fx_gemb, 256, fx_gd0, cur.fx_h1, 1, 0);
             skinny("fx.guidance_in.1", OP_SKINNY, cur.fx_h1, C, fx_gd1, cur.fx_vec, 0, 1);
         }
         skinny("fx.vector_in.0", OP_FX_SKINNY_Y, nullptr, f.vec_in_dim, fx_vec0, cur.fx_h1, 1, 0);      // x bound per call (y)
         skinny("fx.vector_in.1", OP_SKINNY, cur.fx_h1, C, fx_vec1, cur.fx_vec, 0, 1);
-        { Op o{}; o.kind = OP_FX_SILU; o.name = "fx.silu_vec"; o.p0 = cur.fx_vec; o.p1 = cur.fx_svec; o.i0 = B * C; cur.ops.push_back(o); }
+        emit(OP_FX_SILU, "fx.silu_vec").silu = SiluArgs{cur.fx_vec, cur.fx_svec, (size_t)(B * C)};
         skinny("fx.modulation_all", OP_SKINNY, cur.fx_svec, C, fx_mod_all, cur.fx_mod, 0, 0);
         if (fx_fp8 && fx_mod_all.w8) { SkinnyArgs& k = cur.ops.back().sk; k.W8 = fx_mod_all.w8; k.SW = fx_mod_all.sw; k.sw_ld = fx_mod_all.N; }
 
         // joint token buffer and inputs
         Act X = new_act(B * L, C);
         Act ptok = new_act(B * Li, inC);
-        { Op o{}; o.kind = OP_FX_PATCH; o.name = "fx.patchify"; o.p1 = ptr(ptok); o.i0 = B; o.i1 = f.in_channels; o.i2 = h; o.i3 = w; cur.ops.push_back(o); }
+        emit(OP_FX_PATCH, "fx.patchify").patch = FluxPatchArgs{nullptr, ptr(ptok), B, f.in_channels, h, w};
         Act ctx16 = new_act(B * Lt, f.context_in_dim);
-        { Op o{}; o.kind = OP_FX_CVT_CTX; o.name = "fx.ctx.cvt"; o.cvt_out = ptr(ctx16); o.cvt_n = (size_t)B * Lt * f.context_in_dim; cur.ops.push_back(o); }
+        emit(OP_CVT, "fx.ctx.cvt").cvt = CvtArgs{nullptr, ptr(ctx16), (size_t)B * Lt * f.context_in_dim};
         auto rows = [&](const Act& t, int r0, int nr) { Act v = t; v.owned = false; v.off = t.off + (size_t)r0 * t.ld * 2; v.rows = nr; return v; };
         auto img_rows = [&](const Act& t, int b) { return rows(t, b * L + Lt, Li); };
         auto txt_rows = [&](const Act& t, int b) { return rows(t, b * L, Lt); };
@@ -191,7 +183,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
         // MX fp8 mode: an activation that feeds block linears gets an e4m3 shadow [B*L][K] + E8M0 scales [K/128][B*L], filled by
         // a quantise op in front of its consumers; the consumers then run the block-scaled MFMA GEMM on (shadow, MX weight).
         struct Q8 { char* y = nullptr; uint32_t* s = nullptr; int K = 0; };
-        static const int fuse_mask = getenv("LDX_MX_FUSE") ? atoi(getenv("LDX_MX_FUSE")) : 7;      // experiment switch: 1 GEMM epilogue, 2 attention, 4 LayerNorm
+        const int fuse_mask = g_plan_sw.mx_fuse;      // experiment switch: 1 GEMM epilogue, 2 attention, 4 LayerNorm
         const bool fuse_gemm_q = fuse_mask & 1;
         const int RT = B * L;                                   // rows of every joint buffer = scale-array row stride
         auto new_q8 = [&](int K) { Q8 q; q.K = K; const size_t o8 = a_alloc((size_t)RT * K), os = a_alloc((size_t)(K / 128) * RT * 4);
@@ -199,20 +191,18 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
         auto row_of = [&](const Act& base, const Act& v) { return (int)((v.off - base.off) / ((size_t)base.ld * 2)); };
         // qo != null: the output goes to the MX shadow of the buffer Y lives in (returns true), not to Y
         auto ln_mod = [&](const char* name, Act Xin, Act Y, const float* shift, const float* scale, int rpb, const Q8* qo = nullptr, const Act* obase = nullptr) {
-            Op o{}; o.kind = OP_LN; o.name = name;
+            Op& o = emit(OP_LN, name);
             LayerNormArgs& l = o.ln;
             l.X = ptr(Xin); l.ldx = Xin.ld; l.Y = ptr(Y); l.ldy = Y.ld; l.rows = Xin.rows; l.C = C; l.eps = 1e-6f; l.gamma = nullptr; l.beta = nullptr;
             l.scale = scale; l.shift = shift; l.mod_ld = fx_mod_total; l.rows_per_batch = rpb;
             o.bytes = 2.0 * 2.0 * (double)Xin.rows * C; snprintf(o.klabel, sizeof(o.klabel), "ln_kernel");
             const bool fused = fx_fp8 && qo && (fuse_mask & 4);
             if (fused) { const int ro = row_of(*obase, Y); l.Y8 = qo->y + (size_t)ro * qo->K; l.ldy8 = qo->K; l.S8 = qo->s + ro; l.s8_ld = RT; }
-            cur.ops.push_back(o);
             return fused;
         };
         // MX fp8 attention (ldx_flux_set_fp8 mode 1, head dim 128; attn_mx.hip): the QKNorm + RoPE op writes q / k as MX fp8 (+ one scale dword per (row, head)) instead
         // of 16 bit, a transposing quantiser turns v into V^T bytes in the MFMA's key order, and the attention op runs both products on the block-scaled MFMA.
-        static const bool attn8_env = !(getenv("LDX_FLUX_FP8_ATTN") && atoi(getenv("LDX_FLUX_FP8_ATTN")) == 0);      // A/B switch
-        const bool attn8 = fx_fp8 && fx_fp8_attn && attn8_env && D == 128;
+        const bool attn8 = fx_fp8 && fx_fp8_attn && g_plan_sw.flux_fp8_attn && D == 128;      // LDX_FLUX_FP8_ATTN=0: A/B switch
         const int Lp = (L + 127) / 128 * 128;
         char *a8_q = nullptr, *a8_k = nullptr, *a8_vt = nullptr; uint32_t *a8_sq = nullptr, *a8_sk = nullptr, *a8_sv = nullptr;
         if (attn8) {
@@ -221,27 +211,24 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
             a8_sq = (uint32_t*)al((size_t)H * RT * 4); a8_sk = (uint32_t*)al((size_t)H * RT * 4); a8_sv = (uint32_t*)al((size_t)B * H * (Lp / 128) * 128 * 4);
         }
         auto rope = [&](const char* name, Act QKV, const float* qs, const float* ks, int tok0, const Act* qkv_base = nullptr) {
-            Op o{}; o.kind = OP_FX_ROPE; o.name = name;
+            Op& o = emit(OP_FX_ROPE, name);
             o.rp = QkRopeArgs{ptr(QKV), QKV.ld, QKV.rows, L, H, D, qs, ks, nullptr, nullptr, 1e-6f};
             if (attn8 && qkv_base) {
                 o.rp.Q8 = a8_q; o.rp.K8 = a8_k; o.rp.ld8 = C; o.rp.SQ = a8_sq; o.rp.SK = a8_sk; o.rp.s8_ld = RT; o.rp.row8 = row_of(*qkv_base, QKV);
                 snprintf(o.klabel, sizeof(o.klabel), "qk_norm_rope_mx");
             }
-            o.i0 = tok0;                                 // first token index of this slice in the pe tables
-            cur.ops.push_back(o);
+            o.tok0 = tok0;                               // first token index of this slice in the pe tables
         };
         auto vt_quant = [&](const char* name, Act QKVb, int b) {          // QKVb: the L rows of batch b
-            Op o{}; o.kind = OP_MXVT; o.name = name;
+            Op& o = emit(OP_MXVT, name);
             o.vt = MxVtArgs{(const char*)ptr(QKVb) + (size_t)2 * C * 2, QKVb.ld, 1, H, L, a8_vt + (size_t)b * H * 128 * Lp, a8_sv + (size_t)b * H * (Lp / 128) * 128, Lp};
             o.bytes = 3.0 * (double)L * C; snprintf(o.klabel, sizeof(o.klabel), "mx_vt_quant_kernel");
-            cur.ops.push_back(o);
         };
         auto quant = [&](const char* name, const Act& base, const Act& v, const Q8& q, int ncols = 0) {      // v: a row slice of base; its first ncols columns (0 = all)
-            Op o{}; o.kind = OP_MXQ; o.name = name;
+            Op& o = emit(OP_MXQ, name);
             const int r0 = row_of(base, v), K = ncols ? ncols : q.K;
             o.mq = MxQuantArgs{ptr(v), v.ld, v.rows, K, q.y + (size_t)r0 * q.K, q.K, q.s + r0, RT};
             o.bytes = 3.0 * (double)v.rows * K; snprintf(o.klabel, sizeof(o.klabel), "mx_quant_kernel");
-            cur.ops.push_back(o);
         };
         // linear on the rows of `v` (a row slice of `base`): 16-bit path, or MX path reading base's shadow q
         // qo != null (MX mode, no gate / residual): the output goes straight to the shadow qo of the buffer Cc lives in, at
@@ -267,7 +254,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
             }
         };
         // merge the two independent plain GEMM ops just emitted into one two-problem launch
-        static const bool group2 = !(getenv("LDX_FLUX_GROUP") && atoi(getenv("LDX_FLUX_GROUP")) == 0);      // experiment switch
+        const bool group2 = g_plan_sw.flux_group;      // LDX_FLUX_GROUP=0: experiment switch
         auto pair_last_two = [&](const char* name) {
             if (!group2 || cur.ops.size() < 2) return;
             Op& A = cur.ops[cur.ops.size() - 2]; const Op& Bo = cur.ops.back();
@@ -278,7 +265,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
         // returns true if the attention kernel wrote the MX shadow qo of obase itself (head dim 128, large grid)
         auto attn = [&](const char* name, Act QKV, Act O, const Q8* qo = nullptr, const Act* obase = nullptr, int b = 0) {
             if (attn8) {
-                Op o{}; o.kind = OP_ATTN_MX; o.name = name;
+                Op& o = emit(OP_ATTN_MX, name);
                 AttnMxArgs& a = o.am;
                 a.Q8 = a8_q + (size_t)b * L * C; a.ldq8 = C; a.SQ = a8_sq + (size_t)b * L; a.sq_ld = RT;
                 a.K8 = a8_k + (size_t)b * L * C; a.ldk8 = C; a.SK = a8_sk + (size_t)b * L; a.sk_ld = RT;
@@ -289,7 +276,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
                 else { a.O = ptr(O); a.ldo = O.ld; }
                 o.flops = 4.0 * H * (double)L * L * D; o.bytes = (double)H * D * (2.0 * L + 2.0 * L);
                 snprintf(o.klabel, sizeof(o.klabel), "attn_mx_kernel");
-                cur.ops.push_back(o); cur.flops += o.flops;
+                cur.flops += o.flops;
                 return fuse_out;
             }
             const char* base = (const char*)ptr(QKV);
@@ -376,7 +363,7 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
             GemmArgs& g = cur.ops.back().g; g.C = nullptr; g.Cf = cur.fx_tok + (size_t)b * Li * inC; g.ldcf = inC;
         }
         release(N1); release(X);
-        { Op o{}; o.kind = OP_FX_UNPATCH; o.name = "fx.unpatchify"; o.i0 = B; o.i1 = f.in_channels; o.i2 = h; o.i3 = w; cur.ops.push_back(o); }
+        emit(OP_FX_UNPATCH, "fx.unpatchify").unpatch = FluxUnpatchArgs{cur.fx_tok, 4 * f.in_channels, nullptr, nullptr, nullptr, B, f.in_channels, h, w};      // x, sigma and out are the call's
         return LDX_OK;
     });
 }

@@ -15,15 +15,6 @@
 
 namespace ldx {
 
-#define HIP_OK(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) {                                                              \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                    \
-            return LDX_EHIP;                                                                 \
-        }                                                                                    \
-    } while (0)
-
 Engine::Engine(const ldx_vae_config& c, int dev) : cfg{}, device(dev) {
     kind = KIND_VAE; vcfg = c;
     dt = (c.compute_dtype == LDX_F16) ? DT_F16 : DT_BF16;
@@ -40,7 +31,7 @@ bool Engine::mk_vae_res(const std::string& pre, int Cin, int Cout, ResW& r) {
     if (!mk_norm(pre + ".norm1", Cin, r.gn1) || !mk_conv3(pre + ".conv1", Cout, Cin, Cin, r.conv1)) return false;
     if (!mk_norm(pre + ".norm2", Cout, r.gn2)) return false;
     r.has_skip = Cin != Cout;
-    if (r.has_skip && Cin % 64 == 0 && !getenv("LDX_NO_FUSED_SKIP")) {
+    if (r.has_skip && Cin % 64 == 0 && g_plan_sw.fused_skip) {
         // x = nin_shortcut(x); return x + h (ResBlock.py:383-406): folded into conv2 as a second K segment, like the UNet's ResBlock1
         const HostTensor* w2 = get(pre + ".conv2.weight", {Cout, Cout, 3, 3});
         const HostTensor* b2 = get(pre + ".conv2.bias", {Cout});
@@ -199,16 +190,16 @@ void Engine::emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int 
         Act vt = new_act(C, N);
         { LinearW hw; hw.w = ptr(rows(hn, b * N, N)); hw.b = nullptr; hw.N = N; hw.K = C;
           Act wv; wv.valid = true; wv.rows = C; wv.C = C; wv.ld = C; wv.off = 0; wv.col = 0;
-          Op oo{}; oo.kind = OP_GEMM; oo.name = "vae.attn.vT";
+          Op& oo = emit(OP_GEMM, "vae.attn.vT");
           GemmArgs& g = oo.g; g.A = a.v.w; g.lda = C; g.W = hw.w; g.M = C; g.N = N; g.K = C; g.mode = 0; g.rows_per_batch = 1;
           g.C = ptr(vt); g.ldc = N; g.splitk = 1;
           oo.flops = 2.0 * C * (double)N * C; snprintf(oo.klabel, sizeof(oo.klabel), "gemm_kernel<%s,0>", dt == DT_BF16 ? "bf16" : "f16");
-          cur.ops.push_back(oo); cur.flops += oo.flops; (void)wv; }
+          cur.flops += oo.flops; (void)wv; }
         // Query rows in chunks of Rc: S_c[Rc][N] = q_c k_b^T, row softmax, O_c = P_c V.  The score matrix is never materialised as a whole
         // (N x N at 2048^2 is 8 GiB and was the arena's peak; at 4096^2 it would be 128 GiB): one chunk is <= 2 GiB, so a 1024^2 decode still runs
         // the three launches it always ran and a 2048^2 decode 4 x 3 (measured at 2048^2: one chunk 69.3 ms, 512 MiB chunks 71.9, 128 MiB 72.1; the
         // arena peak then sits at the 2048^2 x 128-channel conv level, 6.5 GiB instead of 8.45).  LDX_VAE_ATTN_CHUNK_MIB overrides (0 = one chunk).
-        static const long chunk_mib = getenv("LDX_VAE_ATTN_CHUNK_MIB") ? atol(getenv("LDX_VAE_ATTN_CHUNK_MIB")) : 2048;
+        const long chunk_mib = g_plan_sw.vae_attn_chunk_mib;
         int Rc = N;
         if (chunk_mib > 0) {
             long r = (chunk_mib << 20) / ((long)N * 2);
@@ -222,8 +213,8 @@ void Engine::emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int 
             Act Sc = rows(S, 0, nr);
             { LinearW kw; kw.w = ptr(rows(k, b * N, N)); kw.b = nullptr; kw.N = N; kw.K = C;
               op_gemm("vae.attn.qk", rows(q, b * N + r0, nr), kw, Sc, Act{}); }
-            { Op oo{}; oo.kind = OP_SOFTMAX; oo.name = "vae.attn.softmax"; oo.p1 = ptr(Sc); oo.i0 = nr; oo.i1 = N; oo.i2 = N; oo.f0 = 1.0f / std::sqrt((float)C);
-              oo.bytes = 2.0 * 2.0 * nr * (double)N; snprintf(oo.klabel, sizeof(oo.klabel), "softmax_rows"); cur.ops.push_back(oo); }
+            { Op& oo = emit(OP_SOFTMAX, "vae.attn.softmax"); oo.sm = SoftmaxArgs{ptr(Sc), nr, N, N, 1.0f / std::sqrt((float)C)};
+              oo.bytes = 2.0 * 2.0 * nr * (double)N; snprintf(oo.klabel, sizeof(oo.klabel), "softmax_rows"); }
             // O_c[nr][C] = P_c[nr][N] . V[N][C]  with W = V^T[C][N]
             { LinearW vw; vw.w = ptr(vt); vw.b = nullptr; vw.N = C; vw.K = N;
               op_gemm("vae.attn.pv", Sc, vw, rows(o, b * N + r0, nr), Act{}); }
@@ -241,7 +232,7 @@ int Engine::plan_vae(int B, int h, int w) {
         cur.gn_ws_off = a_alloc(gn_ws_bytes(B, (long)h * w * 64));
         int H = h, W = w;
         Act x0 = new_act(B * H * W, 64);
-        { Op o{}; o.kind = OP_VAEPREP; o.name = "vae.prep"; o.p1 = ptr(x0); o.i0 = B; o.i1 = v.z_channels; o.i2 = H * W; o.i3 = 64; cur.ops.push_back(o); }
+        emit(OP_VAEPREP, "vae.prep").vprep = VaePrepArgs{nullptr, ptr(x0), B, v.z_channels, H * W, 64, vae_pq, vae_pq ? vae_pq + v.z_channels * v.z_channels : nullptr};      // z is the call's
         int C = v.ch * v.ch_mult[v.num_levels - 1];
         Act hcur = new_act(B * H * W, C);
         op_conv("vae.conv_in", x0, B, H, W, 64, conv_in, 1, H, W, hcur, Act{});
@@ -268,7 +259,7 @@ int Engine::plan_vae(int B, int h, int w) {
         float* pix = (float*)((uintptr_t)cur.arena + o_pix);
         op_conv("vae.conv_out", t, B, H, W, Cl, conv_out, 1, H, W, Act{}, Act{}, nullptr, 0, pix, v.out_ch);
         release(t);
-        { Op o{}; o.kind = OP_CLAMP; o.name = "vae.clamp"; o.p0 = pix; o.i0 = B * H * W * v.out_ch; cur.ops.push_back(o); }
+        emit(OP_CLAMP, "vae.clamp").clamp = ClampArgs{pix, nullptr, (size_t)(B * H * W * v.out_ch)};
         fuse_gn_stats();
         return LDX_OK;
     });
@@ -279,10 +270,8 @@ int Engine::run_vae(const float* z, int B, int h, int w, float* out, hipStream_t
     if (!z || !out || B <= 0 || h <= 0 || w <= 0) { set_error("ldx_vae_decode: bad argument"); return LDX_EINVAL; }
     if ((h * w) % 8) { set_error("ldx_vae_decode: h*w must be a multiple of 8 (attention row length)"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
-    if (int rc = select_plan(PlanKey{B, h, w, 1}, st, [&] { return plan_vae(B, h, w); })) return rc;
-    bind = Bindings{}; bind.x = z; bind.out = out; prof_graph = false;
-    if (int rc = exec_ops(st)) return rc;
-    return launch_status();
+    Bindings b; b.x = z; b.out = out;
+    return run_planned(PlanKey{B, h, w, 1}, [&] { return plan_vae(B, h, w); }, b, st);
 }
 
 // Encoder.forward (VariationalAE.py:378-413) + quant_conv: pixels -> moments
@@ -292,7 +281,7 @@ int Engine::plan_vae_encode(int B, int Hpx, int Wpx) {
         cur.gn_ws_off = a_alloc(gn_ws_bytes(B, (long)Hpx * Wpx));
         int H = Hpx, W = Wpx;
         Act x0 = new_act(B * H * W, 64);
-        { Op o{}; o.kind = OP_PIXPREP; o.name = "vae.enc.prep"; o.p1 = ptr(x0); o.i0 = B; o.i1 = 3; o.i2 = H * W; o.i3 = 64; o.f0 = 2.0f; o.f1 = -1.0f; cur.ops.push_back(o); }
+        emit(OP_PIXPREP, "vae.enc.prep").pix = PixelsPrepArgs{nullptr, ptr(x0), B, 3, H * W, 64, 2.0f, -1.0f};      // the pixels are the call's
         Act hcur = new_act(B * H * W, v.ch);
         op_conv("vae.enc.conv_in", x0, B, H, W, 64, enc_conv_in, 1, H, W, hcur, Act{});
         cur.flops -= 2.0 * B * H * W * (double)v.ch * 9.0 * (64 - 3);
@@ -320,7 +309,7 @@ int Engine::plan_vae_encode(int B, int Hpx, int Wpx) {
         float* mom = (float*)((uintptr_t)cur.arena + o_m);
         op_conv("vae.enc.conv_out", t, B, H, W, Cl, enc_conv_out, 1, H, W, Act{}, Act{}, nullptr, 0, mom, zc2);
         release(t);
-        { Op o{}; o.kind = OP_MOMENTS; o.name = "vae.enc.quant_conv"; o.p0 = mom; o.i0 = B; o.i1 = zc2; o.i2 = H * W; cur.ops.push_back(o); }
+        emit(OP_MOMENTS, "vae.enc.quant_conv").mix = MixArgs{mom, zc2, nullptr, B, zc2, H * W, enc_qc, enc_qc ? enc_qc + zc2 * zc2 : nullptr};
         fuse_gn_stats();
         return LDX_OK;
     });
@@ -335,10 +324,8 @@ int Engine::run_vae_encode(const float* px, int B, int H, int W, float* moments,
     if (!px || !moments || B <= 0 || H < f || W < f || ((H / f) * (W / f)) % 8) {
         set_error("ldx_vae_encode: bad argument (H, W >= downscale factor; latent h*w multiple of 8)"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
-    if (int rc = select_plan(PlanKey{B, H, W, 2}, st, [&] { return plan_vae_encode(B, H, W); })) return rc;
-    bind = Bindings{}; bind.x = px; bind.out = moments; prof_graph = false;
-    if (int rc = exec_ops(st)) return rc;
-    return launch_status();
+    Bindings b; b.x = px; b.out = moments;
+    return run_planned(PlanKey{B, H, W, 2}, [&] { return plan_vae_encode(B, H, W); }, b, st);
 }
 
 // =============================================================================================
@@ -399,7 +386,7 @@ int Engine::plan_clip(int B, int T, int inter) {
     const int E = c.hidden_size, M = B * T, heads = c.num_heads, D = E / heads;
     return build_plan(PlanKey{B, T, 0, inter}, [&]() -> int {
         Act x = new_act(M, E);
-        { Op o{}; o.kind = OP_EMBED; o.name = "clip.embed"; o.p1 = ptr(x); o.i0 = B; o.i1 = T; o.i2 = E; o.i3 = c.vocab_size; cur.ops.push_back(o); }
+        emit(OP_EMBED, "clip.embed").emb = ClipEmbedArgs{nullptr, clip_tok, clip_pos, ptr(x), B, T, E, c.vocab_size, nullptr, 0};      // ids and the textual-inversion rows are the call's
         Act n = new_act(M, E), qkv = new_act(M, 3 * E), a = new_act(M, E), f = new_act(M, c.intermediate_size);
         Act xi = new_act(M, E);
         for (int l = 0; l < c.num_layers; ++l) {
@@ -416,11 +403,11 @@ int Engine::plan_clip(int B, int T, int inter) {
             op_gemm("clip.fc2", f, L.fc2, x, x);                 // x += mlp(ln2(x))
             if (l == inter) {                                    // intermediate = x.clone(); final LN applied to it
                 op_ln("clip.final_ln.inter", x, xi, clip_final_ln);
-                Op o{}; o.kind = OP_CVT_OUT; o.name = "clip.out_inter"; o.p0 = ptr(xi); o.i0 = M * E; o.i3 = 1; cur.ops.push_back(o);
+                { Op& o = emit(OP_CVT_OUT, "clip.out_inter"); o.out = CvtOutArgs{ptr(xi), nullptr, (size_t)(M * E)}; o.second_output = true; }
             }
         }
         op_ln("clip.final_ln", x, n, clip_final_ln);
-        { Op o{}; o.kind = OP_CVT_OUT; o.name = "clip.out_last"; o.p0 = ptr(n); o.i0 = M * E; o.i3 = 0; cur.ops.push_back(o); }
+        emit(OP_CVT_OUT, "clip.out_last").out = CvtOutArgs{ptr(n), nullptr, (size_t)(M * E)};
         return LDX_OK;
     });
 }
@@ -462,10 +449,8 @@ int Engine::run_clip(const int* ids, int B, int T, int inter_layer, float* out_l
         inter = inter_layer < 0 ? ccfg.num_layers + inter_layer : inter_layer;
         if (inter < 0 || inter >= ccfg.num_layers) { set_error("ldx_clip_encode: inter_layer out of range"); return LDX_EINVAL; }
     }
-    if (int rc = select_plan(PlanKey{B, T, 0, inter}, st, [&] { return plan_clip(B, T, inter); })) return rc;
-    bind = Bindings{}; bind.ids = ids; bind.out = out_last; bind.out2 = out_inter; prof_graph = false;
-    if (int rc = exec_ops(st)) return rc;
-    return launch_status();
+    Bindings b; b.ids = ids; b.out = out_last; b.out2 = out_inter;
+    return run_planned(PlanKey{B, T, 0, inter}, [&] { return plan_clip(B, T, inter); }, b, st);
 }
 
 }  // namespace ldx

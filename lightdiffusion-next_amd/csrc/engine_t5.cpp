@@ -11,15 +11,6 @@
 
 namespace ldx {
 
-#define HIP_OK(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) {                                                              \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                    \
-            return LDX_EHIP;                                                                 \
-        }                                                                                    \
-    } while (0)
-
 Engine::Engine(const ldx_t5_config& c, int dev) : cfg{}, device(dev) {
     kind = KIND_T5; tcfg = c;
     dt = (c.compute_dtype == LDX_F16) ? DT_F16 : DT_BF16;
@@ -88,7 +79,7 @@ int Engine::plan_t5(int B, int L) {
     const int Lp = ((L + 63) / 64) * 64;
     return build_plan(PlanKey{B, L}, [&]() -> int {
         Act x = new_act(M, E);
-        { Op o{}; o.kind = OP_EMBED; o.name = "t5.embed"; o.p1 = ptr(x); o.i0 = B; o.i1 = L; o.i2 = E; o.i3 = c.vocab_size; cur.ops.push_back(o); }
+        emit(OP_EMBED, "t5.embed").emb = ClipEmbedArgs{nullptr, t5_tok, nullptr, ptr(x), B, L, E, c.vocab_size, nullptr, 0};      // the ids are the call's
         Act n = new_act(M, E), qkv = new_act(M, 3 * E), a = new_act(M, E), f = new_act(M, F);
         auto rms = [&](const char* name, Act X, Act Y, const NormW& w) {
             op_ln(name, X, Y, w);
@@ -100,7 +91,7 @@ int Engine::plan_t5(int B, int L) {
             op_gemm("t5.qkv", n, W.qkv, qkv, Act{});
             const char* base = (const char*)ptr(qkv);
             op_attn("t5.attn", base, 3 * E, base + (size_t)E * 2, 3 * E, base + (size_t)2 * E * 2, 3 * E, a, B, heads, L, L, D);
-            { Op& o = cur.ops.back(); o.at.scale = 1.0f; o.at.bias_ld = Lp; o.at.bias_hs = (long)L * Lp; o.i3 = 1; }
+            { Op& o = cur.ops.back(); o.at.scale = 1.0f; o.at.bias_ld = Lp; o.at.bias_hs = (long)L * Lp; o.bias_from_call = true; }
             op_gemm("t5.o", a, W.o, x, x);                        // x += attention output
             rms("t5.ln2", x, n, W.ln2);
             op_gemm("t5.wi", n, W.wi, f, Act{}, true);            // gelu_tanh(wi_0 n) * (wi_1 n)
@@ -108,7 +99,7 @@ int Engine::plan_t5(int B, int L) {
             op_gemm("t5.wo", f, W.wo, x, x);                      // x += FF output
         }
         rms("t5.final_ln", x, n, t5_final_ln);
-        { Op o{}; o.kind = OP_CVT_OUT; o.name = "t5.out"; o.p0 = ptr(n); o.i0 = M * E; o.i3 = 0; cur.ops.push_back(o); }
+        emit(OP_CVT_OUT, "t5.out").out = CvtOutArgs{ptr(n), nullptr, (size_t)(M * E)};
         return LDX_OK;
     });
 }
@@ -117,10 +108,8 @@ int Engine::run_t5(const int* ids, int B, int L, const float* bias, float* out, 
     if (!finalized || kind != KIND_T5) { set_error("ldx_t5_encode: not a finalized T5 engine"); return LDX_ESTATE; }
     if (!ids || !bias || !out || B <= 0 || L <= 0) { set_error("ldx_t5_encode: bad argument"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
-    if (int rc = select_plan(PlanKey{B, L}, st, [&] { return plan_t5(B, L); })) return rc;
-    bind = Bindings{}; bind.ids = ids; bind.bias = bias; bind.out = out; prof_graph = false;
-    if (int rc = exec_ops(st)) return rc;
-    return launch_status();
+    Bindings b; b.ids = ids; b.bias = bias; b.out = out;
+    return run_planned(PlanKey{B, L}, [&] { return plan_t5(B, L); }, b, st);
 }
 
 }  // namespace ldx

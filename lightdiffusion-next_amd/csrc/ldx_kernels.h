@@ -240,6 +240,13 @@ struct PlanSwitches {
     long lnfold_maxrows;                             // LDX_LNFOLD_MAXROWS: rows at C = 320 up to which a level folds its LayerNorms (0: never)
     long gn_small_max;                               // LDX_GN_SMALL_MAX: elements per (image, group) the one-launch GroupNorm kernel takes
     bool rowgemm, rowgemm640, rowgemm_x2, rowgemm_po, xattn_fuse, ff_fuse;      // LDX_ROWGEMM, LDX_ROWGEMM640, LDX_ROWGEMM_X2, LDX_ROWGEMM_PO, LDX_XATTN_FUSE, LDX_FF_FUSE: 0 switches the kernel (or that use of it) off
+    // the engines' own planning and weight-packing switches (engine*.cpp say what each is for)
+    bool cfg_share_copy; long cfg_share_minrows;     // LDX_CFG_SHARE_COPY != 0: the shared CFG prefix is handed over by copy launches only; LDX_CFG_SHARE_MINROWS: rows per half from which share mode 1 shares
+    bool fused_skip, q_prescale, lnfold, emb_table;  // LDX_NO_FUSED_SKIP / LDX_NO_QPRESCALE set (to anything): off; LDX_LNFOLD / LDX_EMB_TABLE = 0: off
+    double plan_cache_gib;                           // LDX_PLAN_CACHE_GIB: GiB of stashed arenas the plan cache keeps
+    int mx_fuse;                                     // LDX_MX_FUSE: 1 GEMM epilogue, 2 attention, 4 LayerNorm write the MX shadow themselves
+    bool flux_fp8_attn, flux_group, flux_mod_fp8;    // LDX_FLUX_FP8_ATTN / LDX_FLUX_GROUP / LDX_FLUX_MOD_FP8 = 0: off
+    long vae_attn_chunk_mib;                         // LDX_VAE_ATTN_CHUNK_MIB: score rows per chunk of the VAE's three-GEMM attention, in MiB (0: one chunk)
     PlanSwitches();
 };
 extern const PlanSwitches g_plan_sw;
@@ -348,7 +355,8 @@ struct FinishArgs { const float* eps; int ld; const float* x; const float* sigma
 void launch_fill_f32(float* dst, float v, int n, hipStream_t s);
 void launch_fill2_f32(float* a, float va, float* b, float vb, int n, hipStream_t s);      // a[i] = va, b[i] = vb (the sigma and timestep-index slots of a CFG evaluation: one launch)
 // dst[r][0:C) = src[r][0:C) for r in [0, rows): 16-bit elements, both with row stride ld, C % 8 == 0 (the shared CFG prefix's hand-over, Engine::op_dup)
-void launch_dup_rows(const void* src, void* dst, int rows, int C, int ld, DType dt, hipStream_t s);
+struct DupRowsArgs { const void* src; void* dst; int rows, C, ld; };
+void launch_dup_rows(const DupRowsArgs& a, DType dt, hipStream_t s);
 // CLIP pooled output: row of last[b] at the first position whose id == eos_id (position 0 if none: torch argmax of an all-zero row),
 // then, if proj != null, out[b] = row @ proj^T (proj [E][E] fp32, row-major [out][in])
 void launch_clip_pooled(const float* last, const int* ids, int B, int T, int E, int eos_id, const float* proj, float* out, hipStream_t s);
@@ -357,21 +365,34 @@ void launch_finish(const FinishArgs& a, hipStream_t s);
 // 16-bit <-> fp32 conversion helpers for tests / host plumbing
 void launch_f32_to_t(const float* in, void* out, size_t n, DType dt, hipStream_t s);
 void launch_t_to_f32(const void* in, float* out, size_t n, DType dt, hipStream_t s);
+// the same as ops of a plan (fp32 context -> 16 bit, 16-bit result -> fp32 output), and the device-to-device copy of a finished fp32 result (ESRGAN)
+struct CvtArgs { const float* in; void* out; size_t n; };
+struct CvtOutArgs { const void* in; float* out; size_t n; };
+struct CopyOutArgs { const void* src; void* dst; size_t bytes; };
+inline void launch_f32_to_t(const CvtArgs& a, DType dt, hipStream_t s) { launch_f32_to_t(a.in, a.out, a.n, dt, s); }
+inline void launch_t_to_f32(const CvtOutArgs& a, DType dt, hipStream_t s) { launch_t_to_f32(a.in, a.out, a.n, dt, s); }
+inline hipError_t launch_copy_out(const CopyOutArgs& a, hipStream_t s) { return hipMemcpyAsync(a.dst, a.src, a.bytes, hipMemcpyDeviceToDevice, s); }
 // NCHW fp32 <-> NHWC 16-bit (VAE boundary)
 void launch_nchw_to_nhwc(const float* in, void* out, int B, int C, int HW, int Cpad, float scale, DType dt, hipStream_t s);
 
 // VAE boundary (AutoEncoders/VariationalAE.py:130-145, 690-722): z fp32 NCHW [B][C][HW] -> optional 1x1 mix
 // (post_quant_conv, fp32: out[c] = b[c] + sum_k w[c][k] z[k]) -> NHWC 16-bit with Cpad channels.
-void launch_vae_prep(const float* z, void* out, int B, int C, int HW, int Cpad, const float* mix_w, const float* mix_b, DType dt, hipStream_t s);
+struct VaePrepArgs { const float* z; void* out; int B, C, HW, Cpad; const float* mix_w; const float* mix_b; };
+void launch_vae_prep(const VaePrepArgs& a, DType dt, hipStream_t s);
 // encoder input: pixels NHWC fp32 [B][HW][C] in [0,1] -> x*2-1 (process_input, VariationalAE.py:593) -> NHWC 16-bit, Cpad channels
-void launch_pixels_prep(const float* px, void* out, int B, int C, int HW, int Cpad, float scale, float shift, DType dt, hipStream_t s);
+struct PixelsPrepArgs { const float* px; void* out; int B, C, HW, Cpad; float scale, shift; };
+void launch_pixels_prep(const PixelsPrepArgs& a, DType dt, hipStream_t s);
 // pixel post-process: out = clamp((x + 1) / 2, 0, 1) on fp32 (process_output, VariationalAE.py:595-597)
-void launch_clamp01(const float* in, float* out, size_t n, hipStream_t s);
+struct ClampArgs { const float* in; float* out; size_t n; };
+void launch_clamp01(const ClampArgs& a, hipStream_t s);
 // row softmax in place on a 16-bit [rows][ld] matrix: p = softmax(x * scale) (VAE AttnBlock, D = 512 single head)
-void launch_softmax_rows(void* X, int rows, int cols, int ld, float scale, DType dt, hipStream_t s);
+struct SoftmaxArgs { void* X; int rows, cols, ld; float scale; };
+void launch_softmax_rows(const SoftmaxArgs& a, DType dt, hipStream_t s);
 // CLIP embeddings (clip/Clip.py:254-294): x[b][t][:] = tok[id[b][t]][:] + pos[t][:]  (fp32 tables -> 16-bit)
 // ids in [vocab, vocab + n_extra) read row id - vocab of `extra` (textual-inversion vectors, SD15/SDClip.py:213-267)
-void launch_clip_embed(const int* ids, const float* tok, const float* pos, void* out, int B, int T, int C, int vocab, const float* extra, int n_extra, DType dt, hipStream_t s);
+// pos == null: token rows alone (T5)
+struct ClipEmbedArgs { const int* ids; const float* tok; const float* pos; void* out; int B, T, C, vocab; const float* extra; int n_extra; };
+void launch_clip_embed(const ClipEmbedArgs& a, DType dt, hipStream_t s);
 
 // First-block cache helpers on the joint token buffer X [B][L][C] (16-bit; rows [0, Lt) text, [Lt, L) image per batch).
 // fb_diff: sums[0] = sum |(X - S0) - F| , sums[1] = sum |F| over the image rows (deterministic two-stage reduction through
@@ -417,12 +438,16 @@ void launch_attn_mx(const AttnMxArgs& a, DType dt, hipStream_t s);
 struct MxVtArgs { const void* V; int ldv; int B, H, L; void* V8T; uint32_t* SV; int Lp; };
 void launch_mx_vt_quant(const MxVtArgs& a, DType dt, hipStream_t s);
 // timestep_embedding_flux (sample/sampling_util.py:78-104): out[b][:] = [cos(1000 t f_j) | sin(1000 t f_j)], dim 256
-void launch_flux_temb(const float* t, float* out, int B, int dim, float factor, hipStream_t s);
-void launch_silu_f32(const float* in, float* out, size_t n, hipStream_t s);
+struct FluxTembArgs { const float* t; float* out; int B, dim; float factor; };
+void launch_flux_temb(const FluxTembArgs& a, hipStream_t s);
+struct SiluArgs { const float* in; float* out; size_t n; };
+void launch_silu_f32(const SiluArgs& a, hipStream_t s);
 // patchify  x[B][C][H][W] fp32 -> tokens [B*(H/2)*(W/2)][4C] 16-bit, column = c*4 + ph*2 + pw   (Flux3.forward :742-748)
-void launch_flux_patchify(const float* x, void* out, int B, int C, int H, int W, DType dt, hipStream_t s);
+struct FluxPatchArgs { const float* x; void* out; int B, C, H, W; };
+void launch_flux_patchify(const FluxPatchArgs& a, DType dt, hipStream_t s);
 // unpatchify + CONST.calculate_denoised (sampling.py:108-122): out = x - tok*sigma (or tok if x == null), fp32 NCHW
-void launch_flux_unpatchify(const float* tok, int ld, const float* x, const float* sigma, float* out, int B, int C, int H, int W, hipStream_t s);
+struct FluxUnpatchArgs { const float* tok; int ld; const float* x; const float* sigma; float* out; int B, C, H, W; };
+void launch_flux_unpatchify(const FluxUnpatchArgs& a, hipStream_t s);
 
 // Sampler elementwise kernels (fp32, reference samplers.py / CFG.py):
 //  d = lerp(den_uncond, den_cond, cfg)                             (torch.lerp, CFG.py:60)
@@ -442,7 +467,8 @@ void launch_sampler_step(const StepArgs& a, hipStream_t s);
 void launch_bislerp_pass(const float* in, float* out, int N, int C, int H, int W, int axis, int new_len,
                          const int* c1, const int* c2, const float* r, hipStream_t s);
 // VAE encoder tail: moments_nchw[b][c][p] = bias[c] + sum_k w[c][k] * in_nhwc[b][p][k]   (quant_conv 1x1, fp32)
-void launch_mix_nhwc_to_nchw(const float* in, int ld, float* out, int B, int C, int HW, const float* w, const float* bias, hipStream_t s);
+struct MixArgs { const float* in; int ld; float* out; int B, C, HW; const float* w; const float* bias; };
+void launch_mix_nhwc_to_nchw(const MixArgs& a, hipStream_t s);
 // bilinear resize (align_corners=False, antialias=False) of fp32 NCHW planes
 void launch_bilinear(const float* in, float* out, int planes, int Hin, int Win, int Hout, int Wout, hipStream_t s);
 

@@ -158,11 +158,11 @@ __global__ __launch_bounds__(256) void dup_rows_kernel(const uint4* __restrict__
         for (int u = 0; u < 4; ++u) { const long i = i0 + u * stride; if (i < total) { const long r = i / cpr; dst[r * ld16 + (i - r * cpr)] = v[u]; } }
     }
 }
-void launch_dup_rows(const void* src, void* dst, int rows, int C, int ld, DType, hipStream_t s) {
-    if (rows <= 0 || C <= 0) return;
-    const long total = (long)rows * (C / 8);
+void launch_dup_rows(const DupRowsArgs& a, DType, hipStream_t s) {
+    if (a.rows <= 0 || a.C <= 0) return;
+    const long total = (long)a.rows * (a.C / 8);
     long grid = (total + 256 * 4 - 1) / (256 * 4); if (grid > 2048) grid = 2048; if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(dup_rows_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const uint4*)src, (uint4*)dst, total, C / 8, ld / 8);
+    hipLaunchKernelGGL(dup_rows_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const uint4*)a.src, (uint4*)a.dst, total, a.C / 8, a.ld / 8);
 }
 void launch_fill2_f32(float* a, float va, float* b, float vb, int n, hipStream_t s) { hipLaunchKernelGGL(fill2_f32_kernel, dim3((n + 63) / 64), dim3(64), 0, s, a, va, b, vb, n); }
 void launch_fill_f32(float* dst, float v, int n, hipStream_t s) { hipLaunchKernelGGL(fill_f32_kernel, dim3((n + 63) / 64), dim3(64), 0, s, dst, v, n); }
@@ -237,10 +237,10 @@ __global__ __launch_bounds__(256) void vae_prep_kernel(const float* z, T* out, i
         *(uint4*)(out + ((long)b * HW + pix) * Cpad + ch * 8) = pack8<T>(f);
     }
 }
-void launch_vae_prep(const float* z, void* out, int B, int C, int HW, int Cpad, const float* mw, const float* mb, DType dt, hipStream_t s) {
-    const size_t total = (size_t)B * HW * (Cpad / 8);
-    if (dt == DT_BF16) hipLaunchKernelGGL((vae_prep_kernel<__bf16>), dim3(grid_for(total)), dim3(256), 0, s, z, (__bf16*)out, B, C, HW, Cpad, mw, mb);
-    else hipLaunchKernelGGL((vae_prep_kernel<_Float16>), dim3(grid_for(total)), dim3(256), 0, s, z, (_Float16*)out, B, C, HW, Cpad, mw, mb);
+void launch_vae_prep(const VaePrepArgs& a, DType dt, hipStream_t s) {
+    const size_t total = (size_t)a.B * a.HW * (a.Cpad / 8);
+    if (dt == DT_BF16) hipLaunchKernelGGL((vae_prep_kernel<__bf16>), dim3(grid_for(total)), dim3(256), 0, s, a.z, (__bf16*)a.out, a.B, a.C, a.HW, a.Cpad, a.mix_w, a.mix_b);
+    else hipLaunchKernelGGL((vae_prep_kernel<_Float16>), dim3(grid_for(total)), dim3(256), 0, s, a.z, (_Float16*)a.out, a.B, a.C, a.HW, a.Cpad, a.mix_w, a.mix_b);
 }
 
 template <typename T>
@@ -256,18 +256,18 @@ __global__ __launch_bounds__(256) void pixels_prep_kernel(const float* px, T* ou
         *(uint4*)(out + bp * Cpad + ch * 8) = pack8<T>(f);
     }
 }
-void launch_pixels_prep(const float* px, void* out, int B, int C, int HW, int Cpad, float scale, float shift, DType dt, hipStream_t s) {
-    const size_t total = (size_t)B * HW * (Cpad / 8);
-    if (dt == DT_BF16) hipLaunchKernelGGL((pixels_prep_kernel<__bf16>), dim3(grid_for(total)), dim3(256), 0, s, px, (__bf16*)out, B, C, HW, Cpad, scale, shift);
-    else hipLaunchKernelGGL((pixels_prep_kernel<_Float16>), dim3(grid_for(total)), dim3(256), 0, s, px, (_Float16*)out, B, C, HW, Cpad, scale, shift);
+void launch_pixels_prep(const PixelsPrepArgs& a, DType dt, hipStream_t s) {
+    const size_t total = (size_t)a.B * a.HW * (a.Cpad / 8);
+    if (dt == DT_BF16) hipLaunchKernelGGL((pixels_prep_kernel<__bf16>), dim3(grid_for(total)), dim3(256), 0, s, a.px, (__bf16*)a.out, a.B, a.C, a.HW, a.Cpad, a.scale, a.shift);
+    else hipLaunchKernelGGL((pixels_prep_kernel<_Float16>), dim3(grid_for(total)), dim3(256), 0, s, a.px, (_Float16*)a.out, a.B, a.C, a.HW, a.Cpad, a.scale, a.shift);
 }
 
 __global__ __launch_bounds__(256) void clamp01_kernel(const float* in, float* out, size_t n) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
         out[i] = fminf(fmaxf((in[i] + 1.0f) / 2.0f, 0.0f), 1.0f);
 }
-void launch_clamp01(const float* in, float* out, size_t n, hipStream_t s) {
-    hipLaunchKernelGGL(clamp01_kernel, dim3(grid_for(n)), dim3(256), 0, s, in, out, n);
+void launch_clamp01(const ClampArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(clamp01_kernel, dim3(grid_for(a.n)), dim3(256), 0, s, a.in, a.out, a.n);
 }
 
 // one workgroup per row; three passes over the (L2-resident) row: max, sum of exp, normalise
@@ -305,9 +305,9 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(T* X, int cols, int l
         *(uint4*)(x + ch * 8) = pack8<T>(f);
     }
 }
-void launch_softmax_rows(void* X, int rows, int cols, int ld, float scale, DType dt, hipStream_t s) {
-    if (dt == DT_BF16) hipLaunchKernelGGL((softmax_rows_kernel<__bf16>), dim3(rows), dim3(256), 0, s, (__bf16*)X, cols, ld, scale);
-    else hipLaunchKernelGGL((softmax_rows_kernel<_Float16>), dim3(rows), dim3(256), 0, s, (_Float16*)X, cols, ld, scale);
+void launch_softmax_rows(const SoftmaxArgs& a, DType dt, hipStream_t s) {
+    if (dt == DT_BF16) hipLaunchKernelGGL((softmax_rows_kernel<__bf16>), dim3(a.rows), dim3(256), 0, s, (__bf16*)a.X, a.cols, a.ld, a.scale);
+    else hipLaunchKernelGGL((softmax_rows_kernel<_Float16>), dim3(a.rows), dim3(256), 0, s, (_Float16*)a.X, a.cols, a.ld, a.scale);
 }
 
 template <typename T>
@@ -328,10 +328,10 @@ __global__ __launch_bounds__(256) void clip_embed_kernel(const int* ids, const f
         *(uint4*)(out + bt * C + ch * 8) = pack8<T>(f);
     }
 }
-void launch_clip_embed(const int* ids, const float* tok, const float* pos, void* out, int B, int Tn, int C, int vocab, const float* extra, int n_extra, DType dt, hipStream_t s) {
-    const size_t total = (size_t)B * Tn * (C / 8);
-    if (dt == DT_BF16) hipLaunchKernelGGL((clip_embed_kernel<__bf16>), dim3(grid_for(total)), dim3(256), 0, s, ids, tok, pos, (__bf16*)out, B, Tn, C, vocab, extra, n_extra);
-    else hipLaunchKernelGGL((clip_embed_kernel<_Float16>), dim3(grid_for(total)), dim3(256), 0, s, ids, tok, pos, (_Float16*)out, B, Tn, C, vocab, extra, n_extra);
+void launch_clip_embed(const ClipEmbedArgs& a, DType dt, hipStream_t s) {
+    const size_t total = (size_t)a.B * a.T * (a.C / 8);
+    if (dt == DT_BF16) hipLaunchKernelGGL((clip_embed_kernel<__bf16>), dim3(grid_for(total)), dim3(256), 0, s, a.ids, a.tok, a.pos, (__bf16*)a.out, a.B, a.T, a.C, a.vocab, a.extra, a.n_extra);
+    else hipLaunchKernelGGL((clip_embed_kernel<_Float16>), dim3(grid_for(total)), dim3(256), 0, s, a.ids, a.tok, a.pos, (_Float16*)a.out, a.B, a.T, a.C, a.vocab, a.extra, a.n_extra);
 }
 
 __global__ __launch_bounds__(256) void flux_temb_kernel(const float* t, float* out, int B, int dim, float factor) {
@@ -344,14 +344,14 @@ __global__ __launch_bounds__(256) void flux_temb_kernel(const float* t, float* o
         out[(long)b * dim + half + j] = sinf(a);
     }
 }
-void launch_flux_temb(const float* t, float* out, int B, int dim, float factor, hipStream_t s) {
-    hipLaunchKernelGGL(flux_temb_kernel, dim3(grid_for((size_t)B * dim / 2)), dim3(256), 0, s, t, out, B, dim, factor);
+void launch_flux_temb(const FluxTembArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(flux_temb_kernel, dim3(grid_for((size_t)a.B * a.dim / 2)), dim3(256), 0, s, a.t, a.out, a.B, a.dim, a.factor);
 }
 __global__ __launch_bounds__(256) void silu_f32_kernel(const float* in, float* out, size_t n) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) { const float x = in[i]; out[i] = x / (1.0f + expf(-x)); }
 }
-void launch_silu_f32(const float* in, float* out, size_t n, hipStream_t s) {
-    hipLaunchKernelGGL(silu_f32_kernel, dim3(grid_for(n)), dim3(256), 0, s, in, out, n);
+void launch_silu_f32(const SiluArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(silu_f32_kernel, dim3(grid_for(a.n)), dim3(256), 0, s, a.in, a.out, a.n);
 }
 template <typename T>
 __global__ __launch_bounds__(256) void flux_patchify_kernel(const float* x, T* out, int B, int C, int H, int W) {
@@ -365,10 +365,10 @@ __global__ __launch_bounds__(256) void flux_patchify_kernel(const float* x, T* o
         out[idx] = (T)x[(((long)b * C + c) * H + th * 2 + ph) * W + tw * 2 + pw];
     }
 }
-void launch_flux_patchify(const float* x, void* out, int B, int C, int H, int W, DType dt, hipStream_t s) {
-    const size_t total = (size_t)B * (H / 2) * (W / 2) * 4 * C;
-    if (dt == DT_BF16) hipLaunchKernelGGL((flux_patchify_kernel<__bf16>), dim3(grid_for(total)), dim3(256), 0, s, x, (__bf16*)out, B, C, H, W);
-    else hipLaunchKernelGGL((flux_patchify_kernel<_Float16>), dim3(grid_for(total)), dim3(256), 0, s, x, (_Float16*)out, B, C, H, W);
+void launch_flux_patchify(const FluxPatchArgs& a, DType dt, hipStream_t s) {
+    const size_t total = (size_t)a.B * (a.H / 2) * (a.W / 2) * 4 * a.C;
+    if (dt == DT_BF16) hipLaunchKernelGGL((flux_patchify_kernel<__bf16>), dim3(grid_for(total)), dim3(256), 0, s, a.x, (__bf16*)a.out, a.B, a.C, a.H, a.W);
+    else hipLaunchKernelGGL((flux_patchify_kernel<_Float16>), dim3(grid_for(total)), dim3(256), 0, s, a.x, (_Float16*)a.out, a.B, a.C, a.H, a.W);
 }
 __global__ __launch_bounds__(256) void flux_unpatchify_kernel(const float* tok, int ld, const float* x, const float* sigma, float* out, int B, int C, int H, int W) {
     const int h2 = H / 2, w2 = W / 2;
@@ -380,8 +380,8 @@ __global__ __launch_bounds__(256) void flux_unpatchify_kernel(const float* tok, 
         out[idx] = x ? (x[idx] - v * sigma[b]) : v;
     }
 }
-void launch_flux_unpatchify(const float* tok, int ld, const float* x, const float* sigma, float* out, int B, int C, int H, int W, hipStream_t s) {
-    hipLaunchKernelGGL(flux_unpatchify_kernel, dim3(grid_for((size_t)B * C * H * W)), dim3(256), 0, s, tok, ld, x, sigma, out, B, C, H, W);
+void launch_flux_unpatchify(const FluxUnpatchArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(flux_unpatchify_kernel, dim3(grid_for((size_t)a.B * a.C * a.H * a.W)), dim3(256), 0, s, a.tok, a.ld, a.x, a.sigma, a.out, a.B, a.C, a.H, a.W);
 }
 
 #pragma clang fp contract(off)
@@ -458,8 +458,8 @@ __global__ __launch_bounds__(256) void mix_nhwc_to_nchw_kernel(const float* in, 
         out[idx] = v;
     }
 }
-void launch_mix_nhwc_to_nchw(const float* in, int ld, float* out, int B, int C, int HW, const float* w, const float* bias, hipStream_t s) {
-    hipLaunchKernelGGL(mix_nhwc_to_nchw_kernel, dim3(grid_for((size_t)B * C * HW)), dim3(256), 0, s, in, ld, out, B, C, HW, w, bias);
+void launch_mix_nhwc_to_nchw(const MixArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(mix_nhwc_to_nchw_kernel, dim3(grid_for((size_t)a.B * a.C * a.HW)), dim3(256), 0, s, a.in, a.ld, a.out, a.B, a.C, a.HW, a.w, a.bias);
 }
 
 // torch upsample_bilinear2d, align_corners=False: src = max((dst + .5) * in/out - .5, 0)

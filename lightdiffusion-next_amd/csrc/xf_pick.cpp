@@ -18,7 +18,12 @@ PlanSwitches::PlanSwitches()
       plain640_maxm(env_long("LDX_ROWGEMM_PLAIN640_MAXM", 16384)), lnfold_maxrows(env_long("LDX_LNFOLD_MAXROWS", LDX_LNFOLD_MAXROWS_DEFAULT)),
       gn_small_max(env_long("LDX_GN_SMALL_MAX", 256 * 80)),
       rowgemm(env_unless_0("LDX_ROWGEMM")), rowgemm640(env_unless_0("LDX_ROWGEMM640")), rowgemm_x2(env_unless_0("LDX_ROWGEMM_X2")), rowgemm_po(env_unless_0("LDX_ROWGEMM_PO")),
-      xattn_fuse(env_unless_0("LDX_XATTN_FUSE")), ff_fuse(env_unless_0("LDX_FF_FUSE")) {}
+      xattn_fuse(env_unless_0("LDX_XATTN_FUSE")), ff_fuse(env_unless_0("LDX_FF_FUSE")),
+      cfg_share_copy(getenv("LDX_CFG_SHARE_COPY") && atoi(getenv("LDX_CFG_SHARE_COPY")) != 0), cfg_share_minrows(env_long("LDX_CFG_SHARE_MINROWS", 8192)),
+      fused_skip(!getenv("LDX_NO_FUSED_SKIP")), q_prescale(getenv("LDX_NO_QPRESCALE") == nullptr), lnfold(env_unless_0("LDX_LNFOLD")), emb_table(env_unless_0("LDX_EMB_TABLE")),
+      plan_cache_gib(getenv("LDX_PLAN_CACHE_GIB") ? atof(getenv("LDX_PLAN_CACHE_GIB")) : 16.0), mx_fuse(getenv("LDX_MX_FUSE") ? atoi(getenv("LDX_MX_FUSE")) : 7),
+      flux_fp8_attn(env_unless_0("LDX_FLUX_FP8_ATTN")), flux_group(env_unless_0("LDX_FLUX_GROUP")), flux_mod_fp8(env_unless_0("LDX_FLUX_MOD_FP8")),
+      vae_attn_chunk_mib(env_long("LDX_VAE_ATTN_CHUNK_MIB", 2048)) {}
 const PlanSwitches g_plan_sw;
 
 long rowblock_count(long M, int K) { const int bm = rowblock_rows(K); return (M + bm - 1) / bm * (K / 320); }
