@@ -7,7 +7,7 @@
  * Stable-Fast (src/StableFast/StableFast.py:230-274) and FBCache (src/WaveSpeed/fbcache_nodes.py:96-111)
  * sit behind it.  Everything below is what a ctypes binding for that hook needs: plain pointers and
  * sizes, no torch types.  All `const float*` / `void*` tensor arguments of the compute calls are
- * DEVICE pointers on the engine's device; ldx_load_tensor takes HOST pointers.
+ * DEVICE pointers on the engine's device; ldx_load_tensor takes HOST pointers (ldx_load_tensor_device: device pointers).
  *
  * Conventions: every call returns 0 on success or a negative LDX_E* code; ldx_last_error() returns a
  * thread-local human-readable message.  One engine per device, not thread-safe (the reference has a
@@ -123,12 +123,37 @@ void ldx_destroy(ldx_engine* e);
  * "input_blocks.1.1.transformer_blocks.0.attn1.to_q.weight".  Replaces BaseModel.load_model_weights
  * (ModelBase.py:178-202) + the per-forward cast of cond/cast.py:44-78 (cast happens once, here). */
 int ldx_load_tensor(ldx_engine* e, const char* key, const void* data, int dtype, const int64_t* shape, int ndim);
+/* The same for a tensor that already lives on the engine's DEVICE (UNet engines only): contiguous, dtype LDX_F16|LDX_BF16|LDX_F32.  The tensor is
+ * NOT copied: it must stay valid and unchanged until ldx_finalize (or ldx_unet_refresh_commit) returns, and work queued on other streams that
+ * writes it must have completed.  The weights are packed by device kernels (csrc/pack.hip) into exactly the bits the host path produces.
+ * Host and device tensors may be mixed key by key; a later registration of a key replaces the earlier one.  This is how the reference's
+ * hook hands over its model: the state dict is on the GPU after ModelPatcher.patch_model (ModelPatcher.py:515). */
+int ldx_load_tensor_device(ldx_engine* e, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
 /* Sigma / timestep tables built by the host exactly as the reference builds them
  * (ModelSamplingDiscrete.set_sigmas sampling.py:285-289 -> log_sigmas[n];
  *  timestep_embedding sampling_util.py:56-76 evaluated at t = 0..n-1 -> temb[n][model_channels]). */
 int ldx_set_tables(ldx_engine* e, const float* log_sigmas, int n, const float* temb, int temb_dim);
 /* Pack weights into MFMA-friendly layouts and upload them.  After this the host copies are dropped. */
 int ldx_finalize(ldx_engine* e);
+/* Replace the weights of a FINALIZED UNet engine in place: what the reference does to its torch modules at run time with
+ * ModelPatcher.patch_model / unpatch_model (ModelPatcher.py:515,652) when a LoRA is applied, removed or re-weighted.
+ *   ldx_unet_refresh_begin   re-opens ldx_load_tensor / ldx_load_tensor_device (without it both answer LDX_ESTATE after ldx_finalize) and
+ *                            forgets tensors registered by an unfinished refresh.  LDX_ESTATE unless the engine is a finalized UNet engine.
+ *   ldx_unet_refresh_commit  needs the FULL key set again.  It first resolves every key and shape: LDX_EMISSING names the key, nothing has been
+ *                            written and the engine keeps computing with its present weights.  Then every packed buffer is derived again into
+ *                            the SAME device allocations (no allocation of weight memory, no pointer changes: cached plans and captured graphs
+ *                            stay valid), the per-timestep emb_layers table is rebuilt and the cached context projections
+ *                            (ldx_unet_context_cache) are dropped.  Synchronous like ldx_finalize: it waits for the device before (no call may
+ *                            still be reading the weights) and after.  Success or failure, the refresh is over when it returns.
+ *   ldx_unet_refresh_abort   gives up a refresh that was begun: forgets the tensors registered since ldx_unet_refresh_begin and closes the two
+ *                            loaders again.  The weights are untouched.  A no-op on a finalized UNet engine with no refresh open.
+ * The plan switches read from the environment (LDX_LNFOLD, LDX_NO_FUSED_SKIP, ...) must be as they were at ldx_finalize: LDX_ESTATE otherwise. */
+int ldx_unet_refresh_begin(ldx_engine* e);
+int ldx_unet_refresh_commit(ldx_engine* e);
+int ldx_unet_refresh_abort(ldx_engine* e);
+/* Diagnostic (tests): 64-bit FNV-1a over every packed weight buffer of a finalized UNet engine, in allocation order, computed on the host
+ * from copies of the buffers.  Equal digests = bit-identical weights, however they were loaded. */
+int ldx_weights_digest(ldx_engine* e, uint64_t* out);
 
 /* ---- the hot path ----------------------------------------------------------------------------- */
 /* The wrapper body: denoised = x - UNet(x / sqrt(sigma^2+1), t(sigma), ctx) * sigma — i.e. all of

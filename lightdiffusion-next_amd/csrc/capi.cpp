@@ -221,6 +221,36 @@ int ldx_load_tensor(ldx_engine* e, const char* key, const void* data, int dtype,
     return e->impl->load_tensor(key, data, dtype, shape, ndim);
     GUARD_END
 }
+int ldx_load_tensor_device(ldx_engine* e, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
+    GUARD_BEGIN
+    if (!e) { set_error("null engine"); return LDX_EINVAL; }
+    return e->impl->load_tensor_device(key, dev_ptr, dtype, shape, ndim);
+    GUARD_END
+}
+int ldx_unet_refresh_begin(ldx_engine* e) {
+    GUARD_BEGIN
+    if (!e) { set_error("null engine"); return LDX_EINVAL; }
+    return e->impl->refresh_begin();
+    GUARD_END
+}
+int ldx_unet_refresh_commit(ldx_engine* e) {
+    GUARD_BEGIN
+    if (!e) { set_error("null engine"); return LDX_EINVAL; }
+    return e->impl->refresh_commit();
+    GUARD_END
+}
+int ldx_unet_refresh_abort(ldx_engine* e) {
+    GUARD_BEGIN
+    if (!e) { set_error("null engine"); return LDX_EINVAL; }
+    return e->impl->refresh_abort();
+    GUARD_END
+}
+int ldx_weights_digest(ldx_engine* e, uint64_t* out) {
+    GUARD_BEGIN
+    if (!e) { set_error("null engine"); return LDX_EINVAL; }
+    return e->impl->weights_digest(out);
+    GUARD_END
+}
 int ldx_set_tables(ldx_engine* e, const float* log_sigmas, int n, const float* temb, int temb_dim) {
     GUARD_BEGIN
     if (!e) { set_error("null engine"); return LDX_EINVAL; }

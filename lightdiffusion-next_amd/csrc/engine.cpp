@@ -11,6 +11,7 @@
 // activations stay NHWC 16-bit, channel concat is a column offset, and every op is one of the HIP
 // kernels in csrc/*.hip.  No CPU fallback exists: without a HIP device every call fails.
 #include "engine.h"
+#include "weight_convert.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,53 +31,7 @@ int launch_status() {
 }
 
 // ---------------------------------------------------------------------------------------------
-// 16-bit conversions on the host (round-to-nearest-even)
-static inline float half_to_float(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000) << 16;
-    uint32_t exp = (h >> 10) & 0x1f, man = h & 0x3ff, out;
-    if (exp == 0) {
-        if (man == 0) out = sign;
-        else {
-            exp = 127 - 15 + 1;
-            while (!(man & 0x400)) { man <<= 1; --exp; }
-            man &= 0x3ff;
-            out = sign | (exp << 23) | (man << 13);
-        }
-    } else if (exp == 31) out = sign | 0x7f800000u | (man << 13);
-    else out = sign | ((exp + 127 - 15) << 23) | (man << 13);
-    float f; memcpy(&f, &out, 4); return f;
-}
-static inline uint16_t float_to_half(float f) {
-    uint32_t x; memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000;
-    x &= 0x7fffffff;
-    if (x >= 0x7f800000) return (uint16_t)(sign | 0x7c00 | ((x > 0x7f800000) ? 0x200 : 0));
-    if (x >= 0x477ff000) return (uint16_t)(sign | 0x7c00);                       // overflow -> inf
-    if (x < 0x33000001) return (uint16_t)sign;                                  // underflow -> 0
-    int exp = (int)(x >> 23) - 127 + 15;
-    uint32_t man = x & 0x7fffff;
-    if (exp <= 0) {                                                              // subnormal
-        man |= 0x800000;
-        const int shift = 14 - exp;
-        uint32_t hm = man >> shift;
-        const uint32_t rem = man & ((1u << shift) - 1), halfway = 1u << (shift - 1);
-        if (rem > halfway || (rem == halfway && (hm & 1))) ++hm;
-        return (uint16_t)(sign | hm);
-    }
-    uint32_t hm = man >> 13;
-    const uint32_t rem = man & 0x1fff;
-    uint32_t out = ((uint32_t)exp << 10) | hm;
-    if (rem > 0x1000 || (rem == 0x1000 && (hm & 1))) ++out;
-    return (uint16_t)(sign | out);
-}
-static inline float bf16_to_float(uint16_t h) { uint32_t x = (uint32_t)h << 16; float f; memcpy(&f, &x, 4); return f; }
-static inline uint16_t float_to_bf16(float f) {
-    uint32_t x; memcpy(&x, &f, 4);
-    if ((x & 0x7fffffff) > 0x7f800000) return (uint16_t)((x >> 16) | 0x40);
-    x += 0x7fff + ((x >> 16) & 1);
-    return (uint16_t)(x >> 16);
-}
-
+// 16-bit conversions (round-to-nearest-even): weight_convert.h, shared with the device packer (pack.hip)
 float HostTensor::at(size_t i) const {
     switch (dtype) {
         case LDX_F32: return ((const float*)data.data())[i];
@@ -119,6 +74,7 @@ int Engine::validate() const {
     auto bad = [&](const char* m) { set_error(std::string("unsupported UNet config: ") + m); return LDX_EINVAL; };
     if (cfg.model_channels <= 0 || cfg.model_channels % 64) return bad("model_channels must be a multiple of 64");
     if (cfg.context_dim <= 0 || cfg.context_dim % 64) return bad("context_dim must be a multiple of 64");
+    // these two (every level's channels = model_channels * channel_mult) are also what the device packers' 16-byte stores need (Engine::pack16)
     if (cfg.num_levels < 1 || cfg.num_levels > 8) return bad("num_levels out of range");
     if (cfg.num_heads < 1) return bad("num_heads");
     if (cfg.in_channels < 1 || cfg.in_channels > 64 || cfg.out_channels < 1 || cfg.out_channels > 128) return bad("in/out channels");
@@ -131,7 +87,7 @@ int Engine::validate() const {
 }
 
 int Engine::load_tensor(const char* key, const void* data, int dtype, const int64_t* shape, int ndim) {
-    if (finalized) { set_error("ldx_load_tensor after ldx_finalize"); return LDX_ESTATE; }
+    if (finalized && !refreshing) { set_error("ldx_load_tensor after ldx_finalize"); return LDX_ESTATE; }
     if (!key || !data || ndim < 0 || ndim > 8) { set_error("ldx_load_tensor: bad argument"); return LDX_EINVAL; }
     if (dtype != LDX_F32 && dtype != LDX_F16 && dtype != LDX_BF16) { set_error("ldx_load_tensor: bad dtype"); return LDX_EINVAL; }
     HostTensor t;
@@ -142,6 +98,24 @@ int Engine::load_tensor(const char* key, const void* data, int dtype, const int6
     const size_t esz = dtype == LDX_F32 ? 4 : 2;
     t.data.resize(n * esz);
     memcpy(t.data.data(), data, n * esz);
+    host[key] = std::move(t);
+    return LDX_OK;
+}
+
+int Engine::load_tensor_device(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
+    if (kind != KIND_UNET) { set_error("ldx_load_tensor_device: UNet engines only"); return LDX_ESTATE; }
+    if (finalized && !refreshing) { set_error("ldx_load_tensor_device after ldx_finalize"); return LDX_ESTATE; }
+    if (!key || !dev_ptr || ndim < 0 || ndim > 8 || (ndim && !shape)) { set_error("ldx_load_tensor_device: bad argument"); return LDX_EINVAL; }
+    if (dtype != LDX_F32 && dtype != LDX_F16 && dtype != LDX_BF16) { set_error("ldx_load_tensor_device: bad dtype"); return LDX_EINVAL; }
+    if ((uintptr_t)dev_ptr % (dtype == LDX_F32 ? 4 : 2)) { set_error("ldx_load_tensor_device: misaligned pointer"); return LDX_EINVAL; }
+    HostTensor t;
+    t.dtype = dtype;
+    t.numel = 1;
+    for (int i = 0; i < ndim; ++i) {
+        if (shape[i] < 0) { set_error("ldx_load_tensor_device: negative extent"); return LDX_EINVAL; }
+        t.shape.push_back(shape[i]); t.numel *= (size_t)shape[i];
+    }
+    t.dev = dev_ptr;
     host[key] = std::move(t);
     return LDX_OK;
 }
@@ -174,8 +148,27 @@ const HostTensor* Engine::get(const std::string& key, std::initializer_list<int6
     return &t;
 }
 
+// the next weight buffer of the structure walk: a new allocation (ALLOC) or the one the same step of finalize()'s walk made (CHECK / REFILL)
+void* Engine::weight_buf(size_t bytes) {
+    if (walk_mode == WALK_ALLOC) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+        dev_allocs.push_back(p);
+        if (kind == KIND_UNET) weight_allocs.push_back({p, bytes});      // the other engines share upload16 / upload32 but have no refresh and no digest
+        weight_bytes += bytes;
+        return p;
+    }
+    if (walk_next >= weight_allocs.size() || weight_allocs[walk_next].bytes != bytes) {
+        walk_err = "the weight layout differs from the one ldx_finalize built (plan switches changed since?)";
+        return nullptr;
+    }
+    return weight_allocs[walk_next++].p;
+}
+
 // upload a [rows][cols] matrix produced by getter(r, c) as 16-bit
 void* Engine::upload16(size_t rows, size_t cols, const std::function<float(size_t, size_t)>& getter) {
+    void* p = weight_buf(rows * cols * 2);
+    if (!p || walk_mode == WALK_CHECK) return p;
     std::vector<uint16_t> buf(rows * cols);
     const bool bf = dt == DT_BF16;
     parallel_for(rows, [&](size_t b, size_t e) {
@@ -185,34 +178,91 @@ void* Engine::upload16(size_t rows, size_t cols, const std::function<float(size_
                 buf[r * cols + c] = bf ? float_to_bf16(v) : float_to_half(v);
             }
     });
-    void* p = nullptr;
-    if (hipMalloc(&p, buf.size() * 2) != hipSuccess) return nullptr;
-    dev_allocs.push_back(p);
     if (hipMemcpy(p, buf.data(), buf.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    weight_bytes += buf.size() * 2;
     return p;
 }
 float* Engine::upload32(size_t n, const std::function<float(size_t)>& getter) {
+    void* p = weight_buf(n * 4);
+    if (!p || walk_mode == WALK_CHECK) return (float*)p;
     std::vector<float> buf(n);
     for (size_t i = 0; i < n; ++i) buf[i] = getter(i);
-    void* p = nullptr;
-    if (hipMalloc(&p, n * 4) != hipSuccess) return nullptr;
-    dev_allocs.push_back(p);
     if (hipMemcpy(p, buf.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    weight_bytes += n * 4;
     return (float*)p;
+}
+
+// ---- device packing (pack.hip): the same buffers from sources that live on the GPU ----
+static bool on_device(std::initializer_list<const HostTensor*> ts) {
+    for (const HostTensor* t : ts) if (t && t->dev) return true;
+    return false;
+}
+// the device address of a source: its own, or a staged raw copy of a host tensor that shares a packed buffer with device tensors
+const void* Engine::dev_src(const HostTensor* t) {
+    if (t->dev) return t->dev;
+    auto it = staged.find(t);
+    if (it != staged.end()) return it->second;
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(t->data.size(), 4)) != hipSuccess) return nullptr;
+    staged[t] = p;
+    if (hipMemcpy(p, t->data.data(), t->data.size(), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return p;
+}
+void Engine::drop_staged() {
+    for (auto& kv : staged) (void)hipFree(kv.second);
+    staged.clear();
+}
+void* Engine::pack16(size_t rows, size_t cols, const std::vector<Piece>& pieces) {
+    void* p = weight_buf(rows * cols * 2);
+    if (!p) return p;
+    for (const Piece& pc : pieces) {
+        // What the kernel's 16-byte stores and its index arithmetic rely on; the pieces must lie inside [rows][cols].  validate() guarantees the
+        // divisibility for every UNet it accepts (all channel counts and context_dim are multiples of 64, conv_in is padded to 64), so the device path
+        // takes every shape the host path takes; the test runs in every walk mode, so a refresh would report it before anything is written.
+        if (pc.K % 8 || cols % 8 || pc.col0 % 8 || pc.CinPad % 8 || pc.row0 + pc.N > rows || pc.col0 + pc.K > cols ||
+            (pc.CinPad ? (pc.K != 9 * pc.CinPad || pc.Cin > pc.CinPad || pc.src->numel != (size_t)pc.N * pc.Cin * 9)
+                       : pc.src->numel != (size_t)(pc.geglu_inner ? 2 * pc.geglu_inner : pc.N) * pc.K) ||
+            (pc.geglu_inner && (pc.N != 2 * pc.geglu_inner || pc.geglu_inner % 32))) {
+            walk_err = "pack16: piece outside the packed matrix or not 16-byte granular";
+            return nullptr;
+        }
+        if (walk_mode == WALK_CHECK) continue;
+        PackArgs a; memset(&a, 0, sizeof(a));
+        a.src = dev_src(pc.src); a.sdt = pc.src->dtype;
+        if (!a.src) return nullptr;
+        a.out = (uint16_t*)p + pc.row0 * cols; a.ldo = (long)cols; a.col0 = (long)pc.col0; a.out_dt = dt;
+        a.N = pc.N; a.K = pc.K; a.Cin = pc.Cin; a.CinPad = pc.CinPad; a.geglu_inner = pc.geglu_inner; a.scale = pc.scale;
+        launch_pack16(a, nullptr);
+    }
+    return p;
+}
+float* Engine::pack32(size_t n, const std::vector<VecPiece>& pieces) {
+    float* p = (float*)weight_buf(n * 4);
+    if (!p) return p;
+    for (const VecPiece& pc : pieces) {
+        if (pc.off + pc.n > n || pc.a->numel != (size_t)pc.n || (pc.b && pc.b->numel != (size_t)pc.n) || (pc.geglu_inner && pc.n != 2 * pc.geglu_inner)) {
+            walk_err = "pack32: piece outside the packed vector";
+            return nullptr;
+        }
+        if (walk_mode == WALK_CHECK) continue;
+        PackVecArgs a; memset(&a, 0, sizeof(a));
+        a.a = dev_src(pc.a); a.a_dt = pc.a->dtype;
+        if (!a.a) return nullptr;
+        if (pc.b) { a.b = dev_src(pc.b); a.b_dt = pc.b->dtype; if (!a.b) return nullptr; }
+        a.out = p + pc.off; a.n = pc.n; a.geglu_inner = pc.geglu_inner;
+        launch_pack32(a, nullptr);
+    }
+    return p;
 }
 
 bool Engine::mk_linear(const std::string& pre, int N, int K, bool bias, LinearW& out, bool conv1x1) {
     const HostTensor* w = conv1x1 ? get(pre + ".weight", {N, K, 1, 1}) : get(pre + ".weight", {N, K});
     if (!w) return false;
     out.N = N; out.K = K;
-    out.w = upload16(N, K, [&](size_t r, size_t c) { return w->at(r * K + c); });
+    out.w = w->dev ? pack16(N, K, {rows_piece(w, 0, N, K)}) : upload16(N, K, [&](size_t r, size_t c) { return w->at(r * K + c); });
     out.b = nullptr;
     if (bias) {
         const HostTensor* b = get(pre + ".bias", {N});
         if (!b) return false;
-        out.b = upload32(N, [&](size_t i) { return b->at(i); });
+        out.b = b->dev ? pack32(N, {{b, nullptr, 0, N, 0}}) : upload32(N, [&](size_t i) { return b->at(i); });
         if (!out.b) return false;
     }
     return out.w != nullptr;
@@ -223,12 +273,13 @@ bool Engine::mk_conv3(const std::string& pre, int Cout, int Cin, int CinPad, Lin
     if (!w || !b) return false;
     out.N = Cout; out.K = 9 * CinPad;
     // [Cout][ky][kx][CinPad]  <-  [Cout][Cin][ky][kx]
-    out.w = upload16(Cout, (size_t)9 * CinPad, [&](size_t r, size_t c) {
+    if (w->dev) out.w = pack16(Cout, (size_t)9 * CinPad, {Piece{w, 0, 0, Cout, 9 * CinPad, 1.0f, 0, Cin, CinPad}});
+    else out.w = upload16(Cout, (size_t)9 * CinPad, [&](size_t r, size_t c) {
         const size_t tap = c / CinPad, ci = c % CinPad;
         if ((int)ci >= Cin) return 0.f;
         return w->at((r * Cin + ci) * 9 + tap);
     });
-    out.b = upload32(Cout, [&](size_t i) { return b->at(i); });
+    out.b = b->dev ? pack32(Cout, {{b, nullptr, 0, Cout, 0}}) : upload32(Cout, [&](size_t i) { return b->at(i); });
     return out.w && out.b;
 }
 bool Engine::mk_norm(const std::string& pre, int C, NormW& out) {
@@ -236,25 +287,52 @@ bool Engine::mk_norm(const std::string& pre, int C, NormW& out) {
     const HostTensor* b = get(pre + ".bias", {C});
     if (!w || !b) return false;
     out.C = C;
-    out.g = upload32(C, [&](size_t i) { return w->at(i); });
-    out.b = upload32(C, [&](size_t i) { return b->at(i); });
+    out.g = w->dev ? pack32(C, {{w, nullptr, 0, C, 0}}) : upload32(C, [&](size_t i) { return w->at(i); });
+    out.b = b->dev ? pack32(C, {{b, nullptr, 0, C, 0}}) : upload32(C, [&](size_t i) { return b->at(i); });
     return out.g && out.b;
 }
 
 // Linear(LayerNorm(x)) with the norm folded in: y = rstd (x W'^T - mean c1) + c2 with W' = W .* gamma (per input column), c1[n] = sum_k W'[n][k]
 // (of the values as STORED in 16 bit: the epilogue subtracts exactly what the MFMA accumulated for a constant row) and c2 = W beta + b.
 bool Engine::mk_ln_folded(int N, int K, const std::function<float(size_t, size_t)>& W, const std::function<float(size_t)>& bias,
-                          const std::string& norm_pre, LinearW& out, float*& c1) {
+                          const std::string& norm_pre, LinearW& out, float*& c1, const std::vector<Piece>& pieces, const HostTensor* bias_t) {
     const HostTensor* g = get(norm_pre + ".weight", {K});
     const HostTensor* be = get(norm_pre + ".bias", {K});
     if (!g || !be) return false;
+    bool dev = on_device({g, be, bias_t});
+    for (const Piece& pc : pieces) dev = dev || pc.src->dev;
+    if (dev) {
+        // the three buffers in the host path's order, then one launch per source (ln_fold_kernel writes its rows of all three)
+        out.N = N; out.K = K;
+        out.w = weight_buf((size_t)N * K * 2);
+        c1 = (float*)weight_buf((size_t)N * 4);
+        out.b = (float*)weight_buf((size_t)N * 4);
+        if (!out.w || !c1 || !out.b) return false;
+        for (const Piece& pc : pieces) {
+            if (K % 8 || pc.K != K || pc.row0 + pc.N > (size_t)N || (pc.geglu_inner && (pc.N != 2 * pc.geglu_inner || pc.N != N)) ||
+                pc.src->numel != (size_t)pc.N * K || (bias_t && (pieces.size() != 1 || pc.row0 || bias_t->numel != (size_t)N))) {
+                walk_err = "mk_ln_folded: piece outside the packed matrix";
+                return false;
+            }
+            if (walk_mode == WALK_CHECK) continue;
+            LnFoldArgs a; memset(&a, 0, sizeof(a));
+            a.src = dev_src(pc.src); a.sdt = pc.src->dtype;
+            a.gamma = dev_src(g); a.g_dt = g->dtype; a.beta = dev_src(be); a.b_dt = be->dtype;
+            if (bias_t) { a.bias = dev_src(bias_t); a.bias_dt = bias_t->dtype; if (!a.bias) return false; }
+            if (!a.src || !a.gamma || !a.beta) return false;
+            a.out = (uint16_t*)out.w + pc.row0 * K; a.out_dt = dt; a.c1 = c1 + pc.row0; a.c2 = out.b + pc.row0;
+            a.N = pc.N; a.K = K; a.geglu_inner = pc.geglu_inner; a.scale = pc.scale;
+            launch_ln_fold(a, nullptr);
+        }
+        return true;
+    }
     std::vector<float> gam(K), bet(K);
     for (int k = 0; k < K; ++k) { gam[k] = g->at(k); bet[k] = be->at(k); }
     out.N = N; out.K = K;
     out.w = upload16(N, K, [&](size_t r, size_t c) { return W(r, c) * gam[c]; });
     std::vector<float> v1(N), v2(N);
     const bool bf = dt == DT_BF16;
-    parallel_for(N, [&](size_t b, size_t e) {
+    if (walk_mode != WALK_CHECK) parallel_for(N, [&](size_t b, size_t e) {
         for (size_t r = b; r < e; ++r) {
             double s1 = 0.0, s2 = 0.0;
             for (int k = 0; k < K; ++k) {
@@ -295,12 +373,14 @@ bool Engine::mk_res(const std::string& pre, int Cin, int Cout, ResW& r) {
             if (!w2 || !b2 || !ws || !bs) return false;
             r.fused_skip = true;
             r.conv2.N = Cout; r.conv2.K = 9 * Cout + Cin;
-            r.conv2.w = upload16(Cout, (size_t)9 * Cout + Cin, [&](size_t rr, size_t c) {
+            if (on_device({w2, ws})) r.conv2.w = pack16(Cout, (size_t)9 * Cout + Cin, {Piece{w2, 0, 0, Cout, 9 * Cout, 1.0f, 0, Cout, Cout},
+                                                                                     Piece{ws, 0, (size_t)9 * Cout, Cout, Cin, 1.0f, 0, 0, 0}});
+            else r.conv2.w = upload16(Cout, (size_t)9 * Cout + Cin, [&](size_t rr, size_t c) {
                 if (c >= (size_t)9 * Cout) return ws->at(rr * Cin + (c - (size_t)9 * Cout));
                 const size_t tap = c / Cout, ci = c % Cout;
                 return w2->at((rr * Cout + ci) * 9 + tap);
             });
-            r.conv2.b = upload32(Cout, [&](size_t i) { return b2->at(i) + bs->at(i); });
+            r.conv2.b = on_device({b2, bs}) ? pack32(Cout, {{b2, bs, 0, Cout, 0}}) : upload32(Cout, [&](size_t i) { return b2->at(i) + bs->at(i); });
             return r.conv2.w && r.conv2.b;
         }
         if (!mk_linear(pre + ".skip_connection", Cout, Cin, true, r.skip, true)) return false;
@@ -343,16 +423,17 @@ bool Engine::mk_xf(const std::string& pre, int C, int depth, XfW& x) {
         };
         const HostTensor* q2w = get(bp + ".attn2.to_q.weight", {C, C});
         if (!q2w) return false;
+        const std::vector<Piece> qkv_p{rows_piece(q, 0, C, C, cq), rows_piece(k, C, C, C), rows_piece(v, (size_t)2 * C, C, C)}, q2_p{rows_piece(q2w, 0, C, C, cq)};
         if (b.ln_fold) {
-            if (!mk_ln_folded(3 * C, C, qkv_w, nullptr, bp + ".norm1", b.qkv_f, b.c1_qkv)) return false;
-            if (!mk_ln_folded(C, C, [&](size_t r, size_t c) { return q2w->at(r * C + c) * cq; }, nullptr, bp + ".norm2", b.q2_f, b.c1_q2)) return false;
+            if (!mk_ln_folded(3 * C, C, qkv_w, nullptr, bp + ".norm1", b.qkv_f, b.c1_qkv, qkv_p, nullptr)) return false;
+            if (!mk_ln_folded(C, C, [&](size_t r, size_t c) { return q2w->at(r * C + c) * cq; }, nullptr, bp + ".norm2", b.q2_f, b.c1_q2, q2_p, nullptr)) return false;
         }
         {
             b.qkv.N = 3 * C; b.qkv.K = C; b.qkv.b = nullptr;
-            b.qkv.w = upload16((size_t)3 * C, C, qkv_w);
+            b.qkv.w = on_device({q, k, v}) ? pack16((size_t)3 * C, C, qkv_p) : upload16((size_t)3 * C, C, qkv_w);
             if (!b.qkv.w) return false;
             b.q2.N = C; b.q2.K = C; b.q2.b = nullptr;
-            b.q2.w = upload16(C, C, [&](size_t r, size_t c) { return q2w->at(r * C + c) * cq; });
+            b.q2.w = q2w->dev ? pack16(C, C, q2_p) : upload16(C, C, [&](size_t r, size_t c) { return q2w->at(r * C + c) * cq; });
             if (!b.q2.w) return false;
         }
         if (!mk_linear(bp + ".attn1.to_out.0", C, C, true, b.o1)) return false;
@@ -370,14 +451,15 @@ bool Engine::mk_xf(const std::string& pre, int C, int depth, XfW& x) {
         const HostTensor* fb = get(bp + ".ff.net.0.proj.bias", {2 * inner});
         if (!fw || !fb) return false;
         auto src_row = [inner](size_t r) { const size_t slab = r / 64, within = r % 64; return within < 32 ? slab * 32 + within : inner + slab * 32 + (within - 32); };
+        const std::vector<Piece> ff1_p{rows_piece(fw, 0, 2 * inner, C, 1.0f, inner)};
         if (b.ln_fold) {
             if (!mk_ln_folded(2 * inner, C, [&](size_t r, size_t c) { return fw->at(src_row(r) * C + c); }, [&](size_t i) { return fb->at(src_row(i)); },
-                              bp + ".norm3", b.ff1_f, b.c1_ff1)) return false;
+                              bp + ".norm3", b.ff1_f, b.c1_ff1, ff1_p, fb)) return false;
         }
         {
             b.ff1.N = 2 * inner; b.ff1.K = C;
-            b.ff1.w = upload16((size_t)2 * inner, C, [&](size_t r, size_t c) { return fw->at(src_row(r) * C + c); });
-            b.ff1.b = upload32((size_t)2 * inner, [&](size_t i) { return fb->at(src_row(i)); });
+            b.ff1.w = fw->dev ? pack16((size_t)2 * inner, C, ff1_p) : upload16((size_t)2 * inner, C, [&](size_t r, size_t c) { return fw->at(src_row(r) * C + c); });
+            b.ff1.b = fb->dev ? pack32((size_t)2 * inner, {{fb, nullptr, 0, 2 * inner, inner}}) : upload32((size_t)2 * inner, [&](size_t i) { return fb->at(src_row(i)); });
             if (!b.ff1.w || !b.ff1.b) return false;
         }
         if (!mk_linear(bp + ".ff.net.2", C, inner, true, b.ff2)) return false;
@@ -385,13 +467,15 @@ bool Engine::mk_xf(const std::string& pre, int C, int depth, XfW& x) {
     return true;
 }
 
-int Engine::finalize() {
-    if (finalized) return LDX_OK;
-    if (kind != KIND_UNET) { set_error("finalize(): wrong engine kind"); return LDX_ESTATE; }
-    int rc = validate();
-    if (rc) return rc;
-    HIP_OK(hipSetDevice(device));
-    if (!d_log_sigmas) { set_error("ldx_finalize: call ldx_set_tables first"); return LDX_ESTATE; }
+// The structure walk: every packed weight buffer of the UNet from the registered tensors, in one fixed order.  walk_mode says what a buffer is:
+// a new allocation (finalize), nothing (refresh: keys and shapes only) or the allocation finalize made (refresh: refill).  Whatever the mode, the
+// walk rebuilds the weight structs from scratch and, when it succeeds, leaves them holding the same pointers.
+int Engine::walk_weights() {
+    te0 = te2 = conv_in = conv_out = emb_all = kv_all = LinearW{}; out_gn = NormW{};
+    in_blocks.clear(); out_blocks.clear();
+    has_middle = mid_has_xf = false; mid_res0 = mid_res1 = ResW{}; mid_xf = XfW{};
+    emb_total = 0; kv_total = 0; emb_srcs.clear(); kv_srcs.clear();
+    missing.clear(); walk_err.clear(); walk_next = 0;
     const int mc = cfg.model_channels, ted = 4 * mc;
     bool ok = true;
     // --- structure walk, identical in order to UNetModel1.__init__ (unet.py:344-677) ---
@@ -455,8 +539,16 @@ int Engine::finalize() {
         for (auto& s : emb_srcs) { starts.push_back(acc); acc += s.n; }
         auto find = [&](size_t r) { size_t i = std::upper_bound(starts.begin(), starts.end(), r) - starts.begin() - 1; return i; };
         emb_all.N = emb_total; emb_all.K = ted;
-        emb_all.w = upload16(emb_total, ted, [&](size_t r, size_t c) { const size_t i = find(r); return emb_srcs[i].w->at((r - starts[i]) * ted + c); });
-        emb_all.b = upload32(emb_total, [&](size_t r) { const size_t i = find(r); return emb_srcs[i].b->at(r - starts[i]); });
+        bool w_dev = false, b_dev = false;
+        std::vector<Piece> wp; std::vector<VecPiece> bp;
+        for (size_t i = 0; i < emb_srcs.size(); ++i) {
+            w_dev = w_dev || emb_srcs[i].w->dev; b_dev = b_dev || emb_srcs[i].b->dev;
+            wp.push_back(rows_piece(emb_srcs[i].w, starts[i], emb_srcs[i].n, ted));
+            bp.push_back({emb_srcs[i].b, nullptr, starts[i], emb_srcs[i].n, 0});
+        }
+        emb_all.w = w_dev ? pack16(emb_total, ted, wp)
+                          : upload16(emb_total, ted, [&](size_t r, size_t c) { const size_t i = find(r); return emb_srcs[i].w->at((r - starts[i]) * ted + c); });
+        emb_all.b = b_dev ? pack32(emb_total, bp) : upload32(emb_total, [&](size_t r) { const size_t i = find(r); return emb_srcs[i].b->at(r - starts[i]); });
         ok = emb_all.w && emb_all.b;
     }
     if (ok && kv_total > 0) {
@@ -464,22 +556,107 @@ int Engine::finalize() {
         for (auto& s2 : kv_srcs) { starts.push_back(acc); acc += 2 * (size_t)s2.C; }
         const int ctxd = cfg.context_dim;
         kv_all.N = kv_total; kv_all.K = ctxd; kv_all.b = nullptr;
-        kv_all.w = upload16(kv_total, ctxd, [&](size_t r, size_t c) {
+        bool kv_dev = false;
+        std::vector<Piece> kvp;
+        for (size_t i = 0; i < kv_srcs.size(); ++i) {
+            const int C = kv_srcs[i].C;
+            kv_dev = kv_dev || kv_srcs[i].k->dev || kv_srcs[i].v->dev;
+            kvp.push_back(rows_piece(kv_srcs[i].k, starts[i], C, ctxd));
+            kvp.push_back(rows_piece(kv_srcs[i].v, starts[i] + C, C, ctxd));
+        }
+        kv_all.w = kv_dev ? pack16(kv_total, ctxd, kvp) : upload16(kv_total, ctxd, [&](size_t r, size_t c) {
             const size_t i = std::upper_bound(starts.begin(), starts.end(), r) - starts.begin() - 1;
             const size_t rr = r - starts[i]; const int C = kv_srcs[i].C;
             return (rr < (size_t)C ? kv_srcs[i].k : kv_srcs[i].v)->at((rr % C) * ctxd + c);
         });
         ok = kv_all.w != nullptr;
     }
+    emb_srcs.clear(); kv_srcs.clear();
+    if (ok && walk_mode != WALK_ALLOC && walk_next != weight_allocs.size()) { ok = false; walk_err = "the weight layout differs from the one ldx_finalize built (plan switches changed since?)"; }
+    // the device packers run on the null stream, in order behind the host path's copies: one wait for all of them, then the staged copies can go
+    hipError_t sync = ok && walk_mode != WALK_CHECK ? hipDeviceSynchronize() : hipSuccess;
+    if (sync == hipSuccess && walk_mode != WALK_CHECK) sync = hipGetLastError();
+    drop_staged();
     if (!ok) {
         if (!missing.empty()) { set_error("missing or mis-shaped weight: " + missing); return LDX_EMISSING; }
+        if (!walk_err.empty()) { set_error(walk_err); return LDX_ESTATE; }
         set_error(std::string("weight upload failed: ") + hipGetErrorString(hipGetLastError()));
         return LDX_EHIP;
     }
-    emb_srcs.clear(); kv_srcs.clear();
+    if (sync != hipSuccess) { set_error(std::string("weight packing failed: ") + hipGetErrorString(sync)); return LDX_EHIP; }
+    return LDX_OK;
+}
+
+int Engine::finalize() {
+    if (finalized) return LDX_OK;
+    if (kind != KIND_UNET) { set_error("finalize(): wrong engine kind"); return LDX_ESTATE; }
+    int rc = validate();
+    if (rc) return rc;
+    HIP_OK(hipSetDevice(device));
+    if (!d_log_sigmas) { set_error("ldx_finalize: call ldx_set_tables first"); return LDX_ESTATE; }
+    walk_mode = WALK_ALLOC;
+    if ((rc = walk_weights())) return rc;
     host.clear();
     { const int rc2 = build_emb_table(); if (rc2) return rc2; }
     finalized = true;
+    return LDX_OK;
+}
+
+int Engine::refresh_begin() {
+    if (kind != KIND_UNET || !finalized) { set_error("ldx_unet_refresh_begin: not a finalized UNet engine"); return LDX_ESTATE; }
+    host.clear();                          // a second begin starts over
+    refreshing = true;
+    return LDX_OK;
+}
+
+int Engine::refresh_abort() {
+    if (kind != KIND_UNET || !finalized) { set_error("ldx_unet_refresh_abort: not a finalized UNet engine"); return LDX_ESTATE; }
+    host.clear();
+    refreshing = false;
+    return LDX_OK;
+}
+
+int Engine::refresh_commit() {
+    if (kind != KIND_UNET || !finalized || !refreshing) { set_error("ldx_unet_refresh_commit: call ldx_unet_refresh_begin first"); return LDX_ESTATE; }
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipDeviceSynchronize());        // no forward still reads the buffers about to be rewritten
+    // every key and shape first, with nothing written: a failing walk leaves half-built weight structs behind, so the present ones are put back
+    struct Saved { LinearW te0, te2, conv_in, conv_out, emb_all, kv_all; NormW out_gn; std::vector<BlockW> in_blocks, out_blocks; bool has_middle, mid_has_xf;
+                   ResW mid_res0, mid_res1; XfW mid_xf; int emb_total, kv_total; };
+    Saved sv{te0, te2, conv_in, conv_out, emb_all, kv_all, out_gn, in_blocks, out_blocks, has_middle, mid_has_xf, mid_res0, mid_res1, mid_xf, emb_total, kv_total};
+    walk_mode = WALK_CHECK;
+    int rc = walk_weights();
+    if (rc == LDX_OK) {
+        walk_mode = WALK_REFILL;
+        rc = walk_weights();               // an error from here on (a HIP failure) leaves the weights partly rewritten
+    } else {
+        const std::string err = g_last_error;
+        te0 = sv.te0; te2 = sv.te2; conv_in = sv.conv_in; conv_out = sv.conv_out; emb_all = sv.emb_all; kv_all = sv.kv_all; out_gn = sv.out_gn;
+        in_blocks = std::move(sv.in_blocks); out_blocks = std::move(sv.out_blocks); has_middle = sv.has_middle; mid_has_xf = sv.mid_has_xf;
+        mid_res0 = sv.mid_res0; mid_res1 = sv.mid_res1; mid_xf = std::move(sv.mid_xf); emb_total = sv.emb_total; kv_total = sv.kv_total;
+        set_error(err);
+    }
+    walk_mode = WALK_ALLOC;
+    host.clear();
+    refreshing = false;                    // either way the refresh is over: the engine holds the new weights, or (validation failed) still the old ones
+    if (rc) return rc;
+    ++ctx_epoch;                           // cached k|v projections of the context were made with the old weights
+    return build_emb_table();
+}
+
+int Engine::weights_digest(uint64_t* out) {
+    if (kind != KIND_UNET || !finalized) { set_error("ldx_weights_digest: not a finalized UNet engine"); return LDX_ESTATE; }
+    if (!out) { set_error("ldx_weights_digest: bad argument"); return LDX_EINVAL; }
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipDeviceSynchronize());
+    uint64_t h = 0xcbf29ce484222325ull;
+    std::vector<uint8_t> buf;
+    for (const WeightAlloc& a : weight_allocs) {
+        buf.resize(a.bytes);
+        HIP_OK(hipMemcpy(buf.data(), a.p, a.bytes, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < a.bytes; ++i) { h ^= buf[i]; h *= 0x100000001b3ull; }
+    }
+    *out = h;
     return LDX_OK;
 }
 
@@ -1012,26 +1189,29 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
 // The 22 emb_layers outputs for EVERY timestep of the table (ldx_set_tables), by the same three skinny launches a forward would run on its B2 rows:
 // row t of d_emb_table is bit-identical to what those launches write for a sample whose timestep index is t (the skinny kernel's rows are independent).
 int Engine::build_emb_table() {
-    if (!g_plan_sw.emb_table || d_emb_table || !d_temb || n_sigmas <= 0 || emb_total <= 0 || emb_total % 4) return LDX_OK;
+    if (!g_plan_sw.emb_table || !d_temb || n_sigmas <= 0 || emb_total <= 0 || emb_total % 4) return LDX_OK;
+    if (finalized && !d_emb_table) return LDX_OK;        // a refresh rebuilds the table finalize() built, in place (the plans hold its address); it never adds one
+    const bool refill = d_emb_table != nullptr;
     const int mc = cfg.model_channels, ted = 4 * mc, n = n_sigmas;
-    float *e1 = nullptr, *e2 = nullptr, *tab = nullptr;
+    float *e1 = nullptr, *e2 = nullptr, *tab = d_emb_table;
     auto fail = [&](hipError_t err, const char* what) {       // nothing of a half-built table survives an error
         if (e1) (void)hipFree(e1);
         if (e2) (void)hipFree(e2);
-        if (tab) (void)hipFree(tab);
+        if (tab && !refill) (void)hipFree(tab);
         set_error(std::string(what) + ": " + hipGetErrorString(err));
         return LDX_EHIP;
     };
     hipError_t err;
     if ((err = hipMalloc((void**)&e1, (size_t)n * ted * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
     if ((err = hipMalloc((void**)&e2, (size_t)n * ted * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
-    if ((err = hipMalloc((void**)&tab, (size_t)n * emb_total * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
+    if (!refill && (err = hipMalloc((void**)&tab, (size_t)n * emb_total * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
     launch_skinny(skinny_args(d_temb, mc, te0.w, te0.b, e1, ted, n, ted, mc, 0, 1), dt, nullptr);
     launch_skinny(skinny_args(e1, ted, te2.w, te2.b, e2, ted, n, ted, ted, 0, 1), dt, nullptr);
     launch_skinny(skinny_args(e2, ted, emb_all.w, emb_all.b, tab, emb_total, n, emb_total, ted, 0, 0), dt, nullptr);
     if ((err = hipStreamSynchronize(nullptr)) != hipSuccess) return fail(err, "build_emb_table: hipStreamSynchronize");
     if ((err = hipGetLastError()) != hipSuccess) return fail(err, "build_emb_table: kernel launch");
     (void)hipFree(e1); (void)hipFree(e2);
+    if (refill) return LDX_OK;
     dev_allocs.push_back(tab);
     d_emb_table = tab;
     weight_bytes += (size_t)n * emb_total * 4;

@@ -27,11 +27,14 @@ int launch_status();          // LDX_EHIP (and the error text) when a kernel lau
         }                                                                                    \
     } while (0)
 
+// A state-dict tensor as registered: a host copy (ldx_load_tensor: `data`), or the caller's own device memory (ldx_load_tensor_device: `dev`,
+// not copied, `data` empty; UNet engine only).  at() reads the host copy.
 struct HostTensor {
     int dtype = LDX_F32;
     std::vector<int64_t> shape;
     std::vector<uint8_t> data;
     size_t numel = 0;
+    const void* dev = nullptr;
     float at(size_t i) const;
 };
 
@@ -184,8 +187,16 @@ public:
     ~Engine();
     int validate() const;
     int load_tensor(const char* key, const void* data, int dtype, const int64_t* shape, int ndim);
+    int load_tensor_device(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
     int set_tables(const float* ls, int n, const float* temb, int dim);
     int finalize();
+    // Replace the weights of a finalized UNet engine in place (ldx_unet_refresh_begin / _commit): begin re-opens the two loaders, commit validates
+    // the full key set (nothing written on LDX_EMISSING), then runs the structure walk again into the SAME device allocations, rebuilds the
+    // emb_layers table and drops the cached context projections.  No pointer a plan or a captured graph holds changes.
+    int refresh_begin();
+    int refresh_commit();
+    int refresh_abort();                   // forget an unfinished refresh: the loaders close again, the weights are untouched
+    int weights_digest(uint64_t* out);     // FNV-1a over host copies of every weight allocation, in allocation order
     // c_concat [B2][cc_channels][h][w] (fp32, may be null): appended unscaled behind the scaled x, which then carries in_channels - cc_channels channels
     // t_idx [B2] (device fp32, may be null; denoise only): timestep indices supplied by the caller instead of the device's own sigma -> index lookup
     int run(const float* x, const float* sigma_or_t, const float* ctx, int B2, int h, int w, int Mc, float* out, bool denoise, hipStream_t st, int xB = 0,
@@ -238,13 +249,35 @@ private:
     std::string missing;
     std::vector<void*> dev_allocs;
     const HostTensor* get(const std::string& key, std::initializer_list<int64_t> shape);
+    // The structure walk (walk_weights: the mk_* calls in UNetModel1.__init__ order) runs in three modes over the same sequence of weight buffers:
+    // ALLOC (finalize) allocates each one, CHECK (refresh) only resolves keys and shapes, REFILL (refresh) writes into the allocations ALLOC made.
+    enum WalkMode { WALK_ALLOC, WALK_CHECK, WALK_REFILL };
+    WalkMode walk_mode = WALK_ALLOC;
+    struct WeightAlloc { void* p; size_t bytes; };
+    std::vector<WeightAlloc> weight_allocs;                // every upload16 / upload32 / pack16 / pack32 buffer, in allocation order
+    size_t walk_next = 0;                                  // CHECK / REFILL: the next entry of weight_allocs
+    std::string walk_err;
+    bool refreshing = false;                               // between refresh_begin and refresh_commit
+    void* weight_buf(size_t bytes);                        // the walk's next weight buffer (null: error)
+    int walk_weights();
     void* upload16(size_t rows, size_t cols, const std::function<float(size_t, size_t)>& getter);
     float* upload32(size_t n, const std::function<float(size_t)>& getter);
+    // device-side counterparts (pack.hip) for groups with a source registered by ldx_load_tensor_device; host sources of such a group are staged
+    // (raw copy, freed when the walk ends).  Same buffers in the same order as the host path: either can refill what the other allocated.
+    struct Piece { const HostTensor* src; size_t row0, col0; int N, K; float scale; int geglu_inner; int Cin, CinPad; };
+    static Piece rows_piece(const HostTensor* src, size_t row0, int N, int K, float scale = 1.0f, int geglu_inner = 0) { return Piece{src, row0, 0, N, K, scale, geglu_inner, 0, 0}; }
+    struct VecPiece { const HostTensor* a; const HostTensor* b; size_t off; int n; int geglu_inner; };
+    std::unordered_map<const HostTensor*, void*> staged;
+    const void* dev_src(const HostTensor* t);
+    void drop_staged();
+    void* pack16(size_t rows, size_t cols, const std::vector<Piece>& pieces);
+    float* pack32(size_t n, const std::vector<VecPiece>& pieces);
     bool mk_linear(const std::string& pre, int N, int K, bool bias, LinearW& out, bool conv1x1 = false);
     bool mk_conv3(const std::string& pre, int Cout, int Cin, int CinPad, LinearW& out);
     bool mk_norm(const std::string& pre, int C, NormW& out);
+    // pieces / bias_t: the same W and bias as sources, for the device path
     bool mk_ln_folded(int N, int K, const std::function<float(size_t, size_t)>& W, const std::function<float(size_t)>& bias,
-                      const std::string& norm_pre, LinearW& out, float*& c1);
+                      const std::string& norm_pre, LinearW& out, float*& c1, const std::vector<Piece>& pieces, const HostTensor* bias_t);
     bool mk_res(const std::string& pre, int Cin, int Cout, ResW& r);
     bool mk_xf(const std::string& pre, int C, int depth, XfW& x);
 

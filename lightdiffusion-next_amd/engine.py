@@ -70,23 +70,69 @@ class UNetEngine:
         c.transformer_depth_middle = cfg.transformer_depth_middle
         c.num_heads, c.context_dim = cfg.num_heads, cfg.context_dim
         lib.check(self._lib.ldx_create(C.byref(c), device, C.byref(self._h)), "ldx_create")
+        try:
+            keep = self._load_state_dict(state_dict)
+            self.sigmas, self.log_sigmas = sd15_sigmas()
+            temb = timestep_embedding_table(self.sigmas.numel(), cfg.model_channels)
+            lib.check(self._lib.ldx_set_tables(self._h, lib.ptr(self.log_sigmas), self.log_sigmas.numel(),
+                                               lib.ptr(temb), temb.shape[1]), "ldx_set_tables")
+            lib.check(self._lib.ldx_finalize(self._h), "ldx_finalize")
+            del keep
+        except Exception:
+            self.close()
+            raise
+        if graph:
+            self.set_graph_mode(True)
+
+    def _load_state_dict(self, state_dict):
+        """Register every tensor of a state dict.  A tensor on the engine's device is handed over where it lies (ldx_load_tensor_device: not copied,
+        packed by device kernels); anything on the host goes through ldx_load_tensor, which copies it.  Returns the tensors whose memory the engine
+        refers to: the caller keeps them alive until ldx_finalize / ldx_unet_refresh_commit has returned."""
         prefix = "model.diffusion_model."
+        keep = []
         for k, t in state_dict.items():
             if k.startswith(prefix):
                 k = k[len(prefix):]
-            t = t.detach().to("cpu").contiguous()
-            if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-                t = t.float()
+            t = t.detach()
+            if t.is_cuda:
+                if t.device != self.device:
+                    raise ValueError(f"{k}: tensor on {t.device}, the engine is on {self.device} (move the state dict to the host or to that device)")
+                if not t.is_contiguous():
+                    raise ValueError(f"{k}: a device tensor must be contiguous (it is read where it lies, not copied)")
+                if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                    t = t.float()
+                keep.append(t)
+                load, name = self._lib.ldx_load_tensor_device, "ldx_load_tensor_device"
+            else:
+                t = t.to("cpu").contiguous()
+                if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                    t = t.float()
+                load, name = self._lib.ldx_load_tensor, "ldx_load_tensor"
             shape = (C.c_int64 * t.dim())(*t.shape)
-            lib.check(self._lib.ldx_load_tensor(self._h, k.encode(), lib.ptr(t), lib.torch_dtype_code(t.dtype),
-                                                shape, t.dim()), f"ldx_load_tensor({k})")
-        self.sigmas, self.log_sigmas = sd15_sigmas()
-        temb = timestep_embedding_table(self.sigmas.numel(), cfg.model_channels)
-        lib.check(self._lib.ldx_set_tables(self._h, lib.ptr(self.log_sigmas), self.log_sigmas.numel(),
-                                           lib.ptr(temb), temb.shape[1]), "ldx_set_tables")
-        lib.check(self._lib.ldx_finalize(self._h), "ldx_finalize")
-        if graph:
-            self.set_graph_mode(True)
+            lib.check(load(self._h, k.encode(), lib.ptr(t), lib.torch_dtype_code(t.dtype), shape, t.dim()), f"{name}({k})")
+        if keep:
+            torch.cuda.synchronize(self.device)      # whatever produced the device tensors (a LoRA merge on another stream) has finished
+        return keep
+
+    def refresh(self, state_dict):
+        """Replace the weights in place (ldx_unet_refresh_begin / _commit) from a FULL state dict, host or device tensors as in the constructor: what the
+        reference's ModelPatcher.patch_model / unpatch_model does to its modules when a LoRA changes (ModelPatcher.py:515,652).  Plans, arenas and
+        captured graphs stay; the emb_layers table is rebuilt and cached context projections are dropped.  A state dict with a key missing or
+        mis-shaped raises LdxError naming it and leaves the engine computing with its present weights."""
+        lib.check(self._lib.ldx_unet_refresh_begin(self._h), "ldx_unet_refresh_begin")
+        try:
+            keep = self._load_state_dict(state_dict)
+        except Exception:
+            self._lib.ldx_unet_refresh_abort(self._h)      # forget what was registered and close the loaders again
+            raise
+        lib.check(self._lib.ldx_unet_refresh_commit(self._h), "ldx_unet_refresh_commit")
+        del keep
+
+    def weights_digest(self) -> int:
+        """ldx_weights_digest: FNV-1a over every packed weight buffer (diagnostic: equal digests = bit-identical weights)."""
+        d = C.c_uint64(0)
+        lib.check(self._lib.ldx_weights_digest(self._h, C.byref(d)), "ldx_weights_digest")
+        return int(d.value)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

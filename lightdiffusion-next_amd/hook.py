@@ -22,7 +22,8 @@ class LdxUNetPatch:
 
     @classmethod
     def from_state_dict(cls, state_dict, cfg: UNetConfig = None, device: int = 0, dtype: str = "bf16"):
-        """Snapshot weights once (after ModelPatcher.patch_model, i.e. LoRA already merged: SURVEY §8b)."""
+        """Snapshot weights (after ModelPatcher.patch_model, i.e. LoRA already merged: SURVEY §8b); tensors on the engine's device are packed there,
+        without a round trip through the host.  refresh() takes a later state of the same model."""
         return cls(UNetEngine(cfg or UNetConfig.sd15(), state_dict, device=device, dtype=dtype))
 
     def __call__(self, model_function, params):
@@ -41,6 +42,11 @@ class LdxUNetPatch:
         out = self.engine.denoise(x.to(dev, torch.float32), sigma.to(dev, torch.float32), ctx.to(dev, torch.float32),
                                   c_concat=None if cc is None else cc.to(dev, torch.float32))
         return out if src_device == dev else out.to(src_device)
+
+    def refresh(self, state_dict):
+        """The model's weights changed in place (ModelPatcher.patch_model / unpatch_model, ModelPatcher.py:515,652: a LoRA applied, removed or
+        re-weighted): hand the engine the state dict again.  Same engine, same plans and captured graphs (UNetEngine.refresh)."""
+        self.engine.refresh(state_dict)
 
     def to(self, device):
         return self

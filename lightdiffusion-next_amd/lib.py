@@ -66,8 +66,13 @@ _SIGS = {
     "ldx_create": (_i, [C.POINTER(ldx_unet_config), _i, C.POINTER(_vp)]),
     "ldx_destroy": (None, [_vp]),
     "ldx_load_tensor": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(_i64), _i]),
+    "ldx_load_tensor_device": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(_i64), _i]),
     "ldx_set_tables": (_i, [_vp, _vp, _i, _vp, _i]),
     "ldx_finalize": (_i, [_vp]),
+    "ldx_unet_refresh_begin": (_i, [_vp]),
+    "ldx_unet_refresh_commit": (_i, [_vp]),
+    "ldx_unet_refresh_abort": (_i, [_vp]),
+    "ldx_weights_digest": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "ldx_unet_denoise": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ldx_unet_denoise_cfg": (_i, [_vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ldx_unet_denoise_cfg_t": (_i, [_vp, _vp, C.c_float, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
