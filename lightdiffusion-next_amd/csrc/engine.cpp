@@ -11,7 +11,7 @@
 // activations stay NHWC 16-bit, channel concat is a column offset, and every op is one of the HIP
 // kernels in csrc/*.hip.  No CPU fallback exists: without a HIP device every call fails.
 #include "engine.h"
-#include "weight_convert.h"
+#include "weight_layout.h"
 
 #include <algorithm>
 #include <cmath>
@@ -31,7 +31,7 @@ int launch_status() {
 }
 
 // ---------------------------------------------------------------------------------------------
-// 16-bit conversions (round-to-nearest-even): weight_convert.h, shared with the device packer (pack.hip)
+// 16-bit conversions (round-to-nearest-even): weight_convert.h, one copy for the host and the device packers
 float HostTensor::at(size_t i) const {
     switch (dtype) {
         case LDX_F32: return ((const float*)data.data())[i];
@@ -74,7 +74,7 @@ int Engine::validate() const {
     auto bad = [&](const char* m) { set_error(std::string("unsupported UNet config: ") + m); return LDX_EINVAL; };
     if (cfg.model_channels <= 0 || cfg.model_channels % 64) return bad("model_channels must be a multiple of 64");
     if (cfg.context_dim <= 0 || cfg.context_dim % 64) return bad("context_dim must be a multiple of 64");
-    // these two (every level's channels = model_channels * channel_mult) are also what the device packers' 16-byte stores need (Engine::pack16)
+    // these two (every level's channels = model_channels * channel_mult) are also what the pack kernels' 16-byte stores need (Engine::pack16)
     if (cfg.num_levels < 1 || cfg.num_levels > 8) return bad("num_levels out of range");
     if (cfg.num_heads < 1) return bad("num_heads");
     if (cfg.in_channels < 1 || cfg.in_channels > 64 || cfg.out_channels < 1 || cfg.out_channels > 128) return bad("in/out channels");
@@ -154,7 +154,7 @@ void* Engine::weight_buf(size_t bytes) {
         void* p = nullptr;
         if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
         dev_allocs.push_back(p);
-        if (kind == KIND_UNET) weight_allocs.push_back({p, bytes});      // the other engines share upload16 / upload32 but have no refresh and no digest
+        if (kind == KIND_UNET) weight_allocs.push_back({p, bytes});      // the other engines share the packers but have no refresh and no digest
         weight_bytes += bytes;
         return p;
     }
@@ -165,18 +165,14 @@ void* Engine::weight_buf(size_t bytes) {
     return weight_allocs[walk_next++].p;
 }
 
-// upload a [rows][cols] matrix produced by getter(r, c) as 16-bit
+// a [rows][cols] matrix produced by getter(r, c) as 16-bit / a vector produced by getter(i): the few layouts that are no piece list (engine.h)
 void* Engine::upload16(size_t rows, size_t cols, const std::function<float(size_t, size_t)>& getter) {
     void* p = weight_buf(rows * cols * 2);
     if (!p || walk_mode == WALK_CHECK) return p;
     std::vector<uint16_t> buf(rows * cols);
-    const bool bf = dt == DT_BF16;
     parallel_for(rows, [&](size_t b, size_t e) {
         for (size_t r = b; r < e; ++r)
-            for (size_t c = 0; c < cols; ++c) {
-                const float v = getter(r, c);
-                buf[r * cols + c] = bf ? float_to_bf16(v) : float_to_half(v);
-            }
+            for (size_t c = 0; c < cols; ++c) buf[r * cols + c] = to16(getter(r, c), dt);
     });
     if (hipMemcpy(p, buf.data(), buf.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
     return p;
@@ -190,11 +186,7 @@ float* Engine::upload32(size_t n, const std::function<float(size_t)>& getter) {
     return (float*)p;
 }
 
-// ---- device packing (pack.hip): the same buffers from sources that live on the GPU ----
-static bool on_device(std::initializer_list<const HostTensor*> ts) {
-    for (const HostTensor* t : ts) if (t && t->dev) return true;
-    return false;
-}
+// ---- packed buffers from pieces (weight_layout.h): pack.hip's kernels where a source lives on the GPU, the same functions on the CPU where none does ----
 // the device address of a source: its own, or a staged raw copy of a host tensor that shares a packed buffer with device tensors
 const void* Engine::dev_src(const HostTensor* t) {
     if (t->dev) return t->dev;
@@ -213,43 +205,60 @@ void Engine::drop_staged() {
 void* Engine::pack16(size_t rows, size_t cols, const std::vector<Piece>& pieces) {
     void* p = weight_buf(rows * cols * 2);
     if (!p) return p;
+    bool dev = false;
+    for (const Piece& pc : pieces) dev = dev || pc.src->dev;
     for (const Piece& pc : pieces) {
-        // What the kernel's 16-byte stores and its index arithmetic rely on; the pieces must lie inside [rows][cols].  validate() guarantees the
-        // divisibility for every UNet it accepts (all channel counts and context_dim are multiples of 64, conv_in is padded to 64), so the device path
-        // takes every shape the host path takes; the test runs in every walk mode, so a refresh would report it before anything is written.
-        if (pc.K % 8 || cols % 8 || pc.col0 % 8 || pc.CinPad % 8 || pc.row0 + pc.N > rows || pc.col0 + pc.K > cols ||
+        // The pieces must lie inside [rows][cols] and match their sources; the kernel's 16-byte stores need more, which validate() guarantees for every
+        // UNet it accepts (all channel counts and context_dim are multiples of 64, conv_in is padded to 64).  Tested in every walk mode, so a refresh
+        // reports it before anything is written.
+        if (pc.row0 + pc.N > rows || pc.col0 + pc.K > cols || (dev && (pc.K % 8 || cols % 8 || pc.col0 % 8 || pc.CinPad % 8)) ||
             (pc.CinPad ? (pc.K != 9 * pc.CinPad || pc.Cin > pc.CinPad || pc.src->numel != (size_t)pc.N * pc.Cin * 9)
                        : pc.src->numel != (size_t)(pc.geglu_inner ? 2 * pc.geglu_inner : pc.N) * pc.K) ||
             (pc.geglu_inner && (pc.N != 2 * pc.geglu_inner || pc.geglu_inner % 32))) {
-            walk_err = "pack16: piece outside the packed matrix or not 16-byte granular";
+            walk_err = dev ? "pack16: piece outside the packed matrix or not 16-byte granular" : "pack16: piece outside the packed matrix";
             return nullptr;
         }
-        if (walk_mode == WALK_CHECK) continue;
-        PackArgs a; memset(&a, 0, sizeof(a));
-        a.src = dev_src(pc.src); a.sdt = pc.src->dtype;
-        if (!a.src) return nullptr;
-        a.out = (uint16_t*)p + pc.row0 * cols; a.ldo = (long)cols; a.col0 = (long)pc.col0; a.out_dt = dt;
-        a.N = pc.N; a.K = pc.K; a.Cin = pc.Cin; a.CinPad = pc.CinPad; a.geglu_inner = pc.geglu_inner; a.scale = pc.scale;
-        launch_pack16(a, nullptr);
     }
+    if (walk_mode == WALK_CHECK) return p;
+    std::vector<uint16_t> buf(dev ? 0 : rows * cols);
+    for (const Piece& pc : pieces) {
+        PackArgs a; memset(&a, 0, sizeof(a));
+        a.src = piece_src(pc.src, dev); a.sdt = pc.src->dtype;
+        if (!a.src) return nullptr;
+        a.out = (uint16_t*)(dev ? p : buf.data()) + pc.row0 * cols; a.ldo = (long)cols; a.col0 = (long)pc.col0; a.out_dt = dt;
+        a.N = pc.N; a.K = pc.K; a.Cin = pc.Cin; a.CinPad = pc.CinPad; a.geglu_inner = pc.geglu_inner; a.scale = pc.scale;
+        if (dev) launch_pack16(a, nullptr);
+        else parallel_for(pc.N, [&](size_t b, size_t e) {
+            for (size_t r = b; r < e; ++r)
+                for (int c = 0; c < a.K; c += 8) pack16_group(a, r, c, std::min(8, a.K - c));
+        });
+    }
+    if (!dev && hipMemcpy(p, buf.data(), buf.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
     return p;
 }
 float* Engine::pack32(size_t n, const std::vector<VecPiece>& pieces) {
     float* p = (float*)weight_buf(n * 4);
     if (!p) return p;
+    bool dev = false;
     for (const VecPiece& pc : pieces) {
+        dev = dev || pc.a->dev || (pc.b && pc.b->dev);
         if (pc.off + pc.n > n || pc.a->numel != (size_t)pc.n || (pc.b && pc.b->numel != (size_t)pc.n) || (pc.geglu_inner && pc.n != 2 * pc.geglu_inner)) {
             walk_err = "pack32: piece outside the packed vector";
             return nullptr;
         }
-        if (walk_mode == WALK_CHECK) continue;
-        PackVecArgs a; memset(&a, 0, sizeof(a));
-        a.a = dev_src(pc.a); a.a_dt = pc.a->dtype;
-        if (!a.a) return nullptr;
-        if (pc.b) { a.b = dev_src(pc.b); a.b_dt = pc.b->dtype; if (!a.b) return nullptr; }
-        a.out = p + pc.off; a.n = pc.n; a.geglu_inner = pc.geglu_inner;
-        launch_pack32(a, nullptr);
     }
+    if (walk_mode == WALK_CHECK) return p;
+    std::vector<float> buf(dev ? 0 : n);
+    for (const VecPiece& pc : pieces) {
+        PackVecArgs a; memset(&a, 0, sizeof(a));
+        a.a = piece_src(pc.a, dev); a.a_dt = pc.a->dtype;
+        if (!a.a) return nullptr;
+        if (pc.b) { a.b = piece_src(pc.b, dev); a.b_dt = pc.b->dtype; if (!a.b) return nullptr; }
+        a.out = (dev ? p : buf.data()) + pc.off; a.n = pc.n; a.geglu_inner = pc.geglu_inner;
+        if (dev) launch_pack32(a, nullptr);
+        else for (int i = 0; i < a.n; ++i) pack32_at(a, i);
+    }
+    if (!dev && hipMemcpy(p, buf.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
     return p;
 }
 
@@ -257,12 +266,12 @@ bool Engine::mk_linear(const std::string& pre, int N, int K, bool bias, LinearW&
     const HostTensor* w = conv1x1 ? get(pre + ".weight", {N, K, 1, 1}) : get(pre + ".weight", {N, K});
     if (!w) return false;
     out.N = N; out.K = K;
-    out.w = w->dev ? pack16(N, K, {rows_piece(w, 0, N, K)}) : upload16(N, K, [&](size_t r, size_t c) { return w->at(r * K + c); });
+    out.w = pack16(N, K, {rows_piece(w, 0, N, K)});
     out.b = nullptr;
     if (bias) {
         const HostTensor* b = get(pre + ".bias", {N});
         if (!b) return false;
-        out.b = b->dev ? pack32(N, {{b, nullptr, 0, N, 0}}) : upload32(N, [&](size_t i) { return b->at(i); });
+        out.b = pack32(N, {{b, nullptr, 0, N, 0}});
         if (!out.b) return false;
     }
     return out.w != nullptr;
@@ -272,14 +281,8 @@ bool Engine::mk_conv3(const std::string& pre, int Cout, int Cin, int CinPad, Lin
     const HostTensor* b = get(pre + ".bias", {Cout});
     if (!w || !b) return false;
     out.N = Cout; out.K = 9 * CinPad;
-    // [Cout][ky][kx][CinPad]  <-  [Cout][Cin][ky][kx]
-    if (w->dev) out.w = pack16(Cout, (size_t)9 * CinPad, {Piece{w, 0, 0, Cout, 9 * CinPad, 1.0f, 0, Cin, CinPad}});
-    else out.w = upload16(Cout, (size_t)9 * CinPad, [&](size_t r, size_t c) {
-        const size_t tap = c / CinPad, ci = c % CinPad;
-        if ((int)ci >= Cin) return 0.f;
-        return w->at((r * Cin + ci) * 9 + tap);
-    });
-    out.b = b->dev ? pack32(Cout, {{b, nullptr, 0, Cout, 0}}) : upload32(Cout, [&](size_t i) { return b->at(i); });
+    out.w = pack16(Cout, (size_t)9 * CinPad, {conv_piece(w, Cout, Cin, CinPad)});
+    out.b = pack32(Cout, {{b, nullptr, 0, Cout, 0}});
     return out.w && out.b;
 }
 bool Engine::mk_norm(const std::string& pre, int C, NormW& out) {
@@ -287,65 +290,77 @@ bool Engine::mk_norm(const std::string& pre, int C, NormW& out) {
     const HostTensor* b = get(pre + ".bias", {C});
     if (!w || !b) return false;
     out.C = C;
-    out.g = w->dev ? pack32(C, {{w, nullptr, 0, C, 0}}) : upload32(C, [&](size_t i) { return w->at(i); });
-    out.b = b->dev ? pack32(C, {{b, nullptr, 0, C, 0}}) : upload32(C, [&](size_t i) { return b->at(i); });
+    out.g = pack32(C, {{w, nullptr, 0, C, 0}});
+    out.b = pack32(C, {{b, nullptr, 0, C, 0}});
     return out.g && out.b;
 }
 
 // Linear(LayerNorm(x)) with the norm folded in: y = rstd (x W'^T - mean c1) + c2 with W' = W .* gamma (per input column), c1[n] = sum_k W'[n][k]
 // (of the values as STORED in 16 bit: the epilogue subtracts exactly what the MFMA accumulated for a constant row) and c2 = W beta + b.
-bool Engine::mk_ln_folded(int N, int K, const std::function<float(size_t, size_t)>& W, const std::function<float(size_t)>& bias,
-                          const std::string& norm_pre, LinearW& out, float*& c1, const std::vector<Piece>& pieces, const HostTensor* bias_t) {
+// W = the pieces (row ranges of one [N][K] matrix), b = bias_t (may be null); weight_layout.h ln_fold_row writes a row of all three buffers.
+bool Engine::mk_ln_folded(int N, int K, const std::vector<Piece>& pieces, const HostTensor* bias_t, const std::string& norm_pre, LinearW& out, float*& c1) {
     const HostTensor* g = get(norm_pre + ".weight", {K});
     const HostTensor* be = get(norm_pre + ".bias", {K});
     if (!g || !be) return false;
-    bool dev = on_device({g, be, bias_t});
+    bool dev = g->dev || be->dev || (bias_t && bias_t->dev);
     for (const Piece& pc : pieces) dev = dev || pc.src->dev;
-    if (dev) {
-        // the three buffers in the host path's order, then one launch per source (ln_fold_kernel writes its rows of all three)
-        out.N = N; out.K = K;
-        out.w = weight_buf((size_t)N * K * 2);
-        c1 = (float*)weight_buf((size_t)N * 4);
-        out.b = (float*)weight_buf((size_t)N * 4);
-        if (!out.w || !c1 || !out.b) return false;
-        for (const Piece& pc : pieces) {
-            if (K % 8 || pc.K != K || pc.row0 + pc.N > (size_t)N || (pc.geglu_inner && (pc.N != 2 * pc.geglu_inner || pc.N != N)) ||
-                pc.src->numel != (size_t)pc.N * K || (bias_t && (pieces.size() != 1 || pc.row0 || bias_t->numel != (size_t)N))) {
-                walk_err = "mk_ln_folded: piece outside the packed matrix";
-                return false;
-            }
-            if (walk_mode == WALK_CHECK) continue;
-            LnFoldArgs a; memset(&a, 0, sizeof(a));
-            a.src = dev_src(pc.src); a.sdt = pc.src->dtype;
-            a.gamma = dev_src(g); a.g_dt = g->dtype; a.beta = dev_src(be); a.b_dt = be->dtype;
-            if (bias_t) { a.bias = dev_src(bias_t); a.bias_dt = bias_t->dtype; if (!a.bias) return false; }
-            if (!a.src || !a.gamma || !a.beta) return false;
-            a.out = (uint16_t*)out.w + pc.row0 * K; a.out_dt = dt; a.c1 = c1 + pc.row0; a.c2 = out.b + pc.row0;
-            a.N = pc.N; a.K = K; a.geglu_inner = pc.geglu_inner; a.scale = pc.scale;
-            launch_ln_fold(a, nullptr);
-        }
-        return true;
-    }
-    std::vector<float> gam(K), bet(K);
-    for (int k = 0; k < K; ++k) { gam[k] = g->at(k); bet[k] = be->at(k); }
     out.N = N; out.K = K;
-    out.w = upload16(N, K, [&](size_t r, size_t c) { return W(r, c) * gam[c]; });
-    std::vector<float> v1(N), v2(N);
-    const bool bf = dt == DT_BF16;
-    if (walk_mode != WALK_CHECK) parallel_for(N, [&](size_t b, size_t e) {
-        for (size_t r = b; r < e; ++r) {
-            double s1 = 0.0, s2 = 0.0;
-            for (int k = 0; k < K; ++k) {
-                const float w = W(r, k), wg = w * gam[k];
-                s1 += bf ? bf16_to_float(float_to_bf16(wg)) : half_to_float(float_to_half(wg));
-                s2 += (double)w * bet[k];
-            }
-            v1[r] = (float)s1; v2[r] = (float)(s2 + (bias ? bias(r) : 0.f));
+    out.w = weight_buf((size_t)N * K * 2);
+    c1 = (float*)weight_buf((size_t)N * 4);
+    out.b = (float*)weight_buf((size_t)N * 4);
+    if (!out.w || !c1 || !out.b) return false;
+    for (const Piece& pc : pieces)
+        if ((dev && K % 8) || pc.K != K || pc.row0 + pc.N > (size_t)N || (pc.geglu_inner && (pc.N != 2 * pc.geglu_inner || pc.N != N)) ||
+            pc.src->numel != (size_t)pc.N * K || (bias_t && (pieces.size() != 1 || pc.row0 || bias_t->numel != (size_t)N))) {
+            walk_err = "mk_ln_folded: piece outside the packed matrix";
+            return false;
         }
-    });
-    c1 = upload32(N, [&](size_t i) { return v1[i]; });
-    out.b = upload32(N, [&](size_t i) { return v2[i]; });
-    return out.w && c1 && out.b;
+    if (walk_mode == WALK_CHECK) return true;
+    std::vector<uint16_t> hw(dev ? 0 : (size_t)N * K);
+    std::vector<float> h1(dev ? 0 : N), h2(dev ? 0 : N);
+    for (const Piece& pc : pieces) {
+        LnFoldArgs a; memset(&a, 0, sizeof(a));
+        a.src = piece_src(pc.src, dev); a.sdt = pc.src->dtype;
+        a.gamma = piece_src(g, dev); a.g_dt = g->dtype; a.beta = piece_src(be, dev); a.b_dt = be->dtype;
+        if (bias_t) { a.bias = piece_src(bias_t, dev); a.bias_dt = bias_t->dtype; if (!a.bias) return false; }
+        if (!a.src || !a.gamma || !a.beta) return false;
+        a.out = (uint16_t*)(dev ? out.w : hw.data()) + pc.row0 * K; a.out_dt = dt; a.c1 = (dev ? c1 : h1.data()) + pc.row0; a.c2 = (dev ? out.b : h2.data()) + pc.row0;
+        a.N = pc.N; a.K = K; a.geglu_inner = pc.geglu_inner; a.scale = pc.scale;
+        if (dev) launch_ln_fold(a, nullptr);
+        else parallel_for(pc.N, [&](size_t b, size_t e) { for (size_t r = b; r < e; ++r) ln_fold_row(a, r); });
+    }
+    return dev || (hipMemcpy(out.w, hw.data(), hw.size() * 2, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(c1, h1.data(), (size_t)N * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                   hipMemcpy(out.b, h2.data(), (size_t)N * 4, hipMemcpyHostToDevice) == hipSuccess);
+}
+
+// out = conv2(h) + skip(x) as one implicit GEMM over K = 9 * Cout + Cin (GemmArgs::A2): weights [Cout][ky][kx][Cout] | [Cout][Cin], bias b2 + bskip
+bool Engine::mk_fused_skip(const std::string& conv, const std::string& skip, int Cin, int Cout, ResW& r) {
+    const HostTensor* w2 = get(conv + ".weight", {Cout, Cout, 3, 3});
+    const HostTensor* b2 = get(conv + ".bias", {Cout});
+    const HostTensor* ws = get(skip + ".weight", {Cout, Cin, 1, 1});
+    const HostTensor* bs = get(skip + ".bias", {Cout});
+    if (!w2 || !b2 || !ws || !bs) return false;
+    r.fused_skip = true;
+    r.conv2.N = Cout; r.conv2.K = 9 * Cout + Cin;
+    r.conv2.w = pack16(Cout, (size_t)9 * Cout + Cin, {conv_piece(w2, Cout, Cout, Cout), Piece{ws, 0, (size_t)9 * Cout, Cout, Cin, 1.0f, 0, 0, 0}});
+    r.conv2.b = pack32(Cout, {{b2, bs, 0, Cout, 0}});
+    return r.conv2.w && r.conv2.b;
+}
+
+static int stacked_rows(const std::vector<EmbSrc>& srcs) { int n = 0; for (const EmbSrc& s : srcs) n += s.n; return n; }
+// rows of several tensors stacked into one [sum n][K] matrix, their biases (where they have one) into one vector
+bool Engine::mk_stacked(const std::vector<EmbSrc>& srcs, int K, LinearW& out) {
+    std::vector<Piece> wp; std::vector<VecPiece> bp;
+    size_t row = 0;
+    for (const EmbSrc& s : srcs) {
+        wp.push_back(rows_piece(s.w, row, s.n, K));
+        if (s.b) bp.push_back({s.b, nullptr, row, s.n, 0});
+        row += s.n;
+    }
+    out.N = (int)row; out.K = K;
+    out.w = pack16(row, K, wp);
+    out.b = bp.empty() ? nullptr : pack32(row, bp);
+    return out.w && (bp.empty() || out.b);
 }
 
 bool Engine::mk_res(const std::string& pre, int Cin, int Cout, ResW& r) {
@@ -356,36 +371,13 @@ bool Engine::mk_res(const std::string& pre, int Cin, int Cout, ResW& r) {
     const HostTensor* ew = get(pre + ".emb_layers.1.weight", {Cout, 4 * cfg.model_channels});
     const HostTensor* eb = get(pre + ".emb_layers.1.bias", {Cout});
     if (!ew || !eb) return false;
-    r.emb_off = emb_total;
-    emb_total += Cout;
+    r.emb_off = stacked_rows(emb_srcs);
     emb_srcs.push_back({ew, eb, Cout});
     if (!mk_norm(pre + ".out_layers.0", Cout, r.gn2)) return false;
     r.has_skip = Cin != Cout;
-    const bool try_fuse = r.has_skip && Cin % 64 == 0 && g_plan_sw.fused_skip;
-    if (!try_fuse && !mk_conv3(pre + ".out_layers.3", Cout, Cout, Cout, r.conv2)) return false;
-    if (r.has_skip) {
-        // out = conv2(h) + skip_connection(x): one implicit GEMM over K = 9*Cout + Cin (GemmArgs::A2), weights [Cout][ky][kx][Cout | Cin]
-        const HostTensor* w2 = get(pre + ".out_layers.3.weight", {Cout, Cout, 3, 3});
-        const HostTensor* b2 = get(pre + ".out_layers.3.bias", {Cout});
-        const HostTensor* ws = get(pre + ".skip_connection.weight", {Cout, Cin, 1, 1});
-        const HostTensor* bs = get(pre + ".skip_connection.bias", {Cout});
-        if (try_fuse) {
-            if (!w2 || !b2 || !ws || !bs) return false;
-            r.fused_skip = true;
-            r.conv2.N = Cout; r.conv2.K = 9 * Cout + Cin;
-            if (on_device({w2, ws})) r.conv2.w = pack16(Cout, (size_t)9 * Cout + Cin, {Piece{w2, 0, 0, Cout, 9 * Cout, 1.0f, 0, Cout, Cout},
-                                                                                     Piece{ws, 0, (size_t)9 * Cout, Cout, Cin, 1.0f, 0, 0, 0}});
-            else r.conv2.w = upload16(Cout, (size_t)9 * Cout + Cin, [&](size_t rr, size_t c) {
-                if (c >= (size_t)9 * Cout) return ws->at(rr * Cin + (c - (size_t)9 * Cout));
-                const size_t tap = c / Cout, ci = c % Cout;
-                return w2->at((rr * Cout + ci) * 9 + tap);
-            });
-            r.conv2.b = on_device({b2, bs}) ? pack32(Cout, {{b2, bs, 0, Cout, 0}}) : upload32(Cout, [&](size_t i) { return b2->at(i) + bs->at(i); });
-            return r.conv2.w && r.conv2.b;
-        }
-        if (!mk_linear(pre + ".skip_connection", Cout, Cin, true, r.skip, true)) return false;
-    }
-    return true;
+    if (r.has_skip && Cin % 64 == 0 && g_plan_sw.fused_skip) return mk_fused_skip(pre + ".out_layers.3", pre + ".skip_connection", Cin, Cout, r);
+    if (!mk_conv3(pre + ".out_layers.3", Cout, Cout, Cout, r.conv2)) return false;
+    return !r.has_skip || mk_linear(pre + ".skip_connection", Cout, Cin, true, r.skip, true);
 }
 
 static inline bool q_prescale() { return g_plan_sw.q_prescale; }
@@ -417,51 +409,37 @@ bool Engine::mk_xf(const std::string& pre, int C, int depth, XfW& x) {
         // softmax_scale * log2(e) folded into the q projections at load time (one rounding of c * Wq instead of rounding q and multiplying
         // every score): the attention ops then run with scale = 1 / log2(e), i.e. exp2(q.k - m) as before; LDX_NO_QPRESCALE=1 keeps the plain weights
         const float cq = q_prescale() ? (1.0f / std::sqrt((float)(C / cfg.num_heads))) * 1.44269504088896340736f : 1.0f;
-        auto qkv_w = [&](size_t r, size_t c) {
-            const HostTensor* s = r < (size_t)C ? q : (r < (size_t)2 * C ? k : v);
-            return s->at((r % C) * C + c) * (r < (size_t)C ? cq : 1.0f);
-        };
         const HostTensor* q2w = get(bp + ".attn2.to_q.weight", {C, C});
         if (!q2w) return false;
         const std::vector<Piece> qkv_p{rows_piece(q, 0, C, C, cq), rows_piece(k, C, C, C), rows_piece(v, (size_t)2 * C, C, C)}, q2_p{rows_piece(q2w, 0, C, C, cq)};
         if (b.ln_fold) {
-            if (!mk_ln_folded(3 * C, C, qkv_w, nullptr, bp + ".norm1", b.qkv_f, b.c1_qkv, qkv_p, nullptr)) return false;
-            if (!mk_ln_folded(C, C, [&](size_t r, size_t c) { return q2w->at(r * C + c) * cq; }, nullptr, bp + ".norm2", b.q2_f, b.c1_q2, q2_p, nullptr)) return false;
+            if (!mk_ln_folded(3 * C, C, qkv_p, nullptr, bp + ".norm1", b.qkv_f, b.c1_qkv)) return false;
+            if (!mk_ln_folded(C, C, q2_p, nullptr, bp + ".norm2", b.q2_f, b.c1_q2)) return false;
         }
-        {
-            b.qkv.N = 3 * C; b.qkv.K = C; b.qkv.b = nullptr;
-            b.qkv.w = on_device({q, k, v}) ? pack16((size_t)3 * C, C, qkv_p) : upload16((size_t)3 * C, C, qkv_w);
-            if (!b.qkv.w) return false;
-            b.q2.N = C; b.q2.K = C; b.q2.b = nullptr;
-            b.q2.w = q2w->dev ? pack16(C, C, q2_p) : upload16(C, C, [&](size_t r, size_t c) { return q2w->at(r * C + c) * cq; });
-            if (!b.q2.w) return false;
-        }
+        b.qkv.N = 3 * C; b.qkv.K = C; b.qkv.b = nullptr;
+        b.qkv.w = pack16((size_t)3 * C, C, qkv_p);
+        b.q2.N = C; b.q2.K = C; b.q2.b = nullptr;
+        b.q2.w = pack16(C, C, q2_p);
+        if (!b.qkv.w || !b.q2.w) return false;
         if (!mk_linear(bp + ".attn1.to_out.0", C, C, true, b.o1)) return false;
         const HostTensor* k2 = get(bp + ".attn2.to_k.weight", {C, ctx});
         const HostTensor* v2 = get(bp + ".attn2.to_v.weight", {C, ctx});
         if (!k2 || !v2) return false;
         b.kv2.N = 2 * C; b.kv2.K = ctx; b.kv2.b = nullptr; b.kv2.w = nullptr;
-        b.kv_off = kv_total;                       // columns [kv_off, kv_off + 2C) of the batched k|v projection
-        kv_total += 2 * C;
-        kv_srcs.push_back({k2, v2, C});
+        b.kv_off = stacked_rows(kv_srcs);          // columns [kv_off, kv_off + 2C) of the batched k|v projection
+        kv_srcs.push_back({k2, nullptr, C}); kv_srcs.push_back({v2, nullptr, C});
         if (!mk_linear(bp + ".attn2.to_out.0", C, C, true, b.o2)) return false;
-        // GEGLU projection: rows permuted so each 64-column slab holds 32 value rows then their 32 gate rows
+        // GEGLU projection: rows permuted so each 64-column slab holds 32 value rows then their 32 gate rows (geglu_src_row)
         const int inner = 4 * C;
         const HostTensor* fw = get(bp + ".ff.net.0.proj.weight", {2 * inner, C});
         const HostTensor* fb = get(bp + ".ff.net.0.proj.bias", {2 * inner});
         if (!fw || !fb) return false;
-        auto src_row = [inner](size_t r) { const size_t slab = r / 64, within = r % 64; return within < 32 ? slab * 32 + within : inner + slab * 32 + (within - 32); };
         const std::vector<Piece> ff1_p{rows_piece(fw, 0, 2 * inner, C, 1.0f, inner)};
-        if (b.ln_fold) {
-            if (!mk_ln_folded(2 * inner, C, [&](size_t r, size_t c) { return fw->at(src_row(r) * C + c); }, [&](size_t i) { return fb->at(src_row(i)); },
-                              bp + ".norm3", b.ff1_f, b.c1_ff1, ff1_p, fb)) return false;
-        }
-        {
-            b.ff1.N = 2 * inner; b.ff1.K = C;
-            b.ff1.w = fw->dev ? pack16((size_t)2 * inner, C, ff1_p) : upload16((size_t)2 * inner, C, [&](size_t r, size_t c) { return fw->at(src_row(r) * C + c); });
-            b.ff1.b = fb->dev ? pack32((size_t)2 * inner, {{fb, nullptr, 0, 2 * inner, inner}}) : upload32((size_t)2 * inner, [&](size_t i) { return fb->at(src_row(i)); });
-            if (!b.ff1.w || !b.ff1.b) return false;
-        }
+        if (b.ln_fold && !mk_ln_folded(2 * inner, C, ff1_p, fb, bp + ".norm3", b.ff1_f, b.c1_ff1)) return false;
+        b.ff1.N = 2 * inner; b.ff1.K = C;
+        b.ff1.w = pack16((size_t)2 * inner, C, ff1_p);
+        b.ff1.b = pack32((size_t)2 * inner, {{fb, nullptr, 0, 2 * inner, inner}});
+        if (!b.ff1.w || !b.ff1.b) return false;
         if (!mk_linear(bp + ".ff.net.2", C, inner, true, b.ff2)) return false;
     }
     return true;
@@ -469,18 +447,16 @@ bool Engine::mk_xf(const std::string& pre, int C, int depth, XfW& x) {
 
 // The structure walk: every packed weight buffer of the UNet from the registered tensors, in one fixed order.  walk_mode says what a buffer is:
 // a new allocation (finalize), nothing (refresh: keys and shapes only) or the allocation finalize made (refresh: refill).  Whatever the mode, the
-// walk rebuilds the weight structs from scratch and, when it succeeds, leaves them holding the same pointers.
+// walk builds a fresh UNetW which, when it succeeds, holds the same pointers as the one before; only then does it replace `un`.
 int Engine::walk_weights() {
-    te0 = te2 = conv_in = conv_out = emb_all = kv_all = LinearW{}; out_gn = NormW{};
-    in_blocks.clear(); out_blocks.clear();
-    has_middle = mid_has_xf = false; mid_res0 = mid_res1 = ResW{}; mid_xf = XfW{};
-    emb_total = 0; kv_total = 0; emb_srcs.clear(); kv_srcs.clear();
+    UNetW w;
+    emb_srcs.clear(); kv_srcs.clear();
     missing.clear(); walk_err.clear(); walk_next = 0;
     const int mc = cfg.model_channels, ted = 4 * mc;
     bool ok = true;
     // --- structure walk, identical in order to UNetModel1.__init__ (unet.py:344-677) ---
-    ok = ok && mk_linear("time_embed.0", ted, mc, true, te0) && mk_linear("time_embed.2", ted, ted, true, te2);
-    ok = ok && mk_conv3("input_blocks.0.0", mc, cfg.in_channels, 64, conv_in);
+    ok = ok && mk_linear("time_embed.0", ted, mc, true, w.te0) && mk_linear("time_embed.2", ted, ted, true, w.te2);
+    ok = ok && mk_conv3("input_blocks.0.0", mc, cfg.in_channels, 64, w.conv_in);
     int ch = mc, td_i = 0, ib = 1;
     std::vector<int> chans{mc};
     for (int level = 0; ok && level < cfg.num_levels; ++level) {
@@ -493,20 +469,20 @@ int Engine::walk_weights() {
             ch = co;
             const int depth = cfg.transformer_depth[td_i++];
             if (ok && depth > 0) { blk.has_xf = true; ok = mk_xf(pre + ".1", ch, depth, blk.xf); }
-            in_blocks.push_back(std::move(blk)); chans.push_back(ch); ++ib;
+            w.in_blocks.push_back(std::move(blk)); chans.push_back(ch); ++ib;
         }
         if (ok && level != cfg.num_levels - 1) {
             BlockW blk; blk.has_down = true;
             ok = mk_conv3("input_blocks." + std::to_string(ib) + ".0.op", ch, ch, ch, blk.down);
-            in_blocks.push_back(std::move(blk)); chans.push_back(ch); ++ib;
+            w.in_blocks.push_back(std::move(blk)); chans.push_back(ch); ++ib;
         }
     }
     if (ok && cfg.transformer_depth_middle >= -1) {
-        has_middle = true;
-        ok = mk_res("middle_block.0", ch, ch, mid_res0);
+        w.has_middle = true;
+        ok = mk_res("middle_block.0", ch, ch, w.mid_res0);
         if (ok && cfg.transformer_depth_middle >= 0) {
-            mid_has_xf = true;
-            ok = mk_xf("middle_block.1", ch, std::max(1, (int)cfg.transformer_depth_middle), mid_xf) && mk_res("middle_block.2", ch, ch, mid_res1);
+            w.mid_has_xf = true;
+            ok = mk_xf("middle_block.1", ch, std::max(1, (int)cfg.transformer_depth_middle), w.mid_xf) && mk_res("middle_block.2", ch, ch, w.mid_res1);
             if (cfg.transformer_depth_middle == 0) { set_error("transformer_depth_middle == 0 unsupported"); return LDX_EINVAL; }
         }
     }
@@ -529,62 +505,29 @@ int Engine::walk_weights() {
                 blk.has_up = true;
                 ok = mk_conv3(pre + "." + std::to_string(sub) + ".conv", ch, ch, ch, blk.up);
             }
-            out_blocks.push_back(std::move(blk)); ++ob;
+            w.out_blocks.push_back(std::move(blk)); ++ob;
         }
     }
-    ok = ok && mk_norm("out.0", ch, out_gn) && mk_conv3("out.2", cfg.out_channels, mc, mc, conv_out);
-    if (ok) {
-        // batched emb_layers: [emb_total][4*mc]
-        std::vector<size_t> starts; size_t acc = 0;
-        for (auto& s : emb_srcs) { starts.push_back(acc); acc += s.n; }
-        auto find = [&](size_t r) { size_t i = std::upper_bound(starts.begin(), starts.end(), r) - starts.begin() - 1; return i; };
-        emb_all.N = emb_total; emb_all.K = ted;
-        bool w_dev = false, b_dev = false;
-        std::vector<Piece> wp; std::vector<VecPiece> bp;
-        for (size_t i = 0; i < emb_srcs.size(); ++i) {
-            w_dev = w_dev || emb_srcs[i].w->dev; b_dev = b_dev || emb_srcs[i].b->dev;
-            wp.push_back(rows_piece(emb_srcs[i].w, starts[i], emb_srcs[i].n, ted));
-            bp.push_back({emb_srcs[i].b, nullptr, starts[i], emb_srcs[i].n, 0});
-        }
-        emb_all.w = w_dev ? pack16(emb_total, ted, wp)
-                          : upload16(emb_total, ted, [&](size_t r, size_t c) { const size_t i = find(r); return emb_srcs[i].w->at((r - starts[i]) * ted + c); });
-        emb_all.b = b_dev ? pack32(emb_total, bp) : upload32(emb_total, [&](size_t r) { const size_t i = find(r); return emb_srcs[i].b->at(r - starts[i]); });
-        ok = emb_all.w && emb_all.b;
-    }
-    if (ok && kv_total > 0) {
-        std::vector<size_t> starts; size_t acc = 0;
-        for (auto& s2 : kv_srcs) { starts.push_back(acc); acc += 2 * (size_t)s2.C; }
-        const int ctxd = cfg.context_dim;
-        kv_all.N = kv_total; kv_all.K = ctxd; kv_all.b = nullptr;
-        bool kv_dev = false;
-        std::vector<Piece> kvp;
-        for (size_t i = 0; i < kv_srcs.size(); ++i) {
-            const int C = kv_srcs[i].C;
-            kv_dev = kv_dev || kv_srcs[i].k->dev || kv_srcs[i].v->dev;
-            kvp.push_back(rows_piece(kv_srcs[i].k, starts[i], C, ctxd));
-            kvp.push_back(rows_piece(kv_srcs[i].v, starts[i] + C, C, ctxd));
-        }
-        kv_all.w = kv_dev ? pack16(kv_total, ctxd, kvp) : upload16(kv_total, ctxd, [&](size_t r, size_t c) {
-            const size_t i = std::upper_bound(starts.begin(), starts.end(), r) - starts.begin() - 1;
-            const size_t rr = r - starts[i]; const int C = kv_srcs[i].C;
-            return (rr < (size_t)C ? kv_srcs[i].k : kv_srcs[i].v)->at((rr % C) * ctxd + c);
-        });
-        ok = kv_all.w != nullptr;
-    }
+    ok = ok && mk_norm("out.0", ch, w.out_gn) && mk_conv3("out.2", cfg.out_channels, mc, mc, w.conv_out);
+    ok = ok && mk_stacked(emb_srcs, ted, w.emb_all) && (kv_srcs.empty() || mk_stacked(kv_srcs, cfg.context_dim, w.kv_all));
+    w.emb_total = w.emb_all.N; w.kv_total = w.kv_all.N;
     emb_srcs.clear(); kv_srcs.clear();
     if (ok && walk_mode != WALK_ALLOC && walk_next != weight_allocs.size()) { ok = false; walk_err = "the weight layout differs from the one ldx_finalize built (plan switches changed since?)"; }
     // the device packers run on the null stream, in order behind the host path's copies: one wait for all of them, then the staged copies can go
     hipError_t sync = ok && walk_mode != WALK_CHECK ? hipDeviceSynchronize() : hipSuccess;
     if (sync == hipSuccess && walk_mode != WALK_CHECK) sync = hipGetLastError();
     drop_staged();
-    if (!ok) {
-        if (!missing.empty()) { set_error("missing or mis-shaped weight: " + missing); return LDX_EMISSING; }
-        if (!walk_err.empty()) { set_error(walk_err); return LDX_ESTATE; }
-        set_error(std::string("weight upload failed: ") + hipGetErrorString(hipGetLastError()));
-        return LDX_EHIP;
-    }
+    if (!ok) return weights_failed();
     if (sync != hipSuccess) { set_error(std::string("weight packing failed: ") + hipGetErrorString(sync)); return LDX_EHIP; }
+    un = std::move(w);
     return LDX_OK;
+}
+
+int Engine::weights_failed() {
+    if (!missing.empty()) { set_error("missing or mis-shaped weight: " + missing); return LDX_EMISSING; }
+    if (!walk_err.empty()) { set_error(walk_err); return LDX_ESTATE; }
+    set_error(std::string("weight upload failed: ") + hipGetErrorString(hipGetLastError()));
+    return LDX_EHIP;
 }
 
 int Engine::finalize() {
@@ -620,21 +563,12 @@ int Engine::refresh_commit() {
     if (kind != KIND_UNET || !finalized || !refreshing) { set_error("ldx_unet_refresh_commit: call ldx_unet_refresh_begin first"); return LDX_ESTATE; }
     HIP_OK(hipSetDevice(device));
     HIP_OK(hipDeviceSynchronize());        // no forward still reads the buffers about to be rewritten
-    // every key and shape first, with nothing written: a failing walk leaves half-built weight structs behind, so the present ones are put back
-    struct Saved { LinearW te0, te2, conv_in, conv_out, emb_all, kv_all; NormW out_gn; std::vector<BlockW> in_blocks, out_blocks; bool has_middle, mid_has_xf;
-                   ResW mid_res0, mid_res1; XfW mid_xf; int emb_total, kv_total; };
-    Saved sv{te0, te2, conv_in, conv_out, emb_all, kv_all, out_gn, in_blocks, out_blocks, has_middle, mid_has_xf, mid_res0, mid_res1, mid_xf, emb_total, kv_total};
+    // every key and shape first, with nothing written (a failing walk leaves `un` as it is)
     walk_mode = WALK_CHECK;
     int rc = walk_weights();
     if (rc == LDX_OK) {
         walk_mode = WALK_REFILL;
         rc = walk_weights();               // an error from here on (a HIP failure) leaves the weights partly rewritten
-    } else {
-        const std::string err = g_last_error;
-        te0 = sv.te0; te2 = sv.te2; conv_in = sv.conv_in; conv_out = sv.conv_out; emb_all = sv.emb_all; kv_all = sv.kv_all; out_gn = sv.out_gn;
-        in_blocks = std::move(sv.in_blocks); out_blocks = std::move(sv.out_blocks); has_middle = sv.has_middle; mid_has_xf = sv.mid_has_xf;
-        mid_res0 = sv.mid_res0; mid_res1 = sv.mid_res1; mid_xf = std::move(sv.mid_xf); emb_total = sv.emb_total; kv_total = sv.kv_total;
-        set_error(err);
     }
     walk_mode = WALK_ALLOC;
     host.clear();
@@ -896,7 +830,7 @@ void Engine::emit_res(const ResW& r, Act X, Act OUT, int B, int H, int W) {
     Act t1 = new_act(M, r.Cin);
     op_gn("res.gn1", X, t1, B, H * W, r.gn1, r.eps, true);
     Act t2 = new_act(M, r.Cout);
-    if (r.has_emb) op_conv("res.conv1", t1, B, H, W, r.Cin, r.conv1, 1, H, W, t2, Act{}, cur.d_emb_all ? cur.d_emb_all + r.emb_off : nullptr, emb_total);
+    if (r.has_emb) op_conv("res.conv1", t1, B, H, W, r.Cin, r.conv1, 1, H, W, t2, Act{}, cur.d_emb_all ? cur.d_emb_all + r.emb_off : nullptr, un.emb_total);
     else op_conv("res.conv1", t1, B, H, W, r.Cin, r.conv1, 1, H, W, t2, Act{});
     release(t1);
     Act t3 = new_act(M, r.Cout);
@@ -976,7 +910,7 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
             Op& o = emit(OP_XATTN, "xf.xattn2");
             XAttnArgs& xa = o.xa;
             xa.H = ptr(h); xa.ldh = h.ld; xa.M = M; xa.N = H * W; xa.C = C; xa.heads = heads; xa.ln_g = b.ln2.g; xa.ln_b = b.ln2.b; xa.eps = 1e-5f;
-            xa.Wq = b.q2.w; xa.Wo = b.o2.w; xa.bo = b.o2.b; xa.K = kvb; xa.ldk = kv_total; xa.V = kvb + (size_t)C * 2; xa.ldv = kv_total; xa.Mk = Mc;
+            xa.Wq = b.q2.w; xa.Wo = b.o2.w; xa.bo = b.o2.b; xa.K = kvb; xa.ldk = un.kv_total; xa.V = kvb + (size_t)C * 2; xa.ldv = un.kv_total; xa.Mk = Mc;
             xa.scale = q_prescale() ? 1.0f / 1.44269504088896340736f : 1.0f / std::sqrt((float)D);
             o.flops = 2.0 * 2.0 * M * (double)C * C + 4.0 * B * heads * (double)(H * W) * Mc * D;
             o.bytes = 2.0 * 2.0 * (double)M * C;
@@ -985,7 +919,7 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
         } else {
             Act q = new_act(M, C);
             norm_gemm(bp.q2, "xf.ln2+q2", "xf.ln2", "xf.q2", b.ln2, b.q2, b.q2_f, b.c1_q2, q, false);
-            op_attn("xf.attn2", ptr(q), C, kvb, kv_total, kvb + (size_t)C * 2, kv_total, a, B, heads, H * W, Mc, D);
+            op_attn("xf.attn2", ptr(q), C, kvb, un.kv_total, kvb + (size_t)C * 2, un.kv_total, a, B, heads, H * W, Mc, D);
             if (q_prescale()) cur.ops.back().at.scale = 1.0f / 1.44269504088896340736f;       // the q rows of the projection already carry scale * log2(e)
             release(q);
             out_gemm(bp.o2, "xf.o2", a, b.o2);                     // x += attn2(norm2(x), ctx)
@@ -1020,7 +954,7 @@ void Engine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx1
 int Engine::share_for(int B2, int h, int w, int xB, bool denoise, bool concat) const {
     const long share_minrows = g_plan_sw.cfg_share_minrows;
     if (!cfg_share || !denoise || concat || xB <= 0 || B2 != 2 * xB || (cfg_share == 1 && (long)xB * h * w < share_minrows)) return 0;
-    for (auto& blk : in_blocks) if (blk.has_xf) return xB;
+    for (auto& blk : un.in_blocks) if (blk.has_xf) return xB;
     return 0;
 }
 
@@ -1029,7 +963,7 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
         const int mc = cfg.model_channels, ted = 4 * mc;
         // fixed small buffers
         const size_t o_temb = a_alloc((size_t)B2 * mc * 4), o_e1 = a_alloc((size_t)B2 * ted * 4), o_e2 = a_alloc((size_t)B2 * ted * 4);
-        const size_t o_emb = a_alloc((size_t)B2 * emb_total * 4);
+        const size_t o_emb = a_alloc((size_t)B2 * un.emb_total * 4);
         cur.gn_ws_off = a_alloc(gn_ws_bytes(B2, (long)h * w));
         const size_t o_eps = a_alloc((size_t)B2 * h * w * cfg.out_channels * 4);
         auto f32p = [&](size_t off) { return cur.arena ? (float*)((char*)cur.arena + off) : (float*)nullptr; };
@@ -1062,19 +996,19 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
             PrepArgs& p = emit(OP_PREP, "prep").prep;          // x, sigma / timesteps and c_concat are the call's
             p.B = B2; p.C = cfg.in_channels; p.H = h; p.W = w; p.Cpad = 64; p.xc = ptr(xin);
             p.log_sigmas = d_log_sigmas; p.n_sigmas = n_sigmas; p.temb_table = d_temb; p.temb_dim = mc; p.temb_out = cur.d_temb_out;
-            if (d_emb_table) { p.emb_table = d_emb_table; p.emb_n = emb_total; p.emb_out = cur.d_emb_all; }
+            if (d_emb_table) { p.emb_table = d_emb_table; p.emb_n = un.emb_total; p.emb_out = cur.d_emb_all; }
         }
         Act ctx16 = new_act(B2 * Mc, cfg.context_dim);
         { Op& o = emit(OP_CVT, "ctx.cvt"); o.cvt = CvtArgs{nullptr, ptr(ctx16), (size_t)B2 * Mc * cfg.context_dim}; o.ctx_only = true; }
         if (!d_emb_table) {       // per-step time-embedding MLP (LDX_EMB_TABLE=0); otherwise the prep kernel gathers the timestep's row of the table
-            emit(OP_SKINNY, "time_embed.0").sk = skinny_args(cur.d_temb_out, mc, te0.w, te0.b, cur.d_e1, ted, B2, ted, mc, 0, 1);
-            emit(OP_SKINNY, "time_embed.2").sk = skinny_args(cur.d_e1, ted, te2.w, te2.b, cur.d_e2, ted, B2, ted, ted, 0, 1);
-            emit(OP_SKINNY, "emb_layers").sk = skinny_args(cur.d_e2, ted, emb_all.w, emb_all.b, cur.d_emb_all, emb_total, B2, emb_total, ted, 0, 0);
-            cur.flops += 2.0 * B2 * ((double)ted * mc + (double)ted * ted + (double)emb_total * ted);
+            emit(OP_SKINNY, "time_embed.0").sk = skinny_args(cur.d_temb_out, mc, un.te0.w, un.te0.b, cur.d_e1, ted, B2, ted, mc, 0, 1);
+            emit(OP_SKINNY, "time_embed.2").sk = skinny_args(cur.d_e1, ted, un.te2.w, un.te2.b, cur.d_e2, ted, B2, ted, ted, 0, 1);
+            emit(OP_SKINNY, "emb_layers").sk = skinny_args(cur.d_e2, ted, un.emb_all.w, un.emb_all.b, cur.d_emb_all, un.emb_total, B2, un.emb_total, ted, 0, 0);
+            cur.flops += 2.0 * B2 * ((double)ted * mc + (double)ted * ted + (double)un.emb_total * ted);
         }
-        Act kvall = new_act(B2 * Mc, kv_total);
+        Act kvall = new_act(B2 * Mc, un.kv_total);
         cur.kv_all_off = kvall.off;
-        op_gemm("xf.kv2_all", ctx16, kv_all, kvall, Act{});
+        op_gemm("xf.kv2_all", ctx16, un.kv_all, kvall, Act{});
         cur.ops.back().ctx_only = true;
 
         int lv = 0, s = 0;
@@ -1083,11 +1017,11 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
         // that later full-batch ops read (the skip connections), duplicated into the second half's rows when the prefix ends (emit_xf)
         int Bp = share > 0 ? share : B2;
         std::vector<DupReq> pend;
-        op_conv("conv_in", xin, Bp, h, w, 64, conv_in, 1, h, w, hcur, Act{});
+        op_conv("conv_in", xin, Bp, h, w, 64, un.conv_in, 1, h, w, hcur, Act{});
         cur.flops -= 2.0 * Bp * h * w * (double)mc * 9.0 * (64 - cfg.in_channels);   // padded channels are not algorithmic work
         release(xin);
         if (Bp != B2) pend.push_back({hcur, Bp * h * w, cur.ops.size() - 1});
-        for (auto& blk : in_blocks) {
+        for (auto& blk : un.in_blocks) {
             ++s;
             Act dst = skip_view(s);
             if (blk.has_down) {
@@ -1115,23 +1049,23 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
         {
             const int Mm = B2 * Hs[lv] * Ws[lv];
             Act dst = view(cat[0], 0, out_hch[0]);
-            if (!has_middle) { set_error("UNet config without a middle block is not supported by the planner"); return LDX_EINVAL; }
-            if (mid_has_xf) {
-                Act m0 = new_act(Mm, mid_res0.Cout);
-                emit_res(mid_res0, hcur, m0, B2, Hs[lv], Ws[lv]);
-                Act m1 = new_act(Mm, mid_res0.Cout);
-                emit_xf(mid_xf, m0, m1, B2, Hs[lv], Ws[lv], ctx16, Mc);
+            if (!un.has_middle) { set_error("UNet config without a middle block is not supported by the planner"); return LDX_EINVAL; }
+            if (un.mid_has_xf) {
+                Act m0 = new_act(Mm, un.mid_res0.Cout);
+                emit_res(un.mid_res0, hcur, m0, B2, Hs[lv], Ws[lv]);
+                Act m1 = new_act(Mm, un.mid_res0.Cout);
+                emit_xf(un.mid_xf, m0, m1, B2, Hs[lv], Ws[lv], ctx16, Mc);
                 release(m0);
-                emit_res(mid_res1, m1, dst, B2, Hs[lv], Ws[lv]);
+                emit_res(un.mid_res1, m1, dst, B2, Hs[lv], Ws[lv]);
                 release(m1);
             } else {
-                emit_res(mid_res0, hcur, dst, B2, Hs[lv], Ws[lv]);
+                emit_res(un.mid_res0, hcur, dst, B2, Hs[lv], Ws[lv]);
             }
         }
         // output blocks: input of block k is the whole concat buffer cat[k]
         int k = 0;
         Act final_h{};
-        for (auto& blk : out_blocks) {
+        for (auto& blk : un.out_blocks) {
             const int sidx = n_skips - 1 - k; (void)sidx;
             const bool last = (k == n_skips - 1);
             const int Hc = Hs[lv], Wc = Ws[lv], Mrows = B2 * Hc * Wc;
@@ -1168,9 +1102,9 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
         {
             const int Mrows = B2 * h * w;
             Act t = new_act(Mrows, mc);
-            op_gn("out.gn", final_h, t, B2, h * w, out_gn, 1e-5f, true);
+            op_gn("out.gn", final_h, t, B2, h * w, un.out_gn, 1e-5f, true);
             release(final_h);
-            op_conv("out.conv", t, B2, h, w, mc, conv_out, 1, h, w, Act{}, Act{}, nullptr, 0, cur.d_eps, cfg.out_channels);
+            op_conv("out.conv", t, B2, h, w, mc, un.conv_out, 1, h, w, Act{}, Act{}, nullptr, 0, cur.d_eps, cfg.out_channels);
             release(t);
         }
         { FinishArgs& f = emit(OP_FINISH, "finish").fin; f.eps = cur.d_eps; f.ld = cfg.out_channels; f.B = B2; f.C = cfg.out_channels; f.HW = h * w; }          // x, sigma and out are the call's
@@ -1189,7 +1123,7 @@ int Engine::plan(int B2, int h, int w, int Mc, int share) {
 // The 22 emb_layers outputs for EVERY timestep of the table (ldx_set_tables), by the same three skinny launches a forward would run on its B2 rows:
 // row t of d_emb_table is bit-identical to what those launches write for a sample whose timestep index is t (the skinny kernel's rows are independent).
 int Engine::build_emb_table() {
-    if (!g_plan_sw.emb_table || !d_temb || n_sigmas <= 0 || emb_total <= 0 || emb_total % 4) return LDX_OK;
+    if (!g_plan_sw.emb_table || !d_temb || n_sigmas <= 0 || un.emb_total <= 0 || un.emb_total % 4) return LDX_OK;
     if (finalized && !d_emb_table) return LDX_OK;        // a refresh rebuilds the table finalize() built, in place (the plans hold its address); it never adds one
     const bool refill = d_emb_table != nullptr;
     const int mc = cfg.model_channels, ted = 4 * mc, n = n_sigmas;
@@ -1204,17 +1138,17 @@ int Engine::build_emb_table() {
     hipError_t err;
     if ((err = hipMalloc((void**)&e1, (size_t)n * ted * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
     if ((err = hipMalloc((void**)&e2, (size_t)n * ted * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
-    if (!refill && (err = hipMalloc((void**)&tab, (size_t)n * emb_total * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
-    launch_skinny(skinny_args(d_temb, mc, te0.w, te0.b, e1, ted, n, ted, mc, 0, 1), dt, nullptr);
-    launch_skinny(skinny_args(e1, ted, te2.w, te2.b, e2, ted, n, ted, ted, 0, 1), dt, nullptr);
-    launch_skinny(skinny_args(e2, ted, emb_all.w, emb_all.b, tab, emb_total, n, emb_total, ted, 0, 0), dt, nullptr);
+    if (!refill && (err = hipMalloc((void**)&tab, (size_t)n * un.emb_total * 4)) != hipSuccess) return fail(err, "build_emb_table: hipMalloc");
+    launch_skinny(skinny_args(d_temb, mc, un.te0.w, un.te0.b, e1, ted, n, ted, mc, 0, 1), dt, nullptr);
+    launch_skinny(skinny_args(e1, ted, un.te2.w, un.te2.b, e2, ted, n, ted, ted, 0, 1), dt, nullptr);
+    launch_skinny(skinny_args(e2, ted, un.emb_all.w, un.emb_all.b, tab, un.emb_total, n, un.emb_total, ted, 0, 0), dt, nullptr);
     if ((err = hipStreamSynchronize(nullptr)) != hipSuccess) return fail(err, "build_emb_table: hipStreamSynchronize");
     if ((err = hipGetLastError()) != hipSuccess) return fail(err, "build_emb_table: kernel launch");
     (void)hipFree(e1); (void)hipFree(e2);
     if (refill) return LDX_OK;
     dev_allocs.push_back(tab);
     d_emb_table = tab;
-    weight_bytes += (size_t)n * emb_total * 4;
+    weight_bytes += (size_t)n * un.emb_total * 4;
     return LDX_OK;
 }
 

@@ -28,7 +28,7 @@ int launch_status();          // LDX_EHIP (and the error text) when a kernel lau
     } while (0)
 
 // A state-dict tensor as registered: a host copy (ldx_load_tensor: `data`), or the caller's own device memory (ldx_load_tensor_device: `dev`,
-// not copied, `data` empty; UNet engine only).  at() reads the host copy.
+// not copied, `data` empty; UNet engine only).  at() reads the host copy (the getter-style upload16 / upload32; the piece packers read `data` themselves).
 struct HostTensor {
     int dtype = LDX_F32;
     std::vector<int64_t> shape;
@@ -50,6 +50,17 @@ struct XfBlockW { NormW ln1, ln2, ln3; LinearW qkv, o1, q2, kv2, o2, ff1, ff2; L
     bool ln_fold = false; float *c1_qkv = nullptr, *c1_q2 = nullptr, *c1_ff1 = nullptr; };
 struct XfW { NormW gn; LinearW proj_in, proj_out; std::vector<XfBlockW> blocks; int C = 0, depth = 0; };
 struct BlockW { bool has_res = false, has_xf = false, has_down = false, has_up = false; ResW res; XfW xf; LinearW down, up; int skip_ch = 0; };
+// Every weight of the UNet, as the structure walk (Engine::walk_weights) builds it; emb_all / kv_all: the emb_layers of every ResBlock and the k | v projections of
+// every cross-attention, each batched into one GEMM per forward ([emb_total][4 mc] and [kv_total][context_dim])
+struct UNetW {
+    LinearW te0, te2, conv_in, conv_out, emb_all, kv_all;
+    NormW out_gn;
+    std::vector<BlockW> in_blocks, out_blocks;
+    bool has_middle = false, mid_has_xf = false;
+    ResW mid_res0, mid_res1;
+    XfW mid_xf;
+    int emb_total = 0, kv_total = 0;
+};
 
 // activation view inside the arena: rows x C 16-bit elements, row stride ld, starting at column col
 struct Act { bool valid = false; bool owned = false; size_t off = 0; int rows = 0, C = 0, ld = 0, col = 0; };
@@ -131,7 +142,7 @@ inline SkinnyArgs skinny_args(const float* x, int ldx, const void* W, const floa
     return a;
 }
 
-struct EmbSrc { const HostTensor* w; const HostTensor* b; int n; };
+struct EmbSrc { const HostTensor* w; const HostTensor* b; int n; };      // n rows of a stacked matrix (Engine::mk_stacked); b may be null
 
 struct VaeAttnW { NormW norm; LinearW q, k, v, proj; LinearW qkv; /* C = 512: fused q | k | v projection [3C][C] for the flash kernel (attn512.hip); bias = [bq | bk | 0], bv folded into proj's */ };
 struct ClipLayerW { NormW ln1, ln2; LinearW qkv, out, fc1, fc2; };
@@ -191,8 +202,8 @@ public:
     int set_tables(const float* ls, int n, const float* temb, int dim);
     int finalize();
     // Replace the weights of a finalized UNet engine in place (ldx_unet_refresh_begin / _commit): begin re-opens the two loaders, commit validates
-    // the full key set (nothing written on LDX_EMISSING), then runs the structure walk again into the SAME device allocations, rebuilds the
-    // emb_layers table and drops the cached context projections.  No pointer a plan or a captured graph holds changes.
+    // the full key set (nothing written on LDX_EMISSING, and `un` stays as it was), then runs the structure walk again into the SAME device allocations,
+    // rebuilds the emb_layers table and drops the cached context projections.  No pointer a plan or a captured graph holds changes.
     int refresh_begin();
     int refresh_commit();
     int refresh_abort();                   // forget an unfinished refresh: the loaders close again, the weights are untouched
@@ -254,30 +265,40 @@ private:
     enum WalkMode { WALK_ALLOC, WALK_CHECK, WALK_REFILL };
     WalkMode walk_mode = WALK_ALLOC;
     struct WeightAlloc { void* p; size_t bytes; };
-    std::vector<WeightAlloc> weight_allocs;                // every upload16 / upload32 / pack16 / pack32 buffer, in allocation order
+    std::vector<WeightAlloc> weight_allocs;                // every packed buffer (weight_buf), in allocation order
     size_t walk_next = 0;                                  // CHECK / REFILL: the next entry of weight_allocs
     std::string walk_err;
     bool refreshing = false;                               // between refresh_begin and refresh_commit
     void* weight_buf(size_t bytes);                        // the walk's next weight buffer (null: error)
-    int walk_weights();
-    void* upload16(size_t rows, size_t cols, const std::function<float(size_t, size_t)>& getter);
-    float* upload32(size_t n, const std::function<float(size_t)>& getter);
-    // device-side counterparts (pack.hip) for groups with a source registered by ldx_load_tensor_device; host sources of such a group are staged
-    // (raw copy, freed when the walk ends).  Same buffers in the same order as the host path: either can refill what the other allocated.
+    int walk_weights();                                    // builds a fresh UNetW and installs it as `un` on success only
+    int weights_failed();                                  // the tail of a failed walk / finalize_*: missing key -> LDX_EMISSING, walk_err -> LDX_ESTATE, else the HIP error
+    // A packed buffer is described ONCE, as pieces of source tensors; weight_layout.h turns a piece into bits, for both sides.  Per buffer: some source is on
+    // the device (ldx_load_tensor_device) -> one launch per piece of pack.hip's loops over those functions, host sources of that buffer staged as raw copies
+    // (freed when the walk ends); no source on the device -> a CPU loop over the same functions and one copy.  Same buffers in the same order either way:
+    // either can refill what the other allocated.  16-byte granularity (K, cols, col0, CinPad multiples of 8) is asked of the launches only.
     struct Piece { const HostTensor* src; size_t row0, col0; int N, K; float scale; int geglu_inner; int Cin, CinPad; };
     static Piece rows_piece(const HostTensor* src, size_t row0, int N, int K, float scale = 1.0f, int geglu_inner = 0) { return Piece{src, row0, 0, N, K, scale, geglu_inner, 0, 0}; }
-    struct VecPiece { const HostTensor* a; const HostTensor* b; size_t off; int n; int geglu_inner; };
+    static Piece conv_piece(const HostTensor* src, int Cout, int Cin, int CinPad) { return Piece{src, 0, 0, Cout, 9 * CinPad, 1.0f, 0, Cin, CinPad}; }      // [Cout][ky][kx][CinPad] <- [Cout][Cin][ky][kx]
+    struct VecPiece { const HostTensor* a; const HostTensor* b; size_t off; int n; int geglu_inner; };      // out[off + i] = a[i] (+ b[i])
     std::unordered_map<const HostTensor*, void*> staged;
     const void* dev_src(const HostTensor* t);
+    const void* piece_src(const HostTensor* t, bool dev) { return dev ? dev_src(t) : t->numel ? (const void*)t->data.data() : (const void*)t; }      // never null for an empty host tensor (nothing is read)
     void drop_staged();
     void* pack16(size_t rows, size_t cols, const std::vector<Piece>& pieces);
     float* pack32(size_t n, const std::vector<VecPiece>& pieces);
+    // What no piece list describes stays on a getter, element by element on the host (all in engines that load from the host only):
+    //   mk_vae_attn  proj.b    Wp . bv + bp, an fp64 dot product per element
+    //   mk_vae_attn  qkv.b     [bq | bk | 0]: the zero tail has no source
+    //   finalize_t5  wi.w      64-row slabs interleaved from TWO tensors (wi_1 value rows, wi_0 gate rows); geglu_inner permutes one
+    //   finalize_flux lin1_*   linear1 split at a source ROW: a piece takes its whole source, from row 0
+    void* upload16(size_t rows, size_t cols, const std::function<float(size_t, size_t)>& getter);
+    float* upload32(size_t n, const std::function<float(size_t)>& getter);
     bool mk_linear(const std::string& pre, int N, int K, bool bias, LinearW& out, bool conv1x1 = false);
     bool mk_conv3(const std::string& pre, int Cout, int Cin, int CinPad, LinearW& out);
     bool mk_norm(const std::string& pre, int C, NormW& out);
-    // pieces / bias_t: the same W and bias as sources, for the device path
-    bool mk_ln_folded(int N, int K, const std::function<float(size_t, size_t)>& W, const std::function<float(size_t)>& bias,
-                      const std::string& norm_pre, LinearW& out, float*& c1, const std::vector<Piece>& pieces, const HostTensor* bias_t);
+    bool mk_ln_folded(int N, int K, const std::vector<Piece>& pieces, const HostTensor* bias_t, const std::string& norm_pre, LinearW& out, float*& c1);
+    bool mk_fused_skip(const std::string& conv, const std::string& skip, int Cin, int Cout, ResW& r);      // conv2 | skip in one matrix (UNet and VAE ResBlocks)
+    bool mk_stacked(const std::vector<EmbSrc>& srcs, int K, LinearW& out);                                   // rows of several tensors in one matrix, their biases in one vector
     bool mk_res(const std::string& pre, int Cin, int Cout, ResW& r);
     bool mk_xf(const std::string& pre, int C, int depth, XfW& x);
 
@@ -297,7 +318,7 @@ private:
     Bindings bind;                                        // this call's
     // VAE
     std::vector<std::vector<ResW>> vae_up; std::vector<LinearW> vae_upconv; std::vector<bool> vae_has_up;
-    ResW vae_mid1, vae_mid2; VaeAttnW vae_attn; NormW vae_norm_out; float* vae_pq = nullptr;
+    ResW vae_mid1, vae_mid2; VaeAttnW vae_attn; NormW vae_norm_out; LinearW vae_conv_in, vae_conv_out; float* vae_pq = nullptr;
     // VAE encoder (optional: only when encoder.* weights were loaded)
     bool vae_has_enc = false;
     std::vector<std::vector<ResW>> enc_down; std::vector<LinearW> enc_downconv;
@@ -312,17 +333,9 @@ private:
     std::vector<ClipLayerW> clip_layers; NormW clip_final_ln; float* clip_tok = nullptr; float* clip_pos = nullptr;
     float* clip_extra = nullptr; int clip_extra_n = 0, clip_extra_cap = 0;     // textual-inversion rows for ids >= vocab_size
     float* clip_proj = nullptr;                                                // optional text_projection.weight [E][E] fp32 (CLIPTextModel.py:130,152-163)
-    LinearW te0, te2, conv_in, conv_out, emb_all;
-    NormW out_gn;
-    std::vector<BlockW> in_blocks, out_blocks;
-    bool has_middle = false, mid_has_xf = false;
-    ResW mid_res0, mid_res1;
-    XfW mid_xf;
-    int emb_total = 0;
-    std::vector<EmbSrc> emb_srcs;
-    // all cross-attention k|v projections of the context, batched into one GEMM per forward
-    struct KvSrc { const HostTensor* k; const HostTensor* v; int C; };
-    std::vector<KvSrc> kv_srcs; int kv_total = 0; LinearW kv_all;
+    UNetW un;
+    // sources of un.emb_all / un.kv_all (k, v, k, v, ...), collected by the walk
+    std::vector<EmbSrc> emb_srcs, kv_srcs;
     float* d_log_sigmas = nullptr; float* d_temb = nullptr; int n_sigmas = 0;
 
     // planner state of the plan being built (build_plan resets it)

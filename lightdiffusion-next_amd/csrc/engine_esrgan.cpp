@@ -40,11 +40,7 @@ int Engine::finalize_esrgan() {
     for (int u = 0; ok && u < c.num_upscale; ++u) ok = mk_conv3("model." + std::to_string(3 * (u + 1)), nf, nf, nf, es_up[u]);
     ok = ok && mk_conv3("model." + std::to_string(3 * c.num_upscale + 2), nf, nf, nf, es_hr) &&
          mk_conv3("model." + std::to_string(3 * c.num_upscale + 4), c.out_nc, nf, nf, es_last);
-    if (!ok) {
-        if (!missing.empty()) { set_error("missing or mis-shaped weight: " + missing); return LDX_EMISSING; }
-        set_error(std::string("weight upload failed: ") + hipGetErrorString(hipGetLastError()));
-        return LDX_EHIP;
-    }
+    if (!ok) return weights_failed();
     host.clear();
     finalized = true;
     return LDX_OK;

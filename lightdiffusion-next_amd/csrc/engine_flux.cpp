@@ -43,7 +43,7 @@ int Engine::finalize_flux() {
     auto scale_vec = [&](const std::string& key, float*& out) {
         const HostTensor* t = get(key, {D});
         if (!t) return false;
-        out = upload32(D, [&](size_t i) { return t->at(i); });
+        out = pack32(D, {{t, nullptr, 0, D, 0}});
         return out != nullptr;
     };
     auto add_mod = [&](const std::string& pre, int mult, int& off) {
@@ -88,20 +88,8 @@ int Engine::finalize_flux() {
              scale_vec(p + ".norm.query_norm.scale", s.qs) && scale_vec(p + ".norm.key_norm.scale", s.ks);
     }
     ok = ok && add_mod("final_layer.adaLN_modulation.1", 2, fx_final_mod_off) && mk_linear("final_layer.linear", inC, C, true, fx_final);
-    if (ok) {
-        std::vector<size_t> starts; size_t acc = 0;
-        for (auto& s : fx_mod_srcs) { starts.push_back(acc); acc += s.n; }
-        auto find = [&](size_t r) { return (size_t)(std::upper_bound(starts.begin(), starts.end(), r) - starts.begin() - 1); };
-        fx_mod_all.N = fx_mod_total; fx_mod_all.K = C;
-        fx_mod_all.w = upload16(fx_mod_total, C, [&](size_t r, size_t c) { const size_t i = find(r); return fx_mod_srcs[i].w->at((r - starts[i]) * C + c); });
-        fx_mod_all.b = upload32(fx_mod_total, [&](size_t r) { const size_t i = find(r); return fx_mod_srcs[i].b->at(r - starts[i]); });
-        ok = fx_mod_all.w && fx_mod_all.b;
-    }
-    if (!ok) {
-        if (!missing.empty()) { set_error("missing or mis-shaped weight: " + missing); return LDX_EMISSING; }
-        set_error(std::string("weight upload failed: ") + hipGetErrorString(hipGetLastError()));
-        return LDX_EHIP;
-    }
+    ok = ok && mk_stacked(fx_mod_srcs, C, fx_mod_all);
+    if (!ok) return weights_failed();
     fx_mod_srcs.clear();
     host.clear();
     if (fx_fp8) {

@@ -31,23 +31,8 @@ bool Engine::mk_vae_res(const std::string& pre, int Cin, int Cout, ResW& r) {
     if (!mk_norm(pre + ".norm1", Cin, r.gn1) || !mk_conv3(pre + ".conv1", Cout, Cin, Cin, r.conv1)) return false;
     if (!mk_norm(pre + ".norm2", Cout, r.gn2)) return false;
     r.has_skip = Cin != Cout;
-    if (r.has_skip && Cin % 64 == 0 && g_plan_sw.fused_skip) {
-        // x = nin_shortcut(x); return x + h (ResBlock.py:383-406): folded into conv2 as a second K segment, like the UNet's ResBlock1
-        const HostTensor* w2 = get(pre + ".conv2.weight", {Cout, Cout, 3, 3});
-        const HostTensor* b2 = get(pre + ".conv2.bias", {Cout});
-        const HostTensor* ws = get(pre + ".nin_shortcut.weight", {Cout, Cin, 1, 1});
-        const HostTensor* bs = get(pre + ".nin_shortcut.bias", {Cout});
-        if (!w2 || !b2 || !ws || !bs) return false;
-        r.fused_skip = true;
-        r.conv2.N = Cout; r.conv2.K = 9 * Cout + Cin;
-        r.conv2.w = upload16(Cout, (size_t)9 * Cout + Cin, [&](size_t rr, size_t c) {
-            if (c >= (size_t)9 * Cout) return ws->at(rr * Cin + (c - (size_t)9 * Cout));
-            const size_t tap = c / Cout, ci = c % Cout;
-            return w2->at((rr * Cout + ci) * 9 + tap);
-        });
-        r.conv2.b = upload32(Cout, [&](size_t i) { return b2->at(i) + bs->at(i); });
-        return r.conv2.w && r.conv2.b;
-    }
+    // x = nin_shortcut(x); return x + h (ResBlock.py:383-406): folded into conv2 as a second K segment, like the UNet's ResBlock1
+    if (r.has_skip && Cin % 64 == 0 && g_plan_sw.fused_skip) return mk_fused_skip(pre + ".conv2", pre + ".nin_shortcut", Cin, Cout, r);
     if (!mk_conv3(pre + ".conv2", Cout, Cout, Cout, r.conv2)) return false;
     if (r.has_skip && !mk_linear(pre + ".nin_shortcut", Cout, Cin, true, r.skip, true)) return false;
     return true;
@@ -63,7 +48,7 @@ bool Engine::mk_vae_attn(const std::string& pre, int C, VaeAttnW& a) {
     const HostTensor* bv = get(pre + ".v.bias", {C});
     if (!wp || !bp || !bv) return false;
     a.proj.N = C; a.proj.K = C;
-    a.proj.w = upload16(C, C, [&](size_t r, size_t c) { return wp->at(r * C + c); });
+    a.proj.w = pack16(C, C, {rows_piece(wp, 0, C, C)});
     a.proj.b = upload32(C, [&](size_t i) {
         double acc = bp->at(i);
         for (int k = 0; k < C; ++k) acc += (double)wp->at(i * C + k) * (double)bv->at(k);
@@ -75,7 +60,7 @@ bool Engine::mk_vae_attn(const std::string& pre, int C, VaeAttnW& a) {
         const HostTensor *bq = get(pre + ".q.bias", {C}), *bk = get(pre + ".k.bias", {C});
         if (!wq || !wk || !wv || !bq || !bk) return false;
         a.qkv.N = 3 * C; a.qkv.K = C;
-        a.qkv.w = upload16((size_t)3 * C, C, [&](size_t r, size_t c) { const HostTensor* s = r < (size_t)C ? wq : (r < (size_t)2 * C ? wk : wv); return s->at((r % C) * C + c); });
+        a.qkv.w = pack16((size_t)3 * C, C, {rows_piece(wq, 0, C, C), rows_piece(wk, C, C, C), rows_piece(wv, (size_t)2 * C, C, C)});
         a.qkv.b = upload32((size_t)3 * C, [&](size_t i) { return i < (size_t)C ? bq->at(i) : (i < (size_t)2 * C ? bk->at(i - C) : 0.f); });
         if (!a.qkv.w || !a.qkv.b) return false;
     }
@@ -91,7 +76,7 @@ int Engine::finalize_vae() {
     HIP_OK(hipSetDevice(device));
     bool ok = true;
     int block_in = v.ch * v.ch_mult[v.num_levels - 1];
-    ok = ok && mk_conv3("decoder.conv_in", block_in, v.z_channels, 64, conv_in);
+    ok = ok && mk_conv3("decoder.conv_in", block_in, v.z_channels, 64, vae_conv_in);
     ok = ok && mk_vae_res("decoder.mid.block_1", block_in, block_in, vae_mid1);
     ok = ok && mk_vae_attn("decoder.mid.attn_1", block_in, vae_attn);
     ok = ok && mk_vae_res("decoder.mid.block_2", block_in, block_in, vae_mid2);
@@ -109,14 +94,14 @@ int Engine::finalize_vae() {
             ok = mk_conv3("decoder.up." + std::to_string(lv) + ".upsample.conv", block_in, block_in, block_in, vae_upconv[lv]);
         }
     }
-    ok = ok && mk_norm("decoder.norm_out", block_in, vae_norm_out) && mk_conv3("decoder.conv_out", v.out_ch, block_in, block_in, conv_out);
+    ok = ok && mk_norm("decoder.norm_out", block_in, vae_norm_out) && mk_conv3("decoder.conv_out", v.out_ch, block_in, block_in, vae_conv_out);
     if (ok && v.use_post_quant) {
         const HostTensor* w = get("post_quant_conv.weight", {v.z_channels, v.z_channels, 1, 1});
         const HostTensor* b = get("post_quant_conv.bias", {v.z_channels});
         ok = w && b;
         if (ok) {
             const int zc = v.z_channels;
-            vae_pq = upload32((size_t)zc * zc + zc, [&](size_t i) { return i < (size_t)zc * zc ? w->at(i) : b->at(i - (size_t)zc * zc); });
+            vae_pq = pack32((size_t)zc * zc + zc, {{w, nullptr, 0, zc * zc, 0}, {b, nullptr, (size_t)zc * zc, zc, 0}});
             ok = vae_pq != nullptr;
         }
     }
@@ -145,14 +130,10 @@ int Engine::finalize_vae() {
             const HostTensor* w = get("quant_conv.weight", {zc2, zc2, 1, 1});
             const HostTensor* b = get("quant_conv.bias", {zc2});
             ok = w && b;
-            if (ok) { enc_qc = upload32((size_t)zc2 * zc2 + zc2, [&](size_t i) { return i < (size_t)zc2 * zc2 ? w->at(i) : b->at(i - (size_t)zc2 * zc2); }); ok = enc_qc != nullptr; }
+            if (ok) { enc_qc = pack32((size_t)zc2 * zc2 + zc2, {{w, nullptr, 0, zc2 * zc2, 0}, {b, nullptr, (size_t)zc2 * zc2, zc2, 0}}); ok = enc_qc != nullptr; }
         }
     }
-    if (!ok) {
-        if (!missing.empty()) { set_error("missing or mis-shaped weight: " + missing); return LDX_EMISSING; }
-        set_error(std::string("weight upload failed: ") + hipGetErrorString(hipGetLastError()));
-        return LDX_EHIP;
-    }
+    if (!ok) return weights_failed();
     host.clear();
     finalized = true;
     return LDX_OK;
@@ -235,7 +216,7 @@ int Engine::plan_vae(int B, int h, int w) {
         emit(OP_VAEPREP, "vae.prep").vprep = VaePrepArgs{nullptr, ptr(x0), B, v.z_channels, H * W, 64, vae_pq, vae_pq ? vae_pq + v.z_channels * v.z_channels : nullptr};      // z is the call's
         int C = v.ch * v.ch_mult[v.num_levels - 1];
         Act hcur = new_act(B * H * W, C);
-        op_conv("vae.conv_in", x0, B, H, W, 64, conv_in, 1, H, W, hcur, Act{});
+        op_conv("vae.conv_in", x0, B, H, W, 64, vae_conv_in, 1, H, W, hcur, Act{});
         cur.flops -= 2.0 * B * H * W * (double)C * 9.0 * (64 - v.z_channels);
         release(x0);
         auto res = [&](const ResW& r) { Act o = new_act(B * H * W, r.Cout); emit_res(r, hcur, o, B, H, W); release(hcur); hcur = o; };
@@ -257,7 +238,7 @@ int Engine::plan_vae(int B, int h, int w) {
         release(hcur);
         const size_t o_pix = a_alloc((size_t)B * H * W * v.out_ch * 4);
         float* pix = (float*)((uintptr_t)cur.arena + o_pix);
-        op_conv("vae.conv_out", t, B, H, W, Cl, conv_out, 1, H, W, Act{}, Act{}, nullptr, 0, pix, v.out_ch);
+        op_conv("vae.conv_out", t, B, H, W, Cl, vae_conv_out, 1, H, W, Act{}, Act{}, nullptr, 0, pix, v.out_ch);
         release(t);
         emit(OP_CLAMP, "vae.clamp").clamp = ClampArgs{pix, nullptr, (size_t)(B * H * W * v.out_ch)};
         fuse_gn_stats();
@@ -343,8 +324,8 @@ int Engine::finalize_clip() {
     const HostTensor* pos = get("embeddings.position_embedding.weight", {c.max_positions, E});
     ok = tok && pos;
     if (ok) {
-        clip_tok = upload32((size_t)c.vocab_size * E, [&](size_t i) { return tok->at(i); });
-        clip_pos = upload32((size_t)c.max_positions * E, [&](size_t i) { return pos->at(i); });
+        clip_tok = pack32((size_t)c.vocab_size * E, {{tok, nullptr, 0, c.vocab_size * E, 0}});
+        clip_pos = pack32((size_t)c.max_positions * E, {{pos, nullptr, 0, c.max_positions * E, 0}});
         ok = clip_tok && clip_pos;
     }
     clip_layers.resize(c.num_layers);
@@ -358,8 +339,8 @@ int Engine::finalize_clip() {
         ok = ok && qw && kw && vw && qb && kb && vb;
         if (ok) {
             L.qkv.N = 3 * E; L.qkv.K = E;
-            L.qkv.w = upload16((size_t)3 * E, E, [&](size_t r, size_t cc) { const HostTensor* s = r < (size_t)E ? qw : (r < (size_t)2 * E ? kw : vw); return s->at((r % E) * E + cc); });
-            L.qkv.b = upload32((size_t)3 * E, [&](size_t i) { const HostTensor* s = i < (size_t)E ? qb : (i < (size_t)2 * E ? kb : vb); return s->at(i % E); });
+            L.qkv.w = pack16((size_t)3 * E, E, {rows_piece(qw, 0, E, E), rows_piece(kw, E, E, E), rows_piece(vw, (size_t)2 * E, E, E)});
+            L.qkv.b = pack32((size_t)3 * E, {{qb, nullptr, 0, E, 0}, {kb, nullptr, (size_t)E, E, 0}, {vb, nullptr, (size_t)2 * E, E, 0}});
             ok = L.qkv.w && L.qkv.b;
         }
         ok = ok && mk_linear(p + ".self_attn.out_proj", E, E, true, L.out) && mk_linear(p + ".mlp.fc1", c.intermediate_size, E, true, L.fc1) &&
@@ -369,13 +350,9 @@ int Engine::finalize_clip() {
     if (ok && host.count("text_projection.weight")) {          // optional: the pooled output's projection (bias-free Linear)
         const HostTensor* tp = get("text_projection.weight", {E, E});
         ok = tp != nullptr;
-        if (ok) { clip_proj = upload32((size_t)E * E, [&](size_t i) { return tp->at(i); }); ok = clip_proj != nullptr; }
+        if (ok) { clip_proj = pack32((size_t)E * E, {{tp, nullptr, 0, E * E, 0}}); ok = clip_proj != nullptr; }
     }
-    if (!ok) {
-        if (!missing.empty()) { set_error("missing or mis-shaped weight: " + missing); return LDX_EMISSING; }
-        set_error(std::string("weight upload failed: ") + hipGetErrorString(hipGetLastError()));
-        return LDX_EHIP;
-    }
+    if (!ok) return weights_failed();
     host.clear();
     finalized = true;
     return LDX_OK;

@@ -28,12 +28,12 @@ int Engine::finalize_t5() {
     bool ok = true;
     const HostTensor* tok = get("shared.weight", {c.vocab_size, E});
     ok = tok != nullptr;
-    if (ok) { t5_tok = upload32((size_t)c.vocab_size * E, [&](size_t i) { return tok->at(i); }); ok = t5_tok != nullptr; }
+    if (ok) { t5_tok = pack32((size_t)c.vocab_size * E, {{tok, nullptr, 0, c.vocab_size * E, 0}}); ok = t5_tok != nullptr; }
     auto rms = [&](const std::string& name, NormW& n) {
         const HostTensor* w = get(name + ".weight", {E});
         if (!w) return false;
         n.C = E; n.b = nullptr;
-        n.g = upload32(E, [&](size_t i) { return w->at(i); });
+        n.g = pack32(E, {{w, nullptr, 0, E, 0}});
         return n.g != nullptr;
     };
     t5_layers.resize(c.num_layers);
@@ -46,7 +46,7 @@ int Engine::finalize_t5() {
         ok = ok && qw && kw && vw;
         if (ok) {
             L.qkv.N = 3 * E; L.qkv.K = E; L.qkv.b = nullptr;
-            L.qkv.w = upload16((size_t)3 * E, E, [&](size_t r, size_t cc) { const HostTensor* s = r < (size_t)E ? qw : (r < (size_t)2 * E ? kw : vw); return s->at((r % E) * E + cc); });
+            L.qkv.w = pack16((size_t)3 * E, E, {rows_piece(qw, 0, E, E), rows_piece(kw, E, E, E), rows_piece(vw, (size_t)2 * E, E, E)});
             ok = L.qkv.w != nullptr;
         }
         ok = ok && mk_linear(a + ".SelfAttention.o", E, E, false, L.o);
@@ -63,11 +63,7 @@ int Engine::finalize_t5() {
         ok = ok && mk_linear(f + ".DenseReluDense.wo", E, F, false, L.wo);
     }
     ok = ok && rms("encoder.final_layer_norm", t5_final_ln);
-    if (!ok) {
-        if (!missing.empty()) { set_error("missing or mis-shaped weight: " + missing); return LDX_EMISSING; }
-        set_error(std::string("weight upload failed: ") + hipGetErrorString(hipGetLastError()));
-        return LDX_EHIP;
-    }
+    if (!ok) return weights_failed();
     host.clear();
     finalized = true;
     return LDX_OK;

@@ -473,13 +473,14 @@ void launch_mix_nhwc_to_nchw(const MixArgs& a, hipStream_t s);
 void launch_bilinear(const float* in, float* out, int planes, int Hin, int Win, int Hout, int Wout, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
-// Weight packing on the device (pack.hip): what Engine::upload16 / upload32 / mk_ln_folded compute on the host, for state-dict tensors that
-// already live on the GPU (ldx_load_tensor_device).  Bit-identical to the host packers: the same integer rounding (weight_convert.h), single
-// fp32 / fp64 operations with no contraction.  sdt / *_dt are LDX_F32 | LDX_F16 | LDX_BF16 codes of the SOURCE tensors; out_dt is the engine's.
+// Weight packing (Engine::pack16 / pack32 / mk_ln_folded): the three argument structs describe one piece each, and weight_layout.h interprets them, for
+// pack.hip's kernels (state-dict tensors that already live on the GPU, ldx_load_tensor_device) and for the host packers alike, so the two agree bit for
+// bit.  sdt / *_dt are LDX_F32 | LDX_F16 | LDX_BF16 codes of the SOURCE tensors; out_dt is the engine's.  The pointers are device pointers for the
+// launchers below, host pointers in the host loops.
 // One piece of a packed 16-bit matrix: out[r][col0 + c] = scale * src(r, c), r in [0, N), c in [0, K), out row stride ldo (elements).
-//   CinPad == 0: src(r, c) = src[srow(r) * K + c], srow = the GEGLU slab permutation when geglu_inner > 0 (engine.cpp src_row), else r
+//   CinPad == 0: src(r, c) = src[srow(r) * K + c], srow = the GEGLU slab permutation when geglu_inner > 0 (geglu_src_row), else r
 //   CinPad  > 0: 3x3 conv [N][Cin][3][3] -> [N][ky][kx][CinPad] (K = 9 * CinPad): src(r, tap * CinPad + ci) = ci < Cin ? src[(r * Cin + ci) * 9 + tap] : 0
-// K, ldo, col0 and CinPad are multiples of 8 and `out` is 16-byte aligned: every store is 16 bytes.
+// For a launch K, ldo, col0 and CinPad are multiples of 8 and `out` is 16-byte aligned: every store is 16 bytes (the host loop takes any shape).
 struct PackArgs {
     const void* src; int sdt;
     void* out; long ldo; long col0; DType out_dt;
@@ -494,7 +495,7 @@ struct PackVecArgs { const void* a; int a_dt; const void* b; int b_dt; float* ou
 void launch_pack32(const PackVecArgs& a, hipStream_t s);
 // Rows [0, N) of a LayerNorm-folded projection (Engine::mk_ln_folded): w = scale * src[srow(r)][k];
 //   out[r][k] = 16-bit(w * gamma[k]);  c1[r] = (float) sum_k (double) out[r][k];  c2[r] = (float)(sum_k (double) w * beta[k] + bias[srow(r)])   (bias == null: 0)
-// both sums in fp64, ascending k.  K a multiple of 8.
+// both sums in fp64, ascending k.  For a launch K is a multiple of 8.
 struct LnFoldArgs {
     const void* src; int sdt; const void* gamma; int g_dt; const void* beta; int b_dt; const void* bias; int bias_dt;
     void* out; DType out_dt; float* c1; float* c2;

@@ -1,5 +1,6 @@
-// fp32 <-> 16-bit conversions of the weight packers (round-to-nearest-even), in integer arithmetic so that the host packer (engine.cpp upload16) and
-// the device packer (pack.hip) produce the same bits by construction: one copy, compiled for both sides.
+// fp32 <-> 16-bit conversions of the weight packers (round-to-nearest-even), in integer arithmetic so that the host and the device produce the same
+// bits by construction: one copy, compiled for both sides.  weight_layout.h builds the layouts on it in the same way: one interpreter of a piece, which
+// pack.hip's kernels and engine.cpp's host packers both loop over.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

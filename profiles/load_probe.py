@@ -1,5 +1,6 @@
 """How long the SD1.5 UNet engine takes to come up from a state dict that is resident on the GPU (what the reference's hook holds after
-ModelPatcher.patch_model), and how long UNetEngine.refresh takes to replace the weights of a running engine.
+ModelPatcher.patch_model) and from the same state dict on the host (the CPU packers), and how long UNetEngine.refresh takes to replace the
+weights of a running engine.
 
     python profiles/load_probe.py [--runs 3] [--dtype bf16] [--tree DIR]
 
@@ -46,6 +47,11 @@ def main():
             eng.close()
         eng, dt = timed(lambda: ldx.UNetEngine(cfg, sd, device=0, dtype=args.dtype))
         print(json.dumps({"tree": label, "what": "UNetEngine(sd15, fp16 state dict on the GPU)", "run": i, "seconds": round(dt, 4)}), flush=True)
+    sd_host = {k: v.cpu() for k, v in sd.items()}
+    for i in range(args.runs):
+        eng.close()
+        eng, dt = timed(lambda: ldx.UNetEngine(cfg, sd_host, device=0, dtype=args.dtype))
+        print(json.dumps({"tree": label, "what": "UNetEngine(sd15, fp16 state dict on the host)", "run": i, "seconds": round(dt, 4)}), flush=True)
     if hasattr(eng, "refresh"):
         for i in range(args.runs):
             _, dt = timed(lambda: eng.refresh(sd))

@@ -4,6 +4,9 @@
 //     L <mangled kernel name> <grid x,y,z> <block x,y,z> <dynamic LDS bytes> <hex bytes of argument 0>:<argument 1>:...
 //     C <dst> <src> <bytes> <kind>
 //     S <dst> <value> <bytes>
+// With LDX_STANDIN_WEIGHTS set, a synchronous host-to-device hipMemcpy (how every packed weight buffer and every staged source arrives) adds
+//     W <dst> <bytes> <64-bit FNV-1a of the bytes>
+// so that the packed bytes themselves can be held to a table (tests/tools/plan_trace.py --weights); without it hipMemcpy records nothing.
 // The size of every explicit kernel argument comes from the file named by LDX_STANDIN_ARGS (one line per kernel: name, then the sizes; tests/tools/plan_trace.py
 // writes it from the metadata of the real libldx.so's code objects).  tests/tools/plan_trace.py drives the C ABI of the library linked against this file.
 #include <hip/hip_runtime_api.h>
@@ -22,7 +25,7 @@ struct State {
     std::unordered_map<std::string, std::vector<int>> arg_sizes;
     FILE* trace = nullptr;
     uintptr_t next = 0x100000000000ull;                                    // bump allocator: 4 KiB aligned, never reused
-    bool env_read = false;
+    bool env_read = false, weights = false;
     dim3 grid, block; size_t lds = 0; hipStream_t stream = nullptr;        // __hipPushCallConfiguration
 };
 State& S() { static State* s = new State; return *s; }                     // never destroyed: module destructors of the library still call in at exit
@@ -31,6 +34,7 @@ FILE* trace() {
     if (!s.env_read) {
         s.env_read = true;
         if (const char* p = getenv("LDX_STANDIN_TRACE")) s.trace = fopen(p, "w");
+        s.weights = getenv("LDX_STANDIN_WEIGHTS") != nullptr;
         if (s.trace) setvbuf(s.trace, nullptr, _IOLBF, 1 << 16);           // a reader sees every record as soon as the call that made it returns
         if (const char* p = getenv("LDX_STANDIN_ARGS")) {
             if (FILE* f = fopen(p, "r")) {
@@ -82,7 +86,14 @@ hipError_t hipMemset(void* dst, int v, size_t n) {
 }
 hipError_t hipMalloc(void** p, size_t n) { State& s = S(); *p = (void*)s.next; s.next += (n + 4095) & ~(size_t)4095; if (!n) s.next += 4096; return hipSuccess; }
 hipError_t hipFree(void*) { return hipSuccess; }
-hipError_t hipMemcpy(void*, const void*, size_t, hipMemcpyKind) { return hipSuccess; }
+hipError_t hipMemcpy(void* dst, const void* src, size_t n, hipMemcpyKind kind) {
+    FILE* f = trace();
+    if (!f || !S().weights || kind != hipMemcpyHostToDevice) return hipSuccess;
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < n; ++i) { h ^= ((const unsigned char*)src)[i]; h *= 0x100000001b3ull; }
+    fprintf(f, "W %p %zu %016llx\n", dst, n, (unsigned long long)h);
+    return hipSuccess;
+}
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 hipError_t hipSetDevice(int d) { return d == 0 ? hipSuccess : hipErrorInvalidDevice; }

@@ -20,6 +20,13 @@ table was written from (diff the two outputs) shows the first differing record.
     python tests/tools/plan_trace.py --records N        # the records of case N in the current environment, kernel names demangled
     python tests/tools/plan_trace.py --full [DIR]       # not in the table: SD1.5 at latents 64^2 and 128^2, CFG batch 2, share 0 / 1 (the shapes at which dup_rows
                                                         # producers and the 8192-row share threshold are live); prints the digests, writes the traces into DIR
+
+--weights in front of any of the first six turns them to the second table, tests/golden/weight_bytes.json (tests/test_weight_bytes_cpu.py): the packed weights.  With
+LDX_STANDIN_WEIGHTS set the stand-in runtime also records every synchronous host-to-device copy as (destination, bytes, 64-bit FNV-1a of the bytes), so the records of
+a "build" case hold every packed buffer's address and content.  The cases (weight_rows) are the "build" cases above, then the UNets twice more: with every tensor
+registered through ldx_load_tensor_device at a made-up device address ("build_dev": the pack kernels' launches, grids and argument bytes, sizes from libldx_pack.so's
+code objects), and with every third key on the host ("build_mixed": the staging copies too).  The environments (WEIGHT_ENVS) are the four that change packed weights.
+A change to the packers or to a layout's description that is meant to leave the weights alone leaves this table alone.
 """
 import ctypes as C
 import hashlib
@@ -40,6 +47,8 @@ CSRC = os.path.join(ROOT, "lightdiffusion-next_amd", "csrc")
 HOST_LIB = os.path.join(ROOT, "lightdiffusion-next_amd", "libldx_host.so")
 ARG_SIZES = os.path.join(CSRC, "build", "host", "kernel_args.txt")
 FIELDS = ("records", "sha256[:8]")
+WEIGHT_TABLE = os.path.join(ROOT, "tests", "golden", "weight_bytes.json")
+WEIGHT_ENVS = [{}, {"LDX_NO_FUSED_SKIP": "1"}, {"LDX_NO_QPRESCALE": "1"}, {"LDX_LNFOLD": "0"}]
 
 # the planner switches that live in PlanSwitches or are read at planning time, flipped, and the dispatch switches a plan depends on.  No level of the small nets
 # fills the chip with row blocks, so LDX_ROWGEMM=0, LDX_XATTN_FUSE=0 and LDX_FF_FUSE=0 alone change nothing here (DEAD; they are held to the default's digests all the
@@ -89,6 +98,11 @@ def all_rows():
     return rows
 
 
+def weight_rows():
+    build = [r for r in all_rows() if r[3] == "build"]
+    return build + [r[:3] + (how,) + r[4:] for how in ("build_dev", "build_mixed") for r in build if r[0] == "unet"]
+
+
 FULL_ROWS = [("unet", "sd15", "bf16", "build", 0, 0, 0, 0, 0)] + [("unet", "sd15", "bf16", "cfg_t", n, n, b, share, 0) for n in (64, 128) for b in (1, 2) for share in (0, 1)]
 
 
@@ -129,8 +143,9 @@ def build_host():
     if not os.path.exists(kernel_resources.LIB):
         subprocess.run(["make", "-C", CSRC, "-j8"], check=True, capture_output=True)
     subprocess.run(["make", "-C", CSRC, "host", "-j8"], check=True, capture_output=True)
-    if not os.path.exists(ARG_SIZES) or os.path.getmtime(ARG_SIZES) < os.path.getmtime(kernel_resources.LIB):
-        sizes = kernel_arg_sizes()
+    libs = (kernel_resources.LIB, os.path.join(os.path.dirname(kernel_resources.LIB), "libldx_pack.so"))      # the load-time packers' kernels are in the second
+    if not os.path.exists(ARG_SIZES) or os.path.getmtime(ARG_SIZES) < max(map(os.path.getmtime, libs)):
+        sizes = dict(kernel_arg_sizes(libs[1]), **kernel_arg_sizes(libs[0]))
         with open(ARG_SIZES, "w") as f:
             f.write("".join(f"{k} {' '.join(map(str, v))}\n" for k, v in sorted(sizes.items())))
 
@@ -158,18 +173,24 @@ class Host:
     def check(self, rc, what):
         assert rc == 0, (what, rc, self.L.ldx_last_error().decode(errors="replace"))
 
-    def load(self, h, sd, strip=()):
+    def load(self, h, sd, strip=(), how="build"):
+        """how: "build" every tensor from the host; "build_dev" every tensor as device memory at a made-up address (nothing reads it); "build_mixed" every third
+        key from the host."""
         import torch
-        for k, t in sd.items():
+        for i, (k, t) in enumerate(sd.items()):
             for pre in strip:
                 if k.startswith(pre):
                     k = k[len(pre):]
             t = t.detach().contiguous()
             if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
                 t = t.float()
+            if how == "build_dev" or (how == "build_mixed" and i % 3):
+                self.check(self.L.ldx_load_tensor_device(h, k.encode(), C.c_void_p(DEV_SRC + (i << 28)), self.ldx.lib.torch_dtype_code(t.dtype), (C.c_int64 * t.dim())(*t.shape), t.dim()), k)
+                continue
             self.check(self.L.ldx_load_tensor(h, k.encode(), C.c_void_p(t.data_ptr()), self.ldx.lib.torch_dtype_code(t.dtype), (C.c_int64 * t.dim())(*t.shape), t.dim()), k)
 
 
+DEV_SRC = 0x7e0000000000                                                      # ... and its state dict's tensors, 256 MiB apart (build_dev / build_mixed)
 P = {n: 0x7f0000000000 + (i << 32) for i, n in enumerate(("x", "s", "ctx", "out", "cc", "t", "ids", "out2", "bias", "y", "guid", "cos", "sin"))}      # the caller's "device" buffers
 
 
@@ -210,7 +231,7 @@ def _engine(H, row):
                     channel_mult=cfg.channel_mult, num_res_blocks=cfg.num_res_blocks, transformer_depth=cfg.transformer_depth, transformer_depth_output=cfg.transformer_depth_output,
                     transformer_depth_middle=cfg.transformer_depth_middle, num_heads=cfg.num_heads, context_dim=cfg.context_dim)
         H.check(L.ldx_create(C.byref(c), 0, C.byref(h)), "ldx_create")
-        H.load(h, _synth(W, net, W.unet_state_dict_spec(cfg)))
+        H.load(h, _synth(W, net, W.unet_state_dict_spec(cfg)), how=row[3])
         _, ls = ldx.engine.sd15_sigmas()
         temb = ldx.engine.timestep_embedding_table(ls.numel(), cfg.model_channels)
         H.check(L.ldx_set_tables(h, C.c_void_p(ls.data_ptr()), ls.numel(), C.c_void_p(temb.data_ptr()), temb.shape[1]), "ldx_set_tables")
@@ -284,7 +305,7 @@ def traces_of_current_env(rows):
     H.take()
     out, h, cfg = [], None, None
     for row in rows:
-        if row[3] == "build":
+        if row[3].startswith("build"):
             if h:
                 H.L.ldx_destroy(h)
             h, cfg = _engine(H, row)
@@ -293,7 +314,7 @@ def traces_of_current_env(rows):
             _run(H, h, cfg, row)
             n, f, ar = C.c_int64(), C.c_double(), C.c_int64()
             H.check(H.L.ldx_plan_info(h, C.byref(n), C.byref(f), C.byref(ar)), "ldx_plan_info")
-        out.append(H.take() + ([f"P launches={n.value} flops={f.value!r} arena={ar.value}"] if row[3] != "build" else []))
+        out.append(H.take() + ([f"P launches={n.value} flops={f.value!r} arena={ar.value}"] if not row[3].startswith("build") else []))
     if h:
         H.L.ldx_destroy(h)
     os.unlink(H.path)
@@ -368,12 +389,38 @@ def _demangled(records):
     return [" ".join([r.split()[0], dm[r.split()[1]]] + r.split()[2:]) if r.startswith("L ") else r for r in records]
 
 
+class Weights:
+    """The tool (pick_table.cli) of the second table; its --dump processes are told apart by LDX_STANDIN_WEIGHTS, which the stand-in runtime reads too."""
+    ENVS, TABLE, all_rows = WEIGHT_ENVS, WEIGHT_TABLE, staticmethod(weight_rows)
+    picks_of_current_env, decode, describe = staticmethod(picks_of_current_env), staticmethod(pick_table.decode_digests), staticmethod(describe)
+
+    @staticmethod
+    def picks_of_envs(envs):
+        return dict(zip(map(env_key, envs), picks_of_envs([dict(e, LDX_STANDIN_WEIGHTS="1") for e in envs]).values()))
+
+    @staticmethod
+    def load_table():
+        return pick_table.load_table(WEIGHT_TABLE)
+
+    @staticmethod
+    def write_table(per_env, rows):
+        return write_table(per_env, rows, WEIGHT_TABLE)
+
+    @staticmethod
+    def mismatch(env, index, row, got, want):
+        return (f"{env_key(env)}: case {index} {row}: {got[0]} records, digest {got[1]} (table: {want[0]}, {want[1]}); `{' '.join(f'{k}={v}' for k, v in env.items())} "
+                f"python tests/tools/plan_trace.py --weights --records {index}` lists this tree's records, to be compared with those of the tree the table was written from")
+
+
 if __name__ == "__main__":
+    weights = "--weights" in sys.argv or "LDX_STANDIN_WEIGHTS" in os.environ
+    if weights:
+        os.environ["LDX_STANDIN_WEIGHTS"] = "1"
     if "--rows" not in sys.argv and "--show" not in sys.argv:
         build_host()
     if "--records" in sys.argv:
         n = int(sys.argv[sys.argv.index("--records") + 1])
-        print("\n".join(_demangled(traces_of_current_env(all_rows()[:n + 1])[n])))
+        print("\n".join(_demangled(traces_of_current_env((weight_rows() if weights else all_rows())[:n + 1])[n])))
     elif "--full" in sys.argv:
         i = sys.argv.index("--full")
         out_dir = sys.argv[i + 1] if i + 1 < len(sys.argv) else None
@@ -384,4 +431,4 @@ if __name__ == "__main__":
                 with open(os.path.join(out_dir, "_".join(map(str, row)) + ".txt"), "w") as f:
                     f.write("\n".join(t) + "\n")
     else:
-        pick_table.cli(sys.modules[__name__])
+        pick_table.cli(Weights if weights else sys.modules[__name__])
