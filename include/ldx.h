@@ -341,6 +341,38 @@ int ldx_bislerp_pass(const float* in, float* out, int N, int C, int H, int W, in
 /* F.interpolate(mode="bilinear", align_corners=False) on fp32 [planes][H][W] (samplers.py:227-241). */
 int ldx_bilinear(const float* in, float* out, int planes, int hin, int win, int hout, int wout, void* stream);
 
+/* ---- 8-bit image ops of the img2img path (Ultimate SD Upscale, src/UltimateSDUpscale/UltimateSDUpscale.py:126-245) ---------------------- */
+/* What the reference does in PIL between the networks.  Images are HWC uint8 on the device, C = 3 (RGB) or 1 (mask), with a row pitch in BYTES
+ * (>= W * C), so a crop of a canvas is a source or a destination without a copy.  Pillow's 8-bit paths are integer arithmetic: the results are
+ * Pillow's bytes, not approximations of them.  Stateless; every rectangle must lie inside its image (LDX_EINVAL otherwise). */
+/* tensor_to_pil (image_util.py:133-178): in fp32 [H][W][C] dense -> out = (uint8) trunc(clamp(v, 0, 1) * 255.0f).  No rounding: k / 255.0f * 255.0f may
+ * land just under k and give k - 1, as in the reference. */
+int ldx_image_quantize(const float* in_hwc, int H, int W, int C, uint8_t* out, int64_t out_pitch, void* stream);
+/* pil_to_tensor (image_util.py:181-203) of the crop (x0, y0, w, h) of img [H][W][C]: out fp32 [h][w][C] dense = v / 255.0f, the correctly rounded
+ * IEEE quotient: the NHWC tensor ldx_vae_encode reads. */
+int ldx_image_to_float(const uint8_t* img, int64_t pitch, int H, int W, int C, int x0, int y0, int w, int h, float* out_hwc, void* stream);
+/* One axis of Pillow's 8-bit ImagingResample (Image.resize, UltimateSDUpscale.py:178,220-222,356-358): in [H][W][C] -> out with W (axis 1) or H
+ * (axis 0) replaced by new_len.  Per output index i the host supplies bounds[2 i] = first source index, bounds[2 i + 1] = number of taps (<= ksize)
+ * and kk[i][ksize] = the coefficients in 2^-22 units, built in double precision exactly as Pillow's precompute_coeffs / normalize_coeffs_8bpc do;
+ *   out = clip8((2^21 + sum_j kk[i][j] * in[first + j]) >> 22).
+ * A 2-D resize is the axis-1 pass, then the axis-0 pass, through a uint8 intermediate.  in and out must not overlap. */
+int ldx_image_resample_pass(const uint8_t* in, int64_t in_pitch, int H, int W, int C, int axis, int new_len,
+                            const int32_t* bounds, const int32_t* kk, int ksize, uint8_t* out, int64_t out_pitch, void* stream);
+/* One pass of Pillow's box blur on a single-channel image (ImageFilter.GaussianBlur on mode L, UltimateSDUpscale.py:166-167, = three axis-1 passes
+ * then three axis-0 passes with the box radius fr of gaussian_box_params): R = (int) fr, ww = (uint32)(16777216.0f / (fr * 2 + 1)),
+ * fw = (2^24 - (2 R + 1) ww) / 2,
+ *   out[x] = (ww * sum_{i = -R..R} in[clamp(x + i)] + fw * (in[clamp(x - R - 1)] + in[clamp(x + R + 1)]) + 2^23) >> 24,
+ * indices clamped to the line.  0 <= fr < 256; lines shorter than the window work.  in and out must not overlap. */
+int ldx_image_box_blur_pass(const uint8_t* in, int64_t in_pitch, int H, int W, int axis, float box_radius, uint8_t* out, int64_t out_pitch, void* stream);
+/* process_images' paste + alpha_composite (UltimateSDUpscale.py:224-242) in place: for every pixel of the rectangle (x0, y0, w, h) of canvas
+ * [H][W][C], with a = mask [H][W] at the same position, s = tile [h][w][C], d = canvas: a == 0 leaves d; otherwise
+ *   coef1 = a * 255 * 255 * 128 / (a * 255 + 255 * (255 - a)), coef2 = 255 * 128 - coef1, t = s * coef1 + d * coef2 + (0x80 << 7),
+ *   d = (((t >> 8) + t) >> 8) >> 7. */
+int ldx_image_composite(uint8_t* canvas, int64_t canvas_pitch, int H, int W, int C, int x0, int y0, int w, int h,
+                        const uint8_t* tile, int64_t tile_pitch, const uint8_t* mask, int64_t mask_pitch, void* stream);
+/* img [H][W][C]: every byte of the rectangle (x0, y0, w, h) = value (ImageDraw.rectangle / Image.new for the tile masks, :471,514-518). */
+int ldx_image_fill_rect(uint8_t* img, int64_t pitch, int H, int W, int C, int x0, int y0, int w, int h, int value, void* stream);
+
 /* ---- single-op entry points (parity tests call the kernels through these) ----------------------- */
 /* 16-bit tensors are device pointers to bf16/fp16 per `dtype`.  Layouts: see csrc/ldx_kernels.h. */
 int ldx_op_convert(const float* in_f32, void* out_16, int64_t n, int dtype, int to_f32, void* stream);

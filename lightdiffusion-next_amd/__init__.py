@@ -12,6 +12,7 @@ Layout:
   parallel.py  batch shard + single all-gather across the GPUs of a node (RCCL / gloo)
   weights.py   SD1.5 state-dict layout + seeded synthetic weights (no checkpoints offline)
   checkpoint.py  load-time ingestion: checkpoint split, UNet layout sniffing, LoRA key maps + merge
+  usdu.py      UltimateSDUpscale: the img2img tile redraw / seam fix, canvas on the device (ldx_image_* kernels -> libldx_image.so)
 """
 from . import lib, weights  # noqa: F401
 from .engine import UNetEngine, UNetConfig, VAEDecoderEngine, CLIPTextEngine, FluxEngine, T5Engine, ESRGANEngine, bislerp, latent_upscale  # noqa: F401
@@ -19,4 +20,5 @@ VAEEngine = VAEDecoderEngine      # the same engine encodes when encoder.* weigh
 from .weights import VAEConfig, CLIPConfig, FluxConfig, T5Config, ESRGANConfig  # noqa: F401
 from .hook import LdxUNetPatch, LdxFluxPatch  # noqa: F401
 from . import prompt  # noqa: F401
-from . import sampling, parallel, checkpoint  # noqa: F401
+from . import sampling, parallel, checkpoint, usdu  # noqa: F401
+from .usdu import UltimateSDUpscale  # noqa: F401

@@ -158,6 +158,49 @@ int ldx_tile_finish(float* out, const float* div, int64_t n, int clamp01, void* 
     launch_tile_finish(out, div, (size_t)n, clamp01, (hipStream_t)stream);
     return check_launch("ldx_tile_finish");
 }
+// ---- 8-bit image ops (image.hip) -------------------------------------------------------------------------------------------------------
+static bool image_ok(const void* p, int64_t pitch, int H, int W, int C) { return p && H > 0 && W > 0 && (C == 1 || C == 3) && pitch >= (int64_t)W * C; }
+static bool rect_ok(int x0, int y0, int w, int h, int W, int H) { return x0 >= 0 && y0 >= 0 && w > 0 && h > 0 && x0 <= W - w && y0 <= H - h; }
+int ldx_image_quantize(const float* in, int H, int W, int C, uint8_t* out, int64_t out_pitch, void* stream) {
+    if (!in || !image_ok(out, out_pitch, H, W, C)) { set_error("ldx_image_quantize: bad argument (null pointer, C not 1 | 3, pitch < W * C)"); return LDX_EINVAL; }
+    launch_image_quantize(in, out, H, W, C, (long)out_pitch, (hipStream_t)stream);
+    return check_launch("ldx_image_quantize");
+}
+int ldx_image_to_float(const uint8_t* img, int64_t pitch, int H, int W, int C, int x0, int y0, int w, int h, float* out, void* stream) {
+    if (!out || !image_ok(img, pitch, H, W, C) || !rect_ok(x0, y0, w, h, W, H)) {
+        set_error("ldx_image_to_float: bad argument (null pointer, C not 1 | 3, pitch < W * C, crop outside the image)"); return LDX_EINVAL; }
+    launch_image_to_float(img + (int64_t)y0 * pitch + (int64_t)x0 * C, (long)pitch, out, h, w, C, (hipStream_t)stream);
+    return check_launch("ldx_image_to_float");
+}
+int ldx_image_resample_pass(const uint8_t* in, int64_t in_pitch, int H, int W, int C, int axis, int new_len,
+                            const int32_t* bounds, const int32_t* kk, int ksize, uint8_t* out, int64_t out_pitch, void* stream) {
+    if (!image_ok(in, in_pitch, H, W, C) || (axis != 0 && axis != 1) || new_len <= 0 || !bounds || !kk || ksize <= 0 || in == out ||
+        !image_ok(out, out_pitch, axis == 0 ? new_len : H, axis == 1 ? new_len : W, C)) {
+        set_error("ldx_image_resample_pass: bad argument (null pointer, C not 1 | 3, axis 0 | 1, pitch < W * C, in == out)"); return LDX_EINVAL; }
+    launch_image_resample_pass(in, (long)in_pitch, out, (long)out_pitch, H, W, C, axis, new_len, bounds, kk, ksize, (hipStream_t)stream);
+    return check_launch("ldx_image_resample_pass");
+}
+int ldx_image_box_blur_pass(const uint8_t* in, int64_t in_pitch, int H, int W, int axis, float box_radius, uint8_t* out, int64_t out_pitch, void* stream) {
+    if (!image_ok(in, in_pitch, H, W, 1) || !image_ok(out, out_pitch, H, W, 1) || (axis != 0 && axis != 1) || in == out ||
+        !(box_radius >= 0.0f) || !(box_radius < (float)(image_box_max_radius() + 1))) {
+        set_error("ldx_image_box_blur_pass: bad argument (null pointer, axis 0 | 1, pitch < W, in == out, box radius outside [0, 256))"); return LDX_EINVAL; }
+    launch_image_box_blur_pass(in, (long)in_pitch, out, (long)out_pitch, H, W, axis, box_radius, (hipStream_t)stream);
+    return check_launch("ldx_image_box_blur_pass");
+}
+int ldx_image_composite(uint8_t* canvas, int64_t canvas_pitch, int H, int W, int C, int x0, int y0, int w, int h,
+                        const uint8_t* tile, int64_t tile_pitch, const uint8_t* mask, int64_t mask_pitch, void* stream) {
+    if (!image_ok(canvas, canvas_pitch, H, W, C) || !rect_ok(x0, y0, w, h, W, H) || !image_ok(tile, tile_pitch, h, w, C) || !image_ok(mask, mask_pitch, H, W, 1)) {
+        set_error("ldx_image_composite: bad argument (null pointer, C not 1 | 3, pitch < W * C, rectangle outside the canvas)"); return LDX_EINVAL; }
+    launch_image_composite(canvas + (int64_t)y0 * canvas_pitch + (int64_t)x0 * C, (long)canvas_pitch, tile, (long)tile_pitch,
+                           mask + (int64_t)y0 * mask_pitch + x0, (long)mask_pitch, h, w, C, (hipStream_t)stream);
+    return check_launch("ldx_image_composite");
+}
+int ldx_image_fill_rect(uint8_t* img, int64_t pitch, int H, int W, int C, int x0, int y0, int w, int h, int value, void* stream) {
+    if (!image_ok(img, pitch, H, W, C) || !rect_ok(x0, y0, w, h, W, H) || value < 0 || value > 255) {
+        set_error("ldx_image_fill_rect: bad argument (null pointer, C not 1 | 3, pitch < W * C, rectangle outside the image, value outside 0..255)"); return LDX_EINVAL; }
+    launch_image_fill(img + (int64_t)y0 * pitch + (int64_t)x0 * C, (long)pitch, h, w * C, value, (hipStream_t)stream);
+    return check_launch("ldx_image_fill_rect");
+}
 int ldx_t5_create(const ldx_t5_config* cfg, int device, ldx_engine** out) {
     GUARD_BEGIN
     if (!cfg || !out) { set_error("ldx_t5_create: null argument"); return LDX_EINVAL; }

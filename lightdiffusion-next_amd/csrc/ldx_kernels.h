@@ -503,4 +503,17 @@ struct LnFoldArgs {
 };
 void launch_ln_fold(const LnFoldArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// 8-bit image ops of the img2img path (image.hip, libldx_image.so): HWC uint8 device images with a row pitch in bytes; include/ldx.h states each rule.
+// The launchers take validated arguments (capi.cpp): rectangles inside the image, pitch >= W * C, box radius <= image_box_max_radius().
+void launch_image_quantize(const float* in, uint8_t* out, int H, int W, int C, long out_pitch, hipStream_t s);
+void launch_image_to_float(const uint8_t* in, long in_pitch, float* out, int H, int W, int C, hipStream_t s);
+void launch_image_resample_pass(const uint8_t* in, long in_pitch, uint8_t* out, long out_pitch, int H, int W, int C, int axis, int new_len,
+                                const int* bounds, const int* kk, int ksize, hipStream_t s);
+int image_box_max_radius();
+void launch_image_box_blur_pass(const uint8_t* in, long in_pitch, uint8_t* out, long out_pitch, int H, int W, int axis, float radius, hipStream_t s);
+void launch_image_composite(uint8_t* canvas, long canvas_pitch, const uint8_t* tile, long tile_pitch, const uint8_t* mask, long mask_pitch,
+                            int h, int w, int C, hipStream_t s);
+void launch_image_fill(uint8_t* img, long pitch, int h, int rowlen, int value, hipStream_t s);
+
 }  // namespace ldx

@@ -110,6 +110,12 @@ _SIGS = {
     "ldx_bislerp_pass": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ldx_vae_encode": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "ldx_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ldx_image_quantize": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp]),
+    "ldx_image_to_float": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldx_image_resample_pass": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i64, _vp]),
+    "ldx_image_box_blur_pass": (_i, [_vp, _i64, _i, _i, _i, _f, _vp, _i64, _vp]),
+    "ldx_image_composite": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp]),
+    "ldx_image_fill_rect": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ldx_op_convert": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     "ldx_op_gemm": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
     "ldx_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
