@@ -131,7 +131,9 @@ int ldx_load_tensor(ldx_engine* e, const char* key, const void* data, int dtype,
 int ldx_load_tensor_device(ldx_engine* e, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
 /* Sigma / timestep tables built by the host exactly as the reference builds them
  * (ModelSamplingDiscrete.set_sigmas sampling.py:285-289 -> log_sigmas[n];
- *  timestep_embedding sampling_util.py:56-76 evaluated at t = 0..n-1 -> temb[n][model_channels]). */
+ *  timestep_embedding sampling_util.py:56-76 evaluated at t = 0..n-1 -> temb[n][model_channels]).
+ * UNet engines only: on a handle of any other model LDX_ESTATE ("not a UNet engine"), like every ldx_unet_* entry point,
+ * before an argument is looked at. */
 int ldx_set_tables(ldx_engine* e, const float* log_sigmas, int n, const float* temb, int temb_dim);
 /* Pack weights into MFMA-friendly layouts and upload them.  After this the host copies are dropped. */
 int ldx_finalize(ldx_engine* e);

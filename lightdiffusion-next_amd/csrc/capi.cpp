@@ -1,5 +1,6 @@
 // extern "C" surface of libldx.so (include/ldx.h).  No exceptions cross the ABI.
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 
@@ -15,11 +16,35 @@ struct ldx_engine { Engine* impl; };
     catch (const std::bad_alloc&) { set_error("out of host memory"); return LDX_EINVAL; } \
     catch (const std::exception& ex) { set_error(std::string("internal error: ") + ex.what()); return LDX_EINVAL; }
 
+// The engine behind a handle as the class an entry point belongs to: Engine for what every model answers, a model's class for its own entry points.
+// Null, with the error text set and *rc the code to return, for a null handle (LDX_EINVAL) or another model's engine (wrong_model).
+template <class T> static T* engine_as(ldx_engine* e, const char* fn, int* rc, int wrong_model = LDX_ESTATE) {
+    T* t = e ? dynamic_cast<T*>(e->impl) : nullptr;
+    if (!t) { set_error(std::string(fn) + ": not a " + T::model + " engine"); *rc = e ? wrong_model : LDX_EINVAL; }
+    return t;
+}
+// `m`: the engine of handle `e` as a T, or leave the entry point with engine_as's code
+#define ENGINE_AS(T, m, ...)                                          \
+    int m##_rc = LDX_OK;                                              \
+    T* const m = engine_as<T>(e, __func__, &m##_rc, ##__VA_ARGS__);   \
+    if (!m) return m##_rc
+
 static int check_device(int device) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device available (libldx has no CPU fallback)"); return LDX_EHIP; }
     if (device < 0 || device >= n) { set_error("device ordinal out of range"); return LDX_EINVAL; }
     return LDX_OK;
+}
+template <class T, class Config> static int create_engine(const Config* cfg, int device, ldx_engine** out, const char* fn) {
+    GUARD_BEGIN
+    if (!cfg || !out) { set_error(std::string(fn) + ": null argument"); return LDX_EINVAL; }
+    int rc = check_device(device);
+    if (rc) return rc;
+    std::unique_ptr<T> e(new T(*cfg, device));
+    if ((rc = e->validate())) return rc;
+    *out = new ldx_engine{e.release()};
+    return LDX_OK;
+    GUARD_END
 }
 static inline DType dtype_of(int d) { return d == LDX_F16 ? DT_F16 : DT_BF16; }
 static int check_launch(const char* what) {
@@ -76,75 +101,40 @@ extern "C" {
 const char* ldx_version(void) { return "ldx 0.1 (gfx950)"; }
 const char* ldx_last_error(void) { return g_last_error.c_str(); }
 
-int ldx_create(const ldx_unet_config* cfg, int device, ldx_engine** out) {
-    GUARD_BEGIN
-    if (!cfg || !out) { set_error("ldx_create: null argument"); return LDX_EINVAL; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    Engine* e = new Engine(*cfg, device);
-    rc = e->validate();
-    if (rc) { delete e; return rc; }
-    *out = new ldx_engine{e};
-    return LDX_OK;
-    GUARD_END
-}
+int ldx_create(const ldx_unet_config* cfg, int device, ldx_engine** out) { return create_engine<UNetEngine>(cfg, device, out, __func__); }
 void ldx_destroy(ldx_engine* e) { if (e) { delete e->impl; delete e; } }
 
-int ldx_vae_create(const ldx_vae_config* cfg, int device, ldx_engine** out) {
-    GUARD_BEGIN
-    if (!cfg || !out) { set_error("ldx_vae_create: null argument"); return LDX_EINVAL; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    *out = new ldx_engine{new Engine(*cfg, device)};
-    return LDX_OK;
-    GUARD_END
-}
-int ldx_clip_create(const ldx_clip_config* cfg, int device, ldx_engine** out) {
-    GUARD_BEGIN
-    if (!cfg || !out) { set_error("ldx_clip_create: null argument"); return LDX_EINVAL; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    *out = new ldx_engine{new Engine(*cfg, device)};
-    return LDX_OK;
-    GUARD_END
-}
+int ldx_vae_create(const ldx_vae_config* cfg, int device, ldx_engine** out) { return create_engine<VaeEngine>(cfg, device, out, __func__); }
+int ldx_clip_create(const ldx_clip_config* cfg, int device, ldx_engine** out) { return create_engine<ClipEngine>(cfg, device, out, __func__); }
 int ldx_vae_decode(ldx_engine* e, const float* z, int B, int h, int w, float* out, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->run_vae(z, B, h, w, out, (hipStream_t)stream);
+    ENGINE_AS(VaeEngine, m);
+    return m->run_decode(z, B, h, w, out, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_clip_encode(ldx_engine* e, const int32_t* ids, int B, int T, int inter_layer, float* out_last, float* out_inter, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->run_clip((const int*)ids, B, T, inter_layer, out_last, out_inter, (hipStream_t)stream);
+    ENGINE_AS(ClipEngine, m);
+    return m->run((const int*)ids, B, T, inter_layer, out_last, out_inter, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_clip_pooled(ldx_engine* e, const float* last, const int32_t* ids, int B, int T, int eos_token_id, float* out_pooled, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->clip_pooled(last, (const int*)ids, B, T, eos_token_id, out_pooled, (hipStream_t)stream);
+    ENGINE_AS(ClipEngine, m);
+    return m->clip_pooled(last, (const int*)ids, B, T, eos_token_id, out_pooled, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_clip_set_extra_embeddings(ldx_engine* e, const float* rows_host, int n) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->set_clip_extra(rows_host, n);
+    ENGINE_AS(ClipEngine, m);
+    return m->set_clip_extra(rows_host, n);
     GUARD_END
 }
-int ldx_esrgan_create(const ldx_esrgan_config* cfg, int device, ldx_engine** out) {
-    GUARD_BEGIN
-    if (!cfg || !out) { set_error("ldx_esrgan_create: null argument"); return LDX_EINVAL; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    *out = new ldx_engine{new Engine(*cfg, device)};
-    return LDX_OK;
-    GUARD_END
-}
+int ldx_esrgan_create(const ldx_esrgan_config* cfg, int device, ldx_engine** out) { return create_engine<EsrganEngine>(cfg, device, out, __func__); }
 int ldx_esrgan_forward(ldx_engine* e, const float* pixels_nhwc, int B, int H, int W, float* out_nhwc, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->run_esrgan(pixels_nhwc, B, H, W, out_nhwc, (hipStream_t)stream);
+    ENGINE_AS(EsrganEngine, m);
+    return m->run(pixels_nhwc, B, H, W, out_nhwc, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_tile_blend(const float* tile, int th, int tw, float* out, float* div, int H, int W, int C, int y0, int x0, int feather, void* stream) {
@@ -201,191 +191,163 @@ int ldx_image_fill_rect(uint8_t* img, int64_t pitch, int H, int W, int C, int x0
     launch_image_fill(img + (int64_t)y0 * pitch + (int64_t)x0 * C, (long)pitch, h, w * C, value, (hipStream_t)stream);
     return check_launch("ldx_image_fill_rect");
 }
-int ldx_t5_create(const ldx_t5_config* cfg, int device, ldx_engine** out) {
-    GUARD_BEGIN
-    if (!cfg || !out) { set_error("ldx_t5_create: null argument"); return LDX_EINVAL; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    *out = new ldx_engine{new Engine(*cfg, device)};
-    return LDX_OK;
-    GUARD_END
-}
+int ldx_t5_create(const ldx_t5_config* cfg, int device, ldx_engine** out) { return create_engine<T5Engine>(cfg, device, out, __func__); }
 int ldx_t5_encode(ldx_engine* e, const int32_t* ids, int B, int L, const float* bias, float* out, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->run_t5((const int*)ids, B, L, bias, out, (hipStream_t)stream);
+    ENGINE_AS(T5Engine, m);
+    return m->run((const int*)ids, B, L, bias, out, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_flux_fbcache(ldx_engine* e, float residual_diff_threshold) {
     GUARD_BEGIN
-    if (!e || e->impl->kind != KIND_FLUX) { set_error("ldx_flux_fbcache: not a Flux engine"); return LDX_EINVAL; }
-    e->impl->fb_threshold = residual_diff_threshold > 0.f ? residual_diff_threshold : 0.f;
-    e->impl->fb_reset(); e->impl->fb_hits = e->impl->fb_misses = 0;
+    ENGINE_AS(FluxEngine, m, LDX_EINVAL);
+    m->fb_threshold = residual_diff_threshold > 0.f ? residual_diff_threshold : 0.f;
+    m->fb_reset(); m->fb_hits = m->fb_misses = 0;
     return LDX_OK;
     GUARD_END
 }
 int ldx_flux_set_fp8(ldx_engine* e, int enable) {
     GUARD_BEGIN
-    if (!e || e->impl->kind != KIND_FLUX) { set_error("ldx_flux_set_fp8: not a Flux engine"); return LDX_EINVAL; }
-    if (e->impl->finalized) { set_error("ldx_flux_set_fp8: call before ldx_finalize (the weights are quantised there)"); return LDX_ESTATE; }
+    ENGINE_AS(FluxEngine, m, LDX_EINVAL);
+    if (m->finalized) { set_error("ldx_flux_set_fp8: call before ldx_finalize (the weights are quantised there)"); return LDX_ESTATE; }
     if (enable < 0 || enable > 3) { set_error("ldx_flux_set_fp8: mode must be 0 (off), 1 / 2 (linears) or 3 (linears + attention)"); return LDX_EINVAL; }
-    e->impl->fx_fp8 = enable != 0;
-    e->impl->fx_fp8_attn = enable == 3;        // 1 (= 2): the linears only, QK^T / PV stay 16-bit — what the mode has meant since round 2; 3: linears AND attention (explicit opt-in)
+    m->fx_fp8 = enable != 0;
+    m->fx_fp8_attn = enable == 3;        // 1 (= 2): the linears only, QK^T / PV stay 16-bit — what the mode has meant since round 2; 3: linears AND attention (explicit opt-in)
     return LDX_OK;
     GUARD_END
 }
 int ldx_flux_fbcache_stats(ldx_engine* e, int64_t* hits, int64_t* misses) {
     GUARD_BEGIN
-    if (!e || e->impl->kind != KIND_FLUX) { set_error("ldx_flux_fbcache_stats: not a Flux engine"); return LDX_EINVAL; }
-    if (hits) *hits = e->impl->fb_hits;
-    if (misses) *misses = e->impl->fb_misses;
+    ENGINE_AS(FluxEngine, m, LDX_EINVAL);
+    if (hits) *hits = m->fb_hits;
+    if (misses) *misses = m->fb_misses;
     return LDX_OK;
     GUARD_END
 }
-int ldx_flux_create(const ldx_flux_config* cfg, int device, ldx_engine** out) {
-    GUARD_BEGIN
-    if (!cfg || !out) { set_error("ldx_flux_create: null argument"); return LDX_EINVAL; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    *out = new ldx_engine{new Engine(*cfg, device)};
-    return LDX_OK;
-    GUARD_END
-}
+int ldx_flux_create(const ldx_flux_config* cfg, int device, ldx_engine** out) { return create_engine<FluxEngine>(cfg, device, out, __func__); }
 int ldx_flux_forward(ldx_engine* e, const float* x, const float* sigma, const float* ctx, const float* y, const float* guidance,
                      const float* pe_cos, const float* pe_sin, int B, int h, int w, int Lt, int denoise, float* out, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->run_flux(x, sigma, ctx, y, guidance, pe_cos, pe_sin, B, h, w, Lt, denoise != 0, out, (hipStream_t)stream);
+    ENGINE_AS(FluxEngine, m);
+    return m->run(x, sigma, ctx, y, guidance, pe_cos, pe_sin, B, h, w, Lt, denoise != 0, out, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_load_tensor(ldx_engine* e, const char* key, const void* data, int dtype, const int64_t* shape, int ndim) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->load_tensor(key, data, dtype, shape, ndim);
+    ENGINE_AS(Engine, m);
+    return m->load_tensor(key, data, dtype, shape, ndim);
     GUARD_END
 }
 int ldx_load_tensor_device(ldx_engine* e, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->load_tensor_device(key, dev_ptr, dtype, shape, ndim);
+    ENGINE_AS(UNetEngine, m);
+    return m->load_tensor_device(key, dev_ptr, dtype, shape, ndim);
     GUARD_END
 }
 int ldx_unet_refresh_begin(ldx_engine* e) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->refresh_begin();
+    ENGINE_AS(UNetEngine, m);
+    return m->refresh_begin();
     GUARD_END
 }
 int ldx_unet_refresh_commit(ldx_engine* e) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->refresh_commit();
+    ENGINE_AS(UNetEngine, m);
+    return m->refresh_commit();
     GUARD_END
 }
 int ldx_unet_refresh_abort(ldx_engine* e) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->refresh_abort();
+    ENGINE_AS(UNetEngine, m);
+    return m->refresh_abort();
     GUARD_END
 }
 int ldx_weights_digest(ldx_engine* e, uint64_t* out) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->weights_digest(out);
+    ENGINE_AS(UNetEngine, m);
+    return m->weights_digest(out);
     GUARD_END
 }
 int ldx_set_tables(ldx_engine* e, const float* log_sigmas, int n, const float* temb, int temb_dim) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->set_tables(log_sigmas, n, temb, temb_dim);
+    ENGINE_AS(UNetEngine, m);
+    return m->set_tables(log_sigmas, n, temb, temb_dim);
     GUARD_END
 }
 int ldx_finalize(ldx_engine* e) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (e->impl->kind == KIND_VAE) return e->impl->finalize_vae();
-    if (e->impl->kind == KIND_CLIP) return e->impl->finalize_clip();
-    if (e->impl->kind == KIND_FLUX) return e->impl->finalize_flux();
-    if (e->impl->kind == KIND_T5) return e->impl->finalize_t5();
-    if (e->impl->kind == KIND_ESRGAN) return e->impl->finalize_esrgan();
-    return e->impl->finalize();
+    ENGINE_AS(Engine, m);
+    return m->finalize();
     GUARD_END
 }
 int ldx_unet_denoise(ldx_engine* e, const float* x, const float* sigma, const float* ctx, int B2, int h, int w, int M, float* out, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (e->impl->kind != KIND_UNET) { set_error("ldx_unet_denoise: not a UNet engine"); return LDX_ESTATE; }
-    return e->impl->run(x, sigma, ctx, B2, h, w, M, out, true, (hipStream_t)stream);
+    ENGINE_AS(UNetEngine, m);
+    return m->run(x, sigma, ctx, B2, h, w, M, out, true, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_unet_denoise_concat(ldx_engine* e, const float* x, const float* sigma, const float* ctx, const float* c_concat, int cc_channels, int B2, int h, int w, int M,
                             float* out, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (e->impl->kind != KIND_UNET) { set_error("ldx_unet_denoise_concat: not a UNet engine"); return LDX_ESTATE; }
+    ENGINE_AS(UNetEngine, m);
     if (!c_concat) { set_error("ldx_unet_denoise_concat: c_concat is null (use ldx_unet_denoise)"); return LDX_EINVAL; }
-    return e->impl->run(x, sigma, ctx, B2, h, w, M, out, true, (hipStream_t)stream, 0, c_concat, cc_channels);
+    return m->run(x, sigma, ctx, B2, h, w, M, out, true, (hipStream_t)stream, 0, c_concat, cc_channels);
     GUARD_END
 }
 int ldx_unet_denoise_cfg(ldx_engine* e, const float* x, float sigma, const float* ctx, int B, int h, int w, int M, float* out, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (e->impl->kind != KIND_UNET) { set_error("ldx_unet_denoise_cfg: not a UNet engine"); return LDX_ESTATE; }
-    return e->impl->run_cfg(x, sigma, ctx, B, h, w, M, out, (hipStream_t)stream);
+    ENGINE_AS(UNetEngine, m);
+    return m->run_cfg(x, sigma, ctx, B, h, w, M, out, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_unet_denoise_cfg_t(ldx_engine* e, const float* x, float sigma, int t_index, const float* ctx, int B, int h, int w, int M, float* out, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (e->impl->kind != KIND_UNET) { set_error("ldx_unet_denoise_cfg_t: not a UNet engine"); return LDX_ESTATE; }
-    return e->impl->run_cfg(x, sigma, ctx, B, h, w, M, out, (hipStream_t)stream, t_index < 0 ? -1 : t_index);
+    ENGINE_AS(UNetEngine, m);
+    return m->run_cfg(x, sigma, ctx, B, h, w, M, out, (hipStream_t)stream, t_index < 0 ? -1 : t_index);
     GUARD_END
 }
 int ldx_unet_denoise_t(ldx_engine* e, const float* x, const float* sigma, const float* t_index, const float* ctx, int B2, int h, int w, int M, float* out, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (e->impl->kind != KIND_UNET) { set_error("ldx_unet_denoise_t: not a UNet engine"); return LDX_ESTATE; }
+    ENGINE_AS(UNetEngine, m);
     if (!t_index) { set_error("ldx_unet_denoise_t: t_index is null (use ldx_unet_denoise)"); return LDX_EINVAL; }
-    return e->impl->run(x, sigma, ctx, B2, h, w, M, out, true, (hipStream_t)stream, 0, nullptr, 0, t_index);
+    return m->run(x, sigma, ctx, B2, h, w, M, out, true, (hipStream_t)stream, 0, nullptr, 0, t_index);
     GUARD_END
 }
 int ldx_unet_timestep(ldx_engine* e, const float* sigma, int n, int32_t* t_out, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->timestep_lookup(sigma, n, (int*)t_out, (hipStream_t)stream);
+    ENGINE_AS(UNetEngine, m);
+    return m->timestep_lookup(sigma, n, (int*)t_out, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_unet_forward(ldx_engine* e, const float* x, const float* t, const float* ctx, int B2, int h, int w, int M, float* out, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (e->impl->kind != KIND_UNET) { set_error("ldx_unet_forward: not a UNet engine"); return LDX_ESTATE; }
-    return e->impl->run(x, t, ctx, B2, h, w, M, out, false, (hipStream_t)stream);
+    ENGINE_AS(UNetEngine, m);
+    return m->run(x, t, ctx, B2, h, w, M, out, false, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_plan_info(ldx_engine* e, int64_t* n_launches, double* flops, int64_t* arena_bytes) {
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (n_launches) *n_launches = e->impl->n_launches();
-    if (flops) *flops = e->impl->algorithmic_flops();
-    if (arena_bytes) *arena_bytes = (int64_t)e->impl->cur.arena_cap;
+    ENGINE_AS(Engine, m);
+    if (n_launches) *n_launches = m->n_launches();
+    if (flops) *flops = m->algorithmic_flops();
+    if (arena_bytes) *arena_bytes = (int64_t)m->cur.arena_cap;
     return LDX_OK;
 }
 int ldx_plan_flops(ldx_engine* e, double* executed, double* shared) {
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (executed) *executed = e->impl->steady_flops();
-    if (shared) *shared = e->impl->cur.flops_shared;
+    ENGINE_AS(Engine, m);
+    if (executed) *executed = m->steady_flops();
+    if (shared) *shared = m->cur.flops_shared;
     return LDX_OK;
 }
 int ldx_unet_cfg_share(ldx_engine* e, int enable) {
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (e->impl->kind != KIND_UNET) { set_error("ldx_unet_cfg_share: not a UNet engine"); return LDX_ESTATE; }
-    e->impl->cfg_share = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
+    ENGINE_AS(UNetEngine, m);
+    m->cfg_share = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
     return LDX_OK;
 }
 int ldx_profile(ldx_engine* e, int enable, int reset) {
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    e->impl->profiling = enable != 0;
-    e->impl->prof_detail = enable == 2;
-    if (reset) e->impl->prof.clear();
+    ENGINE_AS(Engine, m);
+    m->profiling = enable != 0;
+    m->prof_detail = enable == 2;
+    if (reset) m->prof.clear();
     return LDX_OK;
 }
 int ldx_profile_report(ldx_engine* e, char* buf, int64_t cap) {
@@ -396,14 +358,13 @@ int ldx_profile_report(ldx_engine* e, char* buf, int64_t cap) {
     return LDX_OK;
 }
 int ldx_set_graph_mode(ldx_engine* e, int enable) {
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    e->impl->graph_mode = enable != 0;
+    ENGINE_AS(Engine, m);
+    m->graph_mode = enable != 0;
     return LDX_OK;
 }
 int ldx_unet_context_cache(ldx_engine* e, int enable) {
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    if (e->impl->kind != KIND_UNET) { set_error("ldx_unet_context_cache: not a UNet engine"); return LDX_ESTATE; }
-    return e->impl->set_context_cache(enable);
+    ENGINE_AS(UNetEngine, m);
+    return m->set_context_cache(enable);
 }
 int ldx_reload_env(void) {
     reload_dispatch_env();
@@ -432,8 +393,8 @@ int ldx_bislerp_pass(const float* in, float* out, int N, int C, int H, int W, in
 }
 int ldx_vae_encode(ldx_engine* e, const float* pixels_nhwc, int B, int H, int W, float* moments_nchw, void* stream) {
     GUARD_BEGIN
-    if (!e) { set_error("null engine"); return LDX_EINVAL; }
-    return e->impl->run_vae_encode(pixels_nhwc, B, H, W, moments_nchw, (hipStream_t)stream);
+    ENGINE_AS(VaeEngine, m);
+    return m->run_encode(pixels_nhwc, B, H, W, moments_nchw, (hipStream_t)stream);
     GUARD_END
 }
 int ldx_bilinear(const float* in, float* out, int planes, int hin, int win, int hout, int wout, void* stream) {

@@ -1,4 +1,4 @@
-// Internal declarations of the ldx UNet engine (see engine.cpp).
+// Internal declarations of the ldx engines: the shared planner / executor (engine.cpp) and one class per model (engine_<model>.cpp).
 #pragma once
 #include <cstring>
 #include <functional>
@@ -50,7 +50,7 @@ struct XfBlockW { NormW ln1, ln2, ln3; LinearW qkv, o1, q2, kv2, o2, ff1, ff2; L
     bool ln_fold = false; float *c1_qkv = nullptr, *c1_q2 = nullptr, *c1_ff1 = nullptr; };
 struct XfW { NormW gn; LinearW proj_in, proj_out; std::vector<XfBlockW> blocks; int C = 0, depth = 0; };
 struct BlockW { bool has_res = false, has_xf = false, has_down = false, has_up = false; ResW res; XfW xf; LinearW down, up; int skip_ch = 0; };
-// Every weight of the UNet, as the structure walk (Engine::walk_weights) builds it; emb_all / kv_all: the emb_layers of every ResBlock and the k | v projections of
+// Every weight of the UNet, as the structure walk (UNetEngine::walk_weights) builds it; emb_all / kv_all: the emb_layers of every ResBlock and the k | v projections of
 // every cross-attention, each batched into one GEMM per forward ([emb_total][4 mc] and [kv_total][context_dim])
 struct UNetW {
     LinearW te0, te2, conv_in, conv_out, emb_all, kv_all;
@@ -69,7 +69,6 @@ enum OpKind { OP_PREP, OP_CVT, OP_SKINNY, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_FIN
               OP_VAEPREP, OP_SOFTMAX, OP_CLAMP, OP_EMBED, OP_CVT_OUT,
               OP_PIXPREP, OP_MOMENTS, OP_COPY_OUT,
               OP_FX_PATCH, OP_FX_TEMB, OP_FX_SILU, OP_FX_ROPE, OP_FX_UNPATCH, OP_FX_SKINNY_Y, OP_MXQ, OP_GEMM2, OP_XATTN, OP_FFBLOCK, OP_ROWGEMM, OP_ATTN_MX, OP_MXVT, OP_DUP };
-enum EngineKind { KIND_UNET = 0, KIND_VAE = 1, KIND_CLIP = 2, KIND_FLUX = 3, KIND_T5 = 4, KIND_ESRGAN = 5 };
 // One launch of a plan.  The rule: every kind has ONE argument struct (ldx_kernels.h, beside its launcher), filled by the planner, and Engine::launch_op hands it to
 // that launcher after filling in the pointers of the call (Bindings).  Nothing here has a meaning that depends on `kind`.
 struct Op {
@@ -102,10 +101,11 @@ struct Bindings {
     const float* t = nullptr;                     // UNet: caller-supplied timestep indices (run(): t_idx)
     bool ctxc = false;                            // UNet: context-cache mode (the ctx_only ops are left out)
     const int* ids = nullptr; float* out2 = nullptr; const float* bias = nullptr;       // CLIP / T5
+    const float* extra = nullptr; int n_extra = 0;                                        // CLIP: textual-inversion rows for ids >= vocab_size (T5: none)
     const float *y = nullptr, *guid = nullptr, *pe_cos = nullptr, *pe_sin = nullptr;     // Flux
     bool operator==(const Bindings& o) const {
         return x == o.x && s == o.s && ctx == o.ctx && out == o.out && den == o.den && xB == o.xB && cc == o.cc && ccn == o.ccn && t == o.t &&
-               ctxc == o.ctxc && ids == o.ids && out2 == o.out2 && bias == o.bias && y == o.y && guid == o.guid && pe_cos == o.pe_cos && pe_sin == o.pe_sin;
+               ctxc == o.ctxc && ids == o.ids && out2 == o.out2 && bias == o.bias && extra == o.extra && n_extra == o.n_extra && y == o.y && guid == o.guid && pe_cos == o.pe_cos && pe_sin == o.pe_sin;
     }
 };
 
@@ -152,93 +152,27 @@ struct FluxStreamW { LinearW qkv, proj, mlp0, mlp2; float* qs = nullptr; float* 
 struct FluxDoubleW { FluxStreamW img, txt; };
 struct FluxSingleW { LinearW lin1_qkv, lin1_mlp, lin2; float* qs = nullptr; float* ks = nullptr; int mod_off = 0; };
 
+// The planner / executor every model is built on, and what every model's weights go through.  A model is a derived class (UNetEngine, VaeEngine, ClipEngine,
+// T5Engine, EsrganEngine, FluxEngine) that owns its config, its weight tables, finalize(), its plan functions and its run entry points; the C ABI reaches a model
+// entry point only through that class (capi.cpp engine_as), so nothing here or there asks an engine what it is.
 class Engine {
 public:
-    Engine(const ldx_unet_config& c, int dev);
-    Engine(const ldx_vae_config& c, int dev);
-    Engine(const ldx_clip_config& c, int dev);
-    Engine(const ldx_flux_config& c, int dev);
-    Engine(const ldx_t5_config& c, int dev);
-    Engine(const ldx_esrgan_config& c, int dev);
-    ldx_esrgan_config ecfg{};
-    std::vector<RdbW> es_rdb; LinearW es_first, es_trunk, es_hr, es_last; std::vector<LinearW> es_up;
-    int finalize_esrgan();
-    int plan_esrgan(int B, int H, int W);
-    int run_esrgan(const float* px, int B, int H, int W, float* out, hipStream_t st);
-    ldx_t5_config tcfg{};
-    std::vector<T5LayerW> t5_layers; NormW t5_final_ln; float* t5_tok = nullptr;
-    int finalize_t5();
-    int plan_t5(int B, int L);
-    int run_t5(const int* ids, int B, int L, const float* bias, float* out, hipStream_t st);
-    ldx_flux_config fcfg{};
-    int finalize_flux();
-    // First-block cache (WaveSpeed/first_block_cache.py:105-384, fbcache_nodes.py:8-201): opt-in approximate mode
-    float fb_threshold = 0.f; bool fb_have_first = false, fb_have_res = false; float fb_prev_t = 0.f; bool fb_prev_valid = false;
-    long fb_hits = 0, fb_misses = 0;
-    void fb_reset() { fb_have_first = fb_have_res = false; fb_prev_valid = false; }
-    // MX fp8 mode (BASELINE config 4 "fp8 MFMA"): the block linears run on block-scaled fp8 operands; opt-in, own parity class
-    bool fx_fp8 = false;
-    bool fx_fp8_attn = false;        // ... and QK^T / PV of the joint attention on MX fp8 too (attn_mx.hip; ldx_flux_set_fp8 mode 1, head dim 128)
-    bool mx_quantize_weight(LinearW& w);
-    int plan_flux(int B, int h, int w, int Lt);
-    int run_flux(const float* x, const float* sigma, const float* ctx, const float* y, const float* guidance,
-                 const float* pe_cos, const float* pe_sin, int B, int h, int w, int Lt, bool denoise, float* out, hipStream_t st);
-    EngineKind kind = KIND_UNET;
-    ldx_vae_config vcfg{};
-    ldx_clip_config ccfg{};
-    int finalize_vae();
-    int finalize_clip();
-    int plan_vae(int B, int h, int w);
-    int plan_clip(int B, int T, int inter);
-    int run_vae(const float* z, int B, int h, int w, float* out_nhwc, hipStream_t st);
-    int plan_vae_encode(int B, int H, int W);
-    int run_vae_encode(const float* px, int B, int H, int W, float* moments, hipStream_t st);
-    int run_clip(const int* ids, int B, int T, int inter_layer, float* out_last, float* out_inter, hipStream_t st);
-    int set_clip_extra(const float* rows_host, int n);
-    ~Engine();
-    int validate() const;
+    static constexpr const char* model = "valid";
+    // keep_plans: plans of other input shapes stay in plan_cache (UNet, Flux); otherwise a new shape re-plans into the current plan
+    Engine(int dev, int compute_dtype, bool keep_plans) : device(dev), dt(compute_dtype == LDX_F16 ? DT_F16 : DT_BF16), keep_plans(keep_plans) {}
+    virtual ~Engine();
+    Engine(const Engine&) = delete;
+    Engine& operator=(const Engine&) = delete;
+    int validate() const { return LDX_OK; }              // config checks at creation; a model that has some hides this (ldx_*_create calls it on the model's class)
     int load_tensor(const char* key, const void* data, int dtype, const int64_t* shape, int ndim);
-    int load_tensor_device(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
-    int set_tables(const float* ls, int n, const float* temb, int dim);
-    int finalize();
-    // Replace the weights of a finalized UNet engine in place (ldx_unet_refresh_begin / _commit): begin re-opens the two loaders, commit validates
-    // the full key set (nothing written on LDX_EMISSING, and `un` stays as it was), then runs the structure walk again into the SAME device allocations,
-    // rebuilds the emb_layers table and drops the cached context projections.  No pointer a plan or a captured graph holds changes.
-    int refresh_begin();
-    int refresh_commit();
-    int refresh_abort();                   // forget an unfinished refresh: the loaders close again, the weights are untouched
-    int weights_digest(uint64_t* out);     // FNV-1a over host copies of every weight allocation, in allocation order
-    // c_concat [B2][cc_channels][h][w] (fp32, may be null): appended unscaled behind the scaled x, which then carries in_channels - cc_channels channels
-    // t_idx [B2] (device fp32, may be null; denoise only): timestep indices supplied by the caller instead of the device's own sigma -> index lookup
-    int run(const float* x, const float* sigma_or_t, const float* ctx, int B2, int h, int w, int Mc, float* out, bool denoise, hipStream_t st, int xB = 0,
-            const float* c_concat = nullptr, int cc_channels = 0, const float* t_idx = nullptr);
-    int clip_pooled(const float* last, const int* ids, int B, int T, int eos_id, float* out, hipStream_t st);
-    // one CFG evaluation: x [B] is read by both halves of the [uncond; cond] batch (cond.py:186-226), sigma is one host scalar for every sample
-    // t_index >= 0: the sigma -> timestep index computed by the caller (the reference's own host arithmetic); < 0: the device lookup
-    int run_cfg(const float* x, float sigma, const float* ctx, int B, int h, int w, int Mc, float* out, hipStream_t st, int t_index = -1);
-    int timestep_lookup(const float* sigma_dev, int n, int* out_dev, hipStream_t st);      // ldx_unet_timestep: the prep kernel's lookup alone
-    float* d_sigma_cfg = nullptr; int sigma_cfg_cap = 0;      // [2 * cap] sigma followed by [2 * cap] timestep indices
-    // ---- step-invariant work (round 5) ----
-    // (1) per-timestep table of the 22 emb_layers outputs: time_embed -> SiLU -> emb_layers is a pure function of the INTEGER timestep (a8: t = argmin
-    //     index; unet.py:333-342, ResBlock.py:283-295), so all n_sigmas rows are computed once by the SAME skinny kernels (bit-identical to the per-step
-    //     launches) and the prep kernel gathers the row: three launches per forward gone.  LDX_EMB_TABLE=0 keeps the per-step launches.
-    float* d_emb_table = nullptr;
-    int build_emb_table();
-    // (2) context cache (ldx_unet_context_cache): the caller promises that the bytes behind a ctx pointer do not change until it calls
+    virtual int finalize() = 0;
+    // context cache (ldx_unet_context_cache): the caller promises that the bytes behind a ctx pointer do not change until it calls
     //     ldx_unet_context_cache again; the 16-bit copy of ctx and the batched k|v projection of every cross-attention (transformer.py:186-245 recomputes
     //     them every step only because a torch module has no notion of a sampling run) are then computed on the first evaluation of a (plan, ctx) only.
-    bool ctx_cache = false; uint64_t ctx_epoch = 1;
-    int set_context_cache(int enable) { ctx_cache = enable != 0; ++ctx_epoch; return LDX_OK; }
+    //     Set by the UNet alone; here because the executor and the plan's counts leave the ctx_only ops out while it holds.
+    bool ctx_cache = false;
     double algorithmic_flops() const;                           // steady_flops() + flops_shared
     double steady_flops() const;                                // algorithmic flops of one forward as executed in steady state (cached ops excluded)
-    unsigned* d_sk_count = nullptr;                       // split-K tile counters (sk_counters()): one zeroed buffer per engine, every launch leaves it zeroed
-    unsigned* sk_counters();
-    // share > 0 (ldx_unet_denoise_cfg*): the evaluation batch is [uncond x share ; cond x share] over ONE latent batch x [share] — everything in front of the
-    // first cross-attention (conv_in, the ResBlocks / Downsamples / self-attention up to it) sees identical inputs in both halves and is planned on `share`
-    // samples; its results are copied into the second half's rows where the first cross-attention (and the skip connections) need them (OP_DUP).
-    int plan(int B2, int h, int w, int Mc, int share = 0);
-    int share_for(int B2, int h, int w, int xB, bool denoise, bool concat) const;
-    int cfg_share = 1;                     // ldx_unet_cfg_share / LDX_CFG_SHARE: plan CFG evaluations with the shared prefix (0 never, 1 where it pays, 2 whenever possible)
     int64_t n_launches() const;
     int64_t n_graph_captures = 0, n_graph_replays = 0;      // ldx_graph_stats (tests: the sampler loops must replay, not re-capture)
     // per-kernel-class HIP-event profile of subsequent forwards (bench.py roofline leg)
@@ -246,32 +180,30 @@ public:
     std::map<std::string, ProfEntry> prof;
     std::string profile_json() const;
 
-    ldx_unet_config cfg;
-    int device;
-    DType dt;
+    const int device;
+    const DType dt;
     bool finalized = false;
     bool graph_mode = false;
     size_t weight_bytes = 0;
-    Plan cur;                              // the plan being run (while a plan_* runs: being built)
+    Plan cur;                              // the plan being run (while a plan function runs: being built)
 
-private:
+protected:
     // weights
     std::unordered_map<std::string, HostTensor> host;
     std::string missing;
     std::vector<void*> dev_allocs;
     const HostTensor* get(const std::string& key, std::initializer_list<int64_t> shape);
-    // The structure walk (walk_weights: the mk_* calls in UNetModel1.__init__ order) runs in three modes over the same sequence of weight buffers:
-    // ALLOC (finalize) allocates each one, CHECK (refresh) only resolves keys and shapes, REFILL (refresh) writes into the allocations ALLOC made.
+    // A model's weight buffers are asked for in one fixed order, which lets the UNet run the same sequence of mk_* calls in three modes (UNetEngine::walk_weights):
+    // ALLOC (every model's finalize) allocates each buffer, CHECK (refresh) only resolves keys and shapes, REFILL (refresh) writes into the allocations ALLOC made.
     enum WalkMode { WALK_ALLOC, WALK_CHECK, WALK_REFILL };
     WalkMode walk_mode = WALK_ALLOC;
     struct WeightAlloc { void* p; size_t bytes; };
     std::vector<WeightAlloc> weight_allocs;                // every packed buffer (weight_buf), in allocation order
     size_t walk_next = 0;                                  // CHECK / REFILL: the next entry of weight_allocs
     std::string walk_err;
-    bool refreshing = false;                               // between refresh_begin and refresh_commit
-    void* weight_buf(size_t bytes);                        // the walk's next weight buffer (null: error)
-    int walk_weights();                                    // builds a fresh UNetW and installs it as `un` on success only
-    int weights_failed();                                  // the tail of a failed walk / finalize_*: missing key -> LDX_EMISSING, walk_err -> LDX_ESTATE, else the HIP error
+    bool refreshing = false;                               // UNet, between refresh_begin and refresh_commit: load_tensor is open again
+    void* weight_buf(size_t bytes);                        // the next weight buffer (null: error)
+    int weights_failed();                                  // the tail of a failed walk / finalize: missing key -> LDX_EMISSING, walk_err -> LDX_ESTATE, else the HIP error
     // A packed buffer is described ONCE, as pieces of source tensors; weight_layout.h turns a piece into bits, for both sides.  Per buffer: some source is on
     // the device (ldx_load_tensor_device) -> one launch per piece of pack.hip's loops over those functions, host sources of that buffer staged as raw copies
     // (freed when the walk ends); no source on the device -> a CPU loop over the same functions and one copy.  Same buffers in the same order either way:
@@ -287,10 +219,10 @@ private:
     void* pack16(size_t rows, size_t cols, const std::vector<Piece>& pieces);
     float* pack32(size_t n, const std::vector<VecPiece>& pieces);
     // What no piece list describes stays on a getter, element by element on the host (all in engines that load from the host only):
-    //   mk_vae_attn  proj.b    Wp . bv + bp, an fp64 dot product per element
-    //   mk_vae_attn  qkv.b     [bq | bk | 0]: the zero tail has no source
-    //   finalize_t5  wi.w      64-row slabs interleaved from TWO tensors (wi_1 value rows, wi_0 gate rows); geglu_inner permutes one
-    //   finalize_flux lin1_*   linear1 split at a source ROW: a piece takes its whole source, from row 0
+    //   VaeEngine::mk_vae_attn  proj.b    Wp . bv + bp, an fp64 dot product per element
+    //   VaeEngine::mk_vae_attn  qkv.b     [bq | bk | 0]: the zero tail has no source
+    //   T5Engine::finalize      wi.w      64-row slabs interleaved from TWO tensors (wi_1 value rows, wi_0 gate rows); geglu_inner permutes one
+    //   FluxEngine::finalize    lin1_*    linear1 split at a source ROW: a piece takes its whole source, from row 0
     void* upload16(size_t rows, size_t cols, const std::function<float(size_t, size_t)>& getter);
     float* upload32(size_t n, const std::function<float(size_t)>& getter);
     bool mk_linear(const std::string& pre, int N, int K, bool bias, LinearW& out, bool conv1x1 = false);
@@ -299,46 +231,28 @@ private:
     bool mk_ln_folded(int N, int K, const std::vector<Piece>& pieces, const HostTensor* bias_t, const std::string& norm_pre, LinearW& out, float*& c1);
     bool mk_fused_skip(const std::string& conv, const std::string& skip, int Cin, int Cout, ResW& r);      // conv2 | skip in one matrix (UNet and VAE ResBlocks)
     bool mk_stacked(const std::vector<EmbSrc>& srcs, int K, LinearW& out);                                   // rows of several tensors in one matrix, their biases in one vector
-    bool mk_res(const std::string& pre, int Cin, int Cout, ResW& r);
-    bool mk_xf(const std::string& pre, int C, int depth, XfW& x);
 
+    // executor
     int exec_ops(hipStream_t ls, size_t op_begin = 0, size_t op_end = (size_t)-1, int ctx_sel = 0);      // ctx_sel: 0 all ops, 1 skip ctx_only ops, 2 ONLY ctx_only ops
     int launch_op(const Op& o, hipStream_t ls);           // the op's launcher on its argument struct, with this call's pointers (bind) filled in
     std::string prof_key(const Op& o) const;              // profile label of an op (prof_detail: with its shape)
     // the common tail of the calls that keep one plan and run it whole: make the plan of `key` current, bind the call's buffers, launch
     int run_planned(const PlanKey& key, const std::function<int()>& replan, const Bindings& b, hipStream_t st);
+    Bindings bind;                                        // this call's
+    std::vector<hipEvent_t> prof_events;
+    bool prof_graph = false;
+
+    // planner toolkit; the state is that of the plan being built (build_plan resets it)
     Op& emit(OpKind kind, const char* name);              // appends a zeroed op to the plan being built; the reference holds until the next emit
     // GroupNorm workspace: gn_ws_rows producer rows per image + GN_FOLD folded rows, x 32 groups x 2 floats (ldx_kernels.h gn_workspace_rows)
     int gn_ws_rows = 256;
     size_t gn_ws_bytes(int B, long HWmax) { gn_ws_rows = (int)gn_workspace_rows(HWmax); return (size_t)B * (gn_ws_rows + GN_FOLD) * 32 * 2 * 4; }
     size_t ws_alloc(size_t bytes);                        // split-K workspace of one op (engine.cpp)
+    unsigned* d_sk_count = nullptr;                       // split-K tile counters (sk_counters()): one zeroed buffer per engine, every launch leaves it zeroed
+    unsigned* sk_counters();
     void fuse_gn_stats();                                 // post-pass over ops: GroupNorms whose input was just written by a fusable GEMM / conv get their statistics from its epilogue
     void fuse_gn_rowgemm();                               // post-pass: xf.norm (producer statistics) + xf.proj_in -> one rowgemm launch where xf_proj_in_rowgemm says so
     void op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R, int pro, const NormW* nw);
-    Bindings bind;                                        // this call's
-    // VAE
-    std::vector<std::vector<ResW>> vae_up; std::vector<LinearW> vae_upconv; std::vector<bool> vae_has_up;
-    ResW vae_mid1, vae_mid2; VaeAttnW vae_attn; NormW vae_norm_out; LinearW vae_conv_in, vae_conv_out; float* vae_pq = nullptr;
-    // VAE encoder (optional: only when encoder.* weights were loaded)
-    bool vae_has_enc = false;
-    std::vector<std::vector<ResW>> enc_down; std::vector<LinearW> enc_downconv;
-    ResW enc_mid1, enc_mid2; VaeAttnW enc_attn; NormW enc_norm_out; LinearW enc_conv_in, enc_conv_out; float* enc_qc = nullptr;
-    bool mk_vae_attn(const std::string& pre, int C, VaeAttnW& a);
-    // Flux
-    std::vector<FluxDoubleW> fx_double; std::vector<FluxSingleW> fx_single;
-    LinearW fx_img_in, fx_txt_in, fx_time0, fx_time1, fx_vec0, fx_vec1, fx_gd0, fx_gd1, fx_mod_all, fx_final;
-    int fx_mod_total = 0, fx_final_mod_off = 0;
-    std::vector<EmbSrc> fx_mod_srcs;
-    // CLIP
-    std::vector<ClipLayerW> clip_layers; NormW clip_final_ln; float* clip_tok = nullptr; float* clip_pos = nullptr;
-    float* clip_extra = nullptr; int clip_extra_n = 0, clip_extra_cap = 0;     // textual-inversion rows for ids >= vocab_size
-    float* clip_proj = nullptr;                                                // optional text_projection.weight [E][E] fp32 (CLIPTextModel.py:130,152-163)
-    UNetW un;
-    // sources of un.emb_all / un.kv_all (k, v, k, v, ...), collected by the walk
-    std::vector<EmbSrc> emb_srcs, kv_srcs;
-    float* d_log_sigmas = nullptr; float* d_temb = nullptr; int n_sigmas = 0;
-
-    // planner state of the plan being built (build_plan resets it)
     std::vector<std::pair<size_t, size_t>> free_list;
     std::map<size_t, size_t> live;
     size_t arena_top = 0, arena_peak = 0;
@@ -359,25 +273,165 @@ private:
     void op_gn(const char* name, Act X, Act Y, int B, int HW, const NormW& n, float eps, bool silu);
     void op_ln(const char* name, Act X, Act Y, const NormW& n);
     void op_attn(const char* name, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, Act O, int B, int H, int Nq, int Mk, int D);
-    void emit_res(const ResW& r, Act X, Act OUT, int B, int H, int W);
-    void emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int W);
-    bool mk_vae_res(const std::string& pre, int Cin, int Cout, ResW& r);
+    // UNet and VAE ResBlock; emb [.][emb_ld]: the batched emb_layers output a block with has_emb adds its columns [emb_off, emb_off + Cout) of (null in the dry pass)
+    void emit_res(const ResW& r, Act X, Act OUT, int B, int H, int W, const float* emb = nullptr, int emb_ld = 0);
+
+    // Plans of other input shapes seen (keep_plans: multi-scale samplers alternate between two resolutions, prompts of different lengths change
+    // Flux's Lt): launch plan, arena and captured graph are kept per shape, so switching back costs nothing (a re-plan + two eager passes
+    // before the graph is usable again cost ~17 ms per switch)
+    const bool keep_plans;
+    std::vector<Plan> plan_cache;
+    void plan_stash();                    // move the current plan into plan_cache (evicting the oldest beyond 4)
+    bool plan_restore(const PlanKey& key);
+};
+
+class UNetEngine final : public Engine {
+public:
+    static constexpr const char* model = "UNet";
+    UNetEngine(const ldx_unet_config& c, int dev);
+    ~UNetEngine() override;
+    int validate() const;
+    int load_tensor_device(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
+    int set_tables(const float* ls, int n, const float* temb, int dim);
+    int finalize() override;
+    // Replace the weights of a finalized engine in place (ldx_unet_refresh_begin / _commit): begin re-opens the two loaders, commit validates
+    // the full key set (nothing written on LDX_EMISSING, and `un` stays as it was), then runs the structure walk again into the SAME device allocations,
+    // rebuilds the emb_layers table and drops the cached context projections.  No pointer a plan or a captured graph holds changes.
+    int refresh_begin();
+    int refresh_commit();
+    int refresh_abort();                   // forget an unfinished refresh: the loaders close again, the weights are untouched
+    int weights_digest(uint64_t* out);     // FNV-1a over host copies of every weight allocation, in allocation order
+    // c_concat [B2][cc_channels][h][w] (fp32, may be null): appended unscaled behind the scaled x, which then carries in_channels - cc_channels channels
+    // t_idx [B2] (device fp32, may be null; denoise only): timestep indices supplied by the caller instead of the device's own sigma -> index lookup
+    int run(const float* x, const float* sigma_or_t, const float* ctx, int B2, int h, int w, int Mc, float* out, bool denoise, hipStream_t st, int xB = 0,
+            const float* c_concat = nullptr, int cc_channels = 0, const float* t_idx = nullptr);
+    // one CFG evaluation: x [B] is read by both halves of the [uncond; cond] batch (cond.py:186-226), sigma is one host scalar for every sample
+    // t_index >= 0: the sigma -> timestep index computed by the caller (the reference's own host arithmetic); < 0: the device lookup
+    int run_cfg(const float* x, float sigma, const float* ctx, int B, int h, int w, int Mc, float* out, hipStream_t st, int t_index = -1);
+    int timestep_lookup(const float* sigma_dev, int n, int* out_dev, hipStream_t st);      // ldx_unet_timestep: the prep kernel's lookup alone
+    int set_context_cache(int enable) { ctx_cache = enable != 0; ++ctx_epoch; return LDX_OK; }      // Engine::ctx_cache
+    int cfg_share = 1;                     // ldx_unet_cfg_share / LDX_CFG_SHARE: plan CFG evaluations with the shared prefix (0 never, 1 where it pays, 2 whenever possible)
+    const ldx_unet_config cfg;
+
+private:
+    UNetW un;
+    // sources of un.emb_all / un.kv_all (k, v, k, v, ...), collected by the walk
+    std::vector<EmbSrc> emb_srcs, kv_srcs;
+    bool mk_res(const std::string& pre, int Cin, int Cout, ResW& r);
+    bool mk_xf(const std::string& pre, int C, int depth, XfW& x);
+    int walk_weights();                                    // the mk_* calls in UNetModel1.__init__ order, in walk_mode: builds a fresh UNetW and installs it as `un` on success only
+    float* d_log_sigmas = nullptr; float* d_temb = nullptr; int n_sigmas = 0;
+    float* d_sigma_cfg = nullptr; int sigma_cfg_cap = 0;      // [2 * cap] sigma followed by [2 * cap] timestep indices
+    // ---- step-invariant work (round 5) ----
+    // per-timestep table of the 22 emb_layers outputs: time_embed -> SiLU -> emb_layers is a pure function of the INTEGER timestep (a8: t = argmin
+    //     index; unet.py:333-342, ResBlock.py:283-295), so all n_sigmas rows are computed once by the SAME skinny kernels (bit-identical to the per-step
+    //     launches) and the prep kernel gathers the row: three launches per forward gone.  LDX_EMB_TABLE=0 keeps the per-step launches.
+    float* d_emb_table = nullptr;
+    int build_emb_table();
+    uint64_t ctx_epoch = 1;                // context cache: bumped whenever cached k|v projections stop being valid
+    // share > 0 (ldx_unet_denoise_cfg*): the evaluation batch is [uncond x share ; cond x share] over ONE latent batch x [share] — everything in front of the
+    // first cross-attention (conv_in, the ResBlocks / Downsamples / self-attention up to it) sees identical inputs in both halves and is planned on `share`
+    // samples; its results are copied into the second half's rows where the first cross-attention (and the skip connections) need them (OP_DUP).
+    int plan(int B2, int h, int w, int Mc, int share = 0);
+    int share_for(int B2, int h, int w, int xB, bool denoise, bool concat) const;
     // Bshare > 0: the ops in front of the first cross-attention run on Bshare samples (see plan()); `dups` = views whose first Bshare * (their own H * W)
     // rows are to be copied into the following rows at that point (plus h itself)
     struct DupReq { Act a; int rows; size_t producer; };       // producer: index of the op that writes `a` (its dual store is preferred to a copy launch)
     void emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx16, int Mc, int Bshare = 0, const std::vector<DupReq>* dups = nullptr);
     void op_dup(const Act& a, int rows);          // rows [0, rows) of view a -> rows [rows, 2 rows)
     void dup_second_half(const DupReq& d);        // the producer's dual store (GemmArgs / RowGemmArgs::dup_rows) where it has one, else op_dup
-
-    // UNet / Flux plans of other input shapes seen (multi-scale samplers alternate between two resolutions, prompts of different lengths change
-    // Flux's Lt): launch plan, arena and captured graph are kept per shape, so switching back costs nothing (a re-plan + two eager passes
-    // before the graph is usable again cost ~17 ms per switch)
-    std::vector<Plan> plan_cache;
-    void plan_stash();                    // move the current plan into plan_cache (evicting the oldest beyond 4)
-    bool plan_restore(const PlanKey& key);
-    std::vector<hipEvent_t> prof_events;
-    bool prof_graph = false;
     hipStream_t cap_stream = nullptr;     // graph capture
+};
+
+class VaeEngine final : public Engine {
+public:
+    static constexpr const char* model = "VAE";
+    VaeEngine(const ldx_vae_config& c, int dev) : Engine(dev, c.compute_dtype, false), cfg(c) {}
+    int finalize() override;
+    int run_decode(const float* z, int B, int h, int w, float* out_nhwc, hipStream_t st);
+    int run_encode(const float* px, int B, int H, int W, float* moments, hipStream_t st);
+    const ldx_vae_config cfg;
+
+private:
+    std::vector<std::vector<ResW>> vae_up; std::vector<LinearW> vae_upconv; std::vector<bool> vae_has_up;
+    ResW vae_mid1, vae_mid2; VaeAttnW vae_attn; NormW vae_norm_out; LinearW vae_conv_in, vae_conv_out; float* vae_pq = nullptr;
+    // encoder (optional: only when encoder.* weights were loaded)
+    bool vae_has_enc = false;
+    std::vector<std::vector<ResW>> enc_down; std::vector<LinearW> enc_downconv;
+    ResW enc_mid1, enc_mid2; VaeAttnW enc_attn; NormW enc_norm_out; LinearW enc_conv_in, enc_conv_out; float* enc_qc = nullptr;
+    bool mk_vae_res(const std::string& pre, int Cin, int Cout, ResW& r);
+    bool mk_vae_attn(const std::string& pre, int C, VaeAttnW& a);
+    void emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int W);
+    int plan_decode(int B, int h, int w);
+    int plan_encode(int B, int H, int W);
+};
+
+class ClipEngine final : public Engine {
+public:
+    static constexpr const char* model = "CLIP";
+    ClipEngine(const ldx_clip_config& c, int dev) : Engine(dev, c.compute_dtype, false), cfg(c) {}
+    int finalize() override;
+    int run(const int* ids, int B, int T, int inter_layer, float* out_last, float* out_inter, hipStream_t st);
+    int set_clip_extra(const float* rows_host, int n);
+    int clip_pooled(const float* last, const int* ids, int B, int T, int eos_id, float* out, hipStream_t st);
+    const ldx_clip_config cfg;
+
+private:
+    std::vector<ClipLayerW> clip_layers; NormW clip_final_ln; float* clip_tok = nullptr; float* clip_pos = nullptr;
+    float* clip_extra = nullptr; int clip_extra_n = 0, clip_extra_cap = 0;     // textual-inversion rows for ids >= vocab_size
+    float* clip_proj = nullptr;                                                // optional text_projection.weight [E][E] fp32 (CLIPTextModel.py:130,152-163)
+    int plan(int B, int T, int inter);
+};
+
+class T5Engine final : public Engine {
+public:
+    static constexpr const char* model = "T5";
+    T5Engine(const ldx_t5_config& c, int dev) : Engine(dev, c.compute_dtype, false), cfg(c) {}
+    int finalize() override;
+    int run(const int* ids, int B, int L, const float* bias, float* out, hipStream_t st);
+    const ldx_t5_config cfg;
+
+private:
+    std::vector<T5LayerW> t5_layers; NormW t5_final_ln; float* t5_tok = nullptr;
+    int plan(int B, int L);
+};
+
+class EsrganEngine final : public Engine {
+public:
+    static constexpr const char* model = "ESRGAN";
+    EsrganEngine(const ldx_esrgan_config& c, int dev) : Engine(dev, c.compute_dtype, false), cfg(c) {}
+    int finalize() override;
+    int run(const float* px, int B, int H, int W, float* out, hipStream_t st);
+    const ldx_esrgan_config cfg;
+
+private:
+    std::vector<RdbW> es_rdb; LinearW es_first, es_trunk, es_hr, es_last; std::vector<LinearW> es_up;
+    int plan(int B, int H, int W);
+};
+
+class FluxEngine final : public Engine {
+public:
+    static constexpr const char* model = "Flux";
+    FluxEngine(const ldx_flux_config& c, int dev) : Engine(dev, c.compute_dtype, true), cfg(c) {}
+    int finalize() override;
+    int run(const float* x, const float* sigma, const float* ctx, const float* y, const float* guidance,
+            const float* pe_cos, const float* pe_sin, int B, int h, int w, int Lt, bool denoise, float* out, hipStream_t st);
+    // First-block cache (WaveSpeed/first_block_cache.py:105-384, fbcache_nodes.py:8-201): opt-in approximate mode
+    float fb_threshold = 0.f; bool fb_have_first = false, fb_have_res = false; float fb_prev_t = 0.f; bool fb_prev_valid = false;
+    long fb_hits = 0, fb_misses = 0;
+    void fb_reset() { fb_have_first = fb_have_res = false; fb_prev_valid = false; }
+    // MX fp8 mode (BASELINE config 4 "fp8 MFMA"): the block linears run on block-scaled fp8 operands; opt-in, own parity class
+    bool fx_fp8 = false;
+    bool fx_fp8_attn = false;        // ... and QK^T / PV of the joint attention on MX fp8 too (attn_mx.hip; ldx_flux_set_fp8 mode 1, head dim 128)
+    const ldx_flux_config cfg;
+
+private:
+    std::vector<FluxDoubleW> fx_double; std::vector<FluxSingleW> fx_single;
+    LinearW fx_img_in, fx_txt_in, fx_time0, fx_time1, fx_vec0, fx_vec1, fx_gd0, fx_gd1, fx_mod_all, fx_final;
+    int fx_mod_total = 0, fx_final_mod_off = 0;
+    std::vector<EmbSrc> fx_mod_srcs;
+    bool mx_quantize_weight(LinearW& w);
+    int plan(int B, int h, int w, int Lt);
 };
 
 }  // namespace ldx

@@ -11,14 +11,9 @@
 
 namespace ldx {
 
-Engine::Engine(const ldx_esrgan_config& c, int dev) : cfg{}, device(dev) {
-    kind = KIND_ESRGAN; ecfg = c;
-    dt = (c.compute_dtype == LDX_F16) ? DT_F16 : DT_BF16;
-}
-
-int Engine::finalize_esrgan() {
+int EsrganEngine::finalize() {
     if (finalized) return LDX_OK;
-    const ldx_esrgan_config& c = ecfg;
+    const ldx_esrgan_config& c = cfg;
     auto bad = [&](const char* m) { set_error(std::string("unsupported ESRGAN config: ") + m); return LDX_EINVAL; };
     if (c.nf != 64 || c.gc != 32) return bad("nf must be 64 and gc 32 (the only RRDBNet layout the reference builds, RDRB.py:283-296)");
     if (c.in_nc <= 0 || c.in_nc > 64 || c.out_nc <= 0 || c.out_nc > 64 || c.num_blocks <= 0 || c.num_upscale < 0 || c.num_upscale > 4) return bad("channels / blocks / scale");
@@ -46,8 +41,8 @@ int Engine::finalize_esrgan() {
     return LDX_OK;
 }
 
-int Engine::plan_esrgan(int B, int H, int W) {
-    const ldx_esrgan_config& c = ecfg;
+int EsrganEngine::plan(int B, int H, int W) {
+    const ldx_esrgan_config& c = cfg;
     const int nf = c.nf, gc = c.gc, CW = nf + 4 * gc, M = B * H * W;
     // zero-filled arena: dense-block convs read a few not-yet-written columns against zero weights: those must hold finite values, and a
     // new plan lays the buffers over whatever the previous shape left there (fp32 pixels read as 16-bit can be NaN)
@@ -103,12 +98,12 @@ int Engine::plan_esrgan(int B, int H, int W) {
     }, true);
 }
 
-int Engine::run_esrgan(const float* px, int B, int H, int W, float* out, hipStream_t st) {
-    if (!finalized || kind != KIND_ESRGAN) { set_error("ldx_esrgan_forward: not a finalized ESRGAN engine"); return LDX_ESTATE; }
+int EsrganEngine::run(const float* px, int B, int H, int W, float* out, hipStream_t st) {
+    if (!finalized) { set_error("ldx_esrgan_forward: not a finalized ESRGAN engine"); return LDX_ESTATE; }
     if (!px || !out || B <= 0 || H <= 0 || W <= 0) { set_error("ldx_esrgan_forward: bad argument"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
     Bindings b; b.x = px; b.out = out;
-    return run_planned(PlanKey{B, H, W}, [&] { return plan_esrgan(B, H, W); }, b, st);
+    return run_planned(PlanKey{B, H, W}, [&] { return plan(B, H, W); }, b, st);
 }
 
 }  // namespace ldx

@@ -18,14 +18,9 @@
 
 namespace ldx {
 
-Engine::Engine(const ldx_flux_config& c, int dev) : cfg{}, device(dev) {
-    kind = KIND_FLUX; fcfg = c;
-    dt = (c.compute_dtype == LDX_F16) ? DT_F16 : DT_BF16;
-}
-
-int Engine::finalize_flux() {
+int FluxEngine::finalize() {
     if (finalized) return LDX_OK;
-    const ldx_flux_config& f = fcfg;
+    const ldx_flux_config& f = cfg;
     auto bad = [&](const char* m) { set_error(std::string("unsupported Flux config: ") + m); return LDX_EINVAL; };
     const int C = f.hidden_size, H = f.num_heads;
     if (C <= 0 || C % 64 || f.mlp_hidden % 64 || C > 3072) return bad("hidden_size / mlp_hidden must be multiples of 64, hidden <= 3072");
@@ -107,7 +102,7 @@ int Engine::finalize_flux() {
 }
 
 // W [N][K] 16-bit -> e4m3fn bytes [N][K] + E8M0 scales [K/128][N] (one per 32 consecutive k), on the device
-bool Engine::mx_quantize_weight(LinearW& w) {
+bool FluxEngine::mx_quantize_weight(LinearW& w) {
     void* w8 = nullptr; void* sw = nullptr;
     if (hipMalloc(&w8, (size_t)w.N * w.K) != hipSuccess) return false;
     dev_allocs.push_back(w8);
@@ -122,8 +117,8 @@ bool Engine::mx_quantize_weight(LinearW& w) {
     return hipGetLastError() == hipSuccess;
 }
 
-int Engine::plan_flux(int B, int h, int w, int Lt) {
-    const ldx_flux_config& f = fcfg;
+int FluxEngine::plan(int B, int h, int w, int Lt) {
+    const ldx_flux_config& f = cfg;
     const int C = f.hidden_size, H = f.num_heads, D = C / H, MH = f.mlp_hidden;
     const int Li = (h / 2) * (w / 2), L = Lt + Li, inC = 4 * f.in_channels;
     return build_plan(PlanKey{B, h, w, Lt}, [&]() -> int {
@@ -356,16 +351,16 @@ int Engine::plan_flux(int B, int h, int w, int Lt) {
     });
 }
 
-int Engine::run_flux(const float* x, const float* sigma, const float* ctx, const float* y, const float* guidance,
+int FluxEngine::run(const float* x, const float* sigma, const float* ctx, const float* y, const float* guidance,
                      const float* pe_cos, const float* pe_sin, int B, int h, int w, int Lt, bool denoise, float* out, hipStream_t st) {
-    if (!finalized || kind != KIND_FLUX) { set_error("ldx_flux_forward: not a finalized Flux engine"); return LDX_ESTATE; }
+    if (!finalized) { set_error("ldx_flux_forward: not a finalized Flux engine"); return LDX_ESTATE; }
     if (!x || !sigma || !ctx || !y || !pe_cos || !pe_sin || !out || B <= 0 || h <= 0 || w <= 0 || Lt <= 0 || (h & 1) || (w & 1) ||
-        (fcfg.guidance_embed && !guidance)) { set_error("ldx_flux_forward: bad argument (h, w must be even)"); return LDX_EINVAL; }
+        (cfg.guidance_embed && !guidance)) { set_error("ldx_flux_forward: bad argument (h, w must be even)"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
     // plans (op list + arena) are kept per shape like the UNet's; the first-block cache still resets on every shape change: the cached
     // residuals no longer apply (fbcache_nodes.py:56-66)
     bool switched = false;
-    if (int rc = select_plan(PlanKey{B, h, w, Lt}, st, [&] { return plan_flux(B, h, w, Lt); }, &switched)) return rc;
+    if (int rc = select_plan(PlanKey{B, h, w, Lt}, st, [&] { return plan(B, h, w, Lt); }, &switched)) return rc;
     if (switched) fb_reset();
     bind = Bindings{};
     bind.x = x; bind.s = sigma; bind.ctx = ctx; bind.y = y; bind.guid = guidance; bind.pe_cos = pe_cos; bind.pe_sin = pe_sin; bind.out = out; bind.den = denoise;

@@ -11,14 +11,9 @@
 
 namespace ldx {
 
-Engine::Engine(const ldx_t5_config& c, int dev) : cfg{}, device(dev) {
-    kind = KIND_T5; tcfg = c;
-    dt = (c.compute_dtype == LDX_F16) ? DT_F16 : DT_BF16;
-}
-
-int Engine::finalize_t5() {
+int T5Engine::finalize() {
     if (finalized) return LDX_OK;
-    const ldx_t5_config& c = tcfg;
+    const ldx_t5_config& c = cfg;
     auto bad = [&](const char* m) { set_error(std::string("unsupported T5 config: ") + m); return LDX_EINVAL; };
     if (c.d_model <= 0 || c.d_model % 64 || c.d_ff % 64 || c.d_model > 4096) return bad("d_model / d_ff must be multiples of 64, d_model <= 4096");
     if (c.num_heads <= 0 || c.d_model % c.num_heads || (c.d_model / c.num_heads) % 8 || c.d_model / c.num_heads > 160) return bad("head dim");
@@ -69,8 +64,8 @@ int Engine::finalize_t5() {
     return LDX_OK;
 }
 
-int Engine::plan_t5(int B, int L) {
-    const ldx_t5_config& c = tcfg;
+int T5Engine::plan(int B, int L) {
+    const ldx_t5_config& c = cfg;
     const int E = c.d_model, F = c.d_ff, M = B * L, heads = c.num_heads, D = E / heads;
     const int Lp = ((L + 63) / 64) * 64;
     return build_plan(PlanKey{B, L}, [&]() -> int {
@@ -100,12 +95,12 @@ int Engine::plan_t5(int B, int L) {
     });
 }
 
-int Engine::run_t5(const int* ids, int B, int L, const float* bias, float* out, hipStream_t st) {
-    if (!finalized || kind != KIND_T5) { set_error("ldx_t5_encode: not a finalized T5 engine"); return LDX_ESTATE; }
+int T5Engine::run(const int* ids, int B, int L, const float* bias, float* out, hipStream_t st) {
+    if (!finalized) { set_error("ldx_t5_encode: not a finalized T5 engine"); return LDX_ESTATE; }
     if (!ids || !bias || !out || B <= 0 || L <= 0) { set_error("ldx_t5_encode: bad argument"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
     Bindings b; b.ids = ids; b.bias = bias; b.out = out;
-    return run_planned(PlanKey{B, L}, [&] { return plan_t5(B, L); }, b, st);
+    return run_planned(PlanKey{B, L}, [&] { return plan(B, L); }, b, st);
 }
 
 }  // namespace ldx

@@ -1,12 +1,10 @@
-// VAE decoder and CLIP text encoder on the same planner / kernels as the UNet (engine.cpp).
+// VAE decoder and encoder on the same planner / kernels as the UNet (engine.cpp).
 //
-//   VAE   : Decoder.forward            src/AutoEncoders/VariationalAE.py:532-567
-//           ResnetBlock.forward        src/AutoEncoders/ResBlock.py:383-406      (GroupNorm eps 1e-6, swish)
-//           AttnBlock.forward          src/Attention/Attention.py:159-178        (1 head, D = C = 512)
-//           Upsample.forward           src/AutoEncoders/VariationalAE.py:209-221 (nearest 2x + conv3x3)
-//           AutoencodingEngine.decode  :130-145 (post_quant_conv) ; VAE.decode :690-722 (clamp, NHWC)
-//   CLIP  : CLIPTextModel_.forward     src/clip/CLIPTextModel.py:51-107
-//           CLIPLayer / CLIPAttention / CLIPMLP / CLIPEmbeddings   src/clip/Clip.py:14-294
+//   Decoder.forward            src/AutoEncoders/VariationalAE.py:532-567
+//   ResnetBlock.forward        src/AutoEncoders/ResBlock.py:383-406      (GroupNorm eps 1e-6, swish)
+//   AttnBlock.forward          src/Attention/Attention.py:159-178        (1 head, D = C = 512)
+//   Upsample.forward           src/AutoEncoders/VariationalAE.py:209-221 (nearest 2x + conv3x3)
+//   AutoencodingEngine.decode  :130-145 (post_quant_conv) ; VAE.decode :690-722 (clamp, NHWC)
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -15,18 +13,7 @@
 
 namespace ldx {
 
-Engine::Engine(const ldx_vae_config& c, int dev) : cfg{}, device(dev) {
-    kind = KIND_VAE; vcfg = c;
-    dt = (c.compute_dtype == LDX_F16) ? DT_F16 : DT_BF16;
-}
-Engine::Engine(const ldx_clip_config& c, int dev) : cfg{}, device(dev) {
-    kind = KIND_CLIP; ccfg = c;
-    dt = (c.compute_dtype == LDX_F16) ? DT_F16 : DT_BF16;
-}
-
-// =============================================================================================
-// VAE
-bool Engine::mk_vae_res(const std::string& pre, int Cin, int Cout, ResW& r) {
+bool VaeEngine::mk_vae_res(const std::string& pre, int Cin, int Cout, ResW& r) {
     r.Cin = Cin; r.Cout = Cout; r.eps = 1e-6f; r.has_emb = false;
     if (!mk_norm(pre + ".norm1", Cin, r.gn1) || !mk_conv3(pre + ".conv1", Cout, Cin, Cin, r.conv1)) return false;
     if (!mk_norm(pre + ".norm2", Cout, r.gn2)) return false;
@@ -38,7 +25,7 @@ bool Engine::mk_vae_res(const std::string& pre, int Cin, int Cout, ResW& r) {
     return true;
 }
 
-bool Engine::mk_vae_attn(const std::string& pre, int C, VaeAttnW& a) {
+bool VaeEngine::mk_vae_attn(const std::string& pre, int C, VaeAttnW& a) {
     if (!mk_norm(pre + ".norm", C, a.norm) || !mk_linear(pre + ".q", C, C, true, a.q, true) || !mk_linear(pre + ".k", C, C, true, a.k, true)) return false;
     // v is used as the A operand (V^T = Wv . h^T); its bias is folded through the softmax (rows sum to 1)
     // into the output projection's bias: b' = Wp . bv + bp.
@@ -67,9 +54,9 @@ bool Engine::mk_vae_attn(const std::string& pre, int C, VaeAttnW& a) {
     return true;
 }
 
-int Engine::finalize_vae() {
+int VaeEngine::finalize() {
     if (finalized) return LDX_OK;
-    const ldx_vae_config& v = vcfg;
+    const ldx_vae_config& v = cfg;
     auto bad = [&](const char* m) { set_error(std::string("unsupported VAE config: ") + m); return LDX_EINVAL; };
     if (v.ch <= 0 || v.ch % 64) return bad("ch must be a multiple of 64");
     if (v.num_levels < 1 || v.num_levels > 8 || v.z_channels < 1 || v.z_channels > 16 || v.out_ch < 1 || v.out_ch > 4) return bad("levels/channels");
@@ -140,7 +127,7 @@ int Engine::finalize_vae() {
 }
 
 // AttnBlock: x + proj(softmax(q k^T / sqrt(C)) v), one head of width C, as three GEMMs + a row softmax
-void Engine::emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int W) {
+void VaeEngine::emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int W) {
     const int N = H * W, M = B * N, C = a.q.N;
     Act hn = new_act(M, C);
     op_gn("vae.attn.norm", X, hn, B, N, a.norm, 1e-6f, false);
@@ -207,8 +194,8 @@ void Engine::emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, int 
     release(o);
 }
 
-int Engine::plan_vae(int B, int h, int w) {
-    const ldx_vae_config& v = vcfg;
+int VaeEngine::plan_decode(int B, int h, int w) {
+    const ldx_vae_config& v = cfg;
     return build_plan(PlanKey{B, h, w, 1}, [&]() -> int {
         cur.gn_ws_off = a_alloc(gn_ws_bytes(B, (long)h * w * 64));
         int H = h, W = w;
@@ -246,18 +233,18 @@ int Engine::plan_vae(int B, int h, int w) {
     });
 }
 
-int Engine::run_vae(const float* z, int B, int h, int w, float* out, hipStream_t st) {
-    if (!finalized || kind != KIND_VAE) { set_error("ldx_vae_decode: not a finalized VAE engine"); return LDX_ESTATE; }
+int VaeEngine::run_decode(const float* z, int B, int h, int w, float* out, hipStream_t st) {
+    if (!finalized) { set_error("ldx_vae_decode: not a finalized VAE engine"); return LDX_ESTATE; }
     if (!z || !out || B <= 0 || h <= 0 || w <= 0) { set_error("ldx_vae_decode: bad argument"); return LDX_EINVAL; }
     if ((h * w) % 8) { set_error("ldx_vae_decode: h*w must be a multiple of 8 (attention row length)"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
     Bindings b; b.x = z; b.out = out;
-    return run_planned(PlanKey{B, h, w, 1}, [&] { return plan_vae(B, h, w); }, b, st);
+    return run_planned(PlanKey{B, h, w, 1}, [&] { return plan_decode(B, h, w); }, b, st);
 }
 
 // Encoder.forward (VariationalAE.py:378-413) + quant_conv: pixels -> moments
-int Engine::plan_vae_encode(int B, int Hpx, int Wpx) {
-    const ldx_vae_config& v = vcfg;
+int VaeEngine::plan_encode(int B, int Hpx, int Wpx) {
+    const ldx_vae_config& v = cfg;
     return build_plan(PlanKey{B, Hpx, Wpx, 2}, [&]() -> int {
         cur.gn_ws_off = a_alloc(gn_ws_bytes(B, (long)Hpx * Wpx));
         int H = Hpx, W = Wpx;
@@ -296,138 +283,17 @@ int Engine::plan_vae_encode(int B, int Hpx, int Wpx) {
     });
 }
 
-int Engine::run_vae_encode(const float* px, int B, int H, int W, float* moments, hipStream_t st) {
-    if (!finalized || kind != KIND_VAE) { set_error("ldx_vae_encode: not a finalized VAE engine"); return LDX_ESTATE; }
+int VaeEngine::run_encode(const float* px, int B, int H, int W, float* moments, hipStream_t st) {
+    if (!finalized) { set_error("ldx_vae_encode: not a finalized VAE engine"); return LDX_ESTATE; }
     if (!vae_has_enc) { set_error("ldx_vae_encode: encoder.* weights were not loaded"); return LDX_EMISSING; }
-    const int f = 1 << (vcfg.num_levels - 1);
+    const int f = 1 << (cfg.num_levels - 1);
     // sizes that are not multiples of f are legal in the reference (vae_encode_crop_pixels is a no-op, VariationalAE.py:
     // 677-688): every Downsample yields floor(H/2)
     if (!px || !moments || B <= 0 || H < f || W < f || ((H / f) * (W / f)) % 8) {
         set_error("ldx_vae_encode: bad argument (H, W >= downscale factor; latent h*w multiple of 8)"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
     Bindings b; b.x = px; b.out = moments;
-    return run_planned(PlanKey{B, H, W, 2}, [&] { return plan_vae_encode(B, H, W); }, b, st);
-}
-
-// =============================================================================================
-// CLIP
-int Engine::finalize_clip() {
-    if (finalized) return LDX_OK;
-    const ldx_clip_config& c = ccfg;
-    auto bad = [&](const char* m) { set_error(std::string("unsupported CLIP config: ") + m); return LDX_EINVAL; };
-    if (c.hidden_size % 64 || c.intermediate_size % 64) return bad("hidden/intermediate size must be multiples of 64");
-    if (c.hidden_size % c.num_heads || (c.hidden_size / c.num_heads) % 8 || c.hidden_size / c.num_heads > 160) return bad("head dim");
-    HIP_OK(hipSetDevice(device));
-    const int E = c.hidden_size;
-    bool ok = true;
-    const HostTensor* tok = get("embeddings.token_embedding.weight", {c.vocab_size, E});
-    const HostTensor* pos = get("embeddings.position_embedding.weight", {c.max_positions, E});
-    ok = tok && pos;
-    if (ok) {
-        clip_tok = pack32((size_t)c.vocab_size * E, {{tok, nullptr, 0, c.vocab_size * E, 0}});
-        clip_pos = pack32((size_t)c.max_positions * E, {{pos, nullptr, 0, c.max_positions * E, 0}});
-        ok = clip_tok && clip_pos;
-    }
-    clip_layers.resize(c.num_layers);
-    for (int l = 0; ok && l < c.num_layers; ++l) {
-        ClipLayerW& L = clip_layers[l];
-        const std::string p = "encoder.layers." + std::to_string(l);
-        ok = mk_norm(p + ".layer_norm1", E, L.ln1) && mk_norm(p + ".layer_norm2", E, L.ln2);
-        const HostTensor *qw = get(p + ".self_attn.q_proj.weight", {E, E}), *kw = get(p + ".self_attn.k_proj.weight", {E, E}),
-                         *vw = get(p + ".self_attn.v_proj.weight", {E, E}), *qb = get(p + ".self_attn.q_proj.bias", {E}),
-                         *kb = get(p + ".self_attn.k_proj.bias", {E}), *vb = get(p + ".self_attn.v_proj.bias", {E});
-        ok = ok && qw && kw && vw && qb && kb && vb;
-        if (ok) {
-            L.qkv.N = 3 * E; L.qkv.K = E;
-            L.qkv.w = pack16((size_t)3 * E, E, {rows_piece(qw, 0, E, E), rows_piece(kw, E, E, E), rows_piece(vw, (size_t)2 * E, E, E)});
-            L.qkv.b = pack32((size_t)3 * E, {{qb, nullptr, 0, E, 0}, {kb, nullptr, (size_t)E, E, 0}, {vb, nullptr, (size_t)2 * E, E, 0}});
-            ok = L.qkv.w && L.qkv.b;
-        }
-        ok = ok && mk_linear(p + ".self_attn.out_proj", E, E, true, L.out) && mk_linear(p + ".mlp.fc1", c.intermediate_size, E, true, L.fc1) &&
-             mk_linear(p + ".mlp.fc2", E, c.intermediate_size, true, L.fc2);
-    }
-    ok = ok && mk_norm("final_layer_norm", E, clip_final_ln);
-    if (ok && host.count("text_projection.weight")) {          // optional: the pooled output's projection (bias-free Linear)
-        const HostTensor* tp = get("text_projection.weight", {E, E});
-        ok = tp != nullptr;
-        if (ok) { clip_proj = pack32((size_t)E * E, {{tp, nullptr, 0, E * E, 0}}); ok = clip_proj != nullptr; }
-    }
-    if (!ok) return weights_failed();
-    host.clear();
-    finalized = true;
-    return LDX_OK;
-}
-
-int Engine::plan_clip(int B, int T, int inter) {
-    const ldx_clip_config& c = ccfg;
-    const int E = c.hidden_size, M = B * T, heads = c.num_heads, D = E / heads;
-    return build_plan(PlanKey{B, T, 0, inter}, [&]() -> int {
-        Act x = new_act(M, E);
-        emit(OP_EMBED, "clip.embed").emb = ClipEmbedArgs{nullptr, clip_tok, clip_pos, ptr(x), B, T, E, c.vocab_size, nullptr, 0};      // ids and the textual-inversion rows are the call's
-        Act n = new_act(M, E), qkv = new_act(M, 3 * E), a = new_act(M, E), f = new_act(M, c.intermediate_size);
-        Act xi = new_act(M, E);
-        for (int l = 0; l < c.num_layers; ++l) {
-            const ClipLayerW& L = clip_layers[l];
-            op_ln("clip.ln1", x, n, L.ln1);
-            op_gemm("clip.qkv", n, L.qkv, qkv, Act{});
-            const char* base = (const char*)ptr(qkv);
-            op_attn("clip.attn", base, 3 * E, base + (size_t)E * 2, 3 * E, base + (size_t)2 * E * 2, 3 * E, a, B, heads, T, T, D);
-            cur.ops.back().at.causal = 1;
-            op_gemm("clip.out", a, L.out, x, x);                 // x += self_attn(ln1(x))
-            op_ln("clip.ln2", x, n, L.ln2);
-            op_gemm("clip.fc1", n, L.fc1, f, Act{});
-            cur.ops.back().g.act = 1;                                // quick-GELU
-            op_gemm("clip.fc2", f, L.fc2, x, x);                 // x += mlp(ln2(x))
-            if (l == inter) {                                    // intermediate = x.clone(); final LN applied to it
-                op_ln("clip.final_ln.inter", x, xi, clip_final_ln);
-                { Op& o = emit(OP_CVT_OUT, "clip.out_inter"); o.out = CvtOutArgs{ptr(xi), nullptr, (size_t)(M * E)}; o.second_output = true; }
-            }
-        }
-        op_ln("clip.final_ln", x, n, clip_final_ln);
-        emit(OP_CVT_OUT, "clip.out_last").out = CvtOutArgs{ptr(n), nullptr, (size_t)(M * E)};
-        return LDX_OK;
-    });
-}
-
-// Textual-inversion vectors for the next ldx_clip_encode calls: the reference extends the token table by one row per vector
-// and gives those rows the ids vocab_size, vocab_size + 1, ... (SDClipModel.set_up_textual_embeddings, SD15/SDClip.py:213-267).
-// Host rows [n][hidden] fp32; n = 0 removes them.  Synchronous (cudaMemcpy); the buffer grows, never shrinks.
-int Engine::set_clip_extra(const float* rows_host, int n) {
-    if (!finalized || kind != KIND_CLIP) { set_error("ldx_clip_set_extra_embeddings: not a finalized CLIP engine"); return LDX_ESTATE; }
-    if (n < 0 || (n > 0 && !rows_host)) { set_error("ldx_clip_set_extra_embeddings: bad argument"); return LDX_EINVAL; }
-    HIP_OK(hipSetDevice(device));
-    HIP_OK(hipDeviceSynchronize());                    // a previous encode may still read the old rows
-    const size_t E = (size_t)ccfg.hidden_size;
-    if (n > clip_extra_cap) {
-        float* p = nullptr;
-        HIP_OK(hipMalloc((void**)&p, (size_t)n * E * sizeof(float)));
-        dev_allocs.push_back(p);                       // the old (smaller) buffer stays owned by the engine until it is destroyed
-        clip_extra = p; clip_extra_cap = n;
-    }
-    if (n > 0) HIP_OK(hipMemcpy(clip_extra, rows_host, (size_t)n * E * sizeof(float), hipMemcpyHostToDevice));
-    clip_extra_n = n;
-    return LDX_OK;
-}
-
-int Engine::clip_pooled(const float* last, const int* ids, int B, int T, int eos_id, float* out, hipStream_t st) {
-    if (kind != KIND_CLIP || !finalized) { set_error("ldx_clip_pooled: not a finalized CLIP engine"); return LDX_ESTATE; }
-    if (!last || !ids || !out || B <= 0 || T <= 0) { set_error("ldx_clip_pooled: bad argument"); return LDX_EINVAL; }
-    HIP_OK(hipSetDevice(device));
-    launch_clip_pooled(last, ids, B, T, ccfg.hidden_size, eos_id, clip_proj, out, st);
-    return launch_status();
-}
-
-int Engine::run_clip(const int* ids, int B, int T, int inter_layer, float* out_last, float* out_inter, hipStream_t st) {
-    if (!finalized || kind != KIND_CLIP) { set_error("ldx_clip_encode: not a finalized CLIP engine"); return LDX_ESTATE; }
-    if (!ids || !out_last || B <= 0 || T <= 0 || T > ccfg.max_positions) { set_error("ldx_clip_encode: bad argument"); return LDX_EINVAL; }
-    HIP_OK(hipSetDevice(device));
-    int inter = -1;
-    if (out_inter) {
-        inter = inter_layer < 0 ? ccfg.num_layers + inter_layer : inter_layer;
-        if (inter < 0 || inter >= ccfg.num_layers) { set_error("ldx_clip_encode: inter_layer out of range"); return LDX_EINVAL; }
-    }
-    Bindings b; b.ids = ids; b.out = out_last; b.out2 = out_inter;
-    return run_planned(PlanKey{B, T, 0, inter}, [&] { return plan_clip(B, T, inter); }, b, st);
+    return run_planned(PlanKey{B, H, W, 2}, [&] { return plan_encode(B, H, W); }, b, st);
 }
 
 }  // namespace ldx

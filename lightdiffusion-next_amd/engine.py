@@ -1,7 +1,7 @@
-"""UNetEngine — Python handle on the native SD1.5 UNet engine (libldx.so).
+"""Python handles on the native engines (libldx.so): UNetEngine, VAEDecoderEngine, CLIPTextEngine, ESRGANEngine, T5Engine and FluxEngine over one base.
 
-Host-side responsibilities only: hand the state dict to the C ABI once, build the two lookup tables the
-reference builds on the host (sigma table and sinusoidal timestep embeddings), and pass device pointers.
+Host-side responsibilities only: hand the state dict to the C ABI once, build the lookup tables the
+reference builds on the host (the UNet's sigma table and sinusoidal timestep embeddings), and pass device pointers.
 Reference counterparts: BaseModel.__init__/load_model_weights/apply_model (src/Model/ModelBase.py:38-202).
 """
 import ctypes as C
@@ -48,91 +48,61 @@ def timestep_embedding_table(n: int, dim: int, max_period: int = 10000) -> torch
     return torch.cat([torch.cos(args), torch.sin(args)], dim=-1).contiguous()
 
 
-class UNetEngine:
-    def __init__(self, cfg: UNetConfig, state_dict, device: int = 0, dtype: str = "bf16", graph: bool = False):
+_DTYPE_CODES = {"bf16": lib.LDX_BF16, "f16": lib.LDX_F16, "fp16": lib.LDX_F16}
+
+
+class _Engine:
+    """What the six engines share: the library, the native handle and its lifetime, the way a state dict reaches it, the profile and the plan's figures."""
+
+    def __init__(self, cfg, device: int):
         self._lib = lib.load()
         self._h = C.c_void_p()
-        self.cfg = cfg
-        self.device = torch.device("cuda", device)
-        self.dtype = dtype
-        c = lib.ldx_unet_config()
-        c.compute_dtype = {"bf16": lib.LDX_BF16, "f16": lib.LDX_F16, "fp16": lib.LDX_F16}[dtype]
-        c.in_channels, c.out_channels, c.model_channels = cfg.in_channels, cfg.out_channels, cfg.model_channels
-        c.num_levels = len(cfg.channel_mult)
-        for i, v in enumerate(cfg.channel_mult):
-            c.channel_mult[i] = v
-        for i, v in enumerate(cfg.num_res_blocks):
-            c.num_res_blocks[i] = v
-        for i, v in enumerate(cfg.transformer_depth):
-            c.transformer_depth[i] = v
-        for i, v in enumerate(cfg.transformer_depth_output):
-            c.transformer_depth_output[i] = v
-        c.transformer_depth_middle = cfg.transformer_depth_middle
-        c.num_heads, c.context_dim = cfg.num_heads, cfg.context_dim
-        lib.check(self._lib.ldx_create(C.byref(c), device, C.byref(self._h)), "ldx_create")
-        try:
-            keep = self._load_state_dict(state_dict)
-            self.sigmas, self.log_sigmas = sd15_sigmas()
-            temb = timestep_embedding_table(self.sigmas.numel(), cfg.model_channels)
-            lib.check(self._lib.ldx_set_tables(self._h, lib.ptr(self.log_sigmas), self.log_sigmas.numel(),
-                                               lib.ptr(temb), temb.shape[1]), "ldx_set_tables")
-            lib.check(self._lib.ldx_finalize(self._h), "ldx_finalize")
-            del keep
-        except Exception:
-            self.close()
-            raise
-        if graph:
-            self.set_graph_mode(True)
+        self.cfg, self.device = cfg, torch.device("cuda", device)
 
-    def _load_state_dict(self, state_dict):
-        """Register every tensor of a state dict.  A tensor on the engine's device is handed over where it lies (ldx_load_tensor_device: not copied,
-        packed by device kernels); anything on the host goes through ldx_load_tensor, which copies it.  Returns the tensors whose memory the engine
-        refers to: the caller keeps them alive until ldx_finalize / ldx_unet_refresh_commit has returned."""
-        prefix = "model.diffusion_model."
+    def _create(self, struct, create, dtype: str, **fields):
+        """The native engine: `create` (the name of an ldx_*_create) on a `struct` filled from `fields` (a list fills the head of an array)."""
+        c = struct()
+        c.compute_dtype = _DTYPE_CODES[dtype]
+        for k, v in fields.items():
+            if isinstance(v, (list, tuple)):
+                for i, x in enumerate(v):
+                    getattr(c, k)[i] = x
+            else:
+                setattr(c, k, int(v))
+        lib.check(getattr(self._lib, create)(C.byref(c), self.device.index, C.byref(self._h)), create)
+
+    def _load_state_dict(self, state_dict, strip=(), allow_device=False):
+        """Register every tensor of a state dict, its key without the prefixes in `strip`.  A tensor goes through ldx_load_tensor, which copies it from the
+        host.  allow_device (the UNet): a tensor on the engine's device is handed over where it lies instead (ldx_load_tensor_device: not copied, packed
+        by device kernels).  Returns the tensors whose memory the engine refers to: the caller keeps them alive until ldx_finalize /
+        ldx_unet_refresh_commit has returned."""
         keep = []
         for k, t in state_dict.items():
-            if k.startswith(prefix):
-                k = k[len(prefix):]
+            for pre in strip:
+                if k.startswith(pre):
+                    k = k[len(pre):]
             t = t.detach()
-            if t.is_cuda:
+            on_device = allow_device and t.is_cuda
+            if on_device:
                 if t.device != self.device:
                     raise ValueError(f"{k}: tensor on {t.device}, the engine is on {self.device} (move the state dict to the host or to that device)")
                 if not t.is_contiguous():
                     raise ValueError(f"{k}: a device tensor must be contiguous (it is read where it lies, not copied)")
-                if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-                    t = t.float()
-                keep.append(t)
-                load, name = self._lib.ldx_load_tensor_device, "ldx_load_tensor_device"
             else:
                 t = t.to("cpu").contiguous()
-                if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-                    t = t.float()
-                load, name = self._lib.ldx_load_tensor, "ldx_load_tensor"
+            if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                t = t.float()
+            if on_device:
+                keep.append(t)
+            name = "ldx_load_tensor_device" if on_device else "ldx_load_tensor"
             shape = (C.c_int64 * t.dim())(*t.shape)
-            lib.check(load(self._h, k.encode(), lib.ptr(t), lib.torch_dtype_code(t.dtype), shape, t.dim()), f"{name}({k})")
+            lib.check(getattr(self._lib, name)(self._h, k.encode(), lib.ptr(t), lib.torch_dtype_code(t.dtype), shape, t.dim()), f"{name}({k})")
         if keep:
             torch.cuda.synchronize(self.device)      # whatever produced the device tensors (a LoRA merge on another stream) has finished
         return keep
 
-    def refresh(self, state_dict):
-        """Replace the weights in place (ldx_unet_refresh_begin / _commit) from a FULL state dict, host or device tensors as in the constructor: what the
-        reference's ModelPatcher.patch_model / unpatch_model does to its modules when a LoRA changes (ModelPatcher.py:515,652).  Plans, arenas and
-        captured graphs stay; the emb_layers table is rebuilt and cached context projections are dropped.  A state dict with a key missing or
-        mis-shaped raises LdxError naming it and leaves the engine computing with its present weights."""
-        lib.check(self._lib.ldx_unet_refresh_begin(self._h), "ldx_unet_refresh_begin")
-        try:
-            keep = self._load_state_dict(state_dict)
-        except Exception:
-            self._lib.ldx_unet_refresh_abort(self._h)      # forget what was registered and close the loaders again
-            raise
-        lib.check(self._lib.ldx_unet_refresh_commit(self._h), "ldx_unet_refresh_commit")
-        del keep
-
-    def weights_digest(self) -> int:
-        """ldx_weights_digest: FNV-1a over every packed weight buffer (diagnostic: equal digests = bit-identical weights)."""
-        d = C.c_uint64(0)
-        lib.check(self._lib.ldx_weights_digest(self._h, C.byref(d)), "ldx_weights_digest")
-        return int(d.value)
+    def _finalize(self):
+        lib.check(self._lib.ldx_finalize(self._h), "ldx_finalize")
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -144,6 +114,94 @@ class UNetEngine:
             self.close()
         except Exception:
             pass
+
+    def profile(self, on: bool, reset: bool = True):
+        lib.check(self._lib.ldx_profile(self._h, int(on), int(reset)), "ldx_profile")
+
+    def profile_report(self) -> dict:
+        import json
+        buf = C.create_string_buffer(1 << 18)
+        lib.check(self._lib.ldx_profile_report(self._h, buf, len(buf)), "ldx_profile_report")
+        return json.loads(buf.value.decode())
+
+    def plan_info(self):
+        """launches / algorithmic flops (the reference's arithmetic for this evaluation) / arena bytes of the current plan, plus the flops as EXECUTED
+        (`flops_executed`; smaller than `flops` by `flops_shared` when the plan computes the shared CFG prefix once, ldx_unet_cfg_share)."""
+        n, f, a = C.c_int64(), C.c_double(), C.c_int64()
+        lib.check(self._lib.ldx_plan_info(self._h, C.byref(n), C.byref(f), C.byref(a)), "ldx_plan_info")
+        ex, sh = C.c_double(), C.c_double()
+        lib.check(self._lib.ldx_plan_flops(self._h, C.byref(ex), C.byref(sh)), "ldx_plan_flops")
+        return {"launches": n.value, "flops": f.value, "arena_bytes": a.value, "flops_executed": ex.value, "flops_shared": sh.value}
+
+
+def _encode_token_weights(token_weight_pairs, empty_tokens, encode):
+    """ClipTokenWeightEncoder.encode_token_weights (SDClip.py:36-97) around an encoder: the chunks of (id, weight) pairs go through `encode` in one batch,
+    with the empty prompt (`empty_tokens(length)`, gen_empty_tokens, SDClip.py:10-22) behind them where a weight differs from 1; a weighted token's output
+    is then moved along the line from the empty prompt's.  encode(chunks) -> (host tensor [n, T, E], second result); returns (cond [1, sum T, E], second result)."""
+    to_encode, has_weights, max_len = [], False, 0
+    for x in token_weight_pairs:
+        toks = [a[0] for a in x]
+        max_len = max(max_len, len(toks))
+        has_weights = has_weights or not all(a[1] == 1.0 for a in x)
+        to_encode.append(toks)
+    sections = len(to_encode)
+    if has_weights or sections == 0:
+        to_encode.append(empty_tokens(max_len))
+    out, second = encode(to_encode)
+    output = []
+    for k in range(sections):
+        z = out[k:k + 1].clone()
+        if has_weights:
+            z_empty = out[-1]
+            for j in range(z.shape[1]):
+                wgt = token_weight_pairs[k][j][1]
+                if wgt != 1.0:
+                    z[0][j] = (z[0][j] - z_empty[j]) * wgt + z_empty[j]
+        output.append(z)
+    return (out[-1:] if not output else torch.cat(output, dim=-2)), second
+
+
+class UNetEngine(_Engine):
+    def __init__(self, cfg: UNetConfig, state_dict, device: int = 0, dtype: str = "bf16", graph: bool = False):
+        super().__init__(cfg, device)
+        self.dtype = dtype
+        self._create(lib.ldx_unet_config, "ldx_create", dtype, in_channels=cfg.in_channels, out_channels=cfg.out_channels, model_channels=cfg.model_channels,
+                     num_levels=len(cfg.channel_mult), channel_mult=cfg.channel_mult, num_res_blocks=cfg.num_res_blocks, transformer_depth=cfg.transformer_depth,
+                     transformer_depth_output=cfg.transformer_depth_output, transformer_depth_middle=cfg.transformer_depth_middle,
+                     num_heads=cfg.num_heads, context_dim=cfg.context_dim)
+        try:
+            keep = self._load_state_dict(state_dict, strip=("model.diffusion_model.",), allow_device=True)
+            self.sigmas, self.log_sigmas = sd15_sigmas()
+            temb = timestep_embedding_table(self.sigmas.numel(), cfg.model_channels)
+            lib.check(self._lib.ldx_set_tables(self._h, lib.ptr(self.log_sigmas), self.log_sigmas.numel(),
+                                               lib.ptr(temb), temb.shape[1]), "ldx_set_tables")
+            self._finalize()
+            del keep
+        except Exception:
+            self.close()
+            raise
+        if graph:
+            self.set_graph_mode(True)
+
+    def refresh(self, state_dict):
+        """Replace the weights in place (ldx_unet_refresh_begin / _commit) from a FULL state dict, host or device tensors as in the constructor: what the
+        reference's ModelPatcher.patch_model / unpatch_model does to its modules when a LoRA changes (ModelPatcher.py:515,652).  Plans, arenas and
+        captured graphs stay; the emb_layers table is rebuilt and cached context projections are dropped.  A state dict with a key missing or
+        mis-shaped raises LdxError naming it and leaves the engine computing with its present weights."""
+        lib.check(self._lib.ldx_unet_refresh_begin(self._h), "ldx_unet_refresh_begin")
+        try:
+            keep = self._load_state_dict(state_dict, strip=("model.diffusion_model.",), allow_device=True)
+        except Exception:
+            self._lib.ldx_unet_refresh_abort(self._h)      # forget what was registered and close the loaders again
+            raise
+        lib.check(self._lib.ldx_unet_refresh_commit(self._h), "ldx_unet_refresh_commit")
+        del keep
+
+    def weights_digest(self) -> int:
+        """ldx_weights_digest: FNV-1a over every packed weight buffer (diagnostic: equal digests = bit-identical weights)."""
+        d = C.c_uint64(0)
+        lib.check(self._lib.ldx_weights_digest(self._h, C.byref(d)), "ldx_weights_digest")
+        return int(d.value)
 
     def set_graph_mode(self, on: bool):
         lib.check(self._lib.ldx_set_graph_mode(self._h, int(on)), "ldx_set_graph_mode")
@@ -253,59 +311,21 @@ class UNetEngine:
         """UNetModel1.forward (unet.py:679-770): integer timesteps (as floats), unscaled input."""
         return self._run(self._lib.ldx_unet_forward, x, timesteps, ctx, out)
 
-    def profile(self, on: bool, reset: bool = True):
-        lib.check(self._lib.ldx_profile(self._h, int(on), int(reset)), "ldx_profile")
-
-    def profile_report(self) -> dict:
-        import json
-        buf = C.create_string_buffer(1 << 18)
-        lib.check(self._lib.ldx_profile_report(self._h, buf, len(buf)), "ldx_profile_report")
-        return json.loads(buf.value.decode())
-
-    def plan_info(self):
-        """launches / algorithmic flops (the reference's arithmetic for this evaluation) / arena bytes of the current plan, plus the flops as EXECUTED
-        (`flops_executed`; smaller than `flops` by `flops_shared` when the plan computes the shared CFG prefix once, ldx_unet_cfg_share)."""
-        n, f, a = C.c_int64(), C.c_double(), C.c_int64()
-        lib.check(self._lib.ldx_plan_info(self._h, C.byref(n), C.byref(f), C.byref(a)), "ldx_plan_info")
-        ex, sh = C.c_double(), C.c_double()
-        lib.check(self._lib.ldx_plan_flops(self._h, C.byref(ex), C.byref(sh)), "ldx_plan_flops")
-        return {"launches": n.value, "flops": f.value, "arena_bytes": a.value, "flops_executed": ex.value, "flops_shared": sh.value}
-
     def set_cfg_share(self, mode=True):
         """ldx_unet_cfg_share: denoise_cfg computes the part of the UNet in front of the first cross-attention once for both CFG halves.
         False / 0: never; True / 1 (default): where it pays (>= 8192 rows per half); 2: whenever possible (tests on small latents)."""
         lib.check(self._lib.ldx_unet_cfg_share(self._h, int(mode)), "ldx_unet_cfg_share")
 
 
-def _load_state_dict(L, h, state_dict, strip=()):
-    for k, t in state_dict.items():
-        for pre in strip:
-            if k.startswith(pre):
-                k = k[len(pre):]
-        t = t.detach().to("cpu").contiguous()
-        if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-            t = t.float()
-        shape = (C.c_int64 * t.dim())(*t.shape)
-        lib.check(L.ldx_load_tensor(h, k.encode(), lib.ptr(t), lib.torch_dtype_code(t.dtype), shape, t.dim()),
-                  f"ldx_load_tensor({k})")
-
-
-class VAEDecoderEngine:
+class VAEDecoderEngine(_Engine):
     """VAE.decode (src/AutoEncoders/VariationalAE.py:690-722): latent (already / 0.18215) -> NHWC fp32 in [0, 1]."""
 
     def __init__(self, cfg: VAEConfig, state_dict, device: int = 0, dtype: str = "bf16"):
-        self._lib = lib.load()
-        self._h = C.c_void_p()
-        self.cfg, self.device = cfg, torch.device("cuda", device)
-        c = lib.ldx_vae_config()
-        c.compute_dtype = {"bf16": lib.LDX_BF16, "f16": lib.LDX_F16, "fp16": lib.LDX_F16}[dtype]
-        c.z_channels, c.ch, c.num_levels = cfg.z_channels, cfg.ch, len(cfg.ch_mult)
-        for i, v in enumerate(cfg.ch_mult):
-            c.ch_mult[i] = v
-        c.num_res_blocks, c.out_ch, c.use_post_quant = cfg.num_res_blocks, cfg.out_ch, int(cfg.use_post_quant)
-        lib.check(self._lib.ldx_vae_create(C.byref(c), device, C.byref(self._h)), "ldx_vae_create")
-        _load_state_dict(self._lib, self._h, state_dict, strip=("first_stage_model.",))
-        lib.check(self._lib.ldx_finalize(self._h), "ldx_finalize")
+        super().__init__(cfg, device)
+        self._create(lib.ldx_vae_config, "ldx_vae_create", dtype, z_channels=cfg.z_channels, ch=cfg.ch, num_levels=len(cfg.ch_mult), ch_mult=cfg.ch_mult,
+                     num_res_blocks=cfg.num_res_blocks, out_ch=cfg.out_ch, use_post_quant=cfg.use_post_quant)
+        self._load_state_dict(state_dict, strip=("first_stage_model.",))
+        self._finalize()
 
     def decode(self, z):
         assert z.is_cuda and z.dtype == torch.float32 and z.dim() == 4
@@ -334,12 +354,6 @@ class VAEDecoderEngine:
         mean, logvar = torch.chunk(mom, 2, dim=1)
         eps = torch.randn(mean.shape).to(self.device)
         return mean + torch.exp(0.5 * torch.clamp(logvar, -30.0, 20.0)) * eps
-
-    profile = UNetEngine.profile
-    profile_report = UNetEngine.profile_report
-    plan_info = UNetEngine.plan_info
-    close = UNetEngine.close
-    __del__ = UNetEngine.__del__
 
 
 def _bislerp_data(length_old: int, length_new: int):
@@ -378,21 +392,16 @@ def latent_upscale(samples, width: int, height: int):
     return bislerp(samples, width // 8, height // 8)
 
 
-class CLIPTextEngine:
+class CLIPTextEngine(_Engine):
     """CLIPTextModel_.forward (src/clip/CLIPTextModel.py:51-107) + the token-weight logic of
     ClipTokenWeightEncoder.encode_token_weights (src/SD15/SDClip.py:36-97) on the host."""
 
     def __init__(self, cfg: CLIPConfig, state_dict, device: int = 0, dtype: str = "bf16"):
-        self._lib = lib.load()
-        self._h = C.c_void_p()
-        self.cfg, self.device = cfg, torch.device("cuda", device)
-        c = lib.ldx_clip_config()
-        c.compute_dtype = {"bf16": lib.LDX_BF16, "f16": lib.LDX_F16, "fp16": lib.LDX_F16}[dtype]
-        c.hidden_size, c.num_layers, c.num_heads = cfg.hidden_size, cfg.num_layers, cfg.num_heads
-        c.intermediate_size, c.max_positions, c.vocab_size = cfg.intermediate_size, cfg.max_positions, cfg.vocab_size
-        lib.check(self._lib.ldx_clip_create(C.byref(c), device, C.byref(self._h)), "ldx_clip_create")
-        _load_state_dict(self._lib, self._h, state_dict, strip=("text_model.",))       # incl. the optional "text_projection.weight"
-        lib.check(self._lib.ldx_finalize(self._h), "ldx_finalize")
+        super().__init__(cfg, device)
+        self._create(lib.ldx_clip_config, "ldx_clip_create", dtype, hidden_size=cfg.hidden_size, num_layers=cfg.num_layers, num_heads=cfg.num_heads,
+                     intermediate_size=cfg.intermediate_size, max_positions=cfg.max_positions, vocab_size=cfg.vocab_size)
+        self._load_state_dict(state_dict, strip=("text_model.",))       # incl. the optional "text_projection.weight"
+        self._finalize()
         self._tok_dtype = next(v.dtype for k, v in state_dict.items() if k.endswith("embeddings.token_embedding.weight"))
 
     def forward(self, tokens, intermediate_output=None):
@@ -430,58 +439,33 @@ class CLIPTextEngine:
     def encode_token_weights(self, token_weight_pairs, layer_idx=-2, special_tokens=(49406, 49407, 49407)):
         """ClipTokenWeightEncoder.encode_token_weights (SDClip.py:36-97) for a list of 77-token (id, weight) chunks; an id
         may be a textual-inversion vector (prompt.tokenize_with_weights with embeddings=...)."""
-        to_encode, has_weights, max_len = [], False, 0
-        for x in token_weight_pairs:
-            toks = [a[0] for a in x]
-            max_len = max(max_len, len(toks))
-            has_weights = has_weights or not all(a[1] == 1.0 for a in x)
-            to_encode.append(toks)
-        sections = len(to_encode)
-        if has_weights or sections == 0:
-            start, end, pad = special_tokens
-            to_encode.append([start, end] + [pad] * (max_len - 2))           # gen_empty_tokens (SDClip.py:10-20)
-        to_encode, extra = self._textual_embeddings(to_encode, special_tokens[2])
-        if extra or self._extra_rows:
-            # the reference copies the vectors into a table of the stored weights' dtype (SDClip.py:249-258): same rounding here
-            rows = torch.stack(extra).to(self._tok_dtype).float().contiguous() if extra else None
-            lib.check(self._lib.ldx_clip_set_extra_embeddings(self._h, None if rows is None else C.c_void_p(rows.data_ptr()), len(extra)),
-                      "ldx_clip_set_extra_embeddings")
-            self._extra_rows = len(extra)
-        last, inter, pooled = self.forward(torch.tensor(to_encode, dtype=torch.int64), intermediate_output=layer_idx)
-        out = (inter if layer_idx is not None else last).float().cpu()
-        output = []
-        for k in range(sections):
-            z = out[k:k + 1].clone()
-            if has_weights:
-                z_empty = out[-1]
-                for j in range(z.shape[1]):
-                    wgt = token_weight_pairs[k][j][1]
-                    if wgt != 1.0:
-                        z[0][j] = (z[0][j] - z_empty[j]) * wgt + z_empty[j]
-            output.append(z)
-        cond = out[-1:] if not output else torch.cat(output, dim=-2)
-        return cond, pooled[0:1].float().cpu()
+        start, end, pad = special_tokens
 
-    close = UNetEngine.close
-    __del__ = UNetEngine.__del__
+        def encode(to_encode):
+            to_encode, extra = self._textual_embeddings(to_encode, pad)
+            if extra or self._extra_rows:
+                # the reference copies the vectors into a table of the stored weights' dtype (SDClip.py:249-258): same rounding here
+                rows = torch.stack(extra).to(self._tok_dtype).float().contiguous() if extra else None
+                lib.check(self._lib.ldx_clip_set_extra_embeddings(self._h, None if rows is None else C.c_void_p(rows.data_ptr()), len(extra)),
+                          "ldx_clip_set_extra_embeddings")
+                self._extra_rows = len(extra)
+            last, inter, pooled = self.forward(torch.tensor(to_encode, dtype=torch.int64), intermediate_output=layer_idx)
+            return (inter if layer_idx is not None else last).float().cpu(), pooled[0:1].float().cpu()
+
+        return _encode_token_weights(token_weight_pairs, lambda n: [start, end] + [pad] * (n - 2), encode)
 
 
-class ESRGANEngine:
+class ESRGANEngine(_Engine):
     """RRDBNet.forward (src/UltimateSDUpscale/RDRB.py:216-471) + tiled_scale (src/Utilities/util.py:406-640) as
     UpscaleModelLoader / ImageUpscaleWithModel use them (USDU_upscaler.py:48-96)."""
 
     def __init__(self, cfg, state_dict, device: int = 0, dtype: str = "bf16"):
-        import math as _m
         from .weights import esrgan_new_to_old_arch
-        self._lib = lib.load()
-        self._h = C.c_void_p()
-        self.cfg, self.device = cfg, torch.device("cuda", device)
-        c = lib.ldx_esrgan_config()
-        c.compute_dtype = {"bf16": lib.LDX_BF16, "f16": lib.LDX_F16, "fp16": lib.LDX_F16}[dtype]
-        c.in_nc, c.out_nc, c.nf, c.gc, c.num_blocks, c.num_upscale = cfg.in_nc, cfg.out_nc, cfg.nf, cfg.gc, cfg.num_blocks, int(_m.log2(cfg.scale))
-        lib.check(self._lib.ldx_esrgan_create(C.byref(c), device, C.byref(self._h)), "ldx_esrgan_create")
-        _load_state_dict(self._lib, self._h, esrgan_new_to_old_arch(state_dict))
-        lib.check(self._lib.ldx_finalize(self._h), "ldx_finalize")
+        super().__init__(cfg, device)
+        self._create(lib.ldx_esrgan_config, "ldx_esrgan_create", dtype, in_nc=cfg.in_nc, out_nc=cfg.out_nc, nf=cfg.nf, gc=cfg.gc, num_blocks=cfg.num_blocks,
+                     num_upscale=math.log2(cfg.scale))
+        self._load_state_dict(esrgan_new_to_old_arch(state_dict))
+        self._finalize()
 
     def forward(self, pixels):
         """pixels [B,H,W,in_nc] fp32 (device) -> [B, s*H, s*W, out_nc] fp32."""
@@ -523,12 +507,6 @@ class ESRGANEngine:
             outs.append(out)
         return torch.cat(outs, 0)
 
-    profile = UNetEngine.profile
-    profile_report = UNetEngine.profile_report
-    plan_info = UNetEngine.plan_info
-    close = UNetEngine.close
-    __del__ = UNetEngine.__del__
-
 
 def t5_relative_position_bucket(relative_position, num_buckets=32, max_distance=128):
     """T5Attention._relative_position_bucket, bidirectional (src/clip/FluxClip.py:152-205) — same torch ops in the same
@@ -558,22 +536,18 @@ def t5_bias_table(rel_bias_weight, length: int, num_buckets=32, max_distance=128
     return out
 
 
-class T5Engine:
+class T5Engine(_Engine):
     """T5.forward (src/clip/FluxClip.py:441-519): token ids -> final_layer_norm(encoder output), fp32.  Host side keeps
     the 32 x heads relative-attention embedding and builds the bias table per sequence length (cached)."""
 
     def __init__(self, cfg, state_dict, device: int = 0, dtype: str = "bf16"):
-        self._lib = lib.load()
-        self._h = C.c_void_p()
-        self.cfg, self.device = cfg, torch.device("cuda", device)
-        c = lib.ldx_t5_config()
-        c.compute_dtype = {"bf16": lib.LDX_BF16, "f16": lib.LDX_F16, "fp16": lib.LDX_F16}[dtype]
-        c.d_model, c.d_ff, c.num_layers, c.num_heads, c.vocab_size = cfg.d_model, cfg.d_ff, cfg.num_layers, cfg.num_heads, cfg.vocab_size
-        lib.check(self._lib.ldx_t5_create(C.byref(c), device, C.byref(self._h)), "ldx_t5_create")
+        super().__init__(cfg, device)
+        self._create(lib.ldx_t5_config, "ldx_t5_create", dtype, d_model=cfg.d_model, d_ff=cfg.d_ff, num_layers=cfg.num_layers, num_heads=cfg.num_heads,
+                     vocab_size=cfg.vocab_size)
         rk = "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
         self._rel = state_dict[rk].float().cpu()
-        _load_state_dict(self._lib, self._h, {k: v for k, v in state_dict.items() if k != rk}, strip=("t5xxl.transformer.",))
-        lib.check(self._lib.ldx_finalize(self._h), "ldx_finalize")
+        self._load_state_dict({k: v for k, v in state_dict.items() if k != rk}, strip=("t5xxl.transformer.",))
+        self._finalize()
         self._bias = {}
 
     def bias(self, length: int):
@@ -593,34 +567,8 @@ class T5Engine:
     def encode_token_weights(self, token_weight_pairs):
         """ClipTokenWeightEncoder.encode_token_weights (SDClip.py:36-97) as T5XXLModel runs it (FluxClip.py:521-545):
         special tokens {end: 1, pad: 0}, layer "last", no pooled output.  Returns (cond [1, sum L, d_model], None)."""
-        to_encode, has_weights, max_len = [], False, 0
-        for x in token_weight_pairs:
-            toks = [a[0] for a in x]
-            max_len = max(max_len, len(toks))
-            has_weights = has_weights or not all(a[1] == 1.0 for a in x)
-            to_encode.append(toks)
-        sections = len(to_encode)
-        if has_weights or sections == 0:
-            to_encode.append([1] + [0] * (max_len - 1))                      # gen_empty_tokens (SDClip.py:10-22)
-        out = self.forward(torch.tensor(to_encode, dtype=torch.int64)).float().cpu()
-        output = []
-        for k in range(sections):
-            z = out[k:k + 1].clone()
-            if has_weights:
-                z_empty = out[-1]
-                for j in range(z.shape[1]):
-                    wgt = token_weight_pairs[k][j][1]
-                    if wgt != 1.0:
-                        z[0][j] = (z[0][j] - z_empty[j]) * wgt + z_empty[j]
-            output.append(z)
-        cond = out[-1:] if not output else torch.cat(output, dim=-2)
-        return cond, None
-
-    profile = UNetEngine.profile
-    profile_report = UNetEngine.profile_report
-    plan_info = UNetEngine.plan_info
-    close = UNetEngine.close
-    __del__ = UNetEngine.__del__
+        return _encode_token_weights(token_weight_pairs, lambda n: [1] + [0] * (n - 1),
+                                     lambda chunks: (self.forward(torch.tensor(chunks, dtype=torch.int64)).float().cpu(), None))
 
 
 def flux_rope_tables(cfg: FluxConfig, batch_txt_len: int, h: int, w: int):
@@ -640,26 +588,21 @@ def flux_rope_tables(cfg: FluxConfig, batch_txt_len: int, h: int, w: int):
     return torch.cat(cos, dim=-1).contiguous(), torch.cat(sin, dim=-1).contiguous()
 
 
-class FluxEngine:
+class FluxEngine(_Engine):
     """Flux3.forward behind BaseModel.apply_model with CONST prediction."""
 
     def __init__(self, cfg: FluxConfig, state_dict, device: int = 0, dtype: str = "bf16", fp8: bool = False):
         """fp8=True (or "linears"): the block linears (and the adaLN modulation projections) run on MX fp8 operands, attention in 16 bit (ldx_flux_set_fp8 mode 1;
         approximate, opt-in, own parity class).  fp8="attn": explicit opt-in to the less precise full mode (mode 3): at head dim 128 QK^T / PV of the joint attention run on MX fp8 too."""
-        self._lib = lib.load()
-        self._h = C.c_void_p()
-        self.cfg, self.device = cfg, torch.device("cuda", device)
-        c = lib.ldx_flux_config()
-        c.compute_dtype = {"bf16": lib.LDX_BF16, "f16": lib.LDX_F16, "fp16": lib.LDX_F16}[dtype]
-        c.in_channels, c.vec_in_dim, c.context_in_dim = cfg.in_channels, cfg.vec_in_dim, cfg.context_in_dim
-        c.hidden_size, c.mlp_hidden, c.num_heads = cfg.hidden_size, cfg.mlp_hidden, cfg.num_heads
-        c.depth, c.depth_single, c.guidance_embed = cfg.depth, cfg.depth_single_blocks, int(cfg.guidance_embed)
-        lib.check(self._lib.ldx_flux_create(C.byref(c), device, C.byref(self._h)), "ldx_flux_create")
+        super().__init__(cfg, device)
+        self._create(lib.ldx_flux_config, "ldx_flux_create", dtype, in_channels=cfg.in_channels, vec_in_dim=cfg.vec_in_dim, context_in_dim=cfg.context_in_dim,
+                     hidden_size=cfg.hidden_size, mlp_hidden=cfg.mlp_hidden, num_heads=cfg.num_heads, depth=cfg.depth, depth_single=cfg.depth_single_blocks,
+                     guidance_embed=cfg.guidance_embed)
         if fp8:
             assert fp8 in (True, "linears", "attn"), "fp8 must be False, True / 'linears', or 'attn'"
             lib.check(self._lib.ldx_flux_set_fp8(self._h, 3 if fp8 == "attn" else 1), "ldx_flux_set_fp8")
-        _load_state_dict(self._lib, self._h, state_dict, strip=("model.diffusion_model.",))
-        lib.check(self._lib.ldx_finalize(self._h), "ldx_finalize")
+        self._load_state_dict(state_dict, strip=("model.diffusion_model.",))
+        self._finalize()
         self._pe = {}
 
     def _run(self, x, sigma, ctx, y, guidance, denoise):
@@ -695,9 +638,3 @@ class FluxEngine:
     def denoise(self, x, sigma, ctx, y, guidance):
         """BaseModel.apply_model for ModelType.FLUX: x - Flux3(x, sigma, ...) * sigma (sampling.py:100-155)."""
         return self._run(x, sigma, ctx, y, guidance, True)
-
-    profile = UNetEngine.profile
-    profile_report = UNetEngine.profile_report
-    plan_info = UNetEngine.plan_info
-    close = UNetEngine.close
-    __del__ = UNetEngine.__del__
