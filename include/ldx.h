@@ -96,6 +96,12 @@ typedef struct ldx_esrgan_config {
     int32_t num_upscale;           /* 2 -> x4 */
 } ldx_esrgan_config;
 
+/* TAESD decoder (src/AutoEncoders/taesd.py:105-135, Decoder2): the tiny autoencoder behind the sampler loops' latent previews. */
+typedef struct ldx_taesd_config {
+    int32_t compute_dtype;
+    int32_t latent_channels;       /* 4 */
+} ldx_taesd_config;
+
 /* Flux DiT — FluxParams (src/BlackForest/Flux.py:293-306); flux-dev: 16, 768, 4096, 3072, 4.0, 24, 19, 38,
  * axes [16,56,56], theta 10000, qkv_bias 1, guidance_embed 1. */
 typedef struct ldx_flux_config {
@@ -275,6 +281,16 @@ int ldx_clip_set_extra_embeddings(ldx_engine* e, const float* rows_host, int n);
 int ldx_esrgan_create(const ldx_esrgan_config* cfg, int device, ldx_engine** out);
 /* RRDBNet.forward: pixels [B][H][W][in_nc] fp32 -> [B][sH][sW][out_nc] fp32, s = 2^num_upscale (no clamp). */
 int ldx_esrgan_forward(ldx_engine* e, const float* pixels_nhwc, int B, int H, int W, float* out_nhwc, void* stream);
+/* TAESD decoder.  State-dict keys are Decoder2's nn.Sequential indices ("1.weight", "3.conv.0.weight", ..., "19.bias"; 67 tensors). */
+int ldx_taesd_create(const ldx_taesd_config* cfg, int device, ldx_engine** out);
+/* TAESD.decode / the tensor part of taesd_preview (taesd.py:224-237, 257-304) of a latent [B][4][h][w] fp32.  Each output may be NULL (not both):
+ * out_f32 [B][3][8h][8w] fp32 = (decoder(latent) - 0.5) * 2;  out_u8 [B][8h][8w][3] = trunc(clip(((d + 1) / 2) * 255, 0, 255)) of that d, and with
+ * flux_flag != 0 channel c of it from d[2 - c] clamped to [-1, 1].  A handle of another model: LDX_ESTATE, nothing is launched. */
+int ldx_taesd_decode(ldx_engine* e, const float* latent, int B, int h, int w, float* out_f32, uint8_t* out_u8, int flux_flag, void* stream);
+/* Test surface: ONE launch of the decoder's conv kernel.  Y [B][H][W][64] = relu?(conv3x3(X) + bias + R) on 16-bit rows, H = Hin << up, W = Win << up
+ * (up = 1: nearest x2 of X [B][Hin][Win][64] folded into the gather); Wt [64][(ky * 3 + kx) * 64 + ci] 16-bit; bias [64] fp32 or NULL; R like Y or NULL;
+ * Rf: the residual as fp32 [B][H][W][64] instead (not both); Yf: the unrounded result as fp32 as well, or NULL. */
+int ldx_taesd_conv64(const void* X, const void* Wt, const float* bias, const void* R, const float* Rf, void* Y, float* Yf, int B, int Hin, int Win, int up, int relu, int dtype, void* stream);
 /* tiled_scale's feathered accumulation (src/Utilities/util.py:557-590): out/div [H][W][C] fp32 += tile [th][tw][C] * mask /
  * mask at (y0, x0); then ldx_tile_finish: out = out / div (div may be NULL), optionally clamped to [0,1] (USDU_upscaler.py:94). */
 int ldx_tile_blend(const float* tile, int th, int tw, float* out, float* div, int H, int W, int C, int y0, int x0, int feather, void* stream);

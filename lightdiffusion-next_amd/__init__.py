@@ -8,17 +8,18 @@ Layout:
   lib.py       ctypes binding of libldx.so (fails loudly if the library or a GPU is missing)
   engine.py    UNetEngine: weights in, denoise out (device pointers through the C ABI)
   hook.py      LdxUNetPatch / LdxFluxPatch: drop-ins for model_options["model_function_wrapper"] (cond.py:254-263)
-  sampling.py  host mirror of src/sample (schedulers, CFG batching, Euler / DPM++ loops)
+  sampling.py  host mirror of src/sample (schedulers, CFG batching, Euler / DPM++ loops, the TAESD preview hook: LatentPreviewer)
   parallel.py  batch shard + single all-gather across the GPUs of a node (RCCL / gloo)
   weights.py   SD1.5 state-dict layout + seeded synthetic weights (no checkpoints offline)
   checkpoint.py  load-time ingestion: checkpoint split, UNet layout sniffing, LoRA key maps + merge
   usdu.py      UltimateSDUpscale: the img2img tile redraw / seam fix, canvas on the device (ldx_image_* kernels -> libldx_image.so)
 """
 from . import lib, weights  # noqa: F401
-from .engine import UNetEngine, UNetConfig, VAEDecoderEngine, CLIPTextEngine, FluxEngine, T5Engine, ESRGANEngine, bislerp, latent_upscale  # noqa: F401
+from .engine import UNetEngine, UNetConfig, VAEDecoderEngine, CLIPTextEngine, FluxEngine, T5Engine, ESRGANEngine, TAESDEngine, bislerp, latent_upscale  # noqa: F401
 VAEEngine = VAEDecoderEngine      # the same engine encodes when encoder.* weights are loaded
-from .weights import VAEConfig, CLIPConfig, FluxConfig, T5Config, ESRGANConfig  # noqa: F401
+from .weights import VAEConfig, CLIPConfig, FluxConfig, T5Config, ESRGANConfig, TAESDConfig  # noqa: F401
 from .hook import LdxUNetPatch, LdxFluxPatch  # noqa: F401
 from . import prompt  # noqa: F401
 from . import sampling, parallel, checkpoint, usdu  # noqa: F401
+from .sampling import LatentPreviewer  # noqa: F401
 from .usdu import UltimateSDUpscale  # noqa: F401

@@ -137,6 +137,20 @@ int ldx_esrgan_forward(ldx_engine* e, const float* pixels_nhwc, int B, int H, in
     return m->run(pixels_nhwc, B, H, W, out_nhwc, (hipStream_t)stream);
     GUARD_END
 }
+int ldx_taesd_create(const ldx_taesd_config* cfg, int device, ldx_engine** out) { return create_engine<TaesdEngine>(cfg, device, out, __func__); }
+int ldx_taesd_decode(ldx_engine* e, const float* latent, int B, int h, int w, float* out_f32, uint8_t* out_u8, int flux_flag, void* stream) {
+    GUARD_BEGIN
+    ENGINE_AS(TaesdEngine, m);
+    return m->run(latent, B, h, w, out_f32, out_u8, flux_flag, (hipStream_t)stream);
+    GUARD_END
+}
+int ldx_taesd_conv64(const void* X, const void* Wt, const float* bias, const void* R, const float* Rf, void* Y, float* Yf, int B, int Hin, int Win, int up, int relu, int dtype, void* stream) {
+    TaesdConvArgs a{};
+    a.X = X; a.W = Wt; a.bias = bias; a.R = R; a.Rf = Rf; a.Y = Y; a.Yf = Yf; a.B = B; a.Hin = Hin; a.Win = Win; a.up = up; a.relu = relu ? 1 : 0;
+    if (!taesd_conv_ok(a)) { set_error("ldx_taesd_conv64: bad argument (null pointer, both residuals, up not 0 | 1, 2^31 output pixels or more)"); return LDX_EINVAL; }
+    launch_taesd_conv(a, dtype_of(dtype), (hipStream_t)stream);
+    return check_launch("ldx_taesd_conv64");
+}
 int ldx_tile_blend(const float* tile, int th, int tw, float* out, float* div, int H, int W, int C, int y0, int x0, int feather, void* stream) {
     if (!tile || !out || !div || th <= 0 || tw <= 0 || C <= 0 || y0 < 0 || x0 < 0 || y0 + th > H || x0 + tw > W || feather < 0) {
         set_error("ldx_tile_blend: bad argument (tile must lie inside the output)"); return LDX_EINVAL; }

@@ -1,5 +1,5 @@
 // ldx engines: the host-side planner / executor every model shares, behind the C ABI (include/ldx.h).  The models themselves are the classes
-// derived from Engine (engine_unet.cpp, engine_vae.cpp, engine_clip.cpp, engine_t5.cpp, engine_esrgan.cpp, engine_flux.cpp).
+// derived from Engine (engine_unet.cpp, engine_vae.cpp, engine_clip.cpp, engine_t5.cpp, engine_esrgan.cpp, engine_flux.cpp, engine_taesd.cpp).
 //
 // A model runs as a static launch plan over one activation arena: weights are packed once into MFMA-friendly
 // [N][K] 16-bit matrices (conv3x3 -> [Cout][ky][kx][Cin], q/k/v fused, GEGLU rows slab-interleaved),
@@ -655,6 +655,8 @@ int Engine::launch_op(const Op& o, hipStream_t ls) {
         case OP_MOMENTS: { MixArgs a = o.mix; a.out = bind.out; launch_mix_nhwc_to_nchw(a, ls); } break;
         case OP_EMBED: { ClipEmbedArgs a = o.emb; a.ids = bind.ids; a.extra = bind.extra; a.n_extra = bind.n_extra; launch_clip_embed(a, dt, ls); } break;      // the textual-inversion rows change between calls
         case OP_DUP: launch_dup_rows(o.dup, dt, ls); break;
+        case OP_TAESD_PREP: { TaesdPrepArgs a = o.tprep; a.z = bind.x; launch_taesd_prep(a, dt, ls); } break;
+        case OP_TAESD_CONV: { TaesdConvArgs a = o.tconv; if (a.out3) { a.out_f32 = bind.out; a.out_u8 = bind.out8; a.flux = bind.flux; } launch_taesd_conv(a, dt, ls); } break;
         case OP_FX_TEMB: { FluxTembArgs a = o.temb; a.t = o.of_guidance ? bind.guid : bind.s; launch_flux_temb(a, ls); } break;
         case OP_FX_SILU: launch_silu_f32(o.silu, ls); break;
         case OP_FX_PATCH: { FluxPatchArgs a = o.patch; a.x = bind.x; launch_flux_patchify(a, dt, ls); } break;

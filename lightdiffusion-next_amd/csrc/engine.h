@@ -68,14 +68,15 @@ struct Act { bool valid = false; bool owned = false; size_t off = 0; int rows = 
 enum OpKind { OP_PREP, OP_CVT, OP_SKINNY, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_FINISH,
               OP_VAEPREP, OP_SOFTMAX, OP_CLAMP, OP_EMBED, OP_CVT_OUT,
               OP_PIXPREP, OP_MOMENTS, OP_COPY_OUT,
-              OP_FX_PATCH, OP_FX_TEMB, OP_FX_SILU, OP_FX_ROPE, OP_FX_UNPATCH, OP_FX_SKINNY_Y, OP_MXQ, OP_GEMM2, OP_XATTN, OP_FFBLOCK, OP_ROWGEMM, OP_ATTN_MX, OP_MXVT, OP_DUP };
+              OP_FX_PATCH, OP_FX_TEMB, OP_FX_SILU, OP_FX_ROPE, OP_FX_UNPATCH, OP_FX_SKINNY_Y, OP_MXQ, OP_GEMM2, OP_XATTN, OP_FFBLOCK, OP_ROWGEMM, OP_ATTN_MX, OP_MXVT, OP_DUP,
+              OP_TAESD_PREP, OP_TAESD_CONV };
 // One launch of a plan.  The rule: every kind has ONE argument struct (ldx_kernels.h, beside its launcher), filled by the planner, and Engine::launch_op hands it to
 // that launcher after filling in the pointers of the call (Bindings).  Nothing here has a meaning that depends on `kind`.
 struct Op {
     OpKind kind; const char* name;
     GemmArgs g; GemmArgs g2; GroupNormArgs gn; LayerNormArgs ln; AttnArgs at; SkinnyArgs sk; QkRopeArgs rp; MxQuantArgs mq; XAttnArgs xa; FFBlockArgs fb; RowGemmArgs rg; AttnMxArgs am; MxVtArgs vt;
     PrepArgs prep; FinishArgs fin; CvtArgs cvt; CvtOutArgs out; CopyOutArgs copy; VaePrepArgs vprep; PixelsPrepArgs pix; ClampArgs clamp; SoftmaxArgs sm; ClipEmbedArgs emb; MixArgs mix; DupRowsArgs dup;
-    FluxTembArgs temb; SiluArgs silu; FluxPatchArgs patch; FluxUnpatchArgs unpatch;
+    FluxTembArgs temb; SiluArgs silu; FluxPatchArgs patch; FluxUnpatchArgs unpatch; TaesdPrepArgs tprep; TaesdConvArgs tconv;
     bool ctx_only;                 // depends on the context alone (16-bit copy of ctx, the batched k|v projection): skipped while Engine::ctx_cache holds
     // which of the call's buffers (Bindings) launch_op binds, where the kind alone does not say
     bool bias_from_call;           // the attention's score bias table is the call's (T5)
@@ -87,7 +88,7 @@ struct Op {
 struct ProfEntry { long count = 0; double ms = 0, flops = 0, bytes = 0; };
 
 // What a plan was built for.  Per model: UNet (B2, h, w, Mc, share), Flux (B, h, w, Lt), VAE (B, h, w, 1) decode / (B, Hpx, Wpx, 2) encode,
-// CLIP (B, T, 0, inter_layer), T5 (B, L), ESRGAN (B, H, W).  B = 0: no plan.
+// CLIP (B, T, 0, inter_layer), T5 (B, L), ESRGAN (B, H, W), TAESD (B, h, w).  B = 0: no plan.
 struct PlanKey {
     int B = 0, h = 0, w = 0, m = 0, share = 0;
     bool operator==(const PlanKey& o) const { return B == o.B && h == o.h && w == o.w && m == o.m && share == o.share; }
@@ -103,9 +104,10 @@ struct Bindings {
     const int* ids = nullptr; float* out2 = nullptr; const float* bias = nullptr;       // CLIP / T5
     const float* extra = nullptr; int n_extra = 0;                                        // CLIP: textual-inversion rows for ids >= vocab_size (T5: none)
     const float *y = nullptr, *guid = nullptr, *pe_cos = nullptr, *pe_sin = nullptr;     // Flux
+    uint8_t* out8 = nullptr; int flux = 0;                                                // TAESD: the 8-bit preview and its channel order
     bool operator==(const Bindings& o) const {
         return x == o.x && s == o.s && ctx == o.ctx && out == o.out && den == o.den && xB == o.xB && cc == o.cc && ccn == o.ccn && t == o.t &&
-               ctxc == o.ctxc && ids == o.ids && out2 == o.out2 && bias == o.bias && extra == o.extra && n_extra == o.n_extra && y == o.y && guid == o.guid && pe_cos == o.pe_cos && pe_sin == o.pe_sin;
+               ctxc == o.ctxc && ids == o.ids && out2 == o.out2 && bias == o.bias && extra == o.extra && n_extra == o.n_extra && y == o.y && guid == o.guid && pe_cos == o.pe_cos && pe_sin == o.pe_sin && out8 == o.out8 && flux == o.flux;
     }
 };
 
@@ -153,7 +155,7 @@ struct FluxDoubleW { FluxStreamW img, txt; };
 struct FluxSingleW { LinearW lin1_qkv, lin1_mlp, lin2; float* qs = nullptr; float* ks = nullptr; int mod_off = 0; };
 
 // The planner / executor every model is built on, and what every model's weights go through.  A model is a derived class (UNetEngine, VaeEngine, ClipEngine,
-// T5Engine, EsrganEngine, FluxEngine) that owns its config, its weight tables, finalize(), its plan functions and its run entry points; the C ABI reaches a model
+// T5Engine, EsrganEngine, FluxEngine, TaesdEngine) that owns its config, its weight tables, finalize(), its plan functions and its run entry points; the C ABI reaches a model
 // entry point only through that class (capi.cpp engine_as), so nothing here or there asks an engine what it is.
 class Engine {
 public:
@@ -407,6 +409,25 @@ public:
 private:
     std::vector<RdbW> es_rdb; LinearW es_first, es_trunk, es_hr, es_last; std::vector<LinearW> es_up;
     int plan(int B, int H, int W);
+};
+
+// TAESD decoder (engine_taesd.cpp): latent fp32 NCHW -> decoded fp32 NCHW and / or the 8-bit NHWC preview
+struct TaesdBlockW { LinearW c[3]; };
+class TaesdEngine final : public Engine {
+public:
+    static constexpr const char* model = "TAESD";
+    TaesdEngine(const ldx_taesd_config& c, int dev) : Engine(dev, c.compute_dtype, false), cfg(c) {}
+    ~TaesdEngine() override;
+    int validate() const;
+    int finalize() override;
+    int run(const float* z, int B, int h, int w, float* out_f32, uint8_t* out_u8, int flux, hipStream_t st);
+    const ldx_taesd_config cfg;
+
+private:
+    LinearW ta_first, ta_last, ta_up[3]; TaesdBlockW ta_blocks[10];
+    bool mk_conv64(const std::string& pre, int Cout, int Cin, bool bias, LinearW& out);
+    int plan(int B, int h, int w);
+    hipStream_t cap_stream = nullptr;     // graph capture
 };
 
 class FluxEngine final : public Engine {

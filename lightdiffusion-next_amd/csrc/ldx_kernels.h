@@ -516,4 +516,26 @@ void launch_image_composite(uint8_t* canvas, long canvas_pitch, const uint8_t* t
                             int h, int w, int C, hipStream_t s);
 void launch_image_fill(uint8_t* img, long pitch, int h, int rowlen, int value, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// TAESD decoder (taesd.hip, libldx_taesd.so): the latent preview of the sampler loops (src/AutoEncoders/taesd.py:105-135).
+// 3x3 / stride 1 / pad 1 conv, 64 -> 64 channels, on 16-bit rows [B * H * W][64] with the whole weight matrix resident in LDS:
+//   Y[m][n] = relu?( sum_k W[n][k] X(m, k) + bias[n] + R[m][n] ),  k = (ky * 3 + kx) * 64 + ci,  W [64][576] 16-bit (conv_piece layout, CinPad 64).
+// up = 1: the 3x3 window walks the nearest x2 upsampled image (output [B][2 Hin][2 Win]), X stays [B][Hin][Win].  bias, R may be null.
+// Rf != null: the residual row is fp32 [M][64] instead of R; Yf != null: the value is ALSO stored unrounded as fp32 [M][64].  The decoder's skip stream runs
+// through ten Blocks: kept in fp32 beside the 16-bit copy the next conv multiplies, it is not rounded once per Block (engine_taesd.cpp).
+// out3 = 1: the 64 -> 3 output conv (W [32][576], rows 3 .. 31 zero; bias [3]); instead of Y it writes, each if non-null,
+//   out_f32 [B][3][H][W] = (y - 0.5) * 2  (TAESD.decode, taesd.py:224-237) and
+//   out_u8  [B][H][W][3] = trunc(clip(((d + 1) / 2) * 255, 0, 255))  (taesd_preview :291-304; flux: channel c from d[2 - c] clamped to [-1, 1]).
+struct TaesdConvArgs {
+    const void* X; const void* W; const float* bias; const void* R; void* Y;
+    const float* Rf; float* Yf;
+    float* out_f32; uint8_t* out_u8;
+    int B, Hin, Win; int up, relu, out3, flux;
+};
+bool taesd_conv_ok(const TaesdConvArgs& a);                 // pointers there, up 0 | 1, fewer than 2^31 output pixels
+void launch_taesd_conv(const TaesdConvArgs& a, DType dt, hipStream_t s);
+// Clamp (tanh(z / 3) * 3, taesd.py:30-42) of the latent fp32 NCHW [B][C][HW], C <= 8 -> 16-bit rows [B * HW][64], the other channels zero
+struct TaesdPrepArgs { const float* z; void* out; int B, C; long HW; };
+void launch_taesd_prep(const TaesdPrepArgs& a, DType dt, hipStream_t s);
+
 }  // namespace ldx

@@ -52,7 +52,7 @@ _DTYPE_CODES = {"bf16": lib.LDX_BF16, "f16": lib.LDX_F16, "fp16": lib.LDX_F16}
 
 
 class _Engine:
-    """What the six engines share: the library, the native handle and its lifetime, the way a state dict reaches it, the profile and the plan's figures."""
+    """What the seven engines share: the library, the native handle and its lifetime, the way a state dict reaches it, the profile and the plan's figures."""
 
     def __init__(self, cfg, device: int):
         self._lib = lib.load()
@@ -506,6 +506,76 @@ class ESRGANEngine(_Engine):
             lib.check(L.ldx_tile_finish(lib.ptr(out), lib.ptr(div), out.numel(), 1, lib.current_stream_ptr()), "ldx_tile_finish")
             outs.append(out)
         return torch.cat(outs, 0)
+
+
+class TAESDEngine(_Engine):
+    """The tiny autoencoder's decoder (src/AutoEncoders/taesd.py): TAESD.decode and the tensor part of taesd_preview, the sampler loops' latent preview.
+    state_dict: Decoder2's own keys (weights.taesd_decoder_state_dict_spec; include/vae_approx/taesd_decoder.safetensors as it is).
+    graph=True: the 36 launches of a shape are captured into a hipGraph on the second call and replayed from the third.  A captured graph has its pointers
+    baked in, so in graph mode the engine keeps one latent buffer and one output buffer per (shape, output, flux), copies the latent in and returns a copy
+    of the result (3 MB of bytes for a 1024^2 preview)."""
+
+    def __init__(self, cfg=None, state_dict=None, device: int = 0, dtype: str = "bf16", graph: bool = False):
+        from .weights import TAESDConfig
+        cfg = cfg or TAESDConfig()
+        super().__init__(cfg, device)
+        self._create(lib.ldx_taesd_config, "ldx_taesd_create", dtype, latent_channels=cfg.latent_channels)
+        self._load_state_dict(state_dict, strip=("taesd_decoder.",))
+        self._finalize()
+        self.set_graph_mode(graph)
+
+    def set_graph_mode(self, on: bool):
+        lib.check(self._lib.ldx_set_graph_mode(self._h, int(on)), "ldx_set_graph_mode")
+        self._graph, self._static = bool(on), {}
+
+    def graph_stats(self):
+        """(captures, replays) of the engine's hipGraph path since it was created."""
+        c, r = C.c_int64(0), C.c_int64(0)
+        lib.check(self._lib.ldx_graph_stats(self._h, C.byref(c), C.byref(r)), "ldx_graph_stats")
+        return int(c.value), int(r.value)
+
+    def _latent(self, x):
+        """taesd_preview's channel rule (taesd.py:268-277): more than 4 channels are cut, fewer are zero-padded."""
+        assert x.dim() == 4
+        x = x.to(self.device, torch.float32)
+        c = x.shape[1]
+        if c > 4:
+            x = x[:, :4]
+        elif c < 4:
+            x = torch.cat([x, x.new_zeros((x.shape[0], 4 - c) + tuple(x.shape[2:]))], dim=1)
+        return x.contiguous()
+
+    def _decode(self, x, want_f32, want_u8, flux):
+        b, _, h, w = x.shape
+
+        def buffers():
+            f32 = torch.empty((b, 3, 8 * h, 8 * w), device=self.device, dtype=torch.float32) if want_f32 else None
+            u8 = torch.empty((b, 8 * h, 8 * w, 3), device=self.device, dtype=torch.uint8) if want_u8 else None
+            return f32, u8
+        if not self._graph:
+            f32, u8 = buffers()
+        else:
+            key = (b, h, w, want_f32, want_u8, bool(flux))
+            if key not in self._static:
+                if len(self._static) >= 4:
+                    self._static.clear()
+                self._static[key] = (torch.empty_like(x),) + buffers()
+            xs, f32, u8 = self._static[key]
+            xs.copy_(x)
+            x = xs
+        lib.check(self._lib.ldx_taesd_decode(self._h, lib.ptr(x), b, h, w, lib.ptr(f32), lib.ptr(u8), int(bool(flux)), lib.current_stream_ptr()), "ldx_taesd_decode")
+        if self._graph:
+            f32, u8 = (None if f32 is None else f32.clone()), (None if u8 is None else u8.clone())
+        return f32, u8
+
+    def decode(self, x):
+        """TAESD.decode (taesd.py:224-237; vae_shift 0, vae_scale 1): latent [B,4,h,w] -> [B,3,8h,8w] fp32 = (decoder(x) - 0.5) * 2."""
+        assert x.shape[1] == 4, "TAESD.decode takes 4 latent channels (preview() cuts or pads)"
+        return self._decode(self._latent(x), True, False, False)[0]
+
+    def preview(self, x, flux: bool = False):
+        """The tensor part of taesd_preview (taesd.py:264-304): latent [B,C,h,w] -> device uint8 [B,8h,8w,3], the bytes the reference hands to PIL."""
+        return self._decode(self._latent(x), False, True, flux)[1]
 
 
 def t5_relative_position_bucket(relative_position, num_buckets=32, max_distance=128):

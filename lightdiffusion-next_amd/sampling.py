@@ -327,9 +327,52 @@ class _Multiscale:
         return False
 
 
+def _preview(preview, every, i, x):
+    """The reference's preview call site (samplers.py:160, 324, 605, 737, 959, 1251: `i % 5 == 0` at the end of iteration i, on the updated x)."""
+    if preview is not None and i % every == 0:
+        preview(i, x)
+
+
+class LatentPreviewer:
+    """`preview=` callable of the sampler loops: what taesd_preview (src/AutoEncoders/taesd.py:257-313) does up to the PIL images, without stopping the loop.
+    A call decodes x on the current stream (engine: TAESDEngine, or anything with preview(x, flux) -> uint8 [B,H,W,3]), starts the copy of the bytes into pinned
+    host memory and records an event; nothing waits.  Images whose event has completed are handed to sink(step, images) (images: host uint8 [B,H,W,3]) in
+    step order at the NEXT call, and all that are left from flush(), which is the only place that waits."""
+
+    def __init__(self, engine, sink, flux: bool = False):
+        self.engine, self.sink, self.flux = engine, sink, flux
+        self._pending = []                      # (step, host images, event or None), oldest first
+
+    def __call__(self, step, x):
+        self._deliver(wait=False)
+        img = self.engine.preview(x, self.flux)
+        if img.is_cuda:
+            host = torch.empty(img.shape, dtype=img.dtype, pin_memory=True)
+            host.copy_(img, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(img.device))
+        else:                                   # a host-side engine (tests): finished as it returns
+            host, ev = img.clone(), None
+        self._pending.append((step, host, ev))
+
+    def _deliver(self, wait):
+        while self._pending:
+            step, host, ev = self._pending[0]
+            if ev is not None:
+                if wait:
+                    ev.synchronize()
+                elif not ev.query():
+                    return                      # later ones finish later: the order of delivery is the order of the steps
+            self._pending.pop(0)
+            self.sink(step, host)
+
+    def flush(self):
+        self._deliver(wait=True)
+
+
 @torch.no_grad()
 def sample_euler(model, x, sigmas, enable_multiscale=True, multiscale_factor=0.5, multiscale_fullres_start=3,
-                 multiscale_fullres_end=8, multiscale_intermittent_fullres=False, trace=None):
+                 multiscale_fullres_end=8, multiscale_intermittent_fullres=False, trace=None, preview=None, preview_every=5):
     """samplers.sample_euler (samplers.py:166-327) with s_churn = 0.  `model(x, sigma)` -> (uncond, cond)."""
     n_steps = len(sigmas) - 1
     ms = _Multiscale(x.shape, n_steps, enable_multiscale, multiscale_factor, multiscale_fullres_start,
@@ -351,13 +394,14 @@ def sample_euler(model, x, sigmas, enable_multiscale=True, multiscale_factor=0.5
             _step(2, xs, du, dc, model.cfg, 0.0, 0.0, denoised_out=d)
             d = _bilinear(d, (ms.orig_h, ms.orig_w))
             _step(0, x, d, d, 1.0, sigma_hat, dt)
+        _preview(preview, preview_every, i, x)
     return x
 
 
 @torch.no_grad()
 def sample_dpmpp_2m_cfgpp(model, x, sigmas, enable_multiscale=True, multiscale_factor=0.5,
                           multiscale_fullres_start=5, multiscale_fullres_end=8,
-                          multiscale_intermittent_fullres=True, trace=None):
+                          multiscale_intermittent_fullres=True, trace=None, preview=None, preview_every=5):
     """samplers.sample_dpmpp_2m_cfgpp (samplers.py:754-962).  The CFG++/momentum branch never executes in
     the reference, so every step is  x = (s'/s) x - expm1(-h) * denoised."""
     n_steps = len(sigmas) - 1
@@ -383,6 +427,7 @@ def sample_dpmpp_2m_cfgpp(model, x, sigmas, enable_multiscale=True, multiscale_f
             _step(2, xs, du, dc, model.cfg, 0.0, 0.0, denoised_out=d)
             d = _bilinear(d, (ms.orig_h, ms.orig_w))
             _step(1, x, d, d, 1.0, ratios[i], h_expm1)
+        _preview(preview, preview_every, i, x)
     return x
 
 
@@ -394,7 +439,7 @@ def get_ancestral_step(sigma_from, sigma_to, eta=1.0):
 
 
 @torch.no_grad()
-def sample_euler_ancestral_cfgpp(model, x, sigmas, eta=1.0, s_noise=1.0, noise_sampler=None, trace=None):
+def sample_euler_ancestral_cfgpp(model, x, sigmas, eta=1.0, s_noise=1.0, noise_sampler=None, trace=None, preview=None, preview_every=5):
     """samplers.sample_euler_ancestral_dy_cfg_pp (samplers.py:612-733) with its defaults.  The CFG++ branch is dead
     code in the reference: every step is Euler to sigma_down on the guider's ordinary CFG
     output, then  x += noise * s_noise * sigma_up  (ldx_sampler_step kind 3).  The reference's default noise sampler
@@ -421,6 +466,7 @@ def sample_euler_ancestral_cfgpp(model, x, sigmas, eta=1.0, s_noise=1.0, noise_s
             else:
                 nz = noise_sampler(sigmas[i], sigmas[i + 1]).to(x.device, torch.float32).contiguous()
             _step(3, x, nz, nz, 1.0, s_noise * sigma_up, 0.0)
+        _preview(preview, preview_every, i, x)
     return x
 
 
@@ -440,7 +486,7 @@ def _dy_step_cfgpp(x, model, sigma_next, sigma_hat, current_cfg):
 
 
 @torch.no_grad()
-def sample_euler_cfgpp(model, x, sigmas, cfg_scale=7.5, cfg_min=1.0, s_extra_steps=True, trace=None):
+def sample_euler_cfgpp(model, x, sigmas, cfg_scale=7.5, cfg_min=1.0, s_extra_steps=True, trace=None, preview=None, preview_every=5):
     """samplers.sample_euler_dy_cfg_pp (samplers.py:470-609) with its defaults.  Main step = Euler on the guider's CFG
     output (the CFG++ momentum branch is dead code, SURVEY.md Appendix A-2); after steps 2 and 3 (i // 2 == 1) the dy
     extra step runs.  `model` must evaluate both branches (disable_cfg1_optimization, samplers.py:517-520)."""
@@ -456,6 +502,7 @@ def sample_euler_cfgpp(model, x, sigmas, cfg_scale=7.5, cfg_min=1.0, s_extra_ste
             if trace is not None:
                 trace.append((x.shape[-2] // 2, x.shape[-1] // 2))
             x = _dy_step_cfgpp(x, model, sigmas[i + 1], sigma_hat, current_cfg)
+        _preview(preview, preview_every, i, x)
     return x
 
 
@@ -490,7 +537,7 @@ class BrownianIntervalNoise:
 @torch.no_grad()
 def sample_dpmpp_sde_cfgpp(model, x, sigmas, eta=1.0, s_noise=1.0, noise_sampler=None, r=0.5, seed=None, enable_multiscale=True,
                            multiscale_factor=0.5, multiscale_fullres_start=5, multiscale_fullres_end=8,
-                           multiscale_intermittent_fullres=False, trace=None):
+                           multiscale_intermittent_fullres=False, trace=None, preview=None, preview_every=5):
     """samplers.sample_dpmpp_sde_cfgpp (samplers.py:965-1254) with its defaults (r = 1/2).  As in the other cfgpp samplers the
     CFG++ momentum branch is dead code: the sampler calls its own post-cfg hook with uncond_denoised = None (:1137-1139,
     :1209-1211), which resets old_uncond_denoised and returns the guider's CFG output, so cfg_denoised == denoised.  What
@@ -531,6 +578,7 @@ def sample_dpmpp_sde_cfgpp(model, x, sigmas, eta=1.0, s_noise=1.0, noise_sampler
         d1 = denoise(x, sigmas[i], full)
         if sigmas[i + 1] == 0:
             _step(0, x, d1, d1, 1.0, sigmas[i], sigmas[i + 1] - sigmas[i])                     # Euler on to_d (:1156-1159)
+            _preview(preview, preview_every, i, x)
             continue
         t, t_next = t_fn(sigmas[i]), t_fn(sigmas[i + 1])
         s = t + (t_next - t) * r
@@ -557,6 +605,7 @@ def sample_dpmpp_sde_cfgpp(model, x, sigmas, eta=1.0, s_noise=1.0, noise_sampler
         else:
             nz = noise_sampler(sigma_fn(t), sigma_fn(t_next)).to(x.device, torch.float32).contiguous()
             _step(3, x, nz, nz, 1.0, s_noise * su, 0.0)
+        _preview(preview, preview_every, i, x)
     return x
 
 
@@ -586,7 +635,7 @@ class KSampler:
 
     def sample(self, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0,
                enable_multiscale=True, multiscale_factor=0.5, multiscale_fullres_start=3,
-               multiscale_fullres_end=8, multiscale_intermittent_fullres=False, noise=None, trace=None):
+               multiscale_fullres_end=8, multiscale_intermittent_fullres=False, noise=None, trace=None, preview=None, preview_every=5):
         ms = self.model_sampling
         denoise = denoise or 1.0                                   # sampling.py:875 quirk (A-12)
         latent_image = latent_image.float()
@@ -613,7 +662,7 @@ class KSampler:
             x = noise * sigmas[0]
         x = x.to(dev) + latent_image.to(dev)                       # the latent may already live on the device (HiresFix chain)
         model = CFGDenoiser(self.engine, positive, negative, cfg, b, h, w, disable_cfg1_optimization=disable_cfg1)
-        x = fn(model, x, sigmas, trace=trace, **extra)
+        x = fn(model, x, sigmas, trace=trace, preview=preview, preview_every=preview_every, **extra)
         return x / 0.18215                                         # process_latent_out (CFG.py:294)
 
 
@@ -662,7 +711,7 @@ class FluxKSampler:
 
     def sample(self, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, guidance=3.0, denoise=1.0,
                enable_multiscale=True, multiscale_factor=0.5, multiscale_fullres_start=3, multiscale_fullres_end=8,
-               multiscale_intermittent_fullres=False, noise=None, trace=None):
+               multiscale_intermittent_fullres=False, noise=None, trace=None, preview=None, preview_every=5):
         ms = self.model_sampling
         denoise = denoise or 1.0
         latent_image = latent_image.float()
@@ -679,7 +728,7 @@ class FluxKSampler:
             latent_image = (latent_image - FLUX_LATENT_SHIFT) * FLUX_LATENT_SCALE
         x = ms.noise_scaling(sigmas[0], noise, latent_image).to(self.engine.device)
         model = FluxCFGDenoiser(self.engine, positive, negative, cfg, guidance, x.shape[0], disable_cfg1_optimization=disable_cfg1)
-        x = fn(model, x, sigmas, trace=trace, **extra)
+        x = fn(model, x, sigmas, trace=trace, preview=preview, preview_every=preview_every, **extra)
         x = ms.inverse_noise_scaling(sigmas[-1], x)
         return x / FLUX_LATENT_SCALE + FLUX_LATENT_SHIFT                    # process_latent_out
 

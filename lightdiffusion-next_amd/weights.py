@@ -398,6 +398,36 @@ def esrgan_state_dict_spec(cfg: ESRGANConfig):
     return spec
 
 
+@dataclass
+class TAESDConfig:
+    """Decoder2 of the tiny autoencoder (src/AutoEncoders/taesd.py:105-135): conv 4 -> 64, 3 Blocks, three times (nearest x2, bias-free conv,
+    3 Blocks; the last time 1 Block), conv 64 -> 3.  The reference builds no other size."""
+
+    latent_channels: int = 4
+
+    @staticmethod
+    def tiny() -> "TAESDConfig":
+        return TAESDConfig()          # 1.2 M parameters: the network is its own tiny net
+
+
+def taesd_decoder_state_dict_spec(cfg: TAESDConfig = None):
+    """Decoder2's keys, the nn.Sequential indices, in creation order (taesd.py:114-135): 67 tensors, 1 222 531 parameters."""
+    cfg = cfg or TAESDConfig()
+    spec = [("1.weight", (64, cfg.latent_channels, 3, 3)), ("1.bias", (64,))]
+
+    def blocks(first, n):
+        out = []
+        for i in range(first, first + n):
+            for j in (0, 2, 4):
+                out += [(f"{i}.conv.{j}.weight", (64, 64, 3, 3)), (f"{i}.conv.{j}.bias", (64,))]
+        return out
+
+    spec += blocks(3, 3)
+    for up, n in ((7, 3), (12, 3), (17, 1)):
+        spec += [(f"{up}.weight", (64, 64, 3, 3))] + blocks(up + 1, n)
+    return spec + [("19.weight", (3, 64, 3, 3)), ("19.bias", (3,))]
+
+
 def esrgan_new_to_old_arch(state):
     """RRDBNet.new_to_old_arch (RDRB.py:381-441): Real-ESRGAN / BSRGAN key names -> the module's own names.  A state dict
     already in the old layout is returned unchanged."""
