@@ -234,9 +234,10 @@ int ldx_plan_flops(ldx_engine* e, double* executed, double* shared);
  * enable = 2 keys the report by kernel class *and* op shape (tuning aid). */
 int ldx_profile(ldx_engine* e, int enable, int reset);
 int ldx_profile_report(ldx_engine* e, char* buf, int64_t cap);
-/* Capture the planned forward into a hipGraph for replay (0 = eager launches). */
+/* Capture the planned forward into a hipGraph for replay (0 = eager launches).  UNet and TAESD engines; every other engine accepts the call and
+ * keeps launching eagerly. */
 int ldx_set_graph_mode(ldx_engine* e, int enable);
-/* UNet engine: how many times a forward was captured into a hipGraph and how many times a captured graph was replayed since the engine was
+/* UNet and TAESD engines (0, 0 on every other): how many times a forward was captured into a hipGraph and how many times a captured graph was replayed since the engine was
  * created (a captured graph is tied to the pointers of the call that recorded it: a caller that alternates buffers re-captures instead of
  * replaying — sampling.CFGDenoiser stages such inputs through one persistent buffer per shape). */
 int ldx_graph_stats(ldx_engine* e, int64_t* captures, int64_t* replays);

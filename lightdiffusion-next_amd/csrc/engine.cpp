@@ -56,6 +56,7 @@ Engine::~Engine() {
     for (void* p : dev_allocs) (void)hipFree(p);
     cur.release();
     for (Plan& p : plan_cache) p.release();
+    if (cap_stream) (void)hipStreamDestroy(cap_stream);
     for (hipEvent_t ev : prof_events) (void)hipEventDestroy(ev);
 }
 
@@ -559,8 +560,8 @@ double Engine::algorithmic_flops() const { return steady_flops() + cur.flops_sha
 
 void Plan::release() {
     if (arena) (void)hipFree(arena);
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    arena = nullptr; graph_exec = nullptr;
+    arena = nullptr;
+    graph.release();
 }
 
 int Engine::build_plan(const PlanKey& key, const std::function<int()>& emit, bool zero_arena) {
@@ -582,7 +583,7 @@ int Engine::build_plan(const PlanKey& key, const std::function<int()>& emit, boo
     reset();
     if ((rc = emit())) return rc;
     cur.key = key;
-    cur.graph_valid = false; cur.warm = false;
+    cur.graph.reset();
     cur.kv_ptr = nullptr; cur.kv_epoch = 0;          // a fresh arena holds no projected context
     return LDX_OK;
 }
@@ -734,8 +735,47 @@ int Engine::exec_ops(hipStream_t ls, size_t op_begin, size_t op_end, int ctx_sel
 
 int Engine::run_planned(const PlanKey& key, const std::function<int()>& replan, const Bindings& b, hipStream_t st) {
     if (int rc = select_plan(key, st, replan)) return rc;
-    bind = b; prof_graph = false;
-    if (int rc = exec_ops(st)) return rc;
+    bind = b;
+    return run_bound(st);
+}
+
+// The current plan on this call's bindings.  A captured graph has the call's pointers and flags baked in, so it is replayed only for the bindings it was
+// captured with: once a call arrives with others (in ANY mode: the eager path records them in graph.b) that graph is never replayed again (round 3: a
+// stale graph was replayed after an eager call had moved the pointers).  A plan is captured only once the same (plan, bindings) have run eagerly: that
+// pass also makes the one-time hipFuncSetAttribute calls, which are illegal during capture.
+int Engine::run_bound(hipStream_t st, int ctx_sel) {
+    Plan::Graph& g = cur.graph;
+    const bool graphs = captures && graph_mode, same = g.b == bind;
+    if (!same) g.valid = false;
+    if (graphs && g.valid) {
+        HIP_OK(hipGraphLaunch(g.exec, st));
+        ++n_graph_replays;
+        return LDX_OK;
+    }
+    const bool capture = graphs && g.warm && same;
+    g.b = bind; g.warm = true;
+    prof_graph = capture;
+    if (!capture) {
+        if (int rc = exec_ops(st, 0, (size_t)-1, ctx_sel)) return rc;
+        return launch_status();
+    }
+    g.release();
+    if (!cap_stream) HIP_OK(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
+    // From here every way out ends the capture and destroys the graph it got; the executable is kept, valid and counted only once its first launch has
+    // succeeded.  After a failure the plan is as after an eager call: the next call with these bindings captures again.
+    int rc = exec_ops(cap_stream, 0, (size_t)-1, ctx_sel);
+    hipGraph_t graph = nullptr;
+    const char* what = "hipStreamEndCapture";
+    hipError_t err = hipStreamEndCapture(cap_stream, &graph);
+    if (!rc && err == hipSuccess) { what = "hipGraphInstantiate"; err = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0); }
+    if (graph) (void)hipGraphDestroy(graph);
+    if (!rc && err == hipSuccess) { what = "hipGraphLaunch"; err = hipGraphLaunch(g.exec, st); }
+    if (!rc && err != hipSuccess) { set_error(std::string(what) + ": " + hipGetErrorString(err)); rc = LDX_EHIP; }
+    if (rc) { g.release(); return rc; }
+    g.valid = true;
+    ++n_graph_captures;
     return launch_status();
 }
 

@@ -5,6 +5,7 @@
 #include <initializer_list>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -95,21 +96,19 @@ struct PlanKey {
     bool operator!=(const PlanKey& o) const { return !(*this == o); }
 };
 
-// The caller's buffers of one call, read by exec_ops.  Every field takes part in ==.
+// The caller's buffers of one call, read by exec_ops.  Pointers and ints alone, laid out without padding (the assertion below), so that == is the bytes':
+// a field added here takes part in it.
 struct Bindings {
-    const float *x = nullptr, *s = nullptr, *ctx = nullptr; float* out = nullptr; bool den = false; int xB = 0;
-    const float* cc = nullptr; int ccn = 0;       // UNet c_concat and its channels
-    const float* t = nullptr;                     // UNet: caller-supplied timestep indices (run(): t_idx)
-    bool ctxc = false;                            // UNet: context-cache mode (the ctx_only ops are left out)
+    const float *x = nullptr, *s = nullptr, *ctx = nullptr; float* out = nullptr; int den = 0, xB = 0;
+    const float *cc = nullptr, *t = nullptr;      // UNet: c_concat; caller-supplied timestep indices (run(): t_idx)
+    int ccn = 0, ctxc = 0;                        // UNet: channels of c_concat; context-cache mode (the ctx_only ops are left out)
     const int* ids = nullptr; float* out2 = nullptr; const float* bias = nullptr;       // CLIP / T5
-    const float* extra = nullptr; int n_extra = 0;                                        // CLIP: textual-inversion rows for ids >= vocab_size (T5: none)
+    const float* extra = nullptr;                                                         // CLIP: textual-inversion rows for ids >= vocab_size (T5: none) ...
     const float *y = nullptr, *guid = nullptr, *pe_cos = nullptr, *pe_sin = nullptr;     // Flux
-    uint8_t* out8 = nullptr; int flux = 0;                                                // TAESD: the 8-bit preview and its channel order
-    bool operator==(const Bindings& o) const {
-        return x == o.x && s == o.s && ctx == o.ctx && out == o.out && den == o.den && xB == o.xB && cc == o.cc && ccn == o.ccn && t == o.t &&
-               ctxc == o.ctxc && ids == o.ids && out2 == o.out2 && bias == o.bias && extra == o.extra && n_extra == o.n_extra && y == o.y && guid == o.guid && pe_cos == o.pe_cos && pe_sin == o.pe_sin && out8 == o.out8 && flux == o.flux;
-    }
+    uint8_t* out8 = nullptr; int n_extra = 0, flux = 0;                                   // ... and their number; TAESD: the 8-bit preview and its channel order
+    bool operator==(const Bindings& o) const { return memcmp(this, &o, sizeof(Bindings)) == 0; }
 };
+static_assert(std::has_unique_object_representations_v<Bindings>, "Bindings: a bool, a float or padding would make == compare bytes that are no value");
 
 // Everything that belongs to one planned input shape: the launch list over one activation arena, the buffers inside that arena and the graph
 // captured from it.  Plans move as a whole (Engine::cur <-> Engine::plan_cache); release() frees what a plan owns.
@@ -127,9 +126,15 @@ struct Plan {
     float *d_temb_out = nullptr, *d_e1 = nullptr, *d_e2 = nullptr, *d_emb_all = nullptr, *d_eps = nullptr;
     const void* kv_ptr = nullptr; uint64_t kv_epoch = 0;       // context cache: what the kvall buffer holds
     hipStream_t kv_stream = nullptr;                            // ... and the stream whose order it was filled in: a call on another stream refills (no cross-stream dependency is assumed)
-    hipGraphExec_t graph_exec = nullptr;
-    bool graph_valid = false, warm = false;
-    Bindings graph_b;                      // the bindings of the last eager pass: what a graph captured now has baked in
+    // The graph captured from the plan (Engine::run_bound).  b: the bindings of the last eager or capturing pass, what a graph captured now has baked in;
+    // warm: that pass has happened; valid: exec was captured with b and has been launched once
+    struct Graph {
+        hipGraphExec_t exec = nullptr;
+        bool valid = false, warm = false;
+        Bindings b;
+        void reset() { valid = false; warm = false; }          // a new plan: nothing has run, nothing may be replayed
+        void release() { if (exec) (void)hipGraphExecDestroy(exec); exec = nullptr; valid = false; }
+    } graph;
     // Flux: buffers inside the arena, first-block-cache buffers and op ranges ([0, fb_a_end) through double block 0, [fb_a_end, fb_b_end) the rest)
     float *fx_temb = nullptr, *fx_gemb = nullptr, *fx_h1 = nullptr, *fx_vec = nullptr, *fx_svec = nullptr, *fx_mod = nullptr, *fx_tok = nullptr;
     void *fb_s0 = nullptr, *fb_s1 = nullptr, *fb_x = nullptr; float *fb_first = nullptr, *fb_res = nullptr, *fb_part = nullptr;
@@ -161,7 +166,9 @@ class Engine {
 public:
     static constexpr const char* model = "valid";
     // keep_plans: plans of other input shapes stay in plan_cache (UNet, Flux); otherwise a new shape re-plans into the current plan
-    Engine(int dev, int compute_dtype, bool keep_plans) : device(dev), dt(compute_dtype == LDX_F16 ? DT_F16 : DT_BF16), keep_plans(keep_plans) {}
+    // captures: graph_mode captures and replays this model's plans (UNet, TAESD); the other models accept the mode and ignore it
+    Engine(int dev, int compute_dtype, bool keep_plans, bool captures = false)
+        : device(dev), dt(compute_dtype == LDX_F16 ? DT_F16 : DT_BF16), captures(captures), keep_plans(keep_plans) {}
     virtual ~Engine();
     Engine(const Engine&) = delete;
     Engine& operator=(const Engine&) = delete;
@@ -238,8 +245,12 @@ protected:
     int exec_ops(hipStream_t ls, size_t op_begin = 0, size_t op_end = (size_t)-1, int ctx_sel = 0);      // ctx_sel: 0 all ops, 1 skip ctx_only ops, 2 ONLY ctx_only ops
     int launch_op(const Op& o, hipStream_t ls);           // the op's launcher on its argument struct, with this call's pointers (bind) filled in
     std::string prof_key(const Op& o) const;              // profile label of an op (prof_detail: with its shape)
-    // the common tail of the calls that keep one plan and run it whole: make the plan of `key` current, bind the call's buffers, launch
+    // the calls that keep one plan and run it whole: make the plan of `key` current, bind the call's buffers, run_bound
     int run_planned(const PlanKey& key, const std::function<int()>& replan, const Bindings& b, hipStream_t st);
+    // the tail of every such call: the current plan on `bind`, as a graph replay, a capture or eager launches (ctx_sel: exec_ops')
+    int run_bound(hipStream_t st, int ctx_sel = 0);
+    const bool captures;
+    hipStream_t cap_stream = nullptr;                     // graph capture; made by the first one
     Bindings bind;                                        // this call's
     std::vector<hipEvent_t> prof_events;
     bool prof_graph = false;
@@ -342,7 +353,6 @@ private:
     void emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act ctx16, int Mc, int Bshare = 0, const std::vector<DupReq>* dups = nullptr);
     void op_dup(const Act& a, int rows);          // rows [0, rows) of view a -> rows [rows, 2 rows)
     void dup_second_half(const DupReq& d);        // the producer's dual store (GemmArgs / RowGemmArgs::dup_rows) where it has one, else op_dup
-    hipStream_t cap_stream = nullptr;     // graph capture
 };
 
 class VaeEngine final : public Engine {
@@ -416,8 +426,7 @@ struct TaesdBlockW { LinearW c[3]; };
 class TaesdEngine final : public Engine {
 public:
     static constexpr const char* model = "TAESD";
-    TaesdEngine(const ldx_taesd_config& c, int dev) : Engine(dev, c.compute_dtype, false), cfg(c) {}
-    ~TaesdEngine() override;
+    TaesdEngine(const ldx_taesd_config& c, int dev) : Engine(dev, c.compute_dtype, false, true), cfg(c) {}
     int validate() const;
     int finalize() override;
     int run(const float* z, int B, int h, int w, float* out_f32, uint8_t* out_u8, int flux, hipStream_t st);
@@ -427,7 +436,6 @@ private:
     LinearW ta_first, ta_last, ta_up[3]; TaesdBlockW ta_blocks[10];
     bool mk_conv64(const std::string& pre, int Cout, int Cin, bool bias, LinearW& out);
     int plan(int B, int h, int w);
-    hipStream_t cap_stream = nullptr;     // graph capture
 };
 
 class FluxEngine final : public Engine {

@@ -15,11 +15,6 @@
 
 namespace ldx {
 
-TaesdEngine::~TaesdEngine() {
-    (void)hipSetDevice(device);
-    if (cap_stream) (void)hipStreamDestroy(cap_stream);
-}
-
 int TaesdEngine::validate() const {
     if (cfg.latent_channels != 4) { set_error("unsupported TAESD config: latent_channels must be 4 (taesd_preview cuts or pads every latent to 4 channels, taesd.py:268-277)"); return LDX_EINVAL; }
     return LDX_OK;
@@ -113,41 +108,10 @@ int TaesdEngine::run(const float* z, int B, int h, int w, float* out_f32, uint8_
     if (!z || (!out_f32 && !out_u8) || B <= 0 || h <= 0 || w <= 0 || (long)B * h * w * 64 >= (1L << 31)) {
         set_error("ldx_taesd_decode: bad argument (null latent, no output, or 64 * B * h * w >= 2^31)"); return LDX_EINVAL; }
     HIP_OK(hipSetDevice(device));
-    if (int rc = select_plan(PlanKey{B, h, w}, st, [&] { return plan(B, h, w); })) return rc;
-    bind = Bindings{};
-    bind.x = z; bind.out = out_f32; bind.out8 = out_u8; bind.flux = flux ? 1 : 0;
-    // Graph mode, as the UNet runs it (engine_unet.cpp): a captured graph has the call's pointers and the flux flag baked in, so it is replayed only for the
-    // bindings it was captured with, and captured only once the same (plan, bindings) have run eagerly (that pass makes the one-time hipFuncSetAttribute
-    // calls, which are illegal during capture).  A caller that wants replays keeps its latent and output buffers (TAESDEngine does in graph mode).
-    const bool same = cur.graph_b == bind;
-    if (!same) cur.graph_valid = false;
-    if (graph_mode && cur.graph_valid && same) {
-        HIP_OK(hipGraphLaunch(cur.graph_exec, st));
-        ++n_graph_replays;
-        return LDX_OK;
-    }
-    const bool use_graph = graph_mode && cur.warm && same;
-    cur.graph_b = bind; cur.warm = true;
-    hipStream_t ls = st;
-    if (use_graph) {
-        if (cur.graph_exec) { (void)hipGraphExecDestroy(cur.graph_exec); cur.graph_exec = nullptr; }
-        if (!cap_stream) HIP_OK(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-        HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
-        ls = cap_stream;
-    }
-    prof_graph = use_graph;
-    if (int rc = exec_ops(ls)) return rc;
-    if (use_graph) {
-        hipGraph_t g = nullptr;
-        HIP_OK(hipStreamEndCapture(cap_stream, &g));
-        HIP_OK(hipGraphInstantiate(&cur.graph_exec, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-        cur.graph_valid = true;
-        ++n_graph_captures;
-        HIP_OK(hipGraphLaunch(cur.graph_exec, st));
-    }
-    return launch_status();
+    // the call's three pointers and the flux flag are what a captured graph has baked in (Engine::run_bound): a caller that wants replays keeps its
+    // latent and output buffers (TAESDEngine does in graph mode)
+    Bindings b; b.x = z; b.out = out_f32; b.out8 = out_u8; b.flux = flux ? 1 : 0;
+    return run_planned(PlanKey{B, h, w}, [&] { return plan(B, h, w); }, b, st);
 }
 
 }  // namespace ldx

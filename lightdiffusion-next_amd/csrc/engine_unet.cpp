@@ -15,13 +15,12 @@
 
 namespace ldx {
 
-UNetEngine::UNetEngine(const ldx_unet_config& c, int dev) : Engine(dev, c.compute_dtype, true), cfg(c) {
+UNetEngine::UNetEngine(const ldx_unet_config& c, int dev) : Engine(dev, c.compute_dtype, true, true), cfg(c) {
     cfg_share = getenv("LDX_CFG_SHARE") ? atoi(getenv("LDX_CFG_SHARE")) : 1;      // 0 off, 1 where it pays (share_for), 2 whenever possible
 }
 UNetEngine::~UNetEngine() {
     (void)hipSetDevice(device);
     if (d_sigma_cfg) (void)hipFree(d_sigma_cfg);
-    if (cap_stream) (void)hipStreamDestroy(cap_stream);
 }
 
 int UNetEngine::validate() const {
@@ -661,45 +660,11 @@ int UNetEngine::run(const float* x, const float* sigma_or_t, const float* ctx, i
     // context cache: the ctx_only ops run here, eagerly, only when this plan's buffers do not hold the projections of (ctx, epoch) yet; every
     // other op (and the captured graph) then leaves them out
     if (bind.ctxc && !(cur.kv_ptr == ctx && cur.kv_epoch == ctx_epoch && cur.kv_stream == st)) {
-        const bool pg = prof_graph; prof_graph = false;
-        const int rc = exec_ops(st, 0, (size_t)-1, 2);
-        prof_graph = pg;
-        if (rc) return rc;
+        prof_graph = false;
+        if (int rc = exec_ops(st, 0, (size_t)-1, 2)) return rc;
         cur.kv_ptr = ctx; cur.kv_epoch = ctx_epoch; cur.kv_stream = st;
     }
-    const bool same = cur.graph_b == bind;
-    // a captured graph has its pointers baked in: once a call arrives with other bindings (in ANY mode — the eager path below re-records
-    // graph_b), that graph must never be replayed against the new graph_b (round 3: a stale graph was replayed after an eager call had moved them)
-    if (!same) cur.graph_valid = false;
-    if (graph_mode && cur.graph_valid && same) {
-        HIP_OK(hipGraphLaunch(cur.graph_exec, st));
-        ++n_graph_replays;
-        return LDX_OK;
-    }
-    // capture only once the same (plan, pointers) have been run eagerly before: the first eager pass
-    // also performs the one-time hipFuncSetAttribute calls, which are illegal during capture.
-    const bool use_graph = graph_mode && cur.warm && same;
-    cur.graph_b = bind; cur.warm = true;
-    hipStream_t ls = st;
-    if (use_graph) {
-        if (cur.graph_exec) { (void)hipGraphExecDestroy(cur.graph_exec); cur.graph_exec = nullptr; }
-        if (!cap_stream) HIP_OK(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-        HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
-        ls = cap_stream;
-    }
-    prof_graph = use_graph;
-    { int rc = exec_ops(ls, 0, (size_t)-1, bind.ctxc ? 1 : 0); if (rc) return rc; }
-    if (use_graph) {
-        hipGraph_t g = nullptr;
-        HIP_OK(hipStreamEndCapture(cap_stream, &g));
-        HIP_OK(hipGraphInstantiate(&cur.graph_exec, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-        cur.graph_valid = true;
-        ++n_graph_captures;
-        HIP_OK(hipGraphLaunch(cur.graph_exec, st));
-    }
-    return launch_status();
+    return run_bound(st, bind.ctxc ? 1 : 0);
 }
 
 }  // namespace ldx

@@ -161,7 +161,20 @@ def _encode_token_weights(token_weight_pairs, empty_tokens, encode):
     return (out[-1:] if not output else torch.cat(output, dim=-2)), second
 
 
-class UNetEngine(_Engine):
+class _GraphMode:
+    """The hipGraph mode of the two engines that have one (UNetEngine, TAESDEngine); the native engines of the other models ignore ldx_set_graph_mode."""
+
+    def set_graph_mode(self, on: bool):
+        lib.check(self._lib.ldx_set_graph_mode(self._h, int(on)), "ldx_set_graph_mode")
+
+    def graph_stats(self):
+        """(captures, replays) of the engine's hipGraph path since it was created."""
+        c, r = C.c_int64(0), C.c_int64(0)
+        lib.check(self._lib.ldx_graph_stats(self._h, C.byref(c), C.byref(r)), "ldx_graph_stats")
+        return int(c.value), int(r.value)
+
+
+class UNetEngine(_GraphMode, _Engine):
     def __init__(self, cfg: UNetConfig, state_dict, device: int = 0, dtype: str = "bf16", graph: bool = False):
         super().__init__(cfg, device)
         self.dtype = dtype
@@ -203,9 +216,6 @@ class UNetEngine(_Engine):
         lib.check(self._lib.ldx_weights_digest(self._h, C.byref(d)), "ldx_weights_digest")
         return int(d.value)
 
-    def set_graph_mode(self, on: bool):
-        lib.check(self._lib.ldx_set_graph_mode(self._h, int(on)), "ldx_set_graph_mode")
-
     def set_context_cache(self, on: bool = True):
         """ldx_unet_context_cache: promise that a ctx buffer's contents stay put until the next call of this method (which invalidates the cache)."""
         lib.check(self._lib.ldx_unet_context_cache(self._h, int(on)), "ldx_unet_context_cache")
@@ -220,12 +230,6 @@ class UNetEngine(_Engine):
         # fresh tensor per step (the hook) may get the address of the previous one back from the allocator, with other contents
         if bool(cached) != getattr(self, "_ctx_cached", False):
             self.set_context_cache(cached)
-
-    def graph_stats(self):
-        """(captures, replays) of the engine's hipGraph path since it was created."""
-        c, r = C.c_int64(0), C.c_int64(0)
-        lib.check(self._lib.ldx_graph_stats(self._h, C.byref(c), C.byref(r)), "ldx_graph_stats")
-        return int(c.value), int(r.value)
 
     def timestep_index(self, sigma):
         """ModelSamplingDiscrete.timestep (sample/sampling.py:309-320) with the reference's own torch expression on the HOST: integer work, so it has to be
@@ -508,7 +512,7 @@ class ESRGANEngine(_Engine):
         return torch.cat(outs, 0)
 
 
-class TAESDEngine(_Engine):
+class TAESDEngine(_GraphMode, _Engine):
     """The tiny autoencoder's decoder (src/AutoEncoders/taesd.py): TAESD.decode and the tensor part of taesd_preview, the sampler loops' latent preview.
     state_dict: Decoder2's own keys (weights.taesd_decoder_state_dict_spec; include/vae_approx/taesd_decoder.safetensors as it is).
     graph=True: the 36 launches of a shape are captured into a hipGraph on the second call and replayed from the third.  A captured graph has its pointers
@@ -525,14 +529,8 @@ class TAESDEngine(_Engine):
         self.set_graph_mode(graph)
 
     def set_graph_mode(self, on: bool):
-        lib.check(self._lib.ldx_set_graph_mode(self._h, int(on)), "ldx_set_graph_mode")
-        self._graph, self._static = bool(on), {}
-
-    def graph_stats(self):
-        """(captures, replays) of the engine's hipGraph path since it was created."""
-        c, r = C.c_int64(0), C.c_int64(0)
-        lib.check(self._lib.ldx_graph_stats(self._h, C.byref(c), C.byref(r)), "ldx_graph_stats")
-        return int(c.value), int(r.value)
+        super().set_graph_mode(on)
+        self._graph, self._static = bool(on), {}          # buffers kept for another mode's calls are dropped
 
     def _latent(self, x):
         """taesd_preview's channel rule (taesd.py:268-277): more than 4 channels are cut, fewer are zero-padded."""

@@ -38,12 +38,7 @@ def host(ldx_lib):
         H = T.Host()
     finally:
         T.HOST_LIB = orig
-    W = H.ldx.weights
-    c = H.ldx.lib.ldx_taesd_config()
-    c.compute_dtype, c.latent_channels = 0, 4
-    h = C.c_void_p()
-    H.check(H.L.ldx_taesd_create(C.byref(c), 0, C.byref(h)), "ldx_taesd_create")
-    H.load(h, W.synth_state_dict(W.taesd_decoder_state_dict_spec(), dtype=torch.float32))
+    h, _ = T._engine(H, ("taesd", "tiny", "bf16", "build", 0, 0, 0, 0, 0))
     H.check(H.L.ldx_finalize(h), "ldx_finalize")
     others = {}
     for model in OTHERS:

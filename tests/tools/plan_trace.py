@@ -143,9 +143,10 @@ def build_host():
     if not os.path.exists(kernel_resources.LIB):
         subprocess.run(["make", "-C", CSRC, "-j8"], check=True, capture_output=True)
     subprocess.run(["make", "-C", CSRC, "host", "-j8"], check=True, capture_output=True)
-    libs = (kernel_resources.LIB, os.path.join(os.path.dirname(kernel_resources.LIB), "libldx_pack.so"))      # the load-time packers' kernels are in the second
+    # the load-time packers' kernels are in the second, the TAESD decoder's in the third
+    libs = (kernel_resources.LIB,) + tuple(os.path.join(os.path.dirname(kernel_resources.LIB), n) for n in ("libldx_pack.so", "libldx_taesd.so"))
     if not os.path.exists(ARG_SIZES) or os.path.getmtime(ARG_SIZES) < max(map(os.path.getmtime, libs)):
-        sizes = dict(kernel_arg_sizes(libs[1]), **kernel_arg_sizes(libs[0]))
+        sizes = dict(kernel_arg_sizes(libs[2]), **dict(kernel_arg_sizes(libs[1]), **kernel_arg_sizes(libs[0])))
         with open(ARG_SIZES, "w") as f:
             f.write("".join(f"{k} {' '.join(map(str, v))}\n" for k, v in sorted(sizes.items())))
 
@@ -258,6 +259,12 @@ def _engine(H, row):
         c = _struct(ldx.lib.ldx_esrgan_config, dt, in_nc=cfg.in_nc, out_nc=cfg.out_nc, nf=cfg.nf, gc=cfg.gc, num_blocks=cfg.num_blocks, num_upscale=2)
         H.check(L.ldx_esrgan_create(C.byref(c), 0, C.byref(h)), "ldx_esrgan_create")
         H.load(h, W.synth_state_dict(W.esrgan_state_dict_spec(cfg)))
+    elif model == "taesd":
+        import torch
+        cfg = None
+        c = _struct(ldx.lib.ldx_taesd_config, dt, latent_channels=4)
+        H.check(L.ldx_taesd_create(C.byref(c), 0, C.byref(h)), "ldx_taesd_create")
+        H.load(h, W.synth_state_dict(W.taesd_decoder_state_dict_spec(), dtype=torch.float32))
     else:
         cfg = W.FluxConfig.tiny() if net == "tiny" else W.FluxConfig(**FLUX256)
         c = _struct(ldx.lib.ldx_flux_config, dt, in_channels=cfg.in_channels, vec_in_dim=cfg.vec_in_dim, context_in_dim=cfg.context_in_dim, hidden_size=cfg.hidden_size,
