@@ -392,6 +392,35 @@ int ldx_image_composite(uint8_t* canvas, int64_t canvas_pitch, int H, int W, int
 /* img [H][W][C]: every byte of the rectangle (x0, y0, w, h) = value (ImageDraw.rectangle / Image.new for the tile masks, :471,514-518). */
 int ldx_image_fill_rect(uint8_t* img, int64_t pitch, int H, int W, int C, int x0, int y0, int w, int h, int value, void* stream);
 
+/* ---- AutoHDR, the default post-effect of every pipeline exit (src/AutoHDR/ahdr.py:83-127, HDREffects.apply_hdr2) ------------------------- */
+/* What the reference does in PIL + LittleCMS + numpy after the VAE, on B HWC images of the device, C = 3.  Every step is an integer rule or a single
+ * float32 operation, so the results are the bytes of the numpy statement of the same rules (lightdiffusion-next_amd/hdr.py: autohdr_host), which
+ * differ from Pillow's in about one byte of 10^4 (tests/golden/autohdr.META.txt).  Stateless: every buffer is the caller's, nothing is allocated,
+ * nothing waits for the device; the launches are ordered on `stream` and can be captured in a graph.
+ *
+ * Tables: uint16 [33][33][33][4] (the fourth value is padding), 8-byte aligned, the first input channel on the first axis: what lcms's resampling
+ * optimisation makes of an 8-bit transform (hdr.py: lcms_tables).  The read of input bytes (v0, v1, v2), per channel c:
+ *   a = 32 * 257 * v,  fx = a + (a + 0x7FFF) / 0xFFFF,  i0 = fx >> 16,  r = fx & 0xFFFF,  i1 = min(i0 + 1, 32);
+ * with the channels ordered by r, descending, node_0 = (i0, i0, i0) and node_k = node_k-1 with the k-th channel's coordinate raised to its i1,
+ *   rest = sum_k (T[node_k] - T[node_k-1]) * r_k + 0x8001,  out16 = T[node_0] + ((rest + (rest >> 16)) >> 16)  (signed 64-bit, arithmetic shifts),
+ *   out8 = (out16 * 65281 + 8388608) >> 24. */
+/* out [H][W][3] = the read of `table` at in [H][W][3]; pitches in bytes, >= W * 3. */
+int ldx_hdr_table(const uint8_t* in, int64_t in_pitch, int H, int W, const uint16_t* table, uint8_t* out, int64_t out_pitch, void* stream);
+/* Bytes of workspace the whole effect needs for B images of H x W (LDX_EINVAL, negative, for a shape it refuses: B > 65535, H * W > 16 843 009). */
+int64_t ldx_hdr_workspace_bytes(int B, int H, int W);
+/* The whole effect.  Input: in_f32 dense fp32 [B][H][W][3], quantised as tensor2pil does, (uint8) trunc(clamp(255.0f * v, 0, 255)), OR in_u8
+ * [B][H][W][3] with rows of in_pitch bytes and images H * in_pitch bytes apart; exactly one of the two is non-null.  Per image:
+ *   lab = read of fwd at the bytes;  lab.L = lum_lut[lab.L] (256 bytes; hdr.py: luminance_lut);  rgb = read of inv at lab;
+ *   grey(p) = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16  (Pillow's RGB -> L);  mean = (2 * sum grey(rgb) + n) / (2 n), n = H * W, in integers;
+ *   blend(deg, v, f) = t <= 0 ? 0 : t >= 255 ? 255 : trunc(t),  t = (float) deg + f * ((float) v - (float) deg) in float32, product rounded before the sum;
+ *   c = blend(mean, rgb, contrast_factor)  (ImageEnhance.Contrast, factor 1 + contrast);
+ *   o = blend(grey(c), c, color_factor)    (ImageEnhance.Color, factor 1 + enhance_color * 0.2).
+ * Output, each if non-null (at least one): out_u8 = o with rows of out_pitch bytes, images H * out_pitch apart; out_f32 dense = o / 255.0f, the
+ * correctly rounded quotient (pil2tensor).  The sum is a uint32: H * W <= 16 843 009.  workspace: ldx_hdr_workspace_bytes(B, H, W) bytes, 4-aligned. */
+int ldx_hdr_apply(const float* in_f32, const uint8_t* in_u8, int64_t in_pitch, int B, int H, int W, const uint16_t* fwd, const uint16_t* inv,
+                  const uint8_t* lum_lut, float contrast_factor, float color_factor, void* workspace, uint8_t* out_u8, int64_t out_pitch, float* out_f32,
+                  void* stream);
+
 /* ---- single-op entry points (parity tests call the kernels through these) ----------------------- */
 /* 16-bit tensors are device pointers to bf16/fp16 per `dtype`.  Layouts: see csrc/ldx_kernels.h. */
 int ldx_op_convert(const float* in_f32, void* out_16, int64_t n, int dtype, int to_f32, void* stream);

@@ -13,6 +13,8 @@ Layout:
   weights.py   SD1.5 state-dict layout + seeded synthetic weights (no checkpoints offline)
   checkpoint.py  load-time ingestion: checkpoint split, UNet layout sniffing, LoRA key maps + merge
   usdu.py      UltimateSDUpscale: the img2img tile redraw / seam fix, canvas on the device (ldx_image_* kernels -> libldx_image.so)
+  hdr.py       AutoHDR: the default post-effect after the VAE (LittleCMS Lab round trip as two 33^3 tables, luminance table, Pillow's contrast / colour
+               blends) on device images (ldx_hdr_* kernels -> libldx_hdr.so); autohdr_host is the same in numpy
 """
 from . import lib, weights  # noqa: F401
 from .engine import UNetEngine, UNetConfig, VAEDecoderEngine, CLIPTextEngine, FluxEngine, T5Engine, ESRGANEngine, TAESDEngine, bislerp, latent_upscale  # noqa: F401
@@ -20,6 +22,7 @@ VAEEngine = VAEDecoderEngine      # the same engine encodes when encoder.* weigh
 from .weights import VAEConfig, CLIPConfig, FluxConfig, T5Config, ESRGANConfig, TAESDConfig  # noqa: F401
 from .hook import LdxUNetPatch, LdxFluxPatch  # noqa: F401
 from . import prompt  # noqa: F401
-from . import sampling, parallel, checkpoint, usdu  # noqa: F401
+from . import sampling, parallel, checkpoint, usdu, hdr  # noqa: F401
 from .sampling import LatentPreviewer  # noqa: F401
 from .usdu import UltimateSDUpscale  # noqa: F401
+from .hdr import AutoHDR  # noqa: F401

@@ -205,6 +205,35 @@ int ldx_image_fill_rect(uint8_t* img, int64_t pitch, int H, int W, int C, int x0
     launch_image_fill(img + (int64_t)y0 * pitch + (int64_t)x0 * C, (long)pitch, h, w * C, value, (hipStream_t)stream);
     return check_launch("ldx_image_fill_rect");
 }
+// ---- AutoHDR (hdr.hip) -----------------------------------------------------------------------------------------------------------------------
+static bool hdr_shape_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= hdr_max_pixels(); }
+int64_t ldx_hdr_workspace_bytes(int B, int H, int W) {
+    if (!hdr_shape_ok(B, H, W)) { set_error("ldx_hdr_workspace_bytes: bad shape (1 <= B <= 65535, 1 <= H * W <= 16 843 009)"); return LDX_EINVAL; }
+    return hdr_workspace_bytes(B, H, W);
+}
+int ldx_hdr_table(const uint8_t* in, int64_t in_pitch, int H, int W, const uint16_t* table, uint8_t* out, int64_t out_pitch, void* stream) {
+    if (!image_ok(in, in_pitch, H, W, 3) || !image_ok(out, out_pitch, H, W, 3) || !table || (uintptr_t)table % 8) {
+        set_error("ldx_hdr_table: bad argument (null pointer, pitch < W * 3, table not 8-byte aligned)"); return LDX_EINVAL; }
+    launch_hdr_table(in, (long)in_pitch, out, (long)out_pitch, H, W, table, (hipStream_t)stream);
+    return check_launch("ldx_hdr_table");
+}
+int ldx_hdr_apply(const float* in_f32, const uint8_t* in_u8, int64_t in_pitch, int B, int H, int W, const uint16_t* fwd, const uint16_t* inv,
+                  const uint8_t* lum_lut, float contrast_factor, float color_factor, void* workspace, uint8_t* out_u8, int64_t out_pitch, float* out_f32,
+                  void* stream) {
+    const int64_t row = (int64_t)W * 3;
+    if (!hdr_shape_ok(B, H, W) || (in_f32 != nullptr) == (in_u8 != nullptr) || (in_u8 && in_pitch < row) || (!out_u8 && !out_f32) || (out_u8 && out_pitch < row) ||
+        !fwd || !inv || (uintptr_t)fwd % 8 || (uintptr_t)inv % 8 || !lum_lut || !workspace || (uintptr_t)workspace % 4 ||
+        !(contrast_factor == contrast_factor) || !(color_factor == color_factor)) {
+        set_error("ldx_hdr_apply: bad argument (1 <= B <= 65535, 1 <= H * W <= 16 843 009, exactly one input, at least one output, pitch < W * 3, "
+                  "tables not 8-byte aligned, workspace null or not 4-byte aligned, NaN factor)");
+        return LDX_EINVAL;
+    }
+    HdrArgs a{};
+    a.in_f32 = in_f32; a.in_u8 = in_u8; a.in_pitch = (long)in_pitch; a.B = B; a.H = H; a.W = W; a.fwd = fwd; a.inv = inv; a.lut = lum_lut;
+    a.f_contrast = contrast_factor; a.f_color = color_factor; a.workspace = workspace; a.out_u8 = out_u8; a.out_pitch = (long)out_pitch; a.out_f32 = out_f32;
+    launch_hdr_apply(a, (hipStream_t)stream);
+    return check_launch("ldx_hdr_apply");
+}
 int ldx_t5_create(const ldx_t5_config* cfg, int device, ldx_engine** out) { return create_engine<T5Engine>(cfg, device, out, __func__); }
 int ldx_t5_encode(ldx_engine* e, const int32_t* ids, int B, int L, const float* bias, float* out, void* stream) {
     GUARD_BEGIN

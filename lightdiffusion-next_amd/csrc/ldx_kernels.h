@@ -538,4 +538,23 @@ void launch_taesd_conv(const TaesdConvArgs& a, DType dt, hipStream_t s);
 struct TaesdPrepArgs { const float* z; void* out; int B, C; long HW; };
 void launch_taesd_prep(const TaesdPrepArgs& a, DType dt, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// AutoHDR (hdr.hip, libldx_hdr.so): the reference's default post-effect (src/AutoHDR/ahdr.py:83-127) on B HWC images; include/ldx.h states each rule.
+// Exactly one of in_f32 (dense [B][H][W][3]) and in_u8 (rows of in_pitch bytes, images H * in_pitch apart) is set; out_u8 (out_pitch likewise) and
+// out_f32 (dense) each if non-null.  fwd, inv: the two lcms tables, uint16 [33][33][33][4], 8-byte aligned; lut: the 256 luminance bytes.
+// The launchers take validated arguments (capi.cpp): pitches >= W * 3, H * W <= hdr_max_pixels(), workspace of hdr_workspace_bytes(B, H, W) bytes, 4-aligned.
+struct HdrArgs {
+    const float* in_f32; const uint8_t* in_u8; long in_pitch;
+    int B, H, W;
+    const uint16_t* fwd; const uint16_t* inv; const uint8_t* lut;
+    float f_contrast, f_color;
+    void* workspace;
+    uint8_t* out_u8; long out_pitch; float* out_f32;
+};
+constexpr long hdr_max_pixels() { return 0xFFFFFFFFL / 255; }      // the sum of an image's grey bytes is a uint32
+long hdr_workspace_bytes(int B, int H, int W);
+void launch_hdr_apply(const HdrArgs& a, hipStream_t s);
+// one table read of an HWC byte image: out = tetrahedral read of `table` at in
+void launch_hdr_table(const uint8_t* in, long in_pitch, uint8_t* out, long out_pitch, int H, int W, const uint16_t* table, hipStream_t s);
+
 }  // namespace ldx
