@@ -223,7 +223,9 @@ int ldx_plan_info(ldx_engine* e, int64_t* n_launches, double* flops, int64_t* ar
  * cross-attention for the prefix to end at (tests). */
 int ldx_unet_cfg_share(ldx_engine* e, int enable);
 /* FLOPs of the current plan as EXECUTED in steady state, and the part of ldx_plan_info's algorithmic count that the shared CFG prefix does not
- * execute (algorithmic = executed + shared).  Roofline fractions are quoted on the executed number. */
+ * execute.  algorithmic = executed + shared + what the phase form of the up convs leaves out: a nearest-2x upsample + 3x3 conv run as four 2 x 2 convs
+ * over the stored image executes 4/9 of the reference's arithmetic, and the other 5/9 stay in the algorithmic count only (no plan below the sizes
+ * where the form is taken has such a term; environment LDX_UPCONV_PHASE=0: none has).  Roofline fractions are quoted on the executed number. */
 int ldx_plan_flops(ldx_engine* e, double* executed, double* shared);
 /* Memory behaviour: an engine keeps the launch plan, arena and captured graph of its CURRENT input shape plus up to four earlier
  * shapes (the multi-scale samplers and HiresFix alternate between resolutions; Flux plans are per (B, h, w, prompt length)).  Each
@@ -503,6 +505,13 @@ int ldx_op_conv3x3(const void* X, int ldx, const void* W, int B, int Hin, int Wi
                    int stride, int Hout, int Wout, int resize_to_out, const float* bias,
                    const float* rowvec, int rowvec_ld, const void* R, int ldr, void* Y, int ldy,
                    int dtype, void* stream);
+/* Upsample1 (ResBlock.py:75-138: F.interpolate(nearest, x2) then conv3x3, pad 1) in PHASE form: output pixel (2 i + py, 2 j + px) sees a 2 x 2 neighbourhood of
+ * the stored image, so the op runs as four 2 x 2 convs, one per output parity, whose weights are sums of 1, 2 or 4 of the 3 x 3 taps (fp32 sums, rounded once):
+ * 4/9 of the arithmetic of ldx_op_conv3x3(resize_to_out = 1), which computes the same thing.  X [B][Hin][Win][ldx] and W9 — the packed 9-tap matrix
+ * [Cout][(ky * 3 + kx) * Cin + ci] that ldx_op_conv3x3 takes — in `dtype`, bias [Cout] fp32 (required), Y [B][2 Hin][2 Win][ldy].  The phase weights are derived
+ * into the single-op workspace on every call (one stream per device at a time, as for the split-K ops).  LDX_EINVAL where the form does not exist:
+ * Win % 16, Cin % 64 or Cout % 16 != 0.  The UNet engine derives the phase weights once and takes the form where it pays (LDX_UPCONV_PHASE=0: never). */
+int ldx_op_upconv2x(const void* X, int ldx, const void* W9, int B, int Hin, int Win, int Cin, int Cout, const float* bias, void* Y, int ldy, int dtype, void* stream);
 /* ResBlock1 tail (ResBlock.py:315-335) as ONE implicit GEMM: Y = conv3x3(X, W[:, :9*Cin]) + X2 W[:, 9*Cin:]^T + bias, i.e. conv2(h) +
  * skip_connection(x) with W = [Cout][ky][kx][Cin | Cin2] and the two biases summed; stride 1, pad 1, X2 rows = output rows. */
 int ldx_op_conv3x3_skip(const void* X, int ldx, const void* X2, int ldx2, int Cin2, const void* W, int B, int H, int Wd, int Cin, int Cout,

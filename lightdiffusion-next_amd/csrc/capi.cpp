@@ -635,6 +635,21 @@ int ldx_op_conv3x3(const void* X, int ldx_, const void* W, int B, int Hin, int W
     launch_gemm(g, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_conv3x3");
 }
+int ldx_op_upconv2x(const void* X, int ldx_, const void* W9, int B, int Hin, int Win, int Cin, int Cout, const float* bias, void* Y, int ldy, int dtype, void* stream) {
+    if (!X || !W9 || !Y || !bias || B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0 || ldx_ % 8 || ldx_ < Cin || ldy % 4 || ldy < Cout) {
+        set_error("ldx_op_upconv2x: bad argument (X, W9, bias, Y; ldx % 8, ldy % 4)"); return LDX_EINVAL; }
+    GemmArgs g{}, ph;
+    g.A = X; g.lda = ldx_; g.W = W9; g.M = B * 4 * Hin * Win; g.N = Cout; g.K = 9 * Cin; g.mode = 1;
+    g.Cin = Cin; g.Hin = Hin; g.Win = Win; g.Hout = g.Hv = 2 * Hin; g.Wout = g.Wv = 2 * Win; g.stride = 1; g.resize = 1;
+    g.bias = bias; g.rows_per_batch = g.Hout * g.Wout; g.C = Y; g.ldc = ldy;
+    if (!gemm_upconv_phase(g, false, &ph)) { set_error("ldx_op_upconv2x: no phase form for this shape (Win % 16, Cin % 64, Cout % 16)"); return LDX_EINVAL; }
+    void* wp = op_workspace((size_t)16 * Cout * Cin / 2);      // [4][Cout][4 Cin] 16-bit
+    if (!wp) { set_error("ldx_op_upconv2x: workspace allocation failed"); return LDX_EHIP; }
+    launch_up_phase(UpPhaseArgs{W9, wp, Cout, Cin, dtype_of(dtype)}, (hipStream_t)stream);
+    ph.W = wp; ph.up2x = 2;        // phase-major tiles, as the engine plans it
+    launch_gemm(ph, dtype_of(dtype), (hipStream_t)stream);
+    return check_launch("ldx_op_upconv2x");
+}
 int ldx_op_conv3x3_skip(const void* X, int ldx_, const void* X2, int ldx2, int Cin2, const void* W, int B, int H, int Wd, int Cin, int Cout,
                         const float* bias, void* Y, int ldy, int dtype, void* stream) {
     if (!X || !X2 || !W || !Y || Cin % 64 || Cin2 % 64 || ldx_ % 8 || ldx2 % 8 || B <= 0 || H <= 0 || Wd <= 0) {

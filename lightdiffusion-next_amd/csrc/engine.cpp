@@ -556,7 +556,7 @@ double Engine::steady_flops() const {
     return f;
 }
 // the reference's arithmetic for the same evaluation: what runs plus what the shared CFG prefix computes once instead of twice
-double Engine::algorithmic_flops() const { return steady_flops() + cur.flops_shared; }
+double Engine::algorithmic_flops() const { return steady_flops() + cur.flops_shared + cur.flops_up2x; }
 
 void Plan::release() {
     if (arena) (void)hipFree(arena);
@@ -567,7 +567,7 @@ void Plan::release() {
 int Engine::build_plan(const PlanKey& key, const std::function<int()>& emit, bool zero_arena) {
     auto reset = [&] {
         free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0;
-        cur.ops.clear(); cur.flops = 0; cur.flops_shared = 0; cur.prefix_end = 0;
+        cur.ops.clear(); cur.flops = 0; cur.flops_shared = 0; cur.flops_up2x = 0; cur.prefix_end = 0;
     };
     cur.key = PlanKey{};                  // no plan until the bound pass has completed
     reset();
@@ -688,7 +688,7 @@ std::string Engine::prof_key(const Op& o) const {
     std::string key = o.klabel[0] ? o.klabel : o.name;
     if (!prof_detail) return key;
     char sh[96] = "";
-    if (o.kind == OP_GEMM) snprintf(sh, sizeof(sh), " M%d N%d K%d sk%d%s", o.g.M, o.g.N, o.g.K, o.g.splitk, o.g.geglu ? " geglu" : "");
+    if (o.kind == OP_GEMM) snprintf(sh, sizeof(sh), " M%d N%d K%d sk%d%s", o.g.M, o.g.N, o.g.K, o.g.splitk, o.g.geglu ? " geglu" : o.g.up2x ? " up2x" : "");
     else if (o.kind == OP_ATTN) snprintf(sh, sizeof(sh), " B%d H%d N%d M%d D%d", o.at.B, o.at.H, o.at.Nq, o.at.Mk, o.at.D);
     else if (o.kind == OP_ATTN_MX) snprintf(sh, sizeof(sh), " B%d H%d N%d M%d D128", o.am.B, o.am.H, o.am.Nq, o.am.Mk);
     else if (o.kind == OP_GN) snprintf(sh, sizeof(sh), " B%d HW%d C%d", o.gn.B, o.gn.HW, o.gn.C);

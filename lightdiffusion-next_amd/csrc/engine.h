@@ -116,6 +116,7 @@ struct Plan {
     PlanKey key;
     std::vector<Op> ops;
     double flops = 0;
+    double flops_up2x = 0;                 // flops the plan does NOT execute because its up convs run in phase form (GemmArgs::up2x): 5/9 of their 9-tap arithmetic
     double flops_shared = 0;               // flops the plan does NOT execute because of the shared CFG prefix (the second half's copy of the prefix ops)
     size_t prefix_end = 0;                 // UNet: number of ops in front of the first cross-attention (they ran on `share` samples)
     void* arena = nullptr;
@@ -180,7 +181,7 @@ public:
     //     them every step only because a torch module has no notion of a sampling run) are then computed on the first evaluation of a (plan, ctx) only.
     //     Set by the UNet alone; here because the executor and the plan's counts leave the ctx_only ops out while it holds.
     bool ctx_cache = false;
-    double algorithmic_flops() const;                           // steady_flops() + flops_shared
+    double algorithmic_flops() const;                           // steady_flops() + flops_shared + flops_up2x
     double steady_flops() const;                                // algorithmic flops of one forward as executed in steady state (cached ops excluded)
     int64_t n_launches() const;
     int64_t n_graph_captures = 0, n_graph_replays = 0;      // ldx_graph_stats (tests: the sampler loops must replay, not re-capture)
@@ -341,6 +342,14 @@ private:
     //     launches) and the prep kernel gathers the row: three launches per forward gone.  LDX_EMB_TABLE=0 keeps the per-step launches.
     float* d_emb_table = nullptr;
     int build_emb_table();
+    // phase weights of the up convs that some plan runs in phase form (GemmArgs::up2x; weight_layout.h up_phase_group): derived from the packed 9-tap matrix when the
+    //     first such plan is built — never at finalize, never inside a stream capture (plans are built in front of it) — and again, in place, by refresh_commit: the
+    //     same contract as the table above, plans and captured graphs keep their pointers.  LDX_UPCONV_PHASE=0: every up conv stays a 9-tap op.
+    struct UpPhase { const void* w9; void* wp; int N, Cin; };
+    std::vector<UpPhase> up_phase;
+    int upconv_phase = 1;
+    int up_to_phase(const LinearW& w);                     // the op just emitted (an "up" conv) in phase form, where gemm_upconv_phase admits it
+    int derive_up_phase();                                 // every buffer of up_phase from its 9-tap matrix
     uint64_t ctx_epoch = 1;                // context cache: bumped whenever cached k|v projections stop being valid
     // share > 0 (ldx_unet_denoise_cfg*): the evaluation batch is [uncond x share ; cond x share] over ONE latent batch x [share] — everything in front of the
     // first cross-attention (conv_in, the ResBlocks / Downsamples / self-attention up to it) sees identical inputs in both halves and is planned on `share`

@@ -17,6 +17,7 @@ namespace ldx {
 
 UNetEngine::UNetEngine(const ldx_unet_config& c, int dev) : Engine(dev, c.compute_dtype, true, true), cfg(c) {
     cfg_share = getenv("LDX_CFG_SHARE") ? atoi(getenv("LDX_CFG_SHARE")) : 1;      // 0 off, 1 where it pays (share_for), 2 whenever possible
+    upconv_phase = getenv("LDX_UPCONV_PHASE") ? atoi(getenv("LDX_UPCONV_PHASE")) : 1;      // 0: every up conv stays a 9-tap op; 1 / 2: phase form, tiles phase-major / band-major (GemmArgs::up2x)
 }
 UNetEngine::~UNetEngine() {
     (void)hipSetDevice(device);
@@ -276,6 +277,7 @@ int UNetEngine::refresh_commit() {
     refreshing = false;                    // either way the refresh is over: the engine holds the new weights, or (validation failed) still the old ones
     if (rc) return rc;
     ++ctx_epoch;                           // cached k|v projections of the context were made with the old weights
+    if ((rc = derive_up_phase())) return rc;
     return build_emb_table();
 }
 
@@ -554,6 +556,7 @@ int UNetEngine::plan(int B2, int h, int w, int Mc, int share) {
                 const int Hn = Hs[lv - 1], Wn = Ws[lv - 1];       // output_shape = hs[-1].shape (unet.py:754)
                 Act u_out = target(++sub == nsub, B2 * Hn * Wn);
                 op_conv("up", x, B2, Hc, Wc, co, blk.up, 1, Hn, Wn, u_out, Act{});
+                if (int rc = up_to_phase(blk.up)) return rc;
                 release(x);
                 x = u_out; --lv;
             }
@@ -580,6 +583,44 @@ int UNetEngine::plan(int B2, int h, int w, int Mc, int share) {
         fuse_gn_rowgemm();
         return LDX_OK;
     });
+}
+
+// Upsample1 (ResBlock.py:75-138) as four 2 x 2 convs, one per output parity, over the stored image: 4/9 of the 9-tap op's MFMA work (GemmArgs::up2x).  Taken where
+// gemm_upconv_phase says the form exists and the planner may take it; everything else — odd sizes, where output_shape is no exact double, small levels that need split-K — keeps the op.
+int UNetEngine::up_to_phase(const LinearW& w) {
+    Op& o = cur.ops.back();
+    GemmArgs ph;
+    if (!upconv_phase || !gemm_upconv_phase(o.g, true, &ph)) return LDX_OK;
+    UpPhase* u = nullptr;
+    for (UpPhase& e : up_phase) if (e.w9 == w.w) u = &e;
+    if (!u) {
+        const size_t bytes = (size_t)16 * w.N * ph.Cin * 2;
+        void* p = nullptr;
+        HIP_OK(hipMalloc(&p, bytes));
+        dev_allocs.push_back(p);
+        weight_bytes += bytes;
+        up_phase.push_back({w.w, p, w.N, ph.Cin});
+        u = &up_phase.back();
+        launch_up_phase(UpPhaseArgs{u->w9, u->wp, u->N, u->Cin, dt}, nullptr);
+        HIP_OK(hipStreamSynchronize(nullptr));
+        HIP_OK(hipGetLastError());
+    }
+    ph.W = u->wp;
+    ph.up2x = upconv_phase >= 2 ? 1 : 2;         // the tile order: phase-major unless LDX_UPCONV_PHASE=2 asks for band-major (GemmArgs::up2x)
+    const double full = o.flops;
+    o.g = ph;
+    o.flops = full * 4.0 / 9.0;
+    o.bytes = 2.0 * ((double)(ph.M / 4) * ph.Cin + 16.0 * ph.N * ph.Cin + (double)ph.M * ph.N);
+    cur.flops -= full - o.flops;
+    cur.flops_up2x += full - o.flops;
+    return LDX_OK;
+}
+int UNetEngine::derive_up_phase() {
+    if (up_phase.empty()) return LDX_OK;
+    for (const UpPhase& u : up_phase) launch_up_phase(UpPhaseArgs{u.w9, u.wp, u.N, u.Cin, dt}, nullptr);
+    HIP_OK(hipStreamSynchronize(nullptr));
+    HIP_OK(hipGetLastError());
+    return LDX_OK;
 }
 
 // The 22 emb_layers outputs for EVERY timestep of the table (ldx_set_tables), by the same three skinny launches a forward would run on its B2 rows:

@@ -698,6 +698,7 @@ GemmPick gemm_pick(const GemmArgs& a, const GemmArgs* b) {
         return bn ? tile(p.f8 ? GF_PP2_MX : GF_PP2, 256, bn, 0) : tile(p.f8 ? GF_TILE2_MX : GF_TILE2, 128, 128);
     }
     if (a.M <= 0 || a.N <= 0) { p.launches = 0; return p; }
+    if (a.mode == 1 && a.up2x) return tile(GF_PP, 256, 160, 0);      // phase-form up conv (gemm_upconv_phase made the arguments): the one instantiation of gemm_pp.inc's MODE 2
     if (a.mode == 1 && conv_patch_ok(a)) return tile(GF_CONV_PATCH, CONV_PATCH_BM, a.N <= 16 ? 16 : a.N, 0);      // conv_patch.hip: narrow 3x3 convs with the input patch resident in LDS
     p.f8 = a.mode == 0 && a.f8;
     p.lnf = a.mode == 0 && !p.f8 && a.ln_c1;      // LayerNorm folded in (no split-K): the tile shapes a transformer block's q|k|v / q / GEGLU projections take
@@ -730,10 +731,27 @@ GemmPick gemm_pick(const GemmArgs& a, const GemmArgs* b) {
     return t.bm == 64 ? tile(GF_TILE, 64, 64) : tile(GF_TILE, 128, t.bn == 160 ? 160 : 128);
 }
 
+// The phase form of a nearest-2x upsample + 3x3 conv (ldx_kernels.h).  What it needs: an exact doubling of a stored image whose rows are whole 16-pixel blocks (the output
+// stage maps a 16-row block with one division), whole 16-column blocks, bias as the only epilogue operand, a 16-bit output and one K segment.  The planner (`planned`) also
+// leaves the 9-tap op alone where it was given K splits — few rows under a long K: the phase form has no split-K variant, and four phases of so few rows leave most CUs
+// idle (SD1.5 at 1024^2: the 16^2 -> 32^2 conv, M 2048 N 1280 sk3) — and where the ping-pong kernels are switched off or a tile is forced (LDX_PP=0, LDX_GEMM_TILE, LDX_SPLITK).
+bool gemm_upconv_phase(const GemmArgs& g, bool planned, GemmArgs* ph) {
+    if (g.mode != 1 || g.up2x || g.stride != 1 || g.pad0 || g.Hin <= 0 || g.Win <= 0 || g.Hout != 2 * g.Hin || g.Wout != 2 * g.Win || g.Hv != g.Hout || g.Wv != g.Wout || g.Win % 16) return false;
+    if (g.Cin <= 0 || g.Cin % BK || g.K != 9 * g.Cin || g.N % 16 || g.M <= 0 || g.M != (g.M / (g.Hout * g.Wout)) * g.Hout * g.Wout) return false;
+    if (!g.C || !g.bias || g.Cf || g.A2 || g.R || g.R2 || g.rowvec || g.gate || g.gn_partial || g.dup_rows || g.geglu || g.act || g.oscale != 0.f || g.C8 || g.f8 || g.ln_c1) return false;
+    if (planned && (g.splitk > 1 || !g_sw.pp || g_sw.tile || g_sw.splitk)) return false;
+    if (ph) {
+        *ph = g;
+        ph->up2x = 1; ph->K = 4 * g.Cin; ph->Hv = g.Hin; ph->Wv = g.Win; ph->resize = 0;
+        ph->splitk = 1; ph->ws = nullptr; ph->sk_count = nullptr;
+    }
+    return true;
+}
+
 // Planner query (GemmArgs::gn_partial): can the epilogue of the kernel gemm_pick gives `a` — or its split-K reduce launch — produce the consumer GroupNorm's
 // statistics?  LDX_GN_FUSE=0 switches the fusion off.
 int gemm_gn_fuse(GemmArgs& a, int HW, int G, int max_chunks) {
-    if (!g_sw.gn_fuse || a.f8 || a.C8 || a.geglu || a.ln_c1 || !a.C || G <= 0 || a.N % G || a.N % 4 || HW <= 0 || a.M % HW) return 0;
+    if (!g_sw.gn_fuse || a.f8 || a.C8 || a.geglu || a.ln_c1 || a.up2x || !a.C || G <= 0 || a.N % G || a.N % 4 || HW <= 0 || a.M % HW) return 0;
     GemmArgs t = a; t.gn_partial = nullptr;
     const GemmPick p = gemm_pick(t);
     const int cpg = a.N / G;

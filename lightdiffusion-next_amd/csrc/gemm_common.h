@@ -74,21 +74,29 @@ __device__ __forceinline__ void ln_exchange(const f32x4 (&lnacc)[MI], float* st,
 // Per element the same float operations in the same order as the general stage.  ev_*: the per-column operands in LDS (tile-relative columns);
 // rall: the tile's residuals, ALL requested at the top of gemm_epilogue (one exposed round trip instead of one per row group: a row group's half
 // microsecond of work hides nothing of a cold line's two).
-template <typename T, int MI, int NJ, bool HR, bool HG, bool HX>
+// PH (GemmArgs::up2x, compiled in for the ping-pong kernel's MODE 2 only): the rows are the pixels of the STORED image, M / 4 per phase, and row (b, i, j) of phase
+// (py, px) is stored at output row (b * 2 Hin + 2 i + py) * 2 Win + 2 j + px.  Win % 16 == 0, so a 16-row block lies in one image row: one division per block, and the
+// block's lanes are 2 ldc apart.
+template <typename T, int MI, int NJ, bool HR, bool HG, bool HX, bool PH = false>
 __device__ __forceinline__ void gemm_epilogue_lean(const GemmArgs& p, f32x4 (&acc)[MI][NJ], const int wrow0, const int wcol0, const int wcu, const int n0, const int l15,
-                                                   const float* ev_bias, const float* ev_rv, const float* ev_gt, const uint2 (&rall)[HR ? MI * NJ : 1]) {
+                                                   const float* ev_bias, const float* ev_rv, const float* ev_gt, const uint2 (&rall)[HR ? MI * NJ : 1], const int phase = 0) {
     T* __restrict__ Cp = (T*)p.C;
     const bool has_rv = HX && p.rowvec != nullptr, has_gt = HX && p.gate != nullptr, has_dup = HX && p.dup_rows != 0;
+    const int M = PH ? p.M >> 2 : p.M;
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
-        if (wrow0 + i * 16 >= p.M) {        // wave-uniform (M % 16 == 0): a row block past M
+        if (wrow0 + i * 16 >= M) {        // wave-uniform (M % 16 == 0): a row block past M
             if constexpr (HG) {
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
             continue;
         }
-        const long m = wrow0 + i * 16 + l15;
+        long m = wrow0 + i * 16 + l15;
+        if constexpr (PH) {
+            const int mb = wrow0 + i * 16, hw = p.Hin * p.Win, b = mb / hw, rem = mb - b * hw, iy = rem / p.Win, jx = rem - iy * p.Win + l15;
+            m = ((long)b * 2 * p.Hin + 2 * iy + (phase >> 1)) * (2 * p.Win) + 2 * jx + (phase & 1);
+        }
         T* const crow = Cp + m * p.ldc + wcol0;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -108,6 +116,19 @@ __device__ __forceinline__ void gemm_epilogue_lean(const GemmArgs& p, f32x4 (&ac
             if (has_dup) *(uint2*)(crow + p.dup_rows * p.ldc + 16 * j) = pk;
         }
     }
+}
+
+// The whole output stage of the phase-form up conv (gemm_pp.inc MODE 2): bias through LDS as in gemm_epilogue below, then the lean path with the row map.
+// gemm_upconv_phase (gemm.hip) admits nothing else: 16-bit output, bias, M / 4 and N multiples of 16, no other operand.
+template <typename T, int BM, int BN, int WM, int MI, int NJ>
+__device__ __forceinline__ void gemm_epilogue_up2x(const GemmArgs& p, f32x4 (&acc)[MI][NJ], const int m0, const int n0, const int wm, const int wn, const int l15, const int g4, const int phase) {
+    extern __shared__ __attribute__((aligned(16))) char smem_up[];
+    float* const ev_bias = (float*)(smem_up + 16384);
+    __syncthreads();            // every wave is past its last fragment read; no DMA is in flight
+    for (int t = threadIdx.x; t < BN; t += WM * 128) ev_bias[t] = n0 + t < p.N ? p.bias[n0 + t] : 0.f;
+    __syncthreads();
+    const uint2 none[1] = {make_uint2(0u, 0u)};
+    gemm_epilogue_lean<T, MI, NJ, false, false, false, true>(p, acc, m0 + wm * (BM / WM), n0 + wn * (BN / 2) + 4 * g4, n0 + wn * (BN / 2), n0, l15, ev_bias, nullptr, nullptr, none, phase);
 }
 
 // The same for the MX fp8 output (GemmArgs::C8; bias, optional tanh-GELU as a template parameter): a 32-column block = two adjacent 16-column tiles of

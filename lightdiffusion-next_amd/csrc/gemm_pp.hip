@@ -9,6 +9,7 @@ void launch_gemm_pp2_mx(const GemmArgs& a, const GemmArgs& b, int bn, DType dt, 
 #define LDX_PP_DECL(sfx) \
     void launch_pp_plain_##sfx(const GemmArgs& a, int bn, bool lnf, int S, hipStream_t s); \
     void launch_pp_conv_##sfx(const GemmArgs& a, int bn, int S, hipStream_t s); \
+    void launch_pp_up2x_##sfx(const GemmArgs& a, hipStream_t s); \
     void launch_pp2_narrow_##sfx(const GemmArgs& a, const GemmArgs& b, int bn, hipStream_t s); \
     void launch_pp2_wide_##sfx(const GemmArgs& a, const GemmArgs& b, int bn, hipStream_t s);
 LDX_PP_DECL(bf16)
@@ -17,6 +18,7 @@ LDX_PP_DECL(f16)
 
 void launch_gemm_pp(const GemmArgs& a, int bn, bool lnf, int S, DType dt, hipStream_t s) {
     if (a.mode == 0 && a.f8) { launch_gemm_pp_mx(a, bn, S, dt, s); return; }      // MX fp8 operands
+    if (a.mode == 1 && a.up2x) { if (dt == DT_BF16) launch_pp_up2x_bf16(a, s); else launch_pp_up2x_f16(a, s); return; }      // phase-form up conv: 256 x 160 only (gemm_pick)
     if (a.mode == 0) { if (dt == DT_BF16) launch_pp_plain_bf16(a, bn, lnf, S, s); else launch_pp_plain_f16(a, bn, lnf, S, s); }
     else { if (dt == DT_BF16) launch_pp_conv_bf16(a, bn, S, s); else launch_pp_conv_f16(a, bn, S, s); }
 }

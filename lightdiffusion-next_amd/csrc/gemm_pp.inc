@@ -30,8 +30,19 @@ constexpr int PP_LDS = PP_NSLOT * PP_HALF;
 // consecutive row dwords (even waves the A rows, odd waves the W rows; the two copies of each write identical bytes), so that every wave
 // still issues exactly LB instructions per W half-tile and the counted vmcnt holds.  Scale rows past M / N read whatever follows them
 // in the scale array (or zeros past its end): they only ever meet zero-filled operand rows of outputs that are not stored.
+//
+// MODE 2 (GemmArgs::up2x): the nearest-2x upsample + 3x3 conv as four 2 x 2 convs over the stored image, one per output parity (py, px), in one launch.  The loader, ring
+// and MFMA loop are MODE 1's; the tap walk is 2 x 2 from (oy - (1 - py), ox - (1 - px)), rows are the M / 4 pixels of the STORED image, and the launch has four times the
+// tile rows, each a (phase, row band) pair; the W panel of phase 2 py + px starts phase * N * K elements into the phase weights.  Two orders of the tile rows:
+//  * up2x = 2, phase-major (what the planner asks for): the grouped order below then hands an XCD row bands of ONE phase, so its L2 streams one of the four weight matrices;
+//  * up2x = 1, band-major: a band's four phases form one group of PP_GM = 4 tile rows and share their A rows in one XCD's L2, but every XCD streams all four matrices.
+// The weights are the larger operand: per launch the phase-major order fetches 0.71x / 0.76x of what the 9-tap op fetches (FETCH_SIZE, SD1.5 1024^2: 32^2 -> 64^2 C 1280 /
+// 64^2 -> 128^2 C 640), the band-major order 1.71x / 1.79x; the times are within 1.5 % of each other (profiles/upconv_phase/README.md).  The output stage maps a row back to
+// its pixel (gemm_epilogue_up2x).  A compile-time variant: a runtime branch in the tap walk put the tap state of MODE 1 into scratch.
 template <typename T, int MODE, int BN, bool LNF = false, bool F8 = false>
 __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int block) {
+    constexpr bool CONV = MODE != 0, PH = MODE == 2;
+    static_assert(!PH || (!LNF && !F8 && PP_GM == 4), "phase-form up conv: 16-bit operands; band-major order: a band's four phases form one tile-row group");
     constexpr int BM = 256, WM = 4, MI = 4, NJ = BN / 32, NJ0 = (NJ + 1) / 2, LB = (BN + 63) / 64;
     constexpr int OOB = (int)0x80000000;
     static_assert(!F8 || (MODE == 0 && !LNF && (BN <= 192 || BN == 224)), "MX fp8 ping-pong tiles: plain GEMM, scales in the W slot's tail");
@@ -50,7 +61,8 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int block)
     const int wm = wave >> 1, wn = wave & 1;
     const int l15 = lane & 15, g4 = lane >> 4;
 
-    const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM, ntiles = tiles_m * tiles_n;
+    const int M = PH ? p.M >> 2 : p.M;           // rows of one problem (PH: of one phase = the pixels of the stored images)
+    const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (PH ? 4 : 1) * ((M + BM - 1) / BM), ntiles = tiles_m * tiles_n;
     const int S = p.splitk > 1 ? p.splitk : 1;
     const int lin = xcd_remap(block, ntiles * S);
     const int bid = lin % ntiles, split = lin / ntiles;
@@ -59,7 +71,14 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int block)
     const int gsz = PP_GM * tiles_n, gi = bid / gsz, within = bid - gi * gsz;
     const int gm_eff = min(PP_GM, tiles_m - gi * PP_GM);
     const int tm = gi * PP_GM + within % gm_eff, tn = within / gm_eff;
-    const int m0 = tm * BM, n0 = tn * BN;
+    // PH: tile row tm of the launch -> (phase, row band).  up2x = 1: band-major, tm = 4 band + phase; up2x = 2: phase-major, tm = phase * bands + band
+    int phase = 0, band = tm;
+    if (PH) {
+        const int bands = tiles_m >> 2;
+        if (p.up2x == 2) { phase = tm / bands; band = tm - phase * bands; } else { phase = tm & 3; band = tm >> 2; }
+    }
+    const int py = phase >> 1, px = phase & 1;
+    const int m0 = band * BM, n0 = tn * BN;
     const int nk_all = (p.K + KE - 1) / KE;
     const int kt_begin = (int)((long)split * nk_all / S), kt_end = (int)((long)(split + 1) * nk_all / S);
     const int nk = kt_end - kt_begin;
@@ -69,19 +88,20 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int block)
     const int gchunk = (lane & 7) ^ (srow & 7);      // source chunk that belongs at LDS position lane & 7 of that row
     const char* __restrict__ Ap = (const char*)p.A;
     const char* __restrict__ Wp = (const char*)p.W;
-    const int hw = (MODE == 1) ? p.Hout * p.Wout : 1;
-    const int b0 = (MODE == 1) ? m0 / hw : 0;
+    const int wrow = PH ? p.Win : p.Wout;       // pixels per row of the image the GEMM rows walk
+    const int hw = CONV ? (PH ? p.Hin : p.Hout) * wrow : 1;
+    const int b0 = CONV ? m0 / hw : 0;
     const long img = (long)p.Hin * p.Win * p.lda;
     int row0 = 0;
-    if (MODE == 1) {
-        const int oy0 = (m0 - b0 * hw) / p.Wout;
+    if (CONV) {
+        const int oy0 = (m0 - b0 * hw) / wrow;
         row0 = max(oy0 * p.stride - (p.pad0 ? 0 : 1), 0);
         if (p.resize) row0 = min((int)floorf((float)row0 * ((float)p.Hin / (float)p.Hv)), p.Hin - 1);
     }
     const long a_base = (MODE == 0) ? (long)m0 * p.lda : (long)b0 * img + (long)row0 * p.Win * p.lda;
-    const long a_total = (MODE == 0) ? (long)(p.M - 1) * p.lda + p.K : ((long)(p.M / hw) * p.Hin * p.Win - 1) * p.lda + p.Cin;
+    const long a_total = (MODE == 0) ? (long)(p.M - 1) * p.lda + p.K : ((long)(M / hw) * p.Hin * p.Win - 1) * p.lda + p.Cin;
     const i32x4 rA = make_srd(Ap + a_base * ES, (a_total - a_base) * ES);
-    const i32x4 rW = make_srd(Wp + (long)n0 * p.K * ES, ((long)p.N * p.K - (long)n0 * p.K) * ES);
+    const i32x4 rW = make_srd(Wp + ((long)phase * p.N + n0) * p.K * ES, ((long)p.N * p.K - (long)n0 * p.K) * ES);
     // F8: this wave's scale stream (waves 0-3: 64 A rows each, waves 4-7: 64 W rows each)
     const bool sc_w = SX ? (wave & 1) : grp;
     const i32x4 rS = !F8 ? rA : sc_w ? make_srd(p.SW + n0, ((long)nk_all * p.sw_ld - n0) * 4) : make_srd(p.SA + m0, ((long)nk_all * p.sa_ld - m0) * 4);
@@ -95,17 +115,17 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int block)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int m = m0 + srow + 64 * j;
-        const bool ok = m < p.M;
+        const bool ok = m < M;
         if (MODE == 0) {
             a_voff[j] = ok ? ((srow + 64 * j) * p.lda + gchunk * CE) * ES : OOB;
             a_pix[j] = a_oy[j] = a_ox[j] = 0;
             a2_voff[j] = OOB;
         } else {
             const int b = m / hw, rem = m - b * hw;
-            const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
+            const int oy = rem / wrow, ox = rem - oy * wrow;
             a_pix[j] = ok ? (int)(((long)(b - b0) * img + gchunk * 8) * 2) : OOB;
-            a_oy[j] = oy * p.stride - (p.pad0 ? 0 : 1);
-            a_ox[j] = ox * p.stride - (p.pad0 ? 0 : 1);
+            a_oy[j] = PH ? oy - (1 - py) : oy * p.stride - (p.pad0 ? 0 : 1);
+            a_ox[j] = PH ? ox - (1 - px) : ox * p.stride - (p.pad0 ? 0 : 1);
             a_voff[j] = OOB;
             a2_voff[j] = (has_a2 && ok) ? ((srow + 64 * j) * p.lda2 + gchunk * 8) * 2 : OOB;
         }
@@ -135,13 +155,13 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int block)
 #pragma unroll
             for (int j = 0; j < 4; ++j) lds_dma16(rA, kdead ? OOB : a_voff[j], k0 * ES, dst + j * 8192);
         } else {
-            const bool seg2 = st_ky == 3;       // second input (GemmArgs::A2): a 10th "tap" over plain rows (wave-uniform)
+            const bool seg2 = !PH && st_ky == 3;       // second input (GemmArgs::A2): a 10th "tap" over plain rows (wave-uniform)
             if (st_new_tap) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     int iy = a_oy[j] + st_ky, ix = a_ox[j] + st_kx;
                     const bool ok = a_pix[j] != OOB && iy >= 0 && iy < p.Hv && ix >= 0 && ix < p.Wv;
-                    if (p.resize) {   // nearest: src = min(floor(dst * in/out), in-1)  (torch upsample_nearest)
+                    if (!PH && p.resize) {   // nearest: src = min(floor(dst * in/out), in-1)  (torch upsample_nearest)
                         iy = min((int)floorf((float)iy * rs_y), p.Hin - 1);
                         ix = min((int)floorf((float)ix * rs_x), p.Win - 1);
                     }
@@ -155,7 +175,7 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int block)
             for (int j = 0; j < 4; ++j) lds_dma16(rr, a_voff[j], soff, dst + j * 8192);
             st_ci += BK;
             st_new_tap = false;
-            if (!seg2 && st_ci >= p.Cin) { st_ci = 0; st_new_tap = true; if (++st_kx == 3) { st_kx = 0; ++st_ky; } }
+            if (!seg2 && st_ci >= p.Cin) { st_ci = 0; st_new_tap = true; if (++st_kx == (PH ? 2 : 3)) { st_kx = 0; ++st_ky; } }
         }
     };
     auto issue_w = [&](int kt, int slot) __attribute__((always_inline)) {
@@ -283,6 +303,8 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int block)
         __syncthreads();            // both wave groups are past their last fragment reads; no DMA is in flight (the loop ended on vmcnt(0))
         ln_exchange<MI, BM>(lnacc, (float*)smem, wm * 64, wn, l15, g4, p.K, p.ln_eps, ln1, ln2);
         gemm_epilogue<T, BM, BN, WM, MI, NJ, true>(p, acc, m0, n0, wm, wn, l15, g4, split, S, ln1, ln2);
+    } else if constexpr (PH) {
+        gemm_epilogue_up2x<T, BM, BN, WM, MI, NJ>(p, acc, m0, n0, wm, wn, l15, g4, phase);
     } else {
         gemm_epilogue<T, BM, BN, WM, MI, NJ, false, !F8>(p, acc, m0, n0, wm, wn, l15, g4, split, S);
     }
@@ -304,7 +326,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(const GemmArgs a, cons
 
 template <typename T, int MODE, int BN, bool LNF = false, bool F8 = false>
 static void launch_pp_inst(const GemmArgs& a, int S, hipStream_t s) {
-    const int tiles = ((a.M + 255) / 256) * ((a.N + BN - 1) / BN) * S;
+    const int tiles = (MODE == 2 ? 4 * ((a.M / 4 + 255) / 256) : (a.M + 255) / 256) * ((a.N + BN - 1) / BN) * S;      // MODE 2: four phases of M / 4 rows each
     static DevOnce once;
     set_dyn_lds(once, (const void*)gemm_pp_kernel<T, MODE, BN, LNF, F8>, PP_LDS);
     hipLaunchKernelGGL((gemm_pp_kernel<T, MODE, BN, LNF, F8>), dim3(tiles), dim3(512), PP_LDS, s, a);

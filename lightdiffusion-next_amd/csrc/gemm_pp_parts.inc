@@ -1,6 +1,6 @@
 // One sixth of the 16-bit ping-pong instantiations (gemm_pp.inc): included by gemm_pp_{bf16,f16}_{0,1,2}.hip, which define LDX_PP_T (element type),
 // LDX_PP_SFX (bf16 / f16) and LDX_PP_PART — 0: plain GEMMs incl. the LayerNorm-folded ones, 1: implicit-GEMM convs + the narrow two-problem launches,
-// 2: the wide two-problem launches.  As ONE translation unit these kernels took 700 s to compile (the output stage of gemm_common.h is instantiated in each of the
+// 2: the wide two-problem launches.  (The phase-form up conv, MODE 2, is instantiated in gemm_pp_up2x.hip: libldx_upconv.so.)  As ONE translation unit these kernels took 700 s to compile (the output stage of gemm_common.h is instantiated in each of the
 // 40 kernel bodies); as six they build in parallel with gemm.hip and gemm_pp_mx.hip (≈ 250 s each).  gemm_pp.hip keeps the dispatchers.
 #include "gemm_common.h"
 

@@ -85,7 +85,19 @@ struct GemmArgs {
     // (skip connections, the residual stream) is written for both halves by the producer — no copy launch, no re-read.
     long dup_rows;
     int ep_general;                // experiment switch (LDX_EP_GENERAL=1, set by launch_gemm): the general output stage for every epilogue (A/B against the lean paths of gemm_common.h)
+    // up2x != 0 (conv mode, stride 1; 1 / 2: tile rows band-major / phase-major, gemm_pp.inc): the nearest-2x upsample + 3x3 conv of Upsample1 in PHASE form.  Output pixel (2 i + py, 2 j + px) sees a 2 x 2 neighbourhood of the
+    // stored image, so the op is four 2 x 2 convs, one per output parity: W = the phase weights [4][N][4 * Cin] (weight_layout.h up_phase_group, derived from the packed
+    // 9-tap matrix), K = 4 * Cin, (Hin, Win) = (Hv, Wv) = the stored extent, (Hout, Wout) = twice that, M = B * Hout * Wout as for the 9-tap op.  One launch of the
+    // ping-pong kernel's MODE 2 covers the four phases; bias is the only epilogue operand.  gemm_upconv_phase() below builds these arguments from the 9-tap op's.
+    int up2x;
 };
+// Can the 9-tap conv `g` (as op_conv / ldx_op_conv3x3 build it, W still the packed 9-tap matrix) run in phase form?  Geometry (an exact x2 of a stored image whose rows
+// are whole 16-pixel blocks) and epilogue (bias only, 16-bit output, no split-K).  If so `*ph` = the phase-form arguments, but for W, which the caller points at the
+// phase weights and may ask for the phase-major tile order (up2x = 2).  planned: the planner's question — also no K splits chosen for the 9-tap op and no dispatch switch that takes the ping-pong kernels away.
+bool gemm_upconv_phase(const GemmArgs& g, bool planned, GemmArgs* ph);
+// The phase weights of one up conv: Wp[4][N][4 * Cin] from the packed 9-tap W9[N][9 * Cin] (both 16-bit, on the device); weight_layout.h up_phase_group
+struct UpPhaseArgs { const void* W9; void* Wp; int N, Cin; DType dt; };
+void launch_up_phase(const UpPhaseArgs& a, hipStream_t s);
 // Can launch_gemm(a) produce GroupNorm statistics for a consumer GroupNorm(G groups) over [B][HW][a.N]?  If yes, returns the number of
 // tile rows per batch image (the consumer's chunk count) and fills a.gn_* except gn_partial; 0 = not fusable (the GroupNorm runs its own pass).
 // It asks gemm_pick() below for the kernel and applies that kernel's epilogue conditions; launch_gemm() holds a set gn_partial to the same answer and aborts otherwise.

@@ -93,4 +93,28 @@ __host__ __device__ inline void ln_fold_row(const LnFoldArgs& p, size_t r) {
     p.c2[r] = (float)dadd_rn(s2, (double)(p.bias ? src_at(p.bias, p.bias_dt, sr) : 0.f));
 }
 
+// UpPhaseArgs: the phase weights of a nearest-2x upsample + 3x3 conv (GemmArgs::up2x), [phase = 2 py + px][N][(ty * 2 + tx) * Cin + ci].  Output pixel (2 i + py, 2 j + px)
+// reads the stored rows i - 1 + py + ty, ty = 0 / 1: at py = 0 they stand for the taps ky = {0} / {1, 2}, at py = 1 for ky = {0, 1} / {2}; columns alike.  An entry is the sum of
+// its 1, 2 or 4 taps of the packed 9-tap matrix [N][(ky * 3 + kx) * Cin + ci], added in fp32 in ascending (ky, kx) and rounded once.
+// up_phase_taps: the taps k0 .. k1 behind position t of parity par.  up_phase_group: elements (row, c) .. (row, c + 7) of the [4 * N][4 * Cin] buffer, Cin % 8 == 0.
+__host__ __device__ inline void up_phase_taps(int par, int t, int& k0, int& k1) { k0 = t ? 1 + par : 0; k1 = t ? 2 : par; }
+__host__ __device__ inline void up_phase_group(const UpPhaseArgs& p, size_t row, size_t c) {
+    const int phase = (int)(row / p.N), tap = (int)(c / p.Cin);
+    const size_t n = row % p.N, ci = c % p.Cin;
+    int ky0, ky1, kx0, kx1;
+    up_phase_taps(phase >> 1, tap >> 1, ky0, ky1);
+    up_phase_taps(phase & 1, tap & 1, kx0, kx1);
+    float acc[8];
+    for (int ky = ky0; ky <= ky1; ++ky)
+        for (int kx = kx0; kx <= kx1; ++kx) {
+            const uint16_t* src = (const uint16_t*)p.W9 + (n * 9 + ky * 3 + kx) * p.Cin + ci;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float v = from16(src[j], p.dt); acc[j] = (ky == ky0 && kx == kx0) ? v : add_rn(acc[j], v); }
+        }
+    uint16_t h[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) h[j] = to16(acc[j], p.dt);
+    store16s((uint16_t*)p.Wp + row * 4 * (size_t)p.Cin + c, h, 8);
+}
+
 }  // namespace ldx
