@@ -86,15 +86,16 @@ static unsigned* op_sk_counters() {
     }
     return buf[dev];
 }
+// what the argument builders (ldx_kernels.h) take scratch from here
+static const Scratch op_scratch{[](size_t bytes) -> void* { return op_workspace((bytes + 3) / 4); }, op_sk_counters};
 static int attach_splitk(GemmArgs& g) {
-    g.splitk = gemm_choose_splitk(g.M, g.N, g.K, g.geglu != 0);
-    if (g.splitk > 1) {
-        g.ws = op_workspace(gemm_sk_ws_floats(g.M, g.N, g.splitk));
-        if (!g.ws) { set_error("split-K workspace allocation failed"); return LDX_EHIP; }
-        g.sk_count = op_sk_counters();
-    }
+    gemm_attach_splitk(g, op_scratch);
+    if (g.splitk > 1 && !g.ws) { set_error("split-K workspace allocation failed"); return LDX_EHIP; }
     return LDX_OK;
 }
+// ... and operands that are only ever tested for being there and for their alignment (ldx_op_gemm_pick, ldx_op_attn_pick)
+alignas(16) static char pick_operand[16];
+static const Scratch pick_scratch{[](size_t) -> void* { return pick_operand; }, [] { return (unsigned*)pick_operand; }};
 
 extern "C" {
 
@@ -455,10 +456,9 @@ int ldx_op_convert(const float* in_f32, void* out_16, int64_t n, int dtype, int 
 int ldx_op_gemm(const void* A, int lda, const void* W, int M, int N, int K, const float* bias, const float* rowvec, int rowvec_ld,
                 int rows_per_batch, int geglu, const void* R, int ldr, void* C, int ldc, float* Cf, int ldcf, int dtype, void* stream) {
     if (!A || !W || M <= 0 || N <= 0 || K <= 0 || K % 8 || lda % 8 || (!C && !Cf)) { set_error("ldx_op_gemm: bad argument (K % 8, lda % 8)"); return LDX_EINVAL; }
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.W = W; g.M = M; g.N = N; g.K = K; g.mode = 0; g.bias = bias;
-    g.rowvec = rowvec; g.rowvec_ld = rowvec_ld; g.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1; g.geglu = geglu;
-    g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc; g.Cf = Cf; g.ldcf = ldcf;
+    GemmArgs g = gemm_linear_args(A, lda, W, M, N, K);
+    g.bias = bias; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld; if (rows_per_batch > 0) g.rows_per_batch = rows_per_batch;
+    g.geglu = geglu; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc; g.Cf = Cf; g.ldcf = ldcf;
     if (int rc = attach_splitk(g)) return rc;
     launch_gemm(g, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_gemm");
@@ -474,13 +474,11 @@ int ldx_op_layernorm_mx(const void* X, int ldx_, int rows, int C, float eps, con
 }
 int ldx_op_attention_mx(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O8, int ldo8, void* SO, int so_ld,
                         int B, int H, int Nq, int Mk, float scale, int dtype, void* stream) {
-    AttnArgs a{};
-    a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.B = B; a.H = H; a.Nq = Nq; a.Mk = Mk; a.D = 128; a.scale = scale;
+    AttnArgs a = attn_args(Q, ldq, K, ldk, V, ldv, nullptr, 0, B, H, Nq, Mk, 128, scale);
     a.O8 = O8; a.ldo8 = ldo8; a.SO = (uint32_t*)SO; a.so_ld = so_ld;
     if (!Q || !K || !V || !O8 || !SO || B <= 0 || H <= 0 || Nq <= 0 || Mk <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo8 % 16 || ldo8 < H * 128 || so_ld < B * Nq) {
         set_error("ldx_op_attention_mx: bad argument"); return LDX_EINVAL; }
-    if (attn_pipe_ok(a)) a.knorm_ws = op_workspace((size_t)B * H * ((Mk + 63) / 64));
-    if (!attn_pick(a).mx_out) { set_error("ldx_op_attention_mx: needs head dim 128 and at least 16 query blocks of 128 (B * H * ceil(Nq / 128))"); return LDX_EINVAL; }
+    if (!attn_attach_scratch(a, op_scratch).mx_out) { set_error("ldx_op_attention_mx: needs head dim 128 and at least 16 query blocks of 128 (B * H * ceil(Nq / 128))"); return LDX_EINVAL; }
     launch_attention(a, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_attention_mx");
 }
@@ -524,17 +522,10 @@ int ldx_op_gemm_mx(const void* A8, int lda, const void* SA, int sa_ld, const voi
         set_error("ldx_op_gemm_mx: bad argument (K % 128, lda % 16, sa_ld >= M, sw_ld >= N)"); return LDX_EINVAL; }
     if (C8 && (!SC || N % 128 || ldc8 % 16 || ldc8 < N || sc_ld < M || R || C || Cf)) {
         set_error("ldx_op_gemm_mx: MX output needs N % 128 == 0, ldc8 % 16 == 0, scales_ld >= M and no other output / residual"); return LDX_EINVAL; }
-    GemmArgs g{};
-    g.A = A8; g.lda = lda; g.W = W8; g.M = M; g.N = N; g.K = K; g.mode = 0; g.bias = bias; g.rows_per_batch = 1; g.act = act;
-    g.f8 = 1; g.SA = (const uint32_t*)SA; g.sa_ld = sa_ld; g.SW = (const uint32_t*)SW; g.sw_ld = sw_ld;
-    g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc; g.Cf = Cf; g.ldcf = ldcf;
-    g.C8 = C8; g.ldc8 = ldc8; g.c8_col = 0; g.SC = (uint32_t*)SC; g.sc_ld = sc_ld;
-    g.splitk = C8 ? 1 : gemm_choose_splitk(M, N, K / 2, false);
-    if (g.splitk > 1) {
-        g.ws = op_workspace(gemm_sk_ws_floats(M, N, g.splitk));
-        if (!g.ws) { set_error("split-K workspace allocation failed"); return LDX_EHIP; }
-        g.sk_count = op_sk_counters();
-    }
+    GemmArgs g = gemm_linear_args(A8, lda, W8, M, N, K);
+    gemm_mx_operands(g, (const uint32_t*)SA, sa_ld, W8, (const uint32_t*)SW, sw_ld);
+    g.bias = bias; g.act = act; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc; g.Cf = Cf; g.ldcf = ldcf; g.C8 = C8; g.ldc8 = ldc8; g.SC = (uint32_t*)SC; g.sc_ld = sc_ld;
+    if (int rc = attach_splitk(g)) return rc;
     launch_gemm(g, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_gemm_mx");
 }
@@ -542,9 +533,8 @@ int ldx_op_gemm2(const void* A1, int lda1, const void* W1, int M1, int N1, int K
                  const void* A2, int lda2, const void* W2, int M2, int N2, int K2, const float* bias2, void* C2, int ldc2, int dtype, void* stream) {
     if (!A1 || !W1 || !C1 || !A2 || !W2 || !C2 || M1 <= 0 || N1 <= 0 || K1 <= 0 || M2 <= 0 || N2 <= 0 || K2 <= 0 || K1 % 8 || K2 % 8 || lda1 % 8 || lda2 % 8) {
         set_error("ldx_op_gemm2: bad argument (K % 8, lda % 8)"); return LDX_EINVAL; }
-    GemmArgs a{}, b{};
-    a.A = A1; a.lda = lda1; a.W = W1; a.M = M1; a.N = N1; a.K = K1; a.bias = bias1; a.C = C1; a.ldc = ldc1; a.rows_per_batch = 1;
-    b.A = A2; b.lda = lda2; b.W = W2; b.M = M2; b.N = N2; b.K = K2; b.bias = bias2; b.C = C2; b.ldc = ldc2; b.rows_per_batch = 1;
+    GemmArgs a = gemm_linear_args(A1, lda1, W1, M1, N1, K1), b = gemm_linear_args(A2, lda2, W2, M2, N2, K2);
+    a.bias = bias1; a.C = C1; a.ldc = ldc1; b.bias = bias2; b.C = C2; b.ldc = ldc2;
     launch_gemm2(a, b, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_gemm2");
 }
@@ -555,11 +545,10 @@ int ldx_op_gemm2_mx(const void* A1, int lda1, const void* SA1, int sa_ld1, const
     if (!A1 || !W1 || !SA1 || !SW1 || !C1 || !A2 || !W2 || !SA2 || !SW2 || !C2 || M1 <= 0 || N1 <= 0 || K1 <= 0 || M2 <= 0 || N2 <= 0 || K2 <= 0 ||
         K1 % 128 || K2 % 128 || lda1 % 16 || lda2 % 16 || sa_ld1 < M1 || sw_ld1 < N1 || sa_ld2 < M2 || sw_ld2 < N2) {
         set_error("ldx_op_gemm2_mx: bad argument (K % 128, lda % 16, sa_ld >= M, sw_ld >= N)"); return LDX_EINVAL; }
-    GemmArgs a{}, b{};
-    a.A = A1; a.lda = lda1; a.W = W1; a.M = M1; a.N = N1; a.K = K1; a.bias = bias1; a.C = C1; a.ldc = ldc1; a.rows_per_batch = 1;
-    a.f8 = 1; a.SA = (const uint32_t*)SA1; a.sa_ld = sa_ld1; a.SW = (const uint32_t*)SW1; a.sw_ld = sw_ld1;
-    b.A = A2; b.lda = lda2; b.W = W2; b.M = M2; b.N = N2; b.K = K2; b.bias = bias2; b.C = C2; b.ldc = ldc2; b.rows_per_batch = 1;
-    b.f8 = 1; b.SA = (const uint32_t*)SA2; b.sa_ld = sa_ld2; b.SW = (const uint32_t*)SW2; b.sw_ld = sw_ld2;
+    GemmArgs a = gemm_linear_args(A1, lda1, W1, M1, N1, K1), b = gemm_linear_args(A2, lda2, W2, M2, N2, K2);
+    gemm_mx_operands(a, (const uint32_t*)SA1, sa_ld1, W1, (const uint32_t*)SW1, sw_ld1);
+    gemm_mx_operands(b, (const uint32_t*)SA2, sa_ld2, W2, (const uint32_t*)SW2, sw_ld2);
+    a.bias = bias1; a.C = C1; a.ldc = ldc1; b.bias = bias2; b.C = C2; b.ldc = ldc2;
     launch_gemm2(a, b, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_gemm2_mx");
 }
@@ -568,23 +557,17 @@ int ldx_op_gemm_pick(int M, int N, int K, int mode, int geglu, int splitk, int f
                      int gn_hw, int gn_groups, int gn_max_chunks, int32_t* out) {
     if (!out || M <= 0 || N <= 0 || K <= 0 || (mode != 0 && mode != 1) || (mode == 1 && (Cin <= 0 || Hout <= 0 || Wout <= 0 || (M2 > 0)))) {
         set_error("ldx_op_gemm_pick: bad argument"); return LDX_EINVAL; }
-    static char buf[16];                       // operands are only ever tested for being there
-    void* const P = buf;
-    GemmArgs g{};
-    g.A = P; g.W = P; g.M = M; g.N = N; g.K = K; g.mode = mode; g.lda = mode ? Cin : K; g.geglu = geglu; g.rows_per_batch = mode ? Hout * Wout : 1;
-    if (mode) {
-        g.Cin = Cin; g.Hin = Hin; g.Win = Win; g.Hout = Hout; g.Wout = Wout; g.stride = stride;
-        if (stride == 1) { g.Hv = Hout; g.Wv = Wout; } else { g.Hv = Hin; g.Wv = Win; }
-        g.resize = (g.Hv != Hin || g.Wv != Win) ? 1 : 0;
-        if (K > 9 * Cin) { g.A2 = P; g.lda2 = g.Cin2 = K - 9 * Cin; }
-    }
-    if (f8) { g.f8 = 1; g.SA = g.SW = (const uint32_t*)P; g.sa_ld = M; g.sw_ld = N; }
+    void* const P = pick_operand;
+    // the planner's geometry (resize to the output extent at stride 1) for one image, then the caller's M
+    GemmArgs g = mode ? gemm_conv_args(P, Cin, P, 1, Hin, Win, Cin, N, K, stride, Hout, Wout, stride == 1) : gemm_linear_args(P, K, P, M, N, K);
+    g.M = M; g.geglu = geglu;
+    if (mode && K > 9 * Cin) { g.A2 = P; g.lda2 = g.Cin2 = K - 9 * Cin; }
+    if (f8) gemm_mx_operands(g, (const uint32_t*)P, M, P, (const uint32_t*)P, N);
     if (c8) { g.C8 = P; g.ldc8 = N; g.SC = (uint32_t*)P; g.sc_ld = M; } else { g.C = P; g.ldc = N; }
     if (ln_fold) g.ln_c1 = (const float*)P;
-    g.splitk = splitk >= 0 ? splitk : (c8 ? 1 : gemm_choose_splitk(M, N, f8 ? K / 2 : K, geglu != 0));
-    if (g.splitk > 1) { g.ws = (float*)P; g.sk_count = (unsigned*)P; }
-    GemmArgs b{};
-    b.A = P; b.W = P; b.M = M2; b.N = N2; b.K = K2; b.lda = K2; b.C = P; b.ldc = N2; b.rows_per_batch = 1; b.f8 = g.f8;
+    if (splitk < 0) gemm_attach_splitk(g, pick_scratch);
+    else if ((g.splitk = splitk) > 1) { g.ws = (float*)P; g.sk_count = (unsigned*)P; }      // the caller's K splits instead of the rule's
+    GemmArgs b = gemm_linear_args(P, K2, P, M2, N2, K2); b.C = P; b.ldc = N2; b.f8 = g.f8;
     int gn = 0;
     if (gn_hw > 0 && M2 <= 0 && (gn = gemm_gn_fuse(g, gn_hw, gn_groups, gn_max_chunks)) != 0) g.gn_partial = (float*)P;
     const GemmPick p = gemm_pick(g, M2 > 0 ? &b : nullptr);
@@ -595,16 +578,12 @@ int ldx_op_gemm_pick(int M, int N, int K, int mode, int geglu, int splitk, int f
 int ldx_op_attn_pick(int B, int H, int Nq, int Mk, int D, int causal, int bias, int o8, int ldq, int ldk, int ldv, int ldo, int knorm_ws, int32_t* out) {
     if (!out || B <= 0 || H <= 0 || Nq <= 0 || Mk <= 0 || D <= 0 || D % 8 || (D > 160 && D != 512) || ldq <= 0 || ldk <= 0 || ldv <= 0 || ldo <= 0 || (o8 && D != 128)) {
         set_error("ldx_op_attn_pick: bad argument (D % 8, D <= 160 or D == 512; MX fp8 output: D == 128)"); return LDX_EINVAL; }
-    alignas(16) static char buf[16];           // operands are only ever tested for being there and for their alignment
-    void* const P = buf;
-    AttnArgs a{};
-    a.Q = a.K = a.V = P; a.O = P; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.B = B; a.H = H; a.Nq = Nq; a.Mk = Mk; a.D = D; a.scale = 1.f; a.causal = causal;
+    void* const P = pick_operand;
+    AttnArgs a = attn_args(P, ldq, P, ldk, P, ldv, P, ldo, B, H, Nq, Mk, D, 1.f); a.causal = causal;
     if (bias) { a.bias = (const float*)P; a.bias_ld = (Mk + 63) / 64 * 64; }
     if (o8) { a.O8 = P; a.ldo8 = ldo; a.SO = (uint32_t*)P; a.so_ld = B * Nq; }
-    if (knorm_ws) a.knorm_ws = (float*)P;
-    AttnPick p = attn_pick(a);
-    if (p.nsplit_want > 1) { a.nsplit = p.nsplit_want; a.split_ws = (float*)P; p = attn_pick(a); }      // as the planner and ldx_op_attention launch it
+    AttnPick p = attn_attach_scratch(a, pick_scratch);      // as the planner and ldx_op_attention launch it ...
+    if (!knorm_ws && a.knorm_ws) { a.knorm_ws = nullptr; p = attn_pick(a); }      // ... or, on request, without the key-block norms
     const int32_t r[13] = {p.family, p.targ[0], p.targ[1], p.targ[2], p.kpf, p.qb, p.block, (int32_t)p.grid, p.lds, p.knorm, p.nsplit, p.mx_out, p.launches};
     for (int i = 0; i < 13; ++i) out[i] = r[i];
     return LDX_OK;
@@ -624,13 +603,8 @@ int ldx_op_conv3x3(const void* X, int ldx_, const void* W, int B, int Hin, int W
                    int resize_to_out, const float* bias, const float* rowvec, int rowvec_ld, const void* R, int ldr, void* Y, int ldy,
                    int dtype, void* stream) {
     if (!X || !W || !Y || Cin % 64 || ldx_ % 8 || (stride != 1 && stride != 2)) { set_error("ldx_op_conv3x3: bad argument (Cin % 64)"); return LDX_EINVAL; }
-    GemmArgs g{};
-    g.A = X; g.lda = ldx_; g.W = W; g.M = B * Hout * Wout; g.N = Cout; g.K = 9 * Cin; g.mode = 1;
-    g.Cin = Cin; g.Hin = Hin; g.Win = Win; g.Hout = Hout; g.Wout = Wout; g.stride = stride;
-    if (resize_to_out) { g.Hv = Hout; g.Wv = Wout; } else { g.Hv = Hin; g.Wv = Win; }
-    g.resize = (g.Hv != Hin || g.Wv != Win) ? 1 : 0;
-    g.bias = bias; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld; g.rows_per_batch = Hout * Wout;
-    g.R = R; g.ldr = ldr; g.C = Y; g.ldc = ldy;
+    GemmArgs g = gemm_conv_args(X, ldx_, W, B, Hin, Win, Cin, Cout, 9 * Cin, stride, Hout, Wout, resize_to_out != 0);
+    g.bias = bias; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld; g.R = R; g.ldr = ldr; g.C = Y; g.ldc = ldy;
     if (int rc = attach_splitk(g)) return rc;
     launch_gemm(g, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_conv3x3");
@@ -638,14 +612,12 @@ int ldx_op_conv3x3(const void* X, int ldx_, const void* W, int B, int Hin, int W
 int ldx_op_upconv2x(const void* X, int ldx_, const void* W9, int B, int Hin, int Win, int Cin, int Cout, const float* bias, void* Y, int ldy, int dtype, void* stream) {
     if (!X || !W9 || !Y || !bias || B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0 || ldx_ % 8 || ldx_ < Cin || ldy % 4 || ldy < Cout) {
         set_error("ldx_op_upconv2x: bad argument (X, W9, bias, Y; ldx % 8, ldy % 4)"); return LDX_EINVAL; }
-    GemmArgs g{}, ph;
-    g.A = X; g.lda = ldx_; g.W = W9; g.M = B * 4 * Hin * Win; g.N = Cout; g.K = 9 * Cin; g.mode = 1;
-    g.Cin = Cin; g.Hin = Hin; g.Win = Win; g.Hout = g.Hv = 2 * Hin; g.Wout = g.Wv = 2 * Win; g.stride = 1; g.resize = 1;
-    g.bias = bias; g.rows_per_batch = g.Hout * g.Wout; g.C = Y; g.ldc = ldy;
+    GemmArgs g = gemm_conv_args(X, ldx_, W9, B, Hin, Win, Cin, Cout, 9 * Cin, 1, 2 * Hin, 2 * Win, true), ph;
+    g.bias = bias; g.C = Y; g.ldc = ldy;
     if (!gemm_upconv_phase(g, false, &ph)) { set_error("ldx_op_upconv2x: no phase form for this shape (Win % 16, Cin % 64, Cout % 16)"); return LDX_EINVAL; }
     void* wp = op_workspace((size_t)16 * Cout * Cin / 2);      // [4][Cout][4 Cin] 16-bit
     if (!wp) { set_error("ldx_op_upconv2x: workspace allocation failed"); return LDX_EHIP; }
-    launch_up_phase(UpPhaseArgs{W9, wp, Cout, Cin, dtype_of(dtype)}, (hipStream_t)stream);
+    launch_up_phase(up_phase_args(W9, wp, Cout, Cin, dtype_of(dtype)), (hipStream_t)stream);
     ph.W = wp; ph.up2x = 2;        // phase-major tiles, as the engine plans it
     launch_gemm(ph, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_upconv2x");
@@ -654,11 +626,8 @@ int ldx_op_conv3x3_skip(const void* X, int ldx_, const void* X2, int ldx2, int C
                         const float* bias, void* Y, int ldy, int dtype, void* stream) {
     if (!X || !X2 || !W || !Y || Cin % 64 || Cin2 % 64 || ldx_ % 8 || ldx2 % 8 || B <= 0 || H <= 0 || Wd <= 0) {
         set_error("ldx_op_conv3x3_skip: bad argument (Cin % 64, Cin2 % 64)"); return LDX_EINVAL; }
-    GemmArgs g{};
-    g.A = X; g.lda = ldx_; g.W = W; g.M = B * H * Wd; g.N = Cout; g.K = 9 * Cin + Cin2; g.mode = 1;
-    g.Cin = Cin; g.Hin = H; g.Win = Wd; g.Hout = H; g.Wout = Wd; g.stride = 1; g.Hv = H; g.Wv = Wd; g.resize = 0;
-    g.A2 = X2; g.lda2 = ldx2; g.Cin2 = Cin2;
-    g.bias = bias; g.rows_per_batch = H * Wd; g.C = Y; g.ldc = ldy;
+    GemmArgs g = gemm_conv_args(X, ldx_, W, B, H, Wd, Cin, Cout, 9 * Cin + Cin2, 1, H, Wd, false);
+    g.A2 = X2; g.lda2 = ldx2; g.Cin2 = Cin2; g.bias = bias; g.C = Y; g.ldc = ldy;
     if (int rc = attach_splitk(g)) return rc;
     launch_gemm(g, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_conv3x3_skip");
@@ -680,15 +649,10 @@ int ldx_op_layernorm(const void* X, int ldx_, void* Y, int ldy, int rows, int C,
 int ldx_op_attention(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int B, int H, int Nq, int Mk, int D,
                      float scale, int causal, int dtype, void* stream) {
     if (!Q || !K || !V || !O || D % 8 || (D > 160 && D != 512) || D <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || Mk <= 0) { set_error("ldx_op_attention: bad argument (D % 8, D <= 160 or D == 512)"); return LDX_EINVAL; }
-    AttnArgs a{Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Nq, Mk, D, scale, causal, nullptr, 0, 0};
-    const AttnPick p = attn_pick(a);
-    if (D == 512 && p.family != AF_ATTN512) { set_error("ldx_op_attention: D = 512 without a mask only (attn512.hip)"); return LDX_EINVAL; }
-    if (p.nsplit_want > 1) {
-        a.nsplit = p.nsplit_want;
-        a.split_ws = op_workspace(attn512_ws_floats(a, a.nsplit));
-        if (!a.split_ws) { set_error("attention split workspace allocation failed"); return LDX_EHIP; }
-    }
-    if (attn_pipe_ok(a)) a.knorm_ws = op_workspace((size_t)B * H * ((Mk + 63) / 64));      // (shared single-op scratch: one stream per device, include/ldx.h)
+    AttnArgs a = attn_args(Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Nq, Mk, D, scale); a.causal = causal;
+    if (D == 512 && attn_pick(a).family != AF_ATTN512) { set_error("ldx_op_attention: D = 512 without a mask only (attn512.hip)"); return LDX_EINVAL; }
+    attn_attach_scratch(a, op_scratch);      // (shared single-op scratch: one stream per device, include/ldx.h)
+    if (a.nsplit > 1 && !a.split_ws) { set_error("attention split workspace allocation failed"); return LDX_EHIP; }
     launch_attention(a, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_attention");
 }
@@ -726,7 +690,8 @@ int ldx_op_attention_bias(const void* Q, int ldq, const void* K, int ldk, const 
     if (!Q || !K || !V || !O || !bias || D % 8 || D > 160 || D <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || Mk <= 0 || bias_ld % 4 ||
         bias_ld < ((Mk + 63) / 64) * 64 || bias_head_stride % 4) {
         set_error("ldx_op_attention_bias: bad argument (bias_ld >= Mk rounded up to 64, multiples of 4)"); return LDX_EINVAL; }
-    AttnArgs a{Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Nq, Mk, D, scale, 0, bias, bias_ld, (long)bias_head_stride};
+    AttnArgs a = attn_args(Q, ldq, K, ldk, V, ldv, O, ldo, B, H, Nq, Mk, D, scale);
+    a.bias = bias; a.bias_ld = bias_ld; a.bias_hs = (long)bias_head_stride;
     launch_attention(a, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_attention_bias");
 }

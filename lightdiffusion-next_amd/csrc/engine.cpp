@@ -361,9 +361,6 @@ unsigned* Engine::sk_counters() {
     return d_sk_count;
 }
 
-// Split-K workspace of one op: dead as soon as the op's reduce launch has run, so it is freed at once (the next buffer may reuse it).
-size_t Engine::ws_alloc(size_t bytes) { const size_t off = a_alloc(bytes); a_free(off); return off; }
-
 // ---- op emitters ---------------------------------------------------------------------------------
 Op& Engine::emit(OpKind kind, const char* name) {
     cur.ops.emplace_back();
@@ -371,50 +368,46 @@ Op& Engine::emit(OpKind kind, const char* name) {
     memset(&o, 0, sizeof(o)); o.kind = kind; o.name = name;
     return o;
 }
-void Engine::op_gemm(const char* name, Act A, const LinearW& w, Act C, Act R, bool geglu, const float* rowvec, int rv_ld, int rpb) {
-    Op& o = emit(OP_GEMM, name);
+// a_elems: 16-bit elements of the A operand as stored (a conv reads its image once, not nine times)
+void Engine::seal_gemm(Op& o, const GemmEdit& edit, double a_elems, bool residual) {
     GemmArgs& g = o.g;
-    g.A = ptr(A); g.lda = A.ld; g.W = w.w; g.M = A.rows; g.N = w.N; g.K = w.K; g.mode = 0;
-    g.bias = w.b; g.rowvec = rowvec; g.rowvec_ld = rv_ld; g.rows_per_batch = rpb > 0 ? rpb : 1;
-    g.geglu = geglu ? 1 : 0;
-    g.R = R.valid ? ptr(R) : nullptr; g.ldr = R.ld;
-    g.C = ptr(C); g.ldc = C.ld; g.Cf = nullptr;
-    g.splitk = gemm_choose_splitk(g.M, g.N, g.K, geglu);
-    if (g.splitk > 1) { g.ws = (float*)((uintptr_t)cur.arena + ws_alloc(gemm_sk_ws_floats(g.M, g.N, g.splitk) * 4)); g.sk_count = sk_counters(); }
+    gemm_attach_splitk(g, scratch);
+    edit(o);
+    if (!gemm_splitk_ok(g)) {          // what the planners' guards (xf_pick's folded stages, the edits that lower splitk) promise, checked where it matters
+        set_error(std::string("planner bug: op ") + o.name + " keeps " + std::to_string(g.splitk) + " K splits with an epilogue that has no split-K form (ln_c1, gate, C8, geglu, up2x)");
+        plan_rc = LDX_ESTATE;
+    }
     o.flops = 2.0 * g.M * (double)g.N * g.K;
-    o.bytes = 2.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * (geglu ? g.N / 2 : g.N) * (R.valid ? 2 : 1));
-    snprintf(o.klabel, sizeof(o.klabel), "gemm_kernel<%s,0>", dt == DT_BF16 ? "bf16" : "f16");
+    o.bytes = 2.0 * (a_elems + (double)g.N * g.K + (double)g.M * (g.geglu ? g.N / 2 : g.N) * (residual ? 2 : 1));
+    snprintf(o.klabel, sizeof(o.klabel), "gemm_kernel<%s,%d>", g.f8 ? "mxfp8" : dt_name(), g.mode);
     cur.flops += o.flops;
 }
-void Engine::op_conv(const char* name, Act X, int B, int Hin, int Win, int Cin, const LinearW& w, int stride, int Hout, int Wout,
-                     Act Y, Act R, const float* rowvec, int rv_ld, float* Cf, int ldcf) {
+void Engine::op_gemm(const char* name, Act A, const LinearW& w, Act C, Act R, int geglu, const GemmEdit& edit) {
     Op& o = emit(OP_GEMM, name);
-    GemmArgs& g = o.g;
-    g.A = ptr(X); g.lda = X.ld; g.W = w.w; g.M = B * Hout * Wout; g.N = w.N; g.K = w.K; g.mode = 1;
-    g.Cin = Cin; g.Hin = Hin; g.Win = Win; g.Hout = Hout; g.Wout = Wout; g.stride = stride;
-    if (stride == 1) { g.Hv = Hout; g.Wv = Wout; } else { g.Hv = Hin; g.Wv = Win; }
-    g.resize = (g.Hv != Hin || g.Wv != Win) ? 1 : 0;
-    g.bias = w.b; g.rowvec = rowvec; g.rowvec_ld = rv_ld; g.rows_per_batch = Hout * Wout;
-    g.R = R.valid ? ptr(R) : nullptr; g.ldr = R.ld;
+    GemmArgs& g = o.g = gemm_linear_args(ptr(A), A.ld, w.w, A.rows, w.N, w.K);
+    g.bias = w.b; g.geglu = geglu; g.R = R.valid ? ptr(R) : nullptr; g.ldr = R.ld; g.C = ptr(C); g.ldc = C.ld;
+    seal_gemm(o, edit, (double)g.M * g.K, R.valid);
+}
+void Engine::op_conv(const char* name, Act X, int B, int Hin, int Win, int Cin, const LinearW& w, int stride, int Hout, int Wout,
+                     Act Y, Act R, const float* rowvec, int rv_ld, float* Cf, int ldcf, const GemmEdit& edit) {
+    Op& o = emit(OP_GEMM, name);
+    GemmArgs& g = o.g = gemm_conv_args(ptr(X), X.ld, w.w, B, Hin, Win, Cin, w.N, w.K, stride, Hout, Wout, stride == 1);      // a stride-1 conv whose output is larger reads its input resized
+    g.bias = w.b; g.rowvec = rowvec; g.rowvec_ld = rv_ld; g.R = R.valid ? ptr(R) : nullptr; g.ldr = R.ld;
     g.C = Y.valid ? ptr(Y) : nullptr; g.ldc = Y.ld; g.Cf = Cf; g.ldcf = ldcf;
-    g.splitk = gemm_choose_splitk(g.M, g.N, g.K, false);
-    if (g.splitk > 1) { g.ws = (float*)((uintptr_t)cur.arena + ws_alloc(gemm_sk_ws_floats(g.M, g.N, g.splitk) * 4)); g.sk_count = sk_counters(); }
-    o.flops = 2.0 * g.M * (double)g.N * g.K;
-    o.bytes = 2.0 * ((double)B * Hin * Win * Cin + (double)g.N * g.K + (double)g.M * g.N * (R.valid ? 2 : 1));
-    snprintf(o.klabel, sizeof(o.klabel), "gemm_kernel<%s,1>", dt == DT_BF16 ? "bf16" : "f16");
-    cur.flops += o.flops;
+    seal_gemm(o, edit, (double)B * Hin * Win * Cin, R.valid);
 }
 // the kernels launch_groupnorm runs for the op as it stands (fuse_gn_stats asks again once the statistics come from the producer)
 static void gn_label(Op& o) {
     static const char* const names[] = {"gn_small", "gn_stats+gn_apply", "gn_apply(fused stats)", "gn_fold+gn_apply(fused stats)"};      // by GnKind
     snprintf(o.klabel, sizeof(o.klabel), "%s", names[gn_pick(o.gn).kind]);
 }
-void Engine::op_gn(const char* name, Act X, Act Y, int B, int HW, const NormW& n, float eps, bool silu) {
+void Engine::op_gn(const char* name, Act X, Act Y, int B, int HW, const NormW& n, float eps, bool silu, const GnEdit& edit) {
     Op& o = emit(OP_GN, name);
     GroupNormArgs& g = o.gn;
     g.X = ptr(X); g.ldx = X.ld; g.Y = ptr(Y); g.ldy = Y.ld; g.B = B; g.HW = HW; g.C = n.C; g.G = 32; g.eps = eps; g.silu = silu;
     g.gamma = n.g; g.beta = n.b; g.partial = (float*)(cur.arena ? (char*)cur.arena + cur.gn_ws_off : nullptr);
-    o.bytes = 2.0 * 3.0 * (double)B * HW * n.C;       // read (stats) + read + write (apply)
+    edit(o);
+    o.bytes = 2.0 * 3.0 * (double)g.B * g.HW * g.C;       // read (stats) + read + write (apply)
     gn_label(o);
 }
 // SURVEY §8 a10-a11 / VERDICT r2 item 1c: GroupNorm statistics from the producing conv / GEMM epilogue.  A GroupNorm whose input tensor was written by
@@ -457,7 +450,7 @@ void Engine::op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R,
     if (nw) { a.g = nw->g; a.b = nw->b; }
     o.flops = 2.0 * a.M * (double)a.N * a.K;
     o.bytes = 2.0 * ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N * (R.valid ? 2 : 1));
-    snprintf(o.klabel, sizeof(o.klabel), "rowgemm<%s,%d>", dt == DT_BF16 ? "bf16" : "f16", pro);
+    snprintf(o.klabel, sizeof(o.klabel), "rowgemm<%s,%d>", dt_name(), pro);
     cur.flops += o.flops;
 }
 // SpatialTransformer norm + proj_in, as emit_xf emitted them, become one rowgemm launch with the GroupNorm apply as its prologue where xf_proj_in_rowgemm says so.
@@ -474,39 +467,32 @@ void Engine::fuse_gn_rowgemm() {
         a.X = n.X; a.ldx = n.ldx; a.Y = g.C; a.ldy = g.ldc; a.M = g.M; a.N = g.N; a.K = g.K; a.W = g.W; a.bias = g.bias; a.R = g.R; a.ldr = g.ldr;
         a.pro = 2; a.g = n.gamma; a.b = n.beta; a.eps = n.eps; a.partial = n.partial; a.nchunk = n.stats_chunks; a.HW = n.HW; a.G = n.G;
         o.flops = cur.ops[i + 1].flops; o.bytes = cur.ops[i + 1].bytes;
-        snprintf(o.klabel, sizeof(o.klabel), "rowgemm<%s,2>", dt == DT_BF16 ? "bf16" : "f16");
+        snprintf(o.klabel, sizeof(o.klabel), "rowgemm<%s,2>", dt_name());
         cur.ops[i] = o;
         cur.ops.erase(cur.ops.begin() + (long)i + 1);
         if (i + 1 < cur.prefix_end) --cur.prefix_end;
     }
 }
-void Engine::op_ln(const char* name, Act X, Act Y, const NormW& n) {
+void Engine::op_ln(const char* name, Act X, Act Y, const NormW& n, const LnEdit& edit) {
     Op& o = emit(OP_LN, name);
     LayerNormArgs& l = o.ln;
     l.X = ptr(X); l.ldx = X.ld; l.Y = ptr(Y); l.ldy = Y.ld; l.rows = X.rows; l.C = n.C; l.eps = 1e-5f; l.gamma = n.g; l.beta = n.b;
-    o.bytes = 2.0 * 2.0 * (double)X.rows * n.C;
+    edit(o);
+    o.bytes = 2.0 * 2.0 * (double)l.rows * l.C;
     snprintf(o.klabel, sizeof(o.klabel), "ln_kernel");
 }
-void Engine::op_attn(const char* name, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, Act O, int B, int H, int Nq, int Mk, int D) {
+void Engine::op_attn(const char* name, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, Act O, int B, int H, int Nq, int Mk, int D, const AttnEdit& edit) {
     Op& o = emit(OP_ATTN, name);
-    AttnArgs& a = o.at;
-    a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = ptr(O); a.ldo = O.ld;
-    a.B = B; a.H = H; a.Nq = Nq; a.Mk = Mk; a.D = D; a.scale = 1.0f / std::sqrt((float)D); a.causal = 0;
-    if (attn_pipe_ok(a)) {       // key-block norms for the pipelined kernels' score bound (attn_pipe.hip): a few KiB, live for this op only
-        const size_t off = a_alloc((size_t)B * H * ((Mk + 63) / 64) * 4); a.knorm_ws = (float*)((uintptr_t)cur.arena + off); a_free(off);
-    }
-    const AttnPick p = attn_pick(a);
-    if (p.nsplit_want > 1) {          // D = 512 (VAE): key splits when the query blocks alone leave CUs idle; fp32 partials live for this op only
-        a.nsplit = p.nsplit_want;
-        const size_t off = a_alloc(attn512_ws_floats(a, a.nsplit) * 4); a.split_ws = (float*)((uintptr_t)cur.arena + off); a_free(off);
-    }
+    AttnArgs& a = o.at = attn_args(Q, ldq, K, ldk, V, ldv, ptr(O), O.ld, B, H, Nq, Mk, D, 1.0f / std::sqrt((float)D));
+    edit(o);
+    const AttnPick p = attn_attach_scratch(a, scratch);      // key-block norms of the pipelined kernels, partials of attn512's key splits (the VAE): live for this op only
     o.flops = 4.0 * B * H * (double)Nq * Mk * D;
     o.bytes = 2.0 * (double)B * H * D * (2.0 * Nq + 2.0 * Mk);
     {
         // the device kernel's own name with its template arguments (rocprofv3 reports the same), then self / cross or attn512's key splits
         static const char* const fmt[] = {"attn_kernel<%s,%d,%d,%d>", "attn32_kernel<%s,%d,144,192,%d>", "attn32ap_kernel<%s,144,192,%d>", "attn32g_kernel<%s,%d,%d,1,%d,%d>",
                                           "attn40p_kernel<%s>", "attn128p_kernel<%s>", "attn512_kernel<%s>"};      // by AttnFamily
-        const int n = snprintf(o.klabel, sizeof(o.klabel), fmt[p.family], dt == DT_BF16 ? "bf16" : "f16", p.targ[0], p.targ[1], p.targ[2], (int)p.kpf);
+        const int n = snprintf(o.klabel, sizeof(o.klabel), fmt[p.family], dt_name(), p.targ[0], p.targ[1], p.targ[2], (int)p.kpf);
         if (p.family == AF_ATTN512) snprintf(o.klabel + n, sizeof(o.klabel) - n, "x%d", a.nsplit);
         else snprintf(o.klabel + n, sizeof(o.klabel) - n, "%s", Nq == Mk ? "self" : "cross");
     }
@@ -529,16 +515,13 @@ void Engine::emit_res(const ResW& r, Act X, Act OUT, int B, int H, int W, const 
     Act t1 = new_act(M, r.Cin);
     op_gn("res.gn1", X, t1, B, H * W, r.gn1, r.eps, true);
     Act t2 = new_act(M, r.Cout);
-    if (r.has_emb) op_conv("res.conv1", t1, B, H, W, r.Cin, r.conv1, 1, H, W, t2, Act{}, emb ? emb + r.emb_off : nullptr, emb_ld);
-    else op_conv("res.conv1", t1, B, H, W, r.Cin, r.conv1, 1, H, W, t2, Act{});
+    op_conv("res.conv1", t1, B, H, W, r.Cin, r.conv1, 1, H, W, t2, Act{}, r.has_emb && emb ? emb + r.emb_off : nullptr, r.has_emb ? emb_ld : 0);
     release(t1);
     Act t3 = new_act(M, r.Cout);
     op_gn("res.gn2", t2, t3, B, H * W, r.gn2, r.eps, true);
     release(t2);
     if (r.has_skip && r.fused_skip) {
-        op_conv("res.conv2+skip", t3, B, H, W, r.Cout, r.conv2, 1, H, W, OUT, Act{});
-        GemmArgs& g = cur.ops.back().g;
-        g.A2 = ptr(X); g.lda2 = X.ld; g.Cin2 = r.Cin;
+        op_conv("res.conv2+skip", t3, B, H, W, r.Cout, r.conv2, 1, H, W, OUT, Act{}, nullptr, 0, nullptr, 0, [&](GemmArgs& g) { g.A2 = ptr(X); g.lda2 = X.ld; g.Cin2 = r.Cin; });
     } else if (r.has_skip) {
         Act t4 = new_act(M, r.Cout);
         op_gemm("res.skip", X, r.skip, t4, Act{});
@@ -568,6 +551,7 @@ int Engine::build_plan(const PlanKey& key, const std::function<int()>& emit, boo
     auto reset = [&] {
         free_list.clear(); live.clear(); arena_top = 0; arena_peak = 0;
         cur.ops.clear(); cur.flops = 0; cur.flops_shared = 0; cur.flops_up2x = 0; cur.prefix_end = 0;
+        plan_rc = LDX_OK;
     };
     cur.key = PlanKey{};                  // no plan until the bound pass has completed
     reset();
@@ -575,13 +559,14 @@ int Engine::build_plan(const PlanKey& key, const std::function<int()>& emit, boo
     cur.arena = nullptr;
     int rc = emit();
     cur.arena = arena;
+    if (!rc) rc = plan_rc;                // an emitter's own finding (seal_gemm)
     if (rc) return rc;
     cur.arena_peak_dry = arena_peak;
     if (cur.arena && cur.arena_cap < cur.arena_peak_dry) { HIP_OK(hipFree(cur.arena)); cur.arena = nullptr; cur.arena_cap = 0; }
     if (!cur.arena) { HIP_OK(hipMalloc(&cur.arena, cur.arena_peak_dry)); cur.arena_cap = cur.arena_peak_dry; }
     if (zero_arena) HIP_OK(hipMemset(cur.arena, 0, cur.arena_cap));
     reset();
-    if ((rc = emit())) return rc;
+    if ((rc = emit()) || (rc = plan_rc)) return rc;
     cur.key = key;
     cur.graph.reset();
     cur.kv_ptr = nullptr; cur.kv_epoch = 0;          // a fresh arena holds no projected context

@@ -50,7 +50,8 @@ struct XfBlockW { NormW ln1, ln2, ln3; LinearW qkv, o1, q2, kv2, o2, ff1, ff2; L
     // the GEMM reads the un-normalised rows and applies rstd * (acc - mean * c1) + bias in its epilogue (GemmArgs::ln_stat)
     bool ln_fold = false; float *c1_qkv = nullptr, *c1_q2 = nullptr, *c1_ff1 = nullptr; };
 struct XfW { NormW gn; LinearW proj_in, proj_out; std::vector<XfBlockW> blocks; int C = 0, depth = 0; };
-struct BlockW { bool has_res = false, has_xf = false, has_down = false, has_up = false; ResW res; XfW xf; LinearW down, up; int skip_ch = 0; };
+// level, ch (the walk's bookkeeping, read by UNetEngine::plan): an input block's output, the skip it leaves, has `ch` channels at resolution level `level`; an output block runs at `level` on `ch` channels of h beside its skip_ch
+struct BlockW { bool has_res = false, has_xf = false, has_down = false, has_up = false; ResW res; XfW xf; LinearW down, up; int skip_ch = 0, level = 0, ch = 0; };
 // Every weight of the UNet, as the structure walk (UNetEngine::walk_weights) builds it; emb_all / kv_all: the emb_layers of every ResBlock and the k | v projections of
 // every cross-attention, each batched into one GEMM per forward ([emb_total][4 mc] and [kv_total][context_dim])
 struct UNetW {
@@ -86,6 +87,16 @@ struct Op {
     int tok0;                      // first token of the rope op's rows in the call's rotary tables
     double flops; double bytes; char klabel[48];
 };
+// What a planner has to say about an op beyond its emitter's parameters: a callable on the op's argument struct — [&](GemmArgs& g) { g.act = 1; } — or, where it
+// sets one of the flags above, on the Op.  The emitter runs it BEFORE it derives what depends on the arguments (attention scratch and kernel pick, label, flops,
+// bytes), so nothing is patched after an emitter has returned.  Split-K alone is chosen in front of it: an edit may lower GemmArgs::splitk to 1, never raise it.
+template <class Args, Args Op::*member> struct OpEdit {
+    std::function<void(Op&)> fn;
+    OpEdit() = default;
+    template <class F> OpEdit(F f) { if constexpr (std::is_invocable_v<F, Op&>) fn = f; else fn = [f](Op& o) { f(o.*member); }; }
+    void operator()(Op& o) const { if (fn) fn(o); }
+};
+using GemmEdit = OpEdit<GemmArgs, &Op::g>; using AttnEdit = OpEdit<AttnArgs, &Op::at>; using LnEdit = OpEdit<LayerNormArgs, &Op::ln>; using GnEdit = OpEdit<GroupNormArgs, &Op::gn>;
 struct ProfEntry { long count = 0; double ms = 0, flops = 0, bytes = 0; };
 
 // What a plan was built for.  Per model: UNet (B2, h, w, Mc, share), Flux (B, h, w, Lt), VAE (B, h, w, 1) decode / (B, Hpx, Wpx, 2) encode,
@@ -261,9 +272,13 @@ protected:
     // GroupNorm workspace: gn_ws_rows producer rows per image + GN_FOLD folded rows, x 32 groups x 2 floats (ldx_kernels.h gn_workspace_rows)
     int gn_ws_rows = 256;
     size_t gn_ws_bytes(int B, long HWmax) { gn_ws_rows = (int)gn_workspace_rows(HWmax); return (size_t)B * (gn_ws_rows + GN_FOLD) * 32 * 2 * 4; }
-    size_t ws_alloc(size_t bytes);                        // split-K workspace of one op (engine.cpp)
     unsigned* d_sk_count = nullptr;                       // split-K tile counters (sk_counters()): one zeroed buffer per engine, every launch leaves it zeroed
     unsigned* sk_counters();
+    // What the argument builders (ldx_kernels.h gemm_attach_splitk, attn_attach_scratch) take scratch from.  An op's scratch (split-K partials, attention key
+    // norms / split partials) is dead as soon as the op's launches have run, so its arena range is freed at once: the next buffer may reuse it
+    const Scratch scratch{[this](size_t bytes) -> void* { const size_t off = a_alloc(bytes); a_free(off); return (void*)((uintptr_t)cur.arena + off); }, [this] { return sk_counters(); }};
+    int plan_rc = LDX_OK;                                 // an emitter found a planner bug (set_error holds the text): build_plan fails the plan with it
+    void seal_gemm(Op& o, const GemmEdit& edit, double a_elems, bool residual);      // the tail of op_gemm / op_conv: K splits, the edit, the split-K check, then flops, bytes and label
     void fuse_gn_stats();                                 // post-pass over ops: GroupNorms whose input was just written by a fusable GEMM / conv get their statistics from its epilogue
     void fuse_gn_rowgemm();                               // post-pass: xf.norm (producer statistics) + xf.proj_in -> one rowgemm launch where xf_proj_in_rowgemm says so
     void op_rowgemm(const char* name, Act X, const LinearW& w, Act Y, Act R, int pro, const NormW* nw);
@@ -278,15 +293,20 @@ protected:
     size_t a_alloc(size_t bytes);
     void a_free(size_t off);
     void* ptr(const Act& a) const { return (void*)((uintptr_t)cur.arena + a.off + (size_t)a.col * 2); }
+    // a new arena buffer of `bytes` that is no activation (never released by the plans that use it), as a T* (the dry pass: an offset from a null arena)
+    template <class T> T* arena_ptr(size_t bytes) { return (T*)((uintptr_t)cur.arena + a_alloc(bytes)); }
+    const char* dt_name() const { return dt == DT_BF16 ? "bf16" : "f16"; }      // the compute type as the kernels' labels spell it
     Act new_act(int rows, int C);
     Act view(const Act& base, int col, int C);
+    static Act rows(const Act& t, int r0, int nr) { Act v = t; v.owned = false; v.off = t.off + (size_t)r0 * t.ld * 2; v.rows = nr; return v; }      // rows [r0, r0 + nr) of a buffer
     void release(const Act& a);
-    void op_gemm(const char* name, Act A, const LinearW& w, Act C, Act R, bool geglu = false, const float* rowvec = nullptr, int rv_ld = 0, int rpb = 0);
+    // The op emitters.  `edit` (OpEdit above) is applied before anything is derived from the arguments.
+    void op_gemm(const char* name, Act A, const LinearW& w, Act C, Act R, int geglu = 0, const GemmEdit& edit = {});      // geglu: GemmArgs::geglu (1 erf, 2 tanh)
     void op_conv(const char* name, Act X, int B, int Hin, int Win, int Cin, const LinearW& w, int stride, int Hout, int Wout,
-                 Act Y, Act R, const float* rowvec = nullptr, int rv_ld = 0, float* Cf = nullptr, int ldcf = 0);
-    void op_gn(const char* name, Act X, Act Y, int B, int HW, const NormW& n, float eps, bool silu);
-    void op_ln(const char* name, Act X, Act Y, const NormW& n);
-    void op_attn(const char* name, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, Act O, int B, int H, int Nq, int Mk, int D);
+                 Act Y, Act R, const float* rowvec = nullptr, int rv_ld = 0, float* Cf = nullptr, int ldcf = 0, const GemmEdit& edit = {});
+    void op_gn(const char* name, Act X, Act Y, int B, int HW, const NormW& n, float eps, bool silu, const GnEdit& edit = {});
+    void op_ln(const char* name, Act X, Act Y, const NormW& n, const LnEdit& edit = {});
+    void op_attn(const char* name, const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, Act O, int B, int H, int Nq, int Mk, int D, const AttnEdit& edit = {});
     // UNet and VAE ResBlock; emb [.][emb_ld]: the batched emb_layers output a block with has_emb adds its columns [emb_off, emb_off + Cout) of (null in the dry pass)
     void emit_res(const ResW& r, Act X, Act OUT, int B, int H, int W, const float* emb = nullptr, int emb_ld = 0);
 

@@ -70,12 +70,10 @@ int ClipEngine::plan(int B, int T, int inter) {
             op_ln("clip.ln1", x, n, L.ln1);
             op_gemm("clip.qkv", n, L.qkv, qkv, Act{});
             const char* base = (const char*)ptr(qkv);
-            op_attn("clip.attn", base, 3 * E, base + (size_t)E * 2, 3 * E, base + (size_t)2 * E * 2, 3 * E, a, B, heads, T, T, D);
-            cur.ops.back().at.causal = 1;
+            op_attn("clip.attn", base, 3 * E, base + (size_t)E * 2, 3 * E, base + (size_t)2 * E * 2, 3 * E, a, B, heads, T, T, D, [](AttnArgs& at) { at.causal = 1; });
             op_gemm("clip.out", a, L.out, x, x);                 // x += self_attn(ln1(x))
             op_ln("clip.ln2", x, n, L.ln2);
-            op_gemm("clip.fc1", n, L.fc1, f, Act{});
-            cur.ops.back().g.act = 1;                                // quick-GELU
+            op_gemm("clip.fc1", n, L.fc1, f, Act{}, 0, [](GemmArgs& g) { g.act = 1; });      // quick-GELU
             op_gemm("clip.fc2", f, L.fc2, x, x);                 // x += mlp(ln2(x))
             if (l == inter) {                                    // intermediate = x.clone(); final LN applied to it
                 op_ln("clip.final_ln.inter", x, xi, clip_final_ln);

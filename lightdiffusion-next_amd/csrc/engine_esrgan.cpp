@@ -47,10 +47,8 @@ int EsrganEngine::plan(int B, int H, int W) {
     // zero-filled arena: dense-block convs read a few not-yet-written columns against zero weights: those must hold finite values, and a
     // new plan lays the buffers over whatever the previous shape left there (fp32 pixels read as 16-bit can be NaN)
     return build_plan(PlanKey{B, H, W}, [&]() -> int {
-        auto conv = [&](const char* name, Act X, int Cin, const LinearW& w, int Hin, int Win, int Hout, int Wout, Act Y, Act R, int act) {
-            op_conv(name, X, B, Hin, Win, Cin, w, 1, Hout, Wout, Y, R);
-            GemmArgs& g = cur.ops.back().g; g.act = act;
-            if (g.splitk > 1) g.splitk = 1;
+        auto conv = [&](const char* name, Act X, int Cin, const LinearW& w, int Hin, int Win, int Hout, int Wout, Act Y, Act R, int act, const GemmEdit& more = {}) {      // unsplit; more: beyond the activation
+            op_conv(name, X, B, Hin, Win, Cin, w, 1, Hout, Wout, Y, R, nullptr, 0, nullptr, 0, [&](Op& o) { o.g.act = act; o.g.splitk = 1; more(o); });
         };
         Act x0 = new_act(M, 64);
         emit(OP_PIXPREP, "esrgan.prep").pix = PixelsPrepArgs{nullptr, ptr(x0), B, c.in_nc, H * W, 64, 1.0f, 0.0f};      // the pixels are the call's
@@ -65,9 +63,10 @@ int EsrganEngine::plan(int B, int H, int W) {
                 const int cpad = (nf + j * gc + 63) / 64 * 64;
                 conv("esrgan.rdb.conv", view(cat[src], 0, cpad), cpad, r.c[j], H, W, H, W, view(cat[src], nf + j * gc, gc), Act{}, 3);
             }
-            conv("esrgan.rdb.conv5", view(cat[src], 0, CW), CW, r.c[4], H, W, H, W, view(cat[dst], 0, nf), view(cat[src], 0, nf), 0);
-            GemmArgs& g = cur.ops.back().g; g.oscale = 0.2f;                                      // x5 * 0.2 + x
-            if (rrdb_in) { g.R2 = ptr(*rrdb_in); g.ldr2 = rrdb_in->ld; g.oscale2 = 0.2f; }   // (..) * 0.2 + rrdb input
+            conv("esrgan.rdb.conv5", view(cat[src], 0, CW), CW, r.c[4], H, W, H, W, view(cat[dst], 0, nf), view(cat[src], 0, nf), 0, [&](GemmArgs& g) {
+                g.oscale = 0.2f;                                                                  // x5 * 0.2 + x
+                if (rrdb_in) { g.R2 = ptr(*rrdb_in); g.ldr2 = rrdb_in->ld; g.oscale2 = 0.2f; }   // (..) * 0.2 + rrdb input
+            });
         };
         for (int i = 0; i < c.num_blocks; ++i) {
             const Act xin = view(cat[in], 0, nf);
@@ -89,8 +88,7 @@ int EsrganEngine::plan(int B, int H, int W) {
         Act hr = new_act(B * h * w, nf);
         conv("esrgan.hr_conv", hcur, nf, es_hr, h, w, h, w, hr, Act{}, 3);
         release(hcur);
-        const size_t o_pix = a_alloc((size_t)B * h * w * c.out_nc * 4);
-        float* pix = (float*)((uintptr_t)cur.arena + o_pix);
+        float* pix = arena_ptr<float>((size_t)B * h * w * c.out_nc * 4);
         op_conv("esrgan.conv_last", hr, B, h, w, nf, es_last, 1, h, w, Act{}, Act{}, nullptr, 0, pix, c.out_nc);
         release(hr);
         emit(OP_COPY_OUT, "esrgan.out").copy = CopyOutArgs{pix, nullptr, (size_t)B * h * w * c.out_nc * 4};

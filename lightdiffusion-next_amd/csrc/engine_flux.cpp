@@ -122,16 +122,16 @@ int FluxEngine::plan(int B, int h, int w, int Lt) {
     const int C = f.hidden_size, H = f.num_heads, D = C / H, MH = f.mlp_hidden;
     const int Li = (h / 2) * (w / 2), L = Lt + Li, inC = 4 * f.in_channels;
     return build_plan(PlanKey{B, h, w, Lt}, [&]() -> int {
-        auto f32buf = [&](size_t n) { const size_t off = a_alloc(n * 4); return (float*)((uintptr_t)cur.arena + off); };
+        auto f32buf = [&](size_t n) { return arena_ptr<float>(n * 4); };
         cur.fx_temb = f32buf((size_t)B * 256); cur.fx_gemb = f32buf((size_t)B * 256); cur.fx_h1 = f32buf((size_t)B * C);
         cur.fx_vec = f32buf((size_t)B * C); cur.fx_svec = f32buf((size_t)B * C); cur.fx_mod = f32buf((size_t)B * fx_mod_total);
         cur.fx_tok = f32buf((size_t)B * Li * inC);
         // first-block-cache state lives at the head of the arena and is never released: it survives from call to call
         cur.fb_first = f32buf((size_t)B * Li * C); cur.fb_res = f32buf((size_t)B * L * C); cur.fb_part = f32buf(2 * 1024 + 8);
-        { const size_t o0 = a_alloc((size_t)B * L * C * 2), o1 = a_alloc((size_t)B * L * C * 2); cur.fb_s0 = (void*)((uintptr_t)cur.arena + o0); cur.fb_s1 = (void*)((uintptr_t)cur.arena + o1); }
-        auto skinny = [&](const char* name, OpKind kind, const float* x, int ldx_, const LinearW& lw, float* out, int out_act, int accum) {
-            emit(kind, name).sk = skinny_args(x, ldx_, lw.w, lw.b, out, lw.N, B, lw.N, lw.K, 0, out_act, accum);
+        cur.fb_s0 = arena_ptr<void>((size_t)B * L * C * 2); cur.fb_s1 = arena_ptr<void>((size_t)B * L * C * 2);
+        auto skinny = [&](const char* name, OpKind kind, const float* x, int ldx_, const LinearW& lw, float* out, int out_act, int accum) -> SkinnyArgs& {
             cur.flops += 2.0 * B * (double)lw.N * lw.K;
+            return emit(kind, name).sk = skinny_args(x, ldx_, lw.w, lw.b, out, lw.N, B, lw.N, lw.K, 0, out_act, accum);
         };
         // vec = time_in(temb(t)) + guidance_in(temb(g)) + vector_in(y)           (Flux.py:683-696)
         emit(OP_FX_TEMB, "fx.temb_t").temb = FluxTembArgs{nullptr, cur.fx_temb, B, 256, 1000.0f};
@@ -145,8 +145,10 @@ int FluxEngine::plan(int B, int h, int w, int Lt) {
         skinny("fx.vector_in.0", OP_FX_SKINNY_Y, nullptr, f.vec_in_dim, fx_vec0, cur.fx_h1, 1, 0);      // x bound per call (y)
         skinny("fx.vector_in.1", OP_SKINNY, cur.fx_h1, C, fx_vec1, cur.fx_vec, 0, 1);
         emit(OP_FX_SILU, "fx.silu_vec").silu = SiluArgs{cur.fx_vec, cur.fx_svec, (size_t)(B * C)};
-        skinny("fx.modulation_all", OP_SKINNY, cur.fx_svec, C, fx_mod_all, cur.fx_mod, 0, 0);
-        if (fx_fp8 && fx_mod_all.w8) { SkinnyArgs& k = cur.ops.back().sk; k.W8 = fx_mod_all.w8; k.SW = fx_mod_all.sw; k.sw_ld = fx_mod_all.N; }
+        {
+            SkinnyArgs& k = skinny("fx.modulation_all", OP_SKINNY, cur.fx_svec, C, fx_mod_all, cur.fx_mod, 0, 0);
+            if (fx_fp8 && fx_mod_all.w8) { k.W8 = fx_mod_all.w8; k.SW = fx_mod_all.sw; k.sw_ld = fx_mod_all.N; }
+        }
 
         // joint token buffer and inputs
         Act X = new_act(B * L, C);
@@ -154,7 +156,6 @@ int FluxEngine::plan(int B, int h, int w, int Lt) {
         emit(OP_FX_PATCH, "fx.patchify").patch = FluxPatchArgs{nullptr, ptr(ptok), B, f.in_channels, h, w};
         Act ctx16 = new_act(B * Lt, f.context_in_dim);
         emit(OP_CVT, "fx.ctx.cvt").cvt = CvtArgs{nullptr, ptr(ctx16), (size_t)B * Lt * f.context_in_dim};
-        auto rows = [&](const Act& t, int r0, int nr) { Act v = t; v.owned = false; v.off = t.off + (size_t)r0 * t.ld * 2; v.rows = nr; return v; };
         auto img_rows = [&](const Act& t, int b) { return rows(t, b * L + Lt, Li); };
         auto txt_rows = [&](const Act& t, int b) { return rows(t, b * L, Lt); };
         for (int b = 0; b < B; ++b) {
@@ -169,18 +170,15 @@ int FluxEngine::plan(int B, int h, int w, int Lt) {
         const int fuse_mask = g_plan_sw.mx_fuse;      // experiment switch: 1 GEMM epilogue, 2 attention, 4 LayerNorm
         const bool fuse_gemm_q = fuse_mask & 1;
         const int RT = B * L;                                   // rows of every joint buffer = scale-array row stride
-        auto new_q8 = [&](int K) { Q8 q; q.K = K; const size_t o8 = a_alloc((size_t)RT * K), os = a_alloc((size_t)(K / 128) * RT * 4);
-                                   q.y = (char*)cur.arena + o8; q.s = (uint32_t*)((char*)cur.arena + os); return q; };
+        auto new_q8 = [&](int K) { Q8 q; q.K = K; q.y = arena_ptr<char>((size_t)RT * K); q.s = arena_ptr<uint32_t>((size_t)(K / 128) * RT * 4); return q; };
         auto row_of = [&](const Act& base, const Act& v) { return (int)((v.off - base.off) / ((size_t)base.ld * 2)); };
         // qo != null: the output goes to the MX shadow of the buffer Y lives in (returns true), not to Y
         auto ln_mod = [&](const char* name, Act Xin, Act Y, const float* shift, const float* scale, int rpb, const Q8* qo = nullptr, const Act* obase = nullptr) {
-            Op& o = emit(OP_LN, name);
-            LayerNormArgs& l = o.ln;
-            l.X = ptr(Xin); l.ldx = Xin.ld; l.Y = ptr(Y); l.ldy = Y.ld; l.rows = Xin.rows; l.C = C; l.eps = 1e-6f; l.gamma = nullptr; l.beta = nullptr;
-            l.scale = scale; l.shift = shift; l.mod_ld = fx_mod_total; l.rows_per_batch = rpb;
-            o.bytes = 2.0 * 2.0 * (double)Xin.rows * C; snprintf(o.klabel, sizeof(o.klabel), "ln_kernel");
             const bool fused = fx_fp8 && qo && (fuse_mask & 4);
-            if (fused) { const int ro = row_of(*obase, Y); l.Y8 = qo->y + (size_t)ro * qo->K; l.ldy8 = qo->K; l.S8 = qo->s + ro; l.s8_ld = RT; }
+            op_ln(name, Xin, Y, NormW{nullptr, nullptr, C}, [&](LayerNormArgs& l) {
+                l.eps = 1e-6f; l.scale = scale; l.shift = shift; l.mod_ld = fx_mod_total; l.rows_per_batch = rpb;
+                if (fused) { const int ro = row_of(*obase, Y); l.Y8 = qo->y + (size_t)ro * qo->K; l.ldy8 = qo->K; l.S8 = qo->s + ro; l.s8_ld = RT; }
+            });
             return fused;
         };
         // MX fp8 attention (ldx_flux_set_fp8 mode 1, head dim 128; attn_mx.hip): the QKNorm + RoPE op writes q / k as MX fp8 (+ one scale dword per (row, head)) instead
@@ -189,9 +187,8 @@ int FluxEngine::plan(int B, int h, int w, int Lt) {
         const int Lp = (L + 127) / 128 * 128;
         char *a8_q = nullptr, *a8_k = nullptr, *a8_vt = nullptr; uint32_t *a8_sq = nullptr, *a8_sk = nullptr, *a8_sv = nullptr;
         if (attn8) {
-            auto al = [&](size_t bytes) { return (char*)cur.arena + a_alloc(bytes); };
-            a8_q = al((size_t)RT * C); a8_k = al((size_t)RT * C); a8_vt = al((size_t)B * H * 128 * Lp);
-            a8_sq = (uint32_t*)al((size_t)H * RT * 4); a8_sk = (uint32_t*)al((size_t)H * RT * 4); a8_sv = (uint32_t*)al((size_t)B * H * (Lp / 128) * 128 * 4);
+            a8_q = arena_ptr<char>((size_t)RT * C); a8_k = arena_ptr<char>((size_t)RT * C); a8_vt = arena_ptr<char>((size_t)B * H * 128 * Lp);
+            a8_sq = arena_ptr<uint32_t>((size_t)H * RT * 4); a8_sk = arena_ptr<uint32_t>((size_t)H * RT * 4); a8_sv = arena_ptr<uint32_t>((size_t)B * H * (Lp / 128) * 128 * 4);
         }
         auto rope = [&](const char* name, Act QKV, const float* qs, const float* ks, int tok0, const Act* qkv_base = nullptr) {
             Op& o = emit(OP_FX_ROPE, name);
@@ -218,23 +215,19 @@ int FluxEngine::plan(int B, int h, int w, int Lt) {
         // Cc's rows and columns, quantised in the GEMM epilogue (Cc itself is not written)
         auto lin = [&](const char* name, const Act& base, const Act& v, const Q8& q, const LinearW& lw, Act Cc, Act R, const float* gate, int rpb, int act,
                        const Q8* qo = nullptr, const Act* obase = nullptr) {
-            op_gemm(name, v, lw, Cc, R);
-            GemmArgs& g = cur.ops.back().g;
-            g.gate = gate; g.gate_ld = fx_mod_total; g.rows_per_batch = rpb; g.act = act;
-            if (gate && g.splitk > 1) g.splitk = 1;      // gate/act are not replicated in the split-K reduce path for safety
-            if (fx_fp8 && lw.w8) {
+            op_gemm(name, v, lw, Cc, R, 0, [&](GemmArgs& g) {
+                g.gate = gate; g.gate_ld = fx_mod_total; g.rows_per_batch = rpb; g.act = act;
+                if (gate) g.splitk = 1;      // gate/act are not replicated in the split-K reduce path for safety
+                if (!fx_fp8 || !lw.w8) return;
                 const int r0 = row_of(base, v);
-                g.f8 = 1; g.A = q.y + (size_t)r0 * q.K; g.lda = q.K; g.SA = q.s + r0; g.sa_ld = RT; g.W = lw.w8; g.SW = lw.sw; g.sw_ld = lw.N;
-                if (!gate) {
-                    g.splitk = gemm_choose_splitk(g.M, g.N, g.K / 2, false);
-                    if (g.splitk > 1) { g.ws = (float*)((uintptr_t)cur.arena + ws_alloc(gemm_sk_ws_floats(g.M, g.N, g.splitk) * 4)); g.sk_count = sk_counters(); }
-                }
-                snprintf(cur.ops.back().klabel, sizeof(cur.ops.back().klabel), "gemm_kernel<mxfp8,0>");
+                g.A = q.y + (size_t)r0 * q.K; g.lda = q.K;
+                gemm_mx_operands(g, q.s + r0, RT, lw.w8, lw.sw, lw.N);
+                if (!gate) gemm_attach_splitk(g, scratch);      // the K splits of the MX problem (K tiles twice as deep), not of the 16-bit one op_gemm chose for
                 if (qo && fuse_gemm_q) {
-                    const int ro = (int)((Cc.off - obase->off) / ((size_t)obase->ld * 2));
+                    const int ro = row_of(*obase, Cc);
                     g.C = nullptr; g.C8 = qo->y + (size_t)ro * qo->K; g.ldc8 = qo->K; g.c8_col = Cc.col - obase->col; g.SC = qo->s + ro; g.sc_ld = RT; g.splitk = 1;
                 }
-            }
+            });
         };
         // merge the two independent plain GEMM ops just emitted into one two-problem launch
         const bool group2 = g_plan_sw.flux_group;      // LDX_FLUX_GROUP=0: experiment switch
@@ -263,12 +256,14 @@ int FluxEngine::plan(int B, int h, int w, int Lt) {
                 return fuse_out;
             }
             const char* base = (const char*)ptr(QKV);
-            op_attn(name, base, QKV.ld, base + (size_t)C * 2, QKV.ld, base + (size_t)2 * C * 2, QKV.ld, O, 1, H, QKV.rows, QKV.rows, D);
-            AttnArgs& a = cur.ops.back().at;
-            if (!fx_fp8 || !qo || !(fuse_mask & 2) || !attn_pick(a).mx_out) return false;
-            const int ro = row_of(*obase, O);
-            a.O8 = qo->y + (size_t)ro * qo->K; a.ldo8 = qo->K; a.SO = qo->s + ro; a.so_ld = RT;
-            return true;
+            bool fuse_out = false;
+            op_attn(name, base, QKV.ld, base + (size_t)C * 2, QKV.ld, base + (size_t)2 * C * 2, QKV.ld, O, 1, H, QKV.rows, QKV.rows, D, [&](AttnArgs& a) {
+                if (!fx_fp8 || !qo || !(fuse_mask & 2) || !attn_pick(a).mx_out) return;
+                const int ro = row_of(*obase, O);
+                a.O8 = qo->y + (size_t)ro * qo->K; a.ldo8 = qo->K; a.SO = qo->s + ro; a.so_ld = RT;
+                fuse_out = true;
+            });
+            return fuse_out;
         };
 
         // ---- double-stream blocks ----
@@ -342,8 +337,7 @@ int FluxEngine::plan(int B, int h, int w, int Lt) {
         for (int b = 0; b < B; ++b) {
             const float* m = cur.fx_mod + (size_t)b * fx_mod_total + fx_final_mod_off;
             ln_mod("fx.final.norm", img_rows(X, b), img_rows(N1, b), m + 0 * C, m + 1 * C, Li);       // chunk order: shift, scale
-            op_gemm("fx.final.linear", img_rows(N1, b), fx_final, Act{}, Act{});
-            GemmArgs& g = cur.ops.back().g; g.C = nullptr; g.Cf = cur.fx_tok + (size_t)b * Li * inC; g.ldcf = inC;
+            op_gemm("fx.final.linear", img_rows(N1, b), fx_final, Act{}, Act{}, 0, [&](GemmArgs& g) { g.C = nullptr; g.Cf = cur.fx_tok + (size_t)b * Li * inC; g.ldcf = inC; });
         }
         release(N1); release(X);
         emit(OP_FX_UNPATCH, "fx.unpatchify").unpatch = FluxUnpatchArgs{cur.fx_tok, 4 * f.in_channels, nullptr, nullptr, nullptr, B, f.in_channels, h, w};      // x, sigma and out are the call's

@@ -72,21 +72,17 @@ int T5Engine::plan(int B, int L) {
         Act x = new_act(M, E);
         emit(OP_EMBED, "t5.embed").emb = ClipEmbedArgs{nullptr, t5_tok, nullptr, ptr(x), B, L, E, c.vocab_size, nullptr, 0};      // the ids are the call's
         Act n = new_act(M, E), qkv = new_act(M, 3 * E), a = new_act(M, E), f = new_act(M, F);
-        auto rms = [&](const char* name, Act X, Act Y, const NormW& w) {
-            op_ln(name, X, Y, w);
-            cur.ops.back().ln.eps = 1e-6f; cur.ops.back().ln.rms = 1;
-        };
+        auto rms = [&](const char* name, Act X, Act Y, const NormW& w) { op_ln(name, X, Y, w, [](LayerNormArgs& l) { l.eps = 1e-6f; l.rms = 1; }); };
         for (int l = 0; l < c.num_layers; ++l) {
             const T5LayerW& W = t5_layers[l];
             rms("t5.ln1", x, n, W.ln1);
             op_gemm("t5.qkv", n, W.qkv, qkv, Act{});
             const char* base = (const char*)ptr(qkv);
-            op_attn("t5.attn", base, 3 * E, base + (size_t)E * 2, 3 * E, base + (size_t)2 * E * 2, 3 * E, a, B, heads, L, L, D);
-            { Op& o = cur.ops.back(); o.at.scale = 1.0f; o.at.bias_ld = Lp; o.at.bias_hs = (long)L * Lp; o.bias_from_call = true; }
+            op_attn("t5.attn", base, 3 * E, base + (size_t)E * 2, 3 * E, base + (size_t)2 * E * 2, 3 * E, a, B, heads, L, L, D,
+                    [&](Op& o) { o.at.scale = 1.0f; o.at.bias_ld = Lp; o.at.bias_hs = (long)L * Lp; o.bias_from_call = true; });      // the relative-position table is the call's
             op_gemm("t5.o", a, W.o, x, x);                        // x += attention output
             rms("t5.ln2", x, n, W.ln2);
-            op_gemm("t5.wi", n, W.wi, f, Act{}, true);            // gelu_tanh(wi_0 n) * (wi_1 n)
-            cur.ops.back().g.geglu = 2;
+            op_gemm("t5.wi", n, W.wi, f, Act{}, 2);               // gelu_tanh(wi_0 n) * (wi_1 n)
             op_gemm("t5.wo", f, W.wo, x, x);                      // x += FF output
         }
         rms("t5.final_ln", x, n, t5_final_ln);

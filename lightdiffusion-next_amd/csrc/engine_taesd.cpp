@@ -66,7 +66,7 @@ int TaesdEngine::plan(int B, int h, int w) {
             const double M = (double)B * (Hin << up) * (Win << up);
             o.flops = 2.0 * M * wt.N * wt.K;
             o.bytes = 2.0 * ((double)B * Hin * Win * 64 + (double)wt.N * wt.K + (Y.valid ? M * 64 : 0.0)) + (Y.valid ? 0.0 : M * 3 * 5) + 4.0 * M * 64 * ((Rf.valid ? 1 : 0) + (Yf.valid ? 1 : 0));
-            snprintf(o.klabel, sizeof(o.klabel), "taesd_conv_kernel<%s,%d>", dt == DT_BF16 ? "bf16" : "f16", Y.valid ? 2 : 1);
+            snprintf(o.klabel, sizeof(o.klabel), "taesd_conv_kernel<%s,%d>", dt_name(), Y.valid ? 2 : 1);
             cur.flops += o.flops;
         };
         int H = h, W = w;

@@ -179,11 +179,13 @@ int UNetEngine::walk_weights() {
             ch = co;
             const int depth = cfg.transformer_depth[td_i++];
             if (ok && depth > 0) { blk.has_xf = true; ok = mk_xf(pre + ".1", ch, depth, blk.xf); }
+            blk.level = level; blk.ch = ch;
             w.in_blocks.push_back(std::move(blk)); chans.push_back(ch); ++ib;
         }
         if (ok && level != cfg.num_levels - 1) {
             BlockW blk; blk.has_down = true;
             ok = mk_conv3("input_blocks." + std::to_string(ib) + ".0.op", ch, ch, ch, blk.down);
+            blk.level = level + 1; blk.ch = ch;
             w.in_blocks.push_back(std::move(blk)); chans.push_back(ch); ++ib;
         }
     }
@@ -205,7 +207,7 @@ int UNetEngine::walk_weights() {
             const std::string pre = "output_blocks." + std::to_string(ob);
             const int ich = chans.back(); chans.pop_back();
             const int co = mc * cfg.channel_mult[level];
-            blk.has_res = true; blk.skip_ch = ich;
+            blk.has_res = true; blk.skip_ch = ich; blk.level = level; blk.ch = ch;
             ok = mk_res(pre + ".0", ch + ich, co, blk.res);
             ch = co;
             int sub = 1;
@@ -322,7 +324,7 @@ void UNetEngine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act 
     int Bq = Bshare > 0 ? Bshare : B, Mq = Bq * H * W;
     // which launches the level's stages run as; norm + proj_in become one rowgemm launch in fuse_gn_rowgemm, once norm's statistics come from its producer
     const XfPick pick = xf_pick(XfShape{C, heads, B, H * W, Mc, Bshare, x.blocks[0].ln_fold, 0});
-    auto head = [&](const Act& a) { Act v = a; v.rows = Mq; v.owned = false; return v; };      // the first Mq rows of a buffer
+    auto head = [&](const Act& a) { return rows(a, 0, Mq); };      // the first Mq rows of a buffer
     Act t1 = new_act(M, C);
     op_gn("xf.norm", X, t1, Bq, H * W, x.gn, 1e-6f, false);
     Act h = new_act(M, C);
@@ -333,9 +335,7 @@ void UNetEngine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act 
     auto norm_gemm = [&](XfStage st, const char* rowgemm_name, const char* ln_name, const char* name, const NormW& ln, const LinearW& w, const LinearW& wf, const float* c1, Act Cc, bool geglu) {
         if (st == XS_ROWBLOCK) { op_rowgemm(rowgemm_name, head(h), w, head(Cc), Act{}, 1, &ln); return; }
         if (st == XS_FOLDED) {
-            op_gemm(name, head(h), wf, head(Cc), Act{}, geglu);
-            GemmArgs& g = cur.ops.back().g;
-            g.ln_c1 = c1; g.ln_eps = 1e-5f;
+            op_gemm(name, head(h), wf, head(Cc), Act{}, geglu, [&](GemmArgs& g) { g.ln_c1 = c1; g.ln_eps = 1e-5f; });
             return;
         }
         if (!n.valid) n = new_act(M, C);
@@ -344,6 +344,7 @@ void UNetEngine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act 
         op_ln(ln_name, head(h), head(n), plain);
         op_gemm(name, head(n), st == XS_LN_FOLDED ? wf : w, head(Cc), Act{}, geglu);
     };
+    const AttnEdit prescaled = [](AttnArgs& a) { if (q_prescale()) a.scale = 1.0f / 1.44269504088896340736f; };      // the q rows of the projections already carry scale * log2(e) (mk_xf)
     // projection + residual into h, in place: x += W . a + b
     auto out_gemm = [&](XfStage st, const char* name, Act a, const LinearW& w) {
         if (st == XS_ROWBLOCK) op_rowgemm(name, a, w, head(h), head(h), 0, nullptr); else op_gemm(name, a, w, head(h), head(h));
@@ -355,8 +356,7 @@ void UNetEngine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act 
         norm_gemm(bp.qkv, "xf.ln1+qkv", "xf.ln1", "xf.qkv", b.ln1, b.qkv, b.qkv_f, b.c1_qkv, qkv, false);
         Act a = new_act(M, C);
         const char* base = (const char*)ptr(qkv);
-        op_attn("xf.attn1", base, 3 * C, base + (size_t)C * 2, 3 * C, base + (size_t)2 * C * 2, 3 * C, a, Bq, heads, H * W, H * W, D);
-        if (q_prescale()) cur.ops.back().at.scale = 1.0f / 1.44269504088896340736f;       // the q rows of the projection already carry scale * log2(e)
+        op_attn("xf.attn1", base, 3 * C, base + (size_t)C * 2, 3 * C, base + (size_t)2 * C * 2, 3 * C, a, Bq, heads, H * W, H * W, D, prescaled);
         release(qkv);
         out_gemm(bp.o1, "xf.o1", head(a), b.o1);                   // x += attn1(norm1(x))
         if (Bq != B) {
@@ -377,13 +377,12 @@ void UNetEngine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act 
             xa.scale = q_prescale() ? 1.0f / 1.44269504088896340736f : 1.0f / std::sqrt((float)D);
             o.flops = 2.0 * 2.0 * M * (double)C * C + 4.0 * B * heads * (double)(H * W) * Mc * D;
             o.bytes = 2.0 * 2.0 * (double)M * C;
-            snprintf(o.klabel, sizeof(o.klabel), "xattn_block<%s>", dt == DT_BF16 ? "bf16" : "f16");
+            snprintf(o.klabel, sizeof(o.klabel), "xattn_block<%s>", dt_name());
             cur.flops += o.flops;
         } else {
             Act q = new_act(M, C);
             norm_gemm(bp.q2, "xf.ln2+q2", "xf.ln2", "xf.q2", b.ln2, b.q2, b.q2_f, b.c1_q2, q, false);
-            op_attn("xf.attn2", ptr(q), C, kvb, un.kv_total, kvb + (size_t)C * 2, un.kv_total, a, B, heads, H * W, Mc, D);
-            if (q_prescale()) cur.ops.back().at.scale = 1.0f / 1.44269504088896340736f;       // the q rows of the projection already carry scale * log2(e)
+            op_attn("xf.attn2", ptr(q), C, kvb, un.kv_total, kvb + (size_t)C * 2, un.kv_total, a, B, heads, H * W, Mc, D, prescaled);
             release(q);
             out_gemm(bp.o2, "xf.o2", a, b.o2);                     // x += attn2(norm2(x), ctx)
         }
@@ -396,7 +395,7 @@ void UNetEngine::emit_xf(const XfW& x, Act X, Act OUT, int B, int H, int W, Act 
             fa.W1 = b.ff1.w; fa.b1 = b.ff1.b; fa.W2 = b.ff2.w; fa.b2 = b.ff2.b;
             o.flops = 2.0 * M * (double)C * (8.0 * C) + 2.0 * M * (double)C * (4.0 * C);
             o.bytes = 2.0 * 2.0 * (double)M * C;
-            snprintf(o.klabel, sizeof(o.klabel), "ff_block<%s>", dt == DT_BF16 ? "bf16" : "f16");
+            snprintf(o.klabel, sizeof(o.klabel), "ff_block<%s>", dt_name());
             cur.flops += o.flops;
         } else {
             Act f = new_act(M, 4 * C);
@@ -425,26 +424,21 @@ int UNetEngine::plan(int B2, int h, int w, int Mc, int share) {
     return build_plan(PlanKey{B2, h, w, Mc, share}, [&]() -> int {
         const int mc = cfg.model_channels, ted = 4 * mc;
         // fixed small buffers
-        const size_t o_temb = a_alloc((size_t)B2 * mc * 4), o_e1 = a_alloc((size_t)B2 * ted * 4), o_e2 = a_alloc((size_t)B2 * ted * 4);
-        const size_t o_emb = a_alloc((size_t)B2 * un.emb_total * 4);
+        auto f32buf = [&](size_t n) { float* p = arena_ptr<float>(n * 4); return cur.arena ? p : nullptr; };      // null in the dry pass: emit_res and the prep op test them
+        cur.d_temb_out = f32buf((size_t)B2 * mc); cur.d_e1 = f32buf((size_t)B2 * ted); cur.d_e2 = f32buf((size_t)B2 * ted); cur.d_emb_all = f32buf((size_t)B2 * un.emb_total);
         cur.gn_ws_off = a_alloc(gn_ws_bytes(B2, (long)h * w));
-        const size_t o_eps = a_alloc((size_t)B2 * h * w * cfg.out_channels * 4);
-        auto f32p = [&](size_t off) { return cur.arena ? (float*)((char*)cur.arena + off) : (float*)nullptr; };
-        cur.d_temb_out = f32p(o_temb); cur.d_e1 = f32p(o_e1); cur.d_e2 = f32p(o_e2); cur.d_emb_all = f32p(o_emb); cur.d_eps = f32p(o_eps);
+        cur.d_eps = f32buf((size_t)B2 * h * w * cfg.out_channels);
 
         // ---- level geometry & concat buffers (so skips are written in place, no torch.cat copy) ----
         struct Skip { Act act; int H, W; };
         std::vector<int> Hs{h}, Ws{w};
         for (int l = 1; l < cfg.num_levels; ++l) { Hs.push_back((Hs.back() + 1) / 2); Ws.push_back((Ws.back() + 1) / 2); }
-        // simulate the channel bookkeeping of the ctor to size the concat buffers of the output blocks
-        std::vector<int> in_ch{mc}, in_lv{0};
-        { int c = mc; for (int l = 0; l < cfg.num_levels; ++l) { for (int r = 0; r < cfg.num_res_blocks[l]; ++r) { c = mc * cfg.channel_mult[l]; in_ch.push_back(c); in_lv.push_back(l); }
-              if (l != cfg.num_levels - 1) { in_ch.push_back(c); in_lv.push_back(l + 1); } } }
+        // the walk's bookkeeping (BlockW::level, ch) sizes the concat buffers of the output blocks: skip s is conv_in's output (s = 0) or input block s - 1's;
+        // output block k consumes skip (n_skips - 1 - k) beside its own h channels
+        std::vector<int> in_ch{mc}, in_lv{0}, out_hch;
+        for (const BlockW& blk : un.in_blocks) { in_ch.push_back(blk.ch); in_lv.push_back(blk.level); }
+        for (const BlockW& blk : un.out_blocks) out_hch.push_back(blk.ch);
         const int n_skips = (int)in_ch.size();
-        // output block k consumes skip (n_skips-1-k); its h channels:
-        std::vector<int> out_hch(n_skips);
-        { int c = in_ch.back(); int k = 0;
-          for (int l = cfg.num_levels - 1; l >= 0; --l) for (int i = 0; i <= cfg.num_res_blocks[l]; ++i) { out_hch[k++] = c; c = mc * cfg.channel_mult[l]; } }
         std::vector<Act> cat(n_skips);
         for (int k = 0; k < n_skips; ++k) {
             const int s = n_skips - 1 - k, lv = in_lv[s];
@@ -472,8 +466,7 @@ int UNetEngine::plan(int B2, int h, int w, int Mc, int share) {
         }
         Act kvall = new_act(B2 * Mc, un.kv_total);
         cur.kv_all_off = kvall.off;
-        op_gemm("xf.kv2_all", ctx16, un.kv_all, kvall, Act{});
-        cur.ops.back().ctx_only = true;
+        op_gemm("xf.kv2_all", ctx16, un.kv_all, kvall, Act{}, 0, [](Op& o) { o.ctx_only = true; });
 
         int lv = 0, s = 0;
         Act hcur = skip_view(0);
@@ -530,7 +523,6 @@ int UNetEngine::plan(int B2, int h, int w, int Mc, int share) {
         int k = 0;
         Act final_h{};
         for (auto& blk : un.out_blocks) {
-            const int sidx = n_skips - 1 - k; (void)sidx;
             const bool last = (k == n_skips - 1);
             const int Hc = Hs[lv], Wc = Ws[lv], Mrows = B2 * Hc * Wc;
             // where does this block's result go?  column 0 of the next concat buffer (at the next block's resolution)
@@ -601,7 +593,7 @@ int UNetEngine::up_to_phase(const LinearW& w) {
         weight_bytes += bytes;
         up_phase.push_back({w.w, p, w.N, ph.Cin});
         u = &up_phase.back();
-        launch_up_phase(UpPhaseArgs{u->w9, u->wp, u->N, u->Cin, dt}, nullptr);
+        launch_up_phase(up_phase_args(u->w9, u->wp, u->N, u->Cin, dt), nullptr);
         HIP_OK(hipStreamSynchronize(nullptr));
         HIP_OK(hipGetLastError());
     }
@@ -617,7 +609,7 @@ int UNetEngine::up_to_phase(const LinearW& w) {
 }
 int UNetEngine::derive_up_phase() {
     if (up_phase.empty()) return LDX_OK;
-    for (const UpPhase& u : up_phase) launch_up_phase(UpPhaseArgs{u.w9, u.wp, u.N, u.Cin, dt}, nullptr);
+    for (const UpPhase& u : up_phase) launch_up_phase(up_phase_args(u.w9, u.wp, u.N, u.Cin, dt), nullptr);
     HIP_OK(hipStreamSynchronize(nullptr));
     HIP_OK(hipGetLastError());
     return LDX_OK;

@@ -153,16 +153,13 @@ void VaeEngine::emit_vae_attn(const VaeAttnW& a, Act X, Act OUT, int B, int H, i
     op_gemm("vae.attn.k", hn, a.k, k, Act{});
     Act o = new_act(M, C);
     for (int b = 0; b < B; ++b) {
-        auto rows = [&](const Act& t, int r0, int nr) { Act v = t; v.owned = false; v.off = t.off + (size_t)r0 * t.ld * 2; v.rows = nr; return v; };
-        // V^T[C][N] = Wv[C][C] . hn_b[N][C]^T   (weights as the A operand, activations as "W")
+        // V^T[C][N] = Wv[C][C] . hn_b[N][C]^T   (weights as the A operand, activations as "W": no Act holds the weights, so the op is built here; unsplit)
         Act vt = new_act(C, N);
-        { LinearW hw; hw.w = ptr(rows(hn, b * N, N)); hw.b = nullptr; hw.N = N; hw.K = C;
-          Act wv; wv.valid = true; wv.rows = C; wv.C = C; wv.ld = C; wv.off = 0; wv.col = 0;
-          Op& oo = emit(OP_GEMM, "vae.attn.vT");
-          GemmArgs& g = oo.g; g.A = a.v.w; g.lda = C; g.W = hw.w; g.M = C; g.N = N; g.K = C; g.mode = 0; g.rows_per_batch = 1;
+        { Op& oo = emit(OP_GEMM, "vae.attn.vT");
+          GemmArgs& g = oo.g = gemm_linear_args(a.v.w, C, ptr(rows(hn, b * N, N)), C, N, C);
           g.C = ptr(vt); g.ldc = N; g.splitk = 1;
-          oo.flops = 2.0 * C * (double)N * C; snprintf(oo.klabel, sizeof(oo.klabel), "gemm_kernel<%s,0>", dt == DT_BF16 ? "bf16" : "f16");
-          cur.flops += oo.flops; (void)wv; }
+          oo.flops = 2.0 * C * (double)N * C; snprintf(oo.klabel, sizeof(oo.klabel), "gemm_kernel<%s,0>", dt_name());
+          cur.flops += oo.flops; }
         // Query rows in chunks of Rc: S_c[Rc][N] = q_c k_b^T, row softmax, O_c = P_c V.  The score matrix is never materialised as a whole
         // (N x N at 2048^2 is 8 GiB and was the arena's peak; at 4096^2 it would be 128 GiB): one chunk is <= 2 GiB, so a 1024^2 decode still runs
         // the three launches it always ran and a 2048^2 decode 4 x 3 (measured at 2048^2: one chunk 69.3 ms, 512 MiB chunks 71.9, 128 MiB 72.1; the
@@ -223,8 +220,7 @@ int VaeEngine::plan_decode(int B, int h, int w) {
         Act t = new_act(B * H * W, Cl);
         op_gn("vae.norm_out", hcur, t, B, H * W, vae_norm_out, 1e-6f, true);
         release(hcur);
-        const size_t o_pix = a_alloc((size_t)B * H * W * v.out_ch * 4);
-        float* pix = (float*)((uintptr_t)cur.arena + o_pix);
+        float* pix = arena_ptr<float>((size_t)B * H * W * v.out_ch * 4);
         op_conv("vae.conv_out", t, B, H, W, Cl, vae_conv_out, 1, H, W, Act{}, Act{}, nullptr, 0, pix, v.out_ch);
         release(t);
         emit(OP_CLAMP, "vae.clamp").clamp = ClampArgs{pix, nullptr, (size_t)(B * H * W * v.out_ch)};
@@ -261,8 +257,7 @@ int VaeEngine::plan_encode(int B, int Hpx, int Wpx) {
                 // Downsample: F.pad(x, (0,1,0,1)) then 3x3 stride-2 conv without padding (VariationalAE.py:224-254)
                 const int Cc = enc_down[lv].back().Cout, Ho = H / 2, Wo = W / 2;
                 Act o = new_act(B * Ho * Wo, Cc);
-                op_conv("vae.enc.down", hcur, B, H, W, Cc, enc_downconv[lv], 2, Ho, Wo, o, Act{});
-                cur.ops.back().g.pad0 = 1;
+                op_conv("vae.enc.down", hcur, B, H, W, Cc, enc_downconv[lv], 2, Ho, Wo, o, Act{}, nullptr, 0, nullptr, 0, [](GemmArgs& g) { g.pad0 = 1; });
                 release(hcur); hcur = o; H = Ho; W = Wo;
             }
         }
@@ -273,8 +268,7 @@ int VaeEngine::plan_encode(int B, int Hpx, int Wpx) {
         Act t = new_act(B * H * W, Cl);
         op_gn("vae.enc.norm_out", hcur, t, B, H * W, enc_norm_out, 1e-6f, true);
         release(hcur);
-        const size_t o_m = a_alloc((size_t)B * H * W * zc2 * 4);
-        float* mom = (float*)((uintptr_t)cur.arena + o_m);
+        float* mom = arena_ptr<float>((size_t)B * H * W * zc2 * 4);
         op_conv("vae.enc.conv_out", t, B, H, W, Cl, enc_conv_out, 1, H, W, Act{}, Act{}, nullptr, 0, mom, zc2);
         release(t);
         emit(OP_MOMENTS, "vae.enc.quant_conv").mix = MixArgs{mom, zc2, nullptr, B, zc2, H * W, enc_qc, enc_qc ? enc_qc + zc2 * zc2 : nullptr};

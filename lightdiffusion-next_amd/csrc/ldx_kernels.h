@@ -6,6 +6,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
+
+#include <functional>
 
 namespace ldx {
 
@@ -97,6 +100,12 @@ struct GemmArgs {
 bool gemm_upconv_phase(const GemmArgs& g, bool planned, GemmArgs* ph);
 // The phase weights of one up conv: Wp[4][N][4 * Cin] from the packed 9-tap W9[N][9 * Cin] (both 16-bit, on the device); weight_layout.h up_phase_group
 struct UpPhaseArgs { const void* W9; void* Wp; int N, Cin; DType dt; };
+// ... with every byte defined, the tail padding too (the launch recorders, tests/tools/plan_trace.py and tests/test_op_trace_cpu.py, compare argument bytes)
+inline UpPhaseArgs up_phase_args(const void* W9, void* Wp, int N, int Cin, DType dt) {
+    UpPhaseArgs a; memset(&a, 0, sizeof(a));
+    a.W9 = W9; a.Wp = Wp; a.N = N; a.Cin = Cin; a.dt = dt;
+    return a;
+}
 void launch_up_phase(const UpPhaseArgs& a, hipStream_t s);
 // Can launch_gemm(a) produce GroupNorm statistics for a consumer GroupNorm(G groups) over [B][HW][a.N]?  If yes, returns the number of
 // tile rows per batch image (the consumer's chunk count) and fills a.gn_* except gn_partial; 0 = not fusable (the GroupNorm runs its own pass).
@@ -129,6 +138,36 @@ inline size_t gemm_sk_ws_floats(int M, int N, int S) { return (size_t)S * ((size
 inline size_t gemm_sk_ws_floats(int M, int N, int S) { return (size_t)S * (size_t)M * (size_t)N; }      // [S][M][N] fp32 partials for the reduce launch (the slab layout only exists in fix-up builds)
 #endif
 bool gemm_sk_fixup(const GemmArgs& a);                     // will launch_gemm(a) reduce inside the kernel?  (opt-in: LDX_SK_FIXUP=1; measured slower than the reduce launch)
+
+// ---- where launch arguments are built: the planner's op emitters (engine.cpp) and the single-op C ABI (capi.cpp) both come here ----
+// What a builder takes scratch from: bytes(n) = n bytes that live for the launch being built (the engine: an arena range; the single-op entry points: their one
+// per-device buffer, so no launch may ask twice, and none does), counters() = the zeroed split-K tile counters.
+struct Scratch { std::function<void*(size_t)> bytes; std::function<unsigned*()> counters; };
+// The base fill of a plain GEMM / a 3x3 conv (K = 9 * Cin, + Cin2 with GemmArgs::A2; resize_to_out: the window walks the input resized to the output extent), every
+// other byte zero, the padding too (the launch recorders compare argument bytes).  The caller adds the epilogue operands, then gemm_attach_splitk.
+inline GemmArgs gemm_linear_args(const void* A, int lda, const void* W, int M, int N, int K) {
+    GemmArgs g; memset(&g, 0, sizeof(g));
+    g.A = A; g.lda = lda; g.W = W; g.M = M; g.N = N; g.K = K; g.rows_per_batch = 1;
+    return g;
+}
+inline GemmArgs gemm_conv_args(const void* X, int ldx, const void* W, int B, int Hin, int Win, int Cin, int N, int K, int stride, int Hout, int Wout, bool resize_to_out) {
+    GemmArgs g = gemm_linear_args(X, ldx, W, B * Hout * Wout, N, K);
+    g.mode = 1; g.Cin = Cin; g.Hin = Hin; g.Win = Win; g.Hout = Hout; g.Wout = Wout; g.stride = stride;
+    g.Hv = resize_to_out ? Hout : Hin; g.Wv = resize_to_out ? Wout : Win;
+    g.resize = (g.Hv != Hin || g.Wv != Win) ? 1 : 0;
+    g.rows_per_batch = Hout * Wout;
+    return g;
+}
+// MX fp8 operands: A (already the e4m3 bytes) with scales SA, W8 with scales SW
+inline void gemm_mx_operands(GemmArgs& g, const uint32_t* SA, int sa_ld, const void* W8, const uint32_t* SW, int sw_ld) { g.f8 = 1; g.SA = SA; g.sa_ld = sa_ld; g.W = W8; g.SW = SW; g.sw_ld = sw_ld; }
+// The K splits of `g` as it stands, their workspace and counters: an MX fp8 K-tile is twice as deep, GEGLU and MX output never split.  Whoever changes the epilogue
+// afterwards may only lower splitk to 1 (the workspace then stays in the arguments, unused) ...
+inline void gemm_attach_splitk(GemmArgs& g, const Scratch& s) {
+    g.splitk = g.C8 ? 1 : gemm_choose_splitk(g.M, g.N, g.f8 ? g.K / 2 : g.K, g.geglu != 0);
+    if (g.splitk > 1) { g.ws = (float*)s.bytes(gemm_sk_ws_floats(g.M, g.N, g.splitk) * 4); g.sk_count = s.counters(); }
+}
+// ... and must, for the epilogues launch_gemm has no split-K form of: such a launch would compute a K slice and never reduce it
+inline bool gemm_splitk_ok(const GemmArgs& g) { return g.splitk <= 1 || !(g.ln_c1 || g.gate || g.C8 || g.geglu || g.up2x); }
 // 256-row ping-pong tiles (gemm_pp.hip; GemmPick family GF_PP* ): bn = the tile width as gemm_pick gives it, lnf = GemmArgs::ln_c1 fold, S = K splits
 void launch_gemm_pp(const GemmArgs& a, int bn, bool lnf, int S, DType dt, hipStream_t s);
 void launch_gemm_pp2(const GemmArgs& a, const GemmArgs& b, int bn, DType dt, hipStream_t s);
@@ -205,6 +244,21 @@ void launch_attn_pipe128(const AttnArgs& a, const AttnPick& p, DType dt, hipStre
 void launch_attn512(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s);
 size_t attn512_ws_floats(const AttnArgs& a, int nsplit);
 void launch_attn_knorm(const AttnArgs& a, DType dt, hipStream_t s);      // key-block norms for either pipelined kernel (AttnArgs::knorm_ws)
+// The base fill of an attention launch, every other byte zero (the padding too), and the scratch of `a` once every other field is final: the key-block norms where
+// the pipelined kernels' shape rule holds, the partials of attn512's key splits where attn_pick asks for them (never both: D = 40 / 128 against D = 512); returns the pick
+inline AttnArgs attn_args(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int B, int H, int Nq, int Mk, int D, float scale) {
+    AttnArgs a; memset(&a, 0, sizeof(a));
+    a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = O; a.ldo = ldo; a.B = B; a.H = H; a.Nq = Nq; a.Mk = Mk; a.D = D; a.scale = scale;
+    return a;
+}
+inline AttnPick attn_attach_scratch(AttnArgs& a, const Scratch& s) {
+    if (attn_pipe_ok(a)) a.knorm_ws = (float*)s.bytes((size_t)a.B * a.H * ((a.Mk + 63) / 64) * 4);
+    const AttnPick p = attn_pick(a);
+    if (p.nsplit_want <= 1) return p;
+    a.nsplit = p.nsplit_want;
+    a.split_ws = (float*)s.bytes(attn512_ws_floats(a, a.nsplit) * 4);
+    return attn_pick(a);
+}
 
 // Cross-attention sub-block as one kernel (xattn_block.hip): H[m][:] += to_out(softmax(to_q(LayerNorm(H[m][:])) . K_b^T) . V_b) + bo, in place,
 // for m in [0, M), image b = m / N.  Wq / Wo: [C][C] 16-bit, row = output feature.  K / V: the projected context, rows b * Mk + key, head h at

@@ -143,10 +143,12 @@ def build_host():
     if not os.path.exists(kernel_resources.LIB):
         subprocess.run(["make", "-C", CSRC, "-j8"], check=True, capture_output=True)
     subprocess.run(["make", "-C", CSRC, "host", "-j8"], check=True, capture_output=True)
-    # the load-time packers' kernels are in the second, the TAESD decoder's in the third
-    libs = (kernel_resources.LIB,) + tuple(os.path.join(os.path.dirname(kernel_resources.LIB), n) for n in ("libldx_pack.so", "libldx_taesd.so"))
+    # the load-time packers' kernels are in the second, the TAESD decoder's in the third, the phase-form up conv's in the fourth
+    libs = (kernel_resources.LIB,) + tuple(os.path.join(os.path.dirname(kernel_resources.LIB), n) for n in ("libldx_pack.so", "libldx_taesd.so", "libldx_upconv.so"))
     if not os.path.exists(ARG_SIZES) or os.path.getmtime(ARG_SIZES) < max(map(os.path.getmtime, libs)):
-        sizes = dict(kernel_arg_sizes(libs[2]), **dict(kernel_arg_sizes(libs[1]), **kernel_arg_sizes(libs[0])))
+        sizes = {}
+        for lib in reversed(libs):
+            sizes.update(kernel_arg_sizes(lib))
         with open(ARG_SIZES, "w") as f:
             f.write("".join(f"{k} {' '.join(map(str, v))}\n" for k, v in sorted(sizes.items())))
 
