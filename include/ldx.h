@@ -243,8 +243,10 @@ int ldx_set_graph_mode(ldx_engine* e, int enable);
  * created (a captured graph is tied to the pointers of the call that recorded it: a caller that alternates buffers re-captures instead of
  * replaying — sampling.CFGDenoiser stages such inputs through one persistent buffer per shape). */
 int ldx_graph_stats(ldx_engine* e, int64_t* captures, int64_t* replays);
-/* The kernel-dispatch experiment switches (LDX_ATTN_PIPE, LDX_ATTN_PIPE128, LDX_ATTN_PIPE_MINWG, LDX_ATTN_PIPE_THR) are read ONCE when the library
- * is loaded — no getenv on the launch path.  Tests and same-process A/B runs that change them afterwards call this to re-read them. */
+/* Every LDX_* switch of the library is read from the environment ONCE when the library is loaded (two when a UNet engine is created) — never on a launch path.
+ * This re-reads the attention dispatch switches, all of them and nothing else: the fields of AttnSwitches (csrc/ldx_switches.h; LDX_ATTN_PIPE*, LDX_ATTN32*,
+ * LDX_ATTN_KPF, LDX_ATTN512, LDX_ATTN512_SPLITS).  For tests and same-process A/B runs that change one after loading; the GEMM and planner switches stay as
+ * loaded, because plans bake them into their op lists. */
 int ldx_reload_env(void);
 
 /* ---- VAE decode and CLIP text encode (same ldx_engine handle type; load/finalize/destroy as above) ---------- */

@@ -29,28 +29,21 @@
 
 namespace ldx {
 
-constexpr int AT_KV = 64;         // keys per block
+// AT_KV keys per block (ldx_geometry.h, with the LDS row strides attn_krowb / attn_vrowb: attn_pick plans with them)
 // queries per wave = 16 * QT, per workgroup = 64 * QT (QT = 2, or 4 for small head dims where the
 // accumulators fit: K/V staging and fragment reads are then amortised over twice the queries)
-
-// LDS row strides.  K rows: KS*64 B + 32 B pad -> the four 16-lane groups of ds_read_b128 are conflict-free
-// (brute-forced over the real lane groups).  V rows: >= DT*32 B and == 32 (mod 64) so the 8 key rows a
-// 32-lane half touches in one ds_read_b64_tr_b16 tile the 64 banks.
-template <int KS, int DT> struct AttnCfg {
-    static constexpr int KROWB = KS * 64 + 32;
-    static constexpr int VROWB = (DT * 32) % 64 == 0 ? DT * 32 + 32 : DT * 32;
-};
 
 template <typename T, int KS, int DT, int QT>
 __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnArgs p) {
     constexpr int AT_QW = 16 * QT, AT_QB = 64 * QT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using V8 = typename Vec<T>::v8;
-    constexpr int KROWB = AttnCfg<KS, DT>::KROWB;
-    constexpr int VROWB = AttnCfg<KS, DT>::VROWB;
+    constexpr int KROWB = attn_krowb(KS);
+    constexpr int VROWB = attn_vrowb(DT);
     constexpr int KBYTES = AT_KV * KROWB;
     constexpr int VBYTES = AT_KV * VROWB;
     constexpr int STAGE = KBYTES + VBYTES;
+    static_assert(2 * STAGE == attn_lds(KS, DT), "attn_pick (attn_pick.cpp) plans with this");
     constexpr int MAXCH = (KS * 4 > DT * 2) ? KS * 4 : DT * 2;     // upper bound on D/8
     constexpr int NLD = (AT_KV * MAXCH + 255) / 256;                // staging chunks per thread
 
@@ -334,6 +327,7 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(const AttnArgs p) {
     // stride must be an ODD number of 16-B chunks (9: 144 B).  V rows are read by ds_read_b64_tr_b16, 8 lanes x 8 B per row and
     // 4 rows per 32-lane group: the four 64-B windows tile the 64 banks when the stride is 64 B times an odd number (3: 192 B).
     constexpr int KBYTES = KVB * KROWB, VBYTES = KVB * VROWB, STAGE = KBYTES + VBYTES;
+    static_assert(KROWB == A32_KROW && VROWB == A32_VROW && 2 * STAGE == attn32_lds(KVB), "attn_pick (attn_pick.cpp) plans with these strides");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using V8 = typename Vec<T>::v8;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -568,20 +562,13 @@ __global__ __launch_bounds__(256, 2) void attn32_kernel(const AttnArgs p) {
 // and V rows to 64*NDT + 32 B so that both fragment reads stay bank-conflict free.
 // ONES: denominator from a ones column of V (row D of O^T, needs D + 1 <= 32*NDT); otherwise (D a multiple of 32: the ones row would
 // cost a whole extra d tile) the fp32 P values are summed on the VALU per lane and the two halves are added once at the end.
-// LDS row strides of the generic kernel, same rules as attn32_kernel: K rows an odd number of 16-B chunks, V rows 64 B times an
-// odd number (LDX_G32_OLD_ROWS at build time restores the first layout for A/B)
-#ifdef LDX_G32_OLD_ROWS
-#define G32_KROW(NKS) (((NKS) & 1) ? (NKS) * 32 : (NKS) * 32 + 32)
-#define G32_VROW(NDT) ((NDT) * 64 + 32)
-#else
-#define G32_KROW(NKS) ((NKS) * 32 + 16)
-#define G32_VROW(NDT) (((NDT) & 1) ? (NDT) * 64 : (NDT) * 64 + 64)
-#endif
+// LDS row strides: G32_KROW / G32_VROW (ldx_geometry.h)
 template <typename T, int NKS, int NDT, int QT, bool ONES, bool KPFON = true>
 __global__ __launch_bounds__(256, 2) void attn32g_kernel(const AttnArgs p) {
     constexpr int QW = 32 * QT, QB = 4 * QW;
     constexpr int KROW = G32_KROW(NKS), VROW = G32_VROW(NDT);
     constexpr int KBYTES = AT_KV * KROW, VBYTES = AT_KV * VROW, STAGE = KBYTES + VBYTES;
+    static_assert(2 * STAGE == attn32g_lds(NKS, NDT), "attn_pick (attn_pick.cpp) plans with this");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using V8 = typename Vec<T>::v8;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -859,137 +846,7 @@ __global__ __launch_bounds__(256, 2) void attn32g_kernel(const AttnArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Which kernel launch_attention takes: attn_pick() below, pure host arithmetic over the arguments and these switches.
-// Every runtime LDX_ATTN* switch of the launch path, read ONCE when the library loads — the launch path itself never calls getenv.  Experiments and tests that
-// flip a switch inside one process call reload_dispatch_env() (C ABI: ldx_reload_env) after changing the environment.
-struct AttnSwitches {
-    bool pipe, pipe128;            // LDX_ATTN_PIPE / LDX_ATTN_PIPE128 = 0: the pipelined D = 40 / D = 128 kernels off (attn32ap / attn32, attn32g instead)
-    long pipe_minwg40, pipe_minwg128;      // LDX_ATTN_PIPE_MINWG: fewest 256-query workgroups they take (256: the chip; 192: three quarters of the CUs in one round)
-    float pipe_thr;                // LDX_ATTN_PIPE_THR: their rescale threshold (tests force the rare path with small values); NaN = the type's own
-    bool pipe_kb;                  // LDX_ATTN_PIPE_KB = 0 (experiment): the exact maximum on every key block even with AttnArgs::knorm_ws
-    int attn32;                    // LDX_ATTN32 = 0: D = 40 back on the 16x16 kernel.  On 32x32x16 MFMAs: +4.6 % in isolation, +2.2 % on the whole step
-    // LDX_ATTN32_AP, the 8-wave two-group kernel (round 3, attn32ap.inc) when its 512-query workgroups still fill the chip (LDX_ATTN32_AP_MINWG): 0 off, 1 (default) phases
-    // separated by the barriers only (hipcc interleaves the next PV MFMAs with the softmax), 2 strict phases, 3 strict + s_setprio around the MFMAs.
-    // Same box, B2 H8 N16384 D40: attn32_kernel 1.197 ms, strict 1.14-1.21, default 1.12-1.15; step 60.02 -> 61.18 it/s.
-    int ap; long ap_minwg;
-    // attn32_kernel: LDX_ATTN32_VAR 1: V^T fragments prefetched before the softmax (1.219 -> 1.206 ms at B2 H8 N16384, twice on one box); 0: read at the PV MFMAs, and then
-    // LDX_ATTN32_KVB = 128 (experiment) stages 128 keys per block from Mk = 1024 on
-    int kvb, var;
-    bool kpf;                      // LDX_ATTN_KPF = 0: attn32g without its K fragment prefetch ring (round 3): hipcc's just-in-time reads
-    // head dims served by the generic 32x32x16 kernel (LDX_ATTN32G bit mask 1: D=80, 2: D=160, 4: D=128, 8: D=64).  Default 7: same-box step A/B 54.76 -> 55.34 it/s with
-    // D = 80 and 160; D = 128 (Flux, VALU denominator instead of a fifth d tile) 19.6 -> 18.4 ms of attention per forward; D = 64 only appears with a causal mask or a
-    // bias on this path.  LDX_ATTN32G_MINWG 64 -> 16: +0.9 % on the 512^2 step (the 16x16 D = 160 instantiation spills)
-    int g32_mask; long g32_minwg;
-    bool a512; int a512_splits;    // LDX_ATTN512 = 0: no D = 512 kernel (the VAE falls back to GEMMs and a row softmax); LDX_ATTN512_SPLITS > 0 forces its key-split count
-};
-static AttnSwitches read_attn_switches() {
-    auto num = [](const char* name, long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; };
-    auto unless0 = [](const char* name) { const char* v = getenv(name); return !(v && atoi(v) == 0); };
-    AttnSwitches w;
-    const char* t = getenv("LDX_ATTN_PIPE_THR");
-    w.pipe = unless0("LDX_ATTN_PIPE"); w.pipe128 = unless0("LDX_ATTN_PIPE128"); w.pipe_kb = unless0("LDX_ATTN_PIPE_KB"); w.pipe_thr = t ? (float)atof(t) : __builtin_nanf("");
-    w.pipe_minwg40 = num("LDX_ATTN_PIPE_MINWG", 256); w.pipe_minwg128 = num("LDX_ATTN_PIPE_MINWG", 192);
-    w.attn32 = (int)num("LDX_ATTN32", 1); w.ap = (int)num("LDX_ATTN32_AP", 1); w.ap_minwg = num("LDX_ATTN32_AP_MINWG", 256);
-    w.kvb = (int)num("LDX_ATTN32_KVB", 64); w.var = (int)num("LDX_ATTN32_VAR", 1);
-    w.kpf = unless0("LDX_ATTN_KPF"); w.g32_mask = (int)num("LDX_ATTN32G", 7); w.g32_minwg = num("LDX_ATTN32G_MINWG", 16);
-    w.a512 = unless0("LDX_ATTN512"); w.a512_splits = (int)num("LDX_ATTN512_SPLITS", 0);
-    return w;
-}
-static AttnSwitches g_attn_sw = read_attn_switches();
-void reload_dispatch_env() { g_attn_sw = read_attn_switches(); }
-
-// Shapes the special-purpose kernels take.  attn512.hip: one head of D = 512 (VAE mid-block attention)
-static bool attn512_ok(const AttnArgs& a) {
-    return a.D == 512 && !a.causal && !a.bias && !a.O8 && a.Nq > 0 && a.Mk > 0 && a.B > 0 && a.H > 0 && a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 4 == 0;
-}
-// its key splits: enough workgroups for the chip (>= 224 of 256 CUs), never more than 8, each split at least 16 key blocks
-static int attn512_splits(const AttnArgs& a, int force) {
-    const long wgs = (long)((a.Nq + ATTN512_QB - 1) / ATTN512_QB) * a.H * a.B;
-    const int nblk = (a.Mk + ATTN512_KV - 1) / ATTN512_KV;
-    int s = force > 0 ? force : (int)((255 + wgs) / wgs);
-    if (s > 8) s = 8;
-    while (s > 1 && nblk / s < 16) --s;
-    if (force > 0 && s > nblk) s = nblk;
-    return s < 1 ? 1 : s;
-}
-// attn_pipe.hip (D = 40, 16-bit output) and attn_pipe128.hip (D = 128, 16-bit or MX fp8 output): whole 256-query workgroups, whole pairs of key blocks, 16-byte rows
-bool attn_pipe_ok(const AttnArgs& a) {
-    if ((a.D != 40 && a.D != 128) || a.causal || a.bias || a.Nq % 256 || a.Mk % 128 || a.Mk < 256 || a.ldq % 8 || a.ldk % 8 || a.ldv % 8) return false;
-    if (a.D == 40) return !a.O8 && a.ldo % 4 == 0;
-    return a.O8 ? (a.ldo8 % 16 == 0 && ((uintptr_t)a.O8 & 15) == 0) : (a.ldo % 8 == 0 && ((uintptr_t)a.O & 15) == 0);
-}
-// the head dim the generic 32x32x16 kernel takes `a` at, 0: not taken
-static int attn32g_dim(const AttnArgs& a, const AttnSwitches& w) {
-    if (!w.g32_mask || a.causal || a.bias || (long)((a.Nq + 127) / 128) * a.H * a.B < w.g32_minwg) return 0;
-    const int bit = a.D == 80 ? 1 : a.D == 160 ? 2 : a.D == 128 ? 4 : a.D == 64 ? 8 : 0;
-    return (w.g32_mask & bit) ? a.D : 0;
-}
-
-AttnPick attn_pick(const AttnArgs& a) {
-    const AttnSwitches& w = g_attn_sw;
-    AttnPick p{};
-    p.thr = w.pipe_thr;
-    p.mx_out = attn32g_dim(a, w) == 128;
-    if (a.Nq <= 0 || a.B <= 0) return p;
-    auto take = [&](AttnFamily f, int t0, int t1, int t2, int qb, int block, int lds) {
-        p.family = f; p.targ[0] = t0; p.targ[1] = t1; p.targ[2] = t2; p.qb = qb; p.block = block; p.lds = lds;
-        p.grid = (unsigned)(((a.Nq + qb - 1) / qb) * a.H * a.B);
-        p.nsplit = p.launches = 1;
-    };
-    const long wg256 = (long)((a.Nq + 255) / 256) * a.H * a.B;      // 256-query workgroups
-    if (w.a512 && attn512_ok(a)) {
-        take(AF_ATTN512, 0, 0, 0, ATTN512_QB, 256, ATTN512_LDS);
-        p.nsplit_want = attn512_splits(a, w.a512_splits);
-        p.nsplit = a.nsplit > 1 && a.split_ws ? a.nsplit : 1;        // no workspace: one workgroup walks all keys of its query block
-        p.grid *= (unsigned)p.nsplit;
-        p.launches = p.nsplit > 1 ? 2 : 1;
-        return p;
-    }
-    // D = 40 self-attention of the large levels: the software-pipelined one-wave-per-SIMD kernel when its 256-query workgroups fill the chip;
-    // D = 128 (Flux): the same pipeline when one round of them covers at least three quarters of the CUs
-    if (attn_pipe_ok(a) && (a.D == 40 ? w.pipe && wg256 >= w.pipe_minwg40 : w.pipe128 && wg256 >= w.pipe_minwg128)) {
-        if (a.D == 40) take(AF_ATTN40P, 0, 0, 0, 256, 256, ATTN40P_LDS); else take(AF_ATTN128P, 0, 0, 0, 256, 256, ATTN128P_LDS);
-        p.knorm = a.knorm_ws && w.pipe_kb;
-        p.launches = p.knorm ? 2 : 1;
-        return p;
-    }
-    if (const int d = attn32g_dim(a, w)) {
-        const bool ones = d == 80 || d == 160;                        // the denominator from a ones row of V (one d tile more at 160); 128, 64: summed on the VALU
-        const int nks = d / 16, ndt = d / 32 + (ones ? 1 : 0);        // k-steps of 16, d tiles of 32
-        take(AF_ATTN32G, nks, ndt, ones, 128, 256, 2 * AT_KV * (G32_KROW(nks) + G32_VROW(ndt)));
-        p.kpf = w.kpf;
-        return p;
-    }
-    // 16x16 kernel: KS = ceil(D/32) contraction steps, DT output tiles with room for the ones column at d = D (the instantiations that exist, by largest D)
-    static const struct { int dmax, ks, dt; } ladder[] = {{15, 1, 1}, {31, 1, 2}, {32, 1, 3}, {47, 2, 3}, {63, 2, 4}, {64, 2, 5}, {79, 3, 5}, {95, 3, 6}, {96, 3, 7},
-                                                          {127, 4, 8}, {128, 4, 9}, {159, 5, 10}, {1 << 30, 5, 11}};
-    int i = 0;
-    while (a.D > ladder[i].dmax) ++i;
-    const int ks = ladder[i].ks, dt = ladder[i].dt;
-    if (ks == 2 && dt == 3 && w.attn32 && !a.causal && !a.bias && a.D > 32 && a.D % 8 == 0 && wg256 >= 512) {      // D = 40 (SD1.5 level 0) on 32x32x16 MFMAs
-        if (w.ap && a.Mk >= 64 && (long)((a.Nq + 511) / 512) * a.H * a.B >= w.ap_minwg) {
-            int var = w.ap == 2 ? 0 : w.ap == 3 ? 1 : 2;      // the kernel's VAR: 2 = phases separated by the barriers only
-#ifdef LDX_ATTN_ABLATE      // profiles/ubench/README.md round 3, measured and not adopted (correct, bit-identical): 6 split softmax (VAR & 64), +6 %; 7 K fragments read a phase early (VAR & 128), +-0.5 %;
-            // timing ablations (wrong results): 4 no MFMAs, 8 no softmax, 12 neither (staging + barriers + fragment reads), 34 the default schedule without the 64 fma of exp2(s * c - m * c)
-            var = w.ap == 6 ? 66 : w.ap == 7 ? 130 : w.ap == 4 || w.ap == 8 || w.ap == 12 || w.ap == 34 ? w.ap : var;
-#endif
-            take(AF_ATTN32AP, var, 0, 0, 512, 512, 2 * 64 * (144 + 192));
-            return p;
-        }
-        // K / V row strides 144 / 192 B: 160 / 160 had 2-way conflicts on every fragment read (SQ_LDS_BANK_CONFLICT 88.1 M -> 21.0 M cycles per launch;
-        // same time at D = 40, which is VALU / MFMA bound)
-        const int kvb = w.var != 1 && w.kvb == 128 && a.Mk >= 1024 ? 128 : 64;
-        take(AF_ATTN32, kvb, w.var == 1, 0, 256, 256, 2 * kvb * (144 + 192));
-        return p;
-    }
-    // 64 queries per wave (QT = 4) when the accumulators fit (DT <= 3) and the grid still fills the chip.  D >= 144 (DT >= 10): two 16-query tiles per wave need 12 more
-    // VGPRs than the file has (40 B of scratch per lane, hipcc -Rpass-analysis): one tile per wave there.  Only small grids / masked calls get here (attn32g takes the rest).
-    const int qt = dt <= 3 && wg256 >= 512 && !a.causal ? 4 : dt >= 10 ? 1 : 2;
-    take(AF_ATTN, ks, dt, qt, 64 * qt, 256, 2 * AT_KV * (ks * 64 + 32 + ((dt * 32) % 64 == 0 ? dt * 32 + 32 : dt * 32)));
-    return p;
-}
-
-// every instantiation behind launch_attention, as attn_pick names them in AttnPick::targ
+// every instantiation behind launch_attention, as attn_pick (attn_pick.cpp) names them in AttnPick::targ
 #define ATTN_KERNEL_INSTANCES(X) X(1, 1, 2) X(1, 1, 4) X(1, 2, 2) X(1, 2, 4) X(1, 3, 2) X(1, 3, 4) X(2, 3, 2) X(2, 3, 4) X(2, 4, 2) X(2, 5, 2) X(3, 5, 2) X(3, 6, 2) X(3, 7, 2) \
                                  X(4, 8, 2) X(4, 9, 2) X(5, 10, 1) X(5, 11, 1)                                             /* KS, DT, QT */
 #define ATTN32G_INSTANCES(X) X(5, 3, true) X(10, 6, true) X(8, 4, false) X(4, 2, false)                                    /* NKS, NDT, ONES: D = 80, 160, 128, 64 */
@@ -1007,10 +864,10 @@ static void launch_picked(const AttnPick& p, const AttnArgs& a, hipStream_t s) {
 #define X(KS, DT, QT) if (t0 == KS && t1 == DT && t2 == QT) ATTN_LAUNCH(attn_kernel<T, KS, DT, QT>)
         case AF_ATTN: ATTN_KERNEL_INSTANCES(X) break;
 #undef X
-#define X(KVB, VAR) if (t0 == KVB && t1 == VAR) ATTN_LAUNCH(attn32_kernel<T, KVB, 144, 192, VAR>)
+#define X(KVB, VAR) if (t0 == KVB && t1 == VAR) ATTN_LAUNCH(attn32_kernel<T, KVB, A32_KROW, A32_VROW, VAR>)
         case AF_ATTN32: ATTN32_INSTANCES(X) break;
 #undef X
-#define X(VAR) if (t0 == VAR) ATTN_LAUNCH(attn32ap_kernel<T, 144, 192, VAR>)
+#define X(VAR) if (t0 == VAR) ATTN_LAUNCH(attn32ap_kernel<T, A32_KROW, A32_VROW, VAR>)
         case AF_ATTN32AP: ATTN32AP_INSTANCES(X) break;
 #undef X
 #define X(NKS, NDT, ONES) if (t0 == NKS && t1 == NDT && p.kpf) ATTN_LAUNCH(attn32g_kernel<T, NKS, NDT, 1, ONES, true>) if (t0 == NKS && t1 == NDT) ATTN_LAUNCH(attn32g_kernel<T, NKS, NDT, 1, ONES, false>)

@@ -19,6 +19,7 @@ template <typename T, int KROWB, int VROWB, int VAR>
 __global__ __launch_bounds__(512, 1) void attn32ap_kernel(const AttnArgs p) {
     constexpr int QW = 64, QB = 512, KVB = 64;
     constexpr int KBYTES = KVB * KROWB, VBYTES = KVB * VROWB;
+    static_assert(KROWB == A32_KROW && VROWB == A32_VROW && 2 * (KBYTES + VBYTES) == attn32_lds(KVB), "attn_pick (attn_pick.cpp) plans with these strides");
     extern __shared__ __attribute__((aligned(16))) char smem[];       // K ring [2][KBYTES] | V ring [2][VBYTES]
     using V8 = typename Vec<T>::v8;
     const int tid = threadIdx.x, lane = tid & 63;

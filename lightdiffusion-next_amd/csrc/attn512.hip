@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include "ldx_device.h"
 #include "ldx_kernels.h"
+#include "ldx_switches.h"
 #include "attn_pipe_common.h"
 
 namespace ldx {
@@ -34,7 +35,7 @@ namespace ldx {
 constexpr int A5_D = 512, A5_KV = 32, A5_QB = 128;
 constexpr int A5_KROW = A5_D * 2 + 16, A5_VROW = A5_D * 2 + 64;               // 1040 = 65 x 16 B, 1088 = 17 x 64 B
 constexpr int A5_KB = A5_KV * A5_KROW, A5_VB = A5_KV * A5_VROW, A5_STAGE = A5_KB + A5_VB, A5_LDS = 2 * A5_STAGE;      // 136 192 B
-static_assert(A5_QB == ATTN512_QB && A5_KV == ATTN512_KV && A5_LDS == ATTN512_LDS, "attn_pick (attention.hip) plans with these");
+static_assert(A5_QB == ATTN512_QB && A5_KV == ATTN512_KV && A5_LDS == ATTN512_LDS, "attn_pick (attn_pick.cpp) plans with these");
 constexpr int A5_WS_ROW = A5_D + 4;                                            // floats per (split, query) row of the split workspace: O[512], m, l, pad
 
 // ABL (timing-only builds, wrong results; LDX_ATTN512_ABL, read once): 1 = no LDS-DMA inside the key loop (the two stages keep blocks 0 / 1), 2 = no V^T fragment
@@ -257,13 +258,13 @@ void launch_attn512(const AttnArgs& a0, const AttnPick& p, DType dt, hipStream_t
     a.nsplit = p.nsplit;
     const unsigned grid = p.grid;
     const long mrows = (long)a.B * a.H * a.Nq;
-    static const int abl = getenv("LDX_ATTN512_ABL") ? atoi(getenv("LDX_ATTN512_ABL")) : 0;
+    const int abl = g_launch_sw.attn512_abl;
     if (abl && dt == DT_BF16) {
 #define A5_ABL_CASE(N) case N: { static DevOnce o##N; set_dyn_lds(o##N, (const void*)attn512_kernel<__bf16, N>, A5_LDS); hipLaunchKernelGGL((attn512_kernel<__bf16, N>), dim3(grid), dim3(256), A5_LDS, s, a); return; }
         switch (abl) { A5_ABL_CASE(1) A5_ABL_CASE(2) A5_ABL_CASE(4) A5_ABL_CASE(6) A5_ABL_CASE(7) default: break; }
 #undef A5_ABL_CASE
     }
-    static const int var = getenv("LDX_ATTN512_VAR") ? atoi(getenv("LDX_ATTN512_VAR")) : 0;      // experiment: KPF * 10 + NCH
+    const int var = g_launch_sw.attn512_var;      // experiment: KPF * 10 + NCH
     if (var && dt == DT_BF16) {
 #define A5_VAR_CASE(K, C) case K * 10 + C: { static DevOnce o; set_dyn_lds(o, (const void*)attn512_kernel<__bf16, 0, K, C>, A5_LDS); hipLaunchKernelGGL((attn512_kernel<__bf16, 0, K, C>), dim3(grid), dim3(256), A5_LDS, s, a); \
             if (a.nsplit > 1) hipLaunchKernelGGL((attn512_merge_kernel<__bf16>), dim3((unsigned)((mrows * 128 + 255) / 256)), dim3(256), 0, s, a); return; }

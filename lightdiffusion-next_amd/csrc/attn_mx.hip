@@ -22,6 +22,7 @@
 #include <stdlib.h>
 #include "ldx_device.h"
 #include "ldx_kernels.h"
+#include "ldx_switches.h"
 #include "attn_pipe_common.h"
 
 namespace ldx {
@@ -41,7 +42,7 @@ static __device__ __forceinline__ void am_sacc(f32x16& d, i32x8 a, i32x8 b, int 
     asm volatile("s_nop 1\n\tv_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]" : "+v"(d) : "v"(a), "v"(b), "v"(sa), "v"(sb));
 }
 
-constexpr int AM_D = 128, AM_KB = 128, AM_QB = 256;
+constexpr int AM_D = 128, AM_QB = 256;                           // (AM_KB, the keys per block: ldx_geometry.h, attn_mx_ok plans with it)
 constexpr int AM_TILE = 128 * 128;                               // one K or V^T tile: 128 rows x 128 B
 constexpr int AM_STAGE = 2 * AM_TILE + 1024, AM_LDS = 2 * AM_STAGE;      // + 128 K-scale dwords + 128 V-scale dwords; 67 584 B
 constexpr int AM_PSH = 6;                                        // P is stored as e4m3(P * 2^6) with the hardware scale 2^-6
@@ -421,10 +422,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_mx_kernel(const QkRopeArgs p
     if ((ch & 3) == 0) *((uint8_t*)((which ? p.SK : p.SQ) + (long)h * p.s8_ld + row + p.row8) + (ch >> 2)) = (uint8_t)e8;
 }
 
-bool attn_mx_ok(const AttnMxArgs& a) {
-    return a.Q8 && a.K8 && a.V8T && a.SQ && a.SK && a.SV && (a.O || (a.O8 && a.SO)) && a.B > 0 && a.H > 0 && a.Nq > 0 && a.Mk > 0 && a.ldq8 % 16 == 0 && a.ldk8 % 16 == 0 &&
-           a.Lp % AM_KB == 0 && a.Lp >= a.Mk && (!a.O || a.ldo % 4 == 0) && (!a.O8 || a.ldo8 % 4 == 0);
-}
+// (the shapes it takes: attn_mx_ok, attn_pick.cpp)
 template <typename T, int QT>
 static void launch_attn_mx_inst(const AttnMxArgs& a, unsigned grid, hipStream_t s) {
     static DevOnce once;
@@ -435,7 +433,7 @@ void launch_attn_mx(const AttnMxArgs& a, DType dt, hipStream_t s) {
     const unsigned grid = (unsigned)(((a.Nq + AM_QB - 1) / AM_QB) * a.H * a.B);
     // measured at the Flux shape [1, 24, 4352, 128], same box (profiles/r05/attn_mx_variants.txt): QT = 1 (eight waves x 32 queries, two per SIMD) 203 us, QT = 2 (four
     // waves x 64 queries, skewed schedule) 226 us, 16-bit attn128p 282-287 us.  LDX_ATTN_MX_QT=2 selects the other one (read once).
-    static const int qt = getenv("LDX_ATTN_MX_QT") ? atoi(getenv("LDX_ATTN_MX_QT")) : 1;
+    const int qt = g_launch_sw.attn_mx_qt;
     if (dt == DT_BF16) { if (qt == 1) launch_attn_mx_inst<__bf16, 1>(a, grid, s); else launch_attn_mx_inst<__bf16, 2>(a, grid, s); }
     else { if (qt == 1) launch_attn_mx_inst<_Float16, 1>(a, grid, s); else launch_attn_mx_inst<_Float16, 2>(a, grid, s); }
 }

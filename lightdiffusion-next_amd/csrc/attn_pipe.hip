@@ -36,6 +36,7 @@
 #include <utility>
 #include "ldx_device.h"
 #include "ldx_kernels.h"
+#include "ldx_switches.h"
 #include "attn_pipe_common.h"
 
 namespace ldx {
@@ -81,6 +82,7 @@ template <typename T, int ABL, bool KB>
 __global__ __launch_bounds__(256, 1) void attn40p_kernel(const AttnArgs p, const float thr) {
     constexpr int KROWB = 144, VROWB = 192, KVB = 64, D = 40, DCH = 5;
     constexpr int KBYTES = KVB * KROWB, VBYTES = KVB * VROWB;
+    static_assert(2 * (KBYTES + VBYTES) == ATTN40P_LDS, "attn_pick (attn_pick.cpp) plans with this");
     extern __shared__ __attribute__((aligned(16))) char smem[];       // K ring [2][KBYTES] | V ring [2][VBYTES]
     using V8 = typename Vec<T>::v8;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -419,9 +421,9 @@ static void launch_attn40p(const AttnArgs& a, const AttnPick& p, hipStream_t s, 
 void launch_attn_pipe(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s) {
     const bool ov = p.thr == p.thr;
 #ifdef LDX_ATTN_ABLATE
-    if (const char* e = getenv("LDX_ATTN_PIPE_ABL")) {
+    {
         const float thr = ApT<__bf16>::thr;
-        switch (atoi(e)) {
+        switch (g_launch_sw.attn_pipe_abl) {
             case 1: launch_attn40p<__bf16, 1>(a, p, s, thr); return;
             case 2: launch_attn40p<__bf16, 2>(a, p, s, thr); return;
             case 8: launch_attn40p<__bf16, 8>(a, p, s, thr); return;

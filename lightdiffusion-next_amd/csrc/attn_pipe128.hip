@@ -22,6 +22,7 @@
 #include <math.h>
 #include "ldx_device.h"
 #include "ldx_kernels.h"
+#include "ldx_switches.h"
 #include "attn_pipe_common.h"
 
 namespace ldx {
@@ -56,6 +57,7 @@ template <typename T, int ABL, bool KB>
 __global__ __launch_bounds__(256, 1) void attn128p_kernel(const AttnArgs p, const float thr) {
     constexpr int D = 128, KVB = 64, KROWB = 272, VROWB = 320;      // row strides: conflict-free b128 (K) and transposing b64 (V) fragment reads
     constexpr int KBYTES = KVB * KROWB, VBYTES = KVB * VROWB, VBASE = 3 * KBYTES;
+    static_assert(3 * (KBYTES + VBYTES) == ATTN128P_LDS, "attn_pick (attn_pick.cpp) plans with this");
     extern __shared__ __attribute__((aligned(16))) char smem[];       // K ring [3][KBYTES] | V ring [3][VBYTES]
     using V8 = typename Vec<T>::v8;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -408,9 +410,9 @@ static void launch_attn128p(const AttnArgs& a, const AttnPick& p, hipStream_t s,
 void launch_attn_pipe128(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s) {
     const bool ov = p.thr == p.thr;
 #ifdef LDX_ATTN_ABLATE
-    if (const char* e = getenv("LDX_ATTN_PIPE_ABL")) {
+    {
         const float thr = ApT<__bf16>::thr;
-        switch (atoi(e)) {
+        switch (g_launch_sw.attn_pipe_abl) {
             case 1: launch_attn128p<__bf16, 1>(a, p, s, thr); return;
             case 2: launch_attn128p<__bf16, 2>(a, p, s, thr); return;
             case 4: launch_attn128p<__bf16, 4>(a, p, s, thr); return;

@@ -32,6 +32,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "gemm_common.h"
+#include "ldx_switches.h"
 
 namespace ldx {
 
@@ -72,8 +73,7 @@ static __device__ __forceinline__ void cp_load_residuals(const GemmArgs& p, cons
     for (int j = 0; j < NJ; ++j) { r1[j] = *(const uint2*)(b1 + j * s1); r2[j] = *(const uint2*)(b2 + j * s2); }
 }
 
-constexpr int CP_TH = 16, CP_TW = 32, CP_PW = CP_TW + 2, CP_PIX = (CP_TH + 2) * CP_PW;     // 612 patch pixels
-static_assert(CP_TH * CP_TW == CONV_PATCH_BM, "GemmPick::bm of the patch kernel");
+constexpr int CP_PW = CP_TW + 2, CP_PIX = (CP_TH + 2) * CP_PW;     // 612 patch pixels around a CP_TH x CP_TW tile (ldx_geometry.h)
 constexpr int CP_PP = (CP_PIX * 4 + 63) / 64;                                             // 39 pieces of 64 slots per channel chunk
 constexpr int CP_PATCH = CP_PP * 1024;
 constexpr int CP_RED = 8 * 32 * 2 * 4;                                                    // GroupNorm partials of the 8 waves
@@ -605,32 +605,7 @@ __global__ __launch_bounds__(640, 1) void conv_patch_ws_kernel(const GemmArgs p,
     }
 }
 
-// Which (PR, RW) the launcher instantiates per N, and the LDS they need
-static bool cp_ws_enabled() { static const bool ws = !(getenv("LDX_CONV_PATCH_WS") && atoi(getenv("LDX_CONV_PATCH_WS")) == 0); return ws; }      // 0: every wave loads and multiplies (the kernel N = 128 uses)
-static bool cp_disabled() { static const bool off = getenv("LDX_CONV_PATCH") && atoi(getenv("LDX_CONV_PATCH")) == 0; return off; }
-
-bool conv_patch_ok(const GemmArgs& a) {
-    if (a.dup_rows) return false;          // the dual store of a shared CFG prefix lives in the general output stage (gemm_common.h)
-    if (cp_disabled() || a.mode != 1 || a.stride != 1 || a.A2 || a.pad0 || a.f8 || a.C8 || a.ln_c1 || a.geglu || a.rowvec || a.gate || a.splitk > 1) return false;
-    const bool narrow = a.N <= 16;      // conv_last / conv_out: 3 or 4 output channels, element-wise epilogue (no residuals), loader-wave kernel with one column tile
-    if (!narrow && a.N != 32 && a.N != 64 && a.N != 128) return false;
-    if (narrow && (a.R || a.R2 || a.gn_partial || !cp_ws_enabled())) return false;
-    if (a.act != 0 && a.act != 3) return false;
-    if (a.Cin % 64 || a.Cin < 64 || a.K != 9 * a.Cin || a.Hout % CP_TH || a.Wout % CP_TW || a.Hv != a.Hout || a.Wv != a.Wout) return false;      // Cin % 64: 3 Cin / 32 steps in groups of 6
-    if (a.lda % 8 || (!narrow && ((a.C && a.ldc % 4) || (a.R && a.ldr % 4) || (a.R2 && a.ldr2 % 4) || (a.Cf && a.ldcf % 4)))) return false;
-    const long nimg = a.M / ((long)a.Hout * a.Wout);
-    if (nimg * a.Hin * a.Win * a.lda * 2 >= 0x7fffffffL) return false;      // 32-bit buffer offsets
-    const long ntiles = nimg * (a.Hout / CP_TH) * (a.Wout / CP_TW);
-    if (a.gn_partial && (a.N != 128 || a.gn_cpg != 4 || a.gn_G != 32 || a.gn_hw != a.Hout * a.Wout || a.gn_nchunk != (a.Hout / CP_TH) * (a.Wout / CP_TW))) return false;
-    return ntiles >= (narrow ? 64 : 256);      // at least one tile per CU; the 3 / 4-channel tails win from 64 tiles on (UNet out conv at 128^2 x 2: 39 -> see profiles/r05)
-}
-// gemm_gn_fuse's question for this kernel: chunks per image if the epilogue can produce the consumer GroupNorm's statistics, else 0
-int conv_patch_gn_chunks(const GemmArgs& a, int HW, int G) {
-    GemmArgs t = a; t.gn_partial = nullptr;
-    if (!conv_patch_ok(t) || a.N != 128 || G != 32 || HW != a.Hout * a.Wout) return 0;
-    return (a.Hout / CP_TH) * (a.Wout / CP_TW);
-}
-
+// Which (PR, RW) the launcher instantiates per N, and the LDS they need (which launches come here: conv_patch_ok, gemm_pick.cpp)
 template <typename T, int NJ, int PR, int RW>
 static void launch_conv_patch_t(const GemmArgs& a, hipStream_t s) {
     static DevOnce once;
@@ -640,8 +615,7 @@ static void launch_conv_patch_t(const GemmArgs& a, hipStream_t s) {
     const int ntiles = (a.M / (a.Hout * a.Wout)) * (a.Hout / CP_TH) * (a.Wout / CP_TW);
     static const int ncu = [] { int dev = 0, n = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
     const int grid = ntiles < ncu ? ntiles : ncu;
-    static const int abl = getenv("LDX_CP_ABL") ? atoi(getenv("LDX_CP_ABL")) : 0;      // timing ablations (wrong results): 1 no patch loads, 2 no weight loads, 4 no MFMAs (N = 32), 8 no stores, 16 no fragment reads (N = 32), 32 no per-tile offset recomputation (loader-wave kernel)
-    hipLaunchKernelGGL((conv_patch_kernel<T, NJ, PR, RW>), dim3(grid), dim3(512), lds, s, a, ntiles, abl);
+    hipLaunchKernelGGL((conv_patch_kernel<T, NJ, PR, RW>), dim3(grid), dim3(512), lds, s, a, ntiles, g_launch_sw.cp_abl);
 }
 
 template <typename T, int NJ, int PR, int RW>
@@ -652,13 +626,12 @@ static void launch_conv_patch_ws(const GemmArgs& a, hipStream_t s) {
     set_dyn_lds(once, (const void*)conv_patch_ws_kernel<T, NJ, PR, RW>, lds);
     const int ntiles = (a.M / (a.Hout * a.Wout)) * (a.Hout / CP_TH) * (a.Wout / CP_TW);
     static const int ncu = [] { int dev = 0, n = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-    static const int abl = getenv("LDX_CP_ABL") ? atoi(getenv("LDX_CP_ABL")) : 0;
-    hipLaunchKernelGGL((conv_patch_ws_kernel<T, NJ, PR, RW>), dim3(ntiles < ncu ? ntiles : ncu), dim3(640), lds, s, a, ntiles, abl);
+    hipLaunchKernelGGL((conv_patch_ws_kernel<T, NJ, PR, RW>), dim3(ntiles < ncu ? ntiles : ncu), dim3(640), lds, s, a, ntiles, g_launch_sw.cp_abl);
 }
 
 template <typename T>
 static void launch_conv_patch_n(const GemmArgs& a, hipStream_t s) {
-    const bool ws = cp_ws_enabled();
+    const bool ws = g_launch_sw.conv_patch_ws;
     if (a.N <= 16) launch_conv_patch_ws<T, 1, 3, 6>(a, s);
     else if (a.N == 32) { if (ws) launch_conv_patch_ws<T, 2, 3, 6>(a, s); else launch_conv_patch_t<T, 2, 3, 6>(a, s); }
     else if (a.N == 64) { if (ws) launch_conv_patch_ws<T, 4, 2, 6>(a, s); else launch_conv_patch_t<T, 4, 2, 6>(a, s); }

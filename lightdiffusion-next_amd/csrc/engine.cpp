@@ -688,7 +688,7 @@ std::string Engine::prof_key(const Op& o) const {
 
 int Engine::exec_ops(hipStream_t ls, size_t op_begin, size_t op_end, int ctx_sel) {
     if (op_end > cur.ops.size()) op_end = cur.ops.size();
-    static const bool dbg_nan = getenv("LDX_DEBUG_NAN") != nullptr;          // debug: first GEMM whose 16-bit output holds a NaN / Inf
+    const bool dbg_nan = g_launch_sw.debug_nan;          // debug: first GEMM whose 16-bit output holds a NaN / Inf
     const bool prof_now = profiling && !prof_graph;
     if (prof_now && prof_events.size() < 2 * cur.ops.size()) {
         const size_t old = prof_events.size();

@@ -12,6 +12,7 @@
 
 #include "../../include/ldx.h"
 #include "ldx_kernels.h"
+#include "ldx_switches.h"
 
 namespace ldx {
 

@@ -16,8 +16,9 @@
 namespace ldx {
 
 UNetEngine::UNetEngine(const ldx_unet_config& c, int dev) : Engine(dev, c.compute_dtype, true, true), cfg(c) {
-    cfg_share = getenv("LDX_CFG_SHARE") ? atoi(getenv("LDX_CFG_SHARE")) : 1;      // 0 off, 1 where it pays (share_for), 2 whenever possible
-    upconv_phase = getenv("LDX_UPCONV_PHASE") ? atoi(getenv("LDX_UPCONV_PHASE")) : 1;      // 0: every up conv stays a 9-tap op; 1 / 2: phase form, tiles phase-major / band-major (GemmArgs::up2x)
+    const UNetSwitches sw;          // the environment as it is now, not as it was at load (ldx_switches.h)
+    cfg_share = sw.cfg_share;
+    upconv_phase = sw.upconv_phase;
 }
 UNetEngine::~UNetEngine() {
     (void)hipSetDevice(device);

@@ -21,7 +21,7 @@
 
 namespace ldx {
 
-constexpr int FB_C = 320, FB_I = 1280, FB_BM = 128, FB_CH = 128, FB_NCH = FB_I / FB_CH;
+constexpr int FB_BM = 128, FB_CH = 128, FB_NCH = FB_I / FB_CH;      // (FB_C, FB_I: ldx_geometry.h, ff_block_ok plans with them)
 constexpr int FB_AROW = FB_C * 2 + 16;            // 656 B
 constexpr int FB_GROW = FB_CH * 2 + 16;           // 272 B
 constexpr int FB_ABYTES = FB_BM * FB_AROW, FB_GBYTES = FB_BM * FB_GROW;
@@ -162,9 +162,7 @@ __global__ __launch_bounds__(512, 1) void ff_block_kernel(const FFBlockArgs p) {
     rb_store_rows<T, 8>(Hp, p.ldh, m0, p.M, 0, wave, l15, g4, tid, rr, sGb);
 }
 
-bool ff_block_ok(const FFBlockArgs& a) {
-    return g_plan_sw.ff_fuse && a.C == FB_C && a.inner == FB_I && a.M > 0 && a.ldh % 8 == 0 && a.b1 != nullptr;
-}
+// (the shapes it takes: ff_block_ok, xf_pick.cpp)
 template <typename T>
 static void launch_ff_t(const FFBlockArgs& a, hipStream_t s) {
     static DevOnce once;

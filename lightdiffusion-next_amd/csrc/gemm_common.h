@@ -11,17 +11,11 @@ template <typename T> struct DTypeOf;
 template <> struct DTypeOf<__bf16> { static constexpr DType v = DT_BF16; };
 template <> struct DTypeOf<_Float16> { static constexpr DType v = DT_F16; };
 
-constexpr int BK = 64;
 #ifndef LDX_PP_STAMP
 #define LDX_PP_STAMP(k)        // profiles/ubench/pp_stamp.hip defines it: per-workgroup wall-clock stamps of a tile's phases
 #endif
-// gemm_ring.hip: 64 x 160 LDS-DMA ring tiles for mid-size plain GEMMs; gemm_tile (gemm.hip) asks gemm_ring_ok
-bool gemm_ring_ok(int M, int N, int K, bool plain, int splitk);
+// the launchers of the other two GEMM families (their shape rules, gemm_ring_ok and conv_patch_ok, are in gemm_pick.cpp; BK and the tile extents in ldx_geometry.h)
 void launch_gemm_ring(const GemmArgs& a, DType dt, hipStream_t s);
-// conv_patch.hip: patch-resident 3x3 conv for N = 32 / 64 / 128 (ESRGAN, VAE last level); gemm_pick asks conv_patch_ok
-constexpr int CONV_PATCH_BM = 512;      // output rows per tile: 16 x 32 pixels
-bool conv_patch_ok(const GemmArgs& a);
-int conv_patch_gn_chunks(const GemmArgs& a, int HW, int G);
 void launch_conv_patch(const GemmArgs& a, DType dt, hipStream_t s);
 // BN is a template parameter: 128 (generic) or 160 — every SD1.5 channel count is a multiple of 320, and
 // 160-wide tiles remove the half-empty last column tile (and the half-empty last round of workgroups)

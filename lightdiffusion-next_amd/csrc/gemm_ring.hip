@@ -24,7 +24,7 @@
 
 namespace ldx {
 
-constexpr int GR_BM = 64, GR_BN = 160, GR_NS = 5;
+constexpr int GR_NS = 5;                                 // ring stages; the tile, GR_BM x GR_BN, is in ldx_geometry.h (gemm_ring_ok plans with it)
 constexpr int GR_STAGE = (GR_BM + GR_BN) * 128;          // 28 672 B
 constexpr int GR_LDS = GR_NS * GR_STAGE;                 // 143 360 B
 
@@ -127,16 +127,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ring_kernel(const GemmArgs p) {
     gemm_epilogue<T, GR_BM, GR_BN, 4, MI, NJ, false, MI * NJ, true>(p, acc, m0, n0, wm, wn, l15, g4, 0, 1, nullptr, nullptr, rpre, use_rpre);
 }
 
-// Planner rule (gemm_tile asks it): the shapes the register-staged 64 x 64 tiles serve today — fewer than 400 tiles of 128 x 128 and a short K — whose
-// 64 x 160 tiling still gives (nearly) every CU a workgroup.  LDX_RING=0 switches the kernel off, 2 takes every plain GEMM with N % 160 == 0 that fills the chip.
-bool gemm_ring_ok(int M, int N, int K, bool plain, int splitk) {
-    static const int mode = getenv("LDX_RING") ? atoi(getenv("LDX_RING")) : 1;
-    if (!mode || !plain || splitk > 1 || N % GR_BN || K % BK || K < 2 * BK || M <= 0) return false;
-    const long t = (long)((M + GR_BM - 1) / GR_BM) * (N / GR_BN);
-    if (mode >= 2) return t >= 192;
-    return t >= 192 && t <= 512;
-}
-
+// (which launches come here: gemm_ring_ok, gemm_pick.cpp)
 void launch_gemm_ring(const GemmArgs& a, DType dt, hipStream_t s) {
     const unsigned tiles = (unsigned)(((a.M + GR_BM - 1) / GR_BM) * ((a.N + GR_BN - 1) / GR_BN));
     if (dt == DT_BF16) {

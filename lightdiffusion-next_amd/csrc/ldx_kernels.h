@@ -10,6 +10,8 @@
 
 #include <functional>
 
+#include "ldx_geometry.h"
+
 namespace ldx {
 
 enum DType : int { DT_BF16 = 0, DT_F16 = 1 };
@@ -116,8 +118,8 @@ void launch_gemm(const GemmArgs& a, DType dt, hipStream_t s);
 // two independent plain GEMMs (mode 0, no split-K / GEGLU, both 16-bit or both MX) as one launch of 128x128 tiles
 void launch_gemm2(const GemmArgs& a, const GemmArgs& b, DType dt, hipStream_t s);
 int gemm_choose_splitk(int M, int N, int K, bool geglu);   // 1 = no split
-// Which kernel launch_gemm(a) — launch_gemm2(a, *b) with a second problem — runs: pure host arithmetic over the arguments and the LDX_* dispatch switches, which are
-// read once when the library loads.  The launchers switch on it, the planner asks it (gemm_gn_fuse, Engine::n_launches), ldx_op_gemm_pick shows it to tests.
+// Which kernel launch_gemm(a) — launch_gemm2(a, *b) with a second problem — runs: pure host arithmetic (gemm_pick.cpp) over the arguments and the LDX_* dispatch switches, which are
+// read once when the library loads (ldx_switches.h: GemmSwitches).  The launchers switch on it, the planner asks it (gemm_gn_fuse, Engine::n_launches), ldx_op_gemm_pick shows it to tests.
 enum GemmFamily : int { GF_TILE = 0, GF_TILE2, GF_PP, GF_PP2, GF_RING, GF_CONV_PATCH, GF_TILE_MX, GF_TILE2_MX, GF_PP_MX, GF_PP2_MX };      // register-staged tile (gemm.hip), ping-pong (gemm_pp.inc), ring, patch-resident conv; 2: two problems; MX: fp8 operands
 enum GemmReduce : int { RED_NONE = 0, RED_LAUNCH, RED_LAUNCH_GN, RED_IN_KERNEL };      // split-K partials: no split / reduce launch / reduce launch that also writes the GroupNorm statistics / last workgroup of a tile
 struct GemmPick {
@@ -130,6 +132,12 @@ struct GemmPick {
     int launches;                  // kernel launches in all (0: empty problem)
 };
 GemmPick gemm_pick(const GemmArgs& a, const GemmArgs* b = nullptr);
+// The shape rules gemm_pick asks, and what launch_gemm asks back (all of it host arithmetic in gemm_pick.cpp, next to the pick):
+bool gemm_ring_ok(int M, int N, int K, bool plain, int splitk);      // gemm_ring.hip: 64 x 160 LDS-DMA ring tiles for mid-size plain GEMMs
+bool conv_patch_ok(const GemmArgs& a);                               // conv_patch.hip: patch-resident 3x3 conv for N = 32 / 64 / 128 (ESRGAN, VAE last level) and the 3 / 4-channel tails
+int conv_patch_gn_chunks(const GemmArgs& a, int HW, int G);
+int splitk_gn_geom(const GemmArgs& a, int HW, int G, int max_chunks, int* R_out);      // geometry of the reduce + GroupNorm-statistics launch
+void gemm_gn_check(const GemmArgs& a);                               // aborts unless a set GemmArgs::gn_partial carries the geometry gemm_gn_fuse gives this very launch
 constexpr int SK_FIXUP_MAX_S = 4;                          // in-kernel fix-up up to this many splits (the last arriver reads S slabs back to back); above: reduce launch
 constexpr int SK_COUNTERS = 8192;                          // per-tile counters a caller keeps for it
 #ifdef LDX_SK_FIXUP_BUILD
@@ -213,7 +221,7 @@ struct AttnArgs {
     float* split_ws; int nsplit;
 };
 void launch_attention(const AttnArgs& a, DType dt, hipStream_t s);
-// Which kernel launch_attention(a) runs: pure host arithmetic over the arguments and the LDX_ATTN* dispatch switches, which are read once when the library loads.
+// Which kernel launch_attention(a) runs: pure host arithmetic (attn_pick.cpp) over the arguments and the LDX_ATTN* dispatch switches (ldx_switches.h: AttnSwitches).
 // launch_attention switches on it, the planner asks it (Engine::op_attn, Engine::n_launches, the single-op C ABI), ldx_op_attn_pick shows it to tests.
 enum AttnFamily : int { AF_ATTN = 0, AF_ATTN32, AF_ATTN32AP, AF_ATTN32G, AF_ATTN40P, AF_ATTN128P, AF_ATTN512 };      // attn_kernel (16x16 MFMAs), attn32_kernel, attn32ap_kernel, attn32g_kernel (attention.hip, attn32ap.inc); attn40p_kernel (attn_pipe.hip), attn128p_kernel (attn_pipe128.hip), attn512_kernel (attn512.hip)
 struct AttnPick {
@@ -231,14 +239,10 @@ struct AttnPick {
 };
 AttnPick attn_pick(const AttnArgs& a);
 bool attn_pipe_ok(const AttnArgs& a);      // the shape rule of the two pipelined kernels, grid-fill gates aside: the planner provides AttnArgs::knorm_ws for these
-// the LDX_ATTN* switches are read once at load; this re-reads all of them (tests / same-process A/B runs only — never on the launch path)
-void reload_dispatch_env();
 
 // The kernels of the other files, launched by launch_attention with the pick that chose them (grid, LDS size; threshold and key-norm launch; key splits).
 // attn_pipe.hip: software-pipelined D = 40 kernel (round 4); attn_pipe128.hip: the same pipeline for D = 128 (Flux joint attention), 16-bit or MX fp8 output (AttnArgs::O8);
 // attn512.hip: flash attention for D = 512 heads, keys split over AttnPick::nsplit workgroups per query block
-constexpr int ATTN40P_LDS = 2 * 64 * (144 + 192), ATTN128P_LDS = 3 * 64 * (272 + 320);
-constexpr int ATTN512_QB = 128, ATTN512_KV = 32, ATTN512_LDS = 2 * ATTN512_KV * ((512 * 2 + 16) + (512 * 2 + 64));      // queries per workgroup, keys per block, two stages of K and V rows
 void launch_attn_pipe(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s);
 void launch_attn_pipe128(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s);
 void launch_attn512(const AttnArgs& a, const AttnPick& p, DType dt, hipStream_t s);
@@ -298,26 +302,7 @@ void launch_rowgemm(const RowGemmArgs& a, DType dt, hipStream_t s);
 bool xattn_block_ok(const XAttnArgs& a);
 void launch_xattn_block(const XAttnArgs& a, DType dt, hipStream_t s);
 
-// Every LDX_* switch behind the stage choice of a SpatialTransformer and the one-launch GroupNorm, read once when the library loads (xf_pick.cpp, next to the pick).
-// Deliberately NOT re-read by reload_dispatch_env(): plans bake these decisions into their op lists, and a reload between planning and launching would make the two disagree.
-struct PlanSwitches {
-    long rowblock_minwg, rowblock_minwg_prefix;      // LDX_ROWBLOCK_MINWG / _PREFIX: fewest workgroups a row-block launch may have (rowblock_fills_chip)
-    long plain640_maxm;                              // LDX_ROWGEMM_PLAIN640_MAXM: most rows of a K = 640 rowgemm without a prologue
-    long lnfold_maxrows;                             // LDX_LNFOLD_MAXROWS: rows at C = 320 up to which a level folds its LayerNorms (0: never)
-    long gn_small_max;                               // LDX_GN_SMALL_MAX: elements per (image, group) the one-launch GroupNorm kernel takes
-    bool rowgemm, rowgemm640, rowgemm_x2, rowgemm_po, xattn_fuse, ff_fuse;      // LDX_ROWGEMM, LDX_ROWGEMM640, LDX_ROWGEMM_X2, LDX_ROWGEMM_PO, LDX_XATTN_FUSE, LDX_FF_FUSE: 0 switches the kernel (or that use of it) off
-    // the engines' own planning and weight-packing switches (engine*.cpp say what each is for)
-    bool cfg_share_copy; long cfg_share_minrows;     // LDX_CFG_SHARE_COPY != 0: the shared CFG prefix is handed over by copy launches only; LDX_CFG_SHARE_MINROWS: rows per half from which share mode 1 shares
-    bool fused_skip, q_prescale, lnfold, emb_table;  // LDX_NO_FUSED_SKIP / LDX_NO_QPRESCALE set (to anything): off; LDX_LNFOLD / LDX_EMB_TABLE = 0: off
-    double plan_cache_gib;                           // LDX_PLAN_CACHE_GIB: GiB of stashed arenas the plan cache keeps
-    int mx_fuse;                                     // LDX_MX_FUSE: 1 GEMM epilogue, 2 attention, 4 LayerNorm write the MX shadow themselves
-    bool flux_fp8_attn, flux_group, flux_mod_fp8;    // LDX_FLUX_FP8_ATTN / LDX_FLUX_GROUP / LDX_FLUX_MOD_FP8 = 0: off
-    long vae_attn_chunk_mib;                         // LDX_VAE_ATTN_CHUNK_MIB: score rows per chunk of the VAE's three-GEMM attention, in MiB (0: one chunk)
-    PlanSwitches();
-};
-extern const PlanSwitches g_plan_sw;
-
-// The stage choice of one SpatialTransformer: pure host arithmetic over the level's shape, the switches above and the kernels' own shape rules (rowgemm_ok,
+// The stage choice of one SpatialTransformer: pure host arithmetic over the level's shape, the planner's switches (ldx_switches.h: PlanSwitches) and the kernels' own shape rules (rowgemm_ok,
 // xattn_block_ok, ff_block_ok).  Engine::emit_xf emits what it says, Engine::fuse_gn_rowgemm asks xf_proj_in_rowgemm again once the producer's statistics are known,
 // ldx_op_xf_pick shows it to tests (xf_pick.cpp).
 struct XfShape {

@@ -15,18 +15,11 @@
 #include <stdlib.h>
 #include "ldx_device.h"
 #include "ldx_kernels.h"
+#include "ldx_switches.h"
 
 namespace ldx {
 
-struct GnGeom { int CH, TX, RY; };
-static inline GnGeom gn_geom(int C) {
-    const int cpp = C / 8;
-    int ch = 1;                                   // chunks per thread: 1, 2 or 4 (template instances)
-    while (ch < 4 && (cpp / ch > 256 || cpp % ch)) ch *= 2;
-    GnGeom g; g.CH = ch; g.TX = cpp / ch; g.RY = 256 / g.TX; if (g.RY < 1) g.RY = 1;
-    return g;
-}
-
+// (CH, TX, RY of a launch: gn_pick, xf_pick.cpp)
 template <typename T, int CH>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const GroupNormArgs p, int TX, int RY) {
     extern __shared__ float sred[];                 // [RY][C][2]
@@ -356,41 +349,6 @@ __global__ __launch_bounds__(64) void gn_fold_kernel(const float* in, float* out
     out[((long)b * GN_FOLD + f) * G * 2 + t] = (a0 + a1) + (a2 + a3);
 }
 
-bool gn_uses_small_kernel(int B, long HW, int C, int G) {
-    return G > 0 && (C / G) % 8 == 0 && HW * (C / G) <= g_plan_sw.gn_small_max && (long)G * B >= 32;
-}
-
-GnPick gn_pick(const GroupNormArgs& a) {
-    GnPick p{};
-    if (a.stats_chunks <= 0 && gn_uses_small_kernel(a.B, a.HW, a.C, a.G)) {
-        p.kind = GN_SMALL; p.grid1[0] = a.G; p.grid1[1] = a.B; p.launches = 1;
-        return p;
-    }
-    const GnGeom g = gn_geom(a.C);
-    p.CH = g.CH; p.TX = g.TX; p.RY = g.RY;
-    if (a.stats_chunks > 0) {           // statistics came with the producer's epilogue: apply only, behind a fold of more rows than gn_apply wants
-        p.kind = a.stats_chunks > GN_NCHUNK ? GN_FOLD_APPLY : GN_APPLY;
-        p.nchunk = p.kind == GN_FOLD_APPLY ? GN_FOLD : a.stats_chunks;
-        if (p.kind == GN_FOLD_APPLY) { p.grid1[0] = GN_FOLD; p.grid1[1] = a.B; }
-    } else {
-        p.kind = GN_STATS_APPLY;
-        // enough pixel chunks to fill the chip (~1024 workgroups), but >= 4 pixels per thread row
-        int nchunk = (1024 + a.B - 1) / a.B;
-        const int maxc = (a.HW + g.RY * 4 - 1) / (g.RY * 4);
-        if (nchunk > maxc) nchunk = maxc;
-        if (nchunk > GN_NCHUNK) nchunk = GN_NCHUNK;
-        if (nchunk < 1) nchunk = 1;
-        p.nchunk = nchunk; p.grid1[0] = nchunk; p.grid1[1] = a.B;
-        p.lds = (int)((size_t)g.RY * a.C * 2 * sizeof(float));
-    }
-    int nblk = (a.HW + g.RY * 8 - 1) / (g.RY * 8);
-    if (nblk > 512) nblk = 512;
-    if (nblk < 1) nblk = 1;
-    p.grid2[0] = nblk; p.grid2[1] = a.B;
-    p.launches = p.kind == GN_APPLY ? 1 : 2;
-    return p;
-}
-
 template <typename T>
 static void launch_gn_t(const GroupNormArgs& a_in, hipStream_t s) {
     const GnPick p = gn_pick(a_in);
@@ -509,7 +467,7 @@ static void launch_ln_t(const LayerNormArgs& a, hipStream_t s) {
     dim3 block(256);
 #define LDX_LN(LPR, NCH) do { const int rpb = 4 * (64 / LPR); \
         hipLaunchKernelGGL((ln_kernel<T, LPR, NCH>), dim3((unsigned)((a.rows + rpb - 1) / rpb)), block, 0, s, a); } while (0)
-    static const int force = getenv("LDX_LN_LPR") ? atoi(getenv("LDX_LN_LPR")) : 0;
+    const int force = g_launch_sw.ln_lpr;
     if (force == 64 && nch <= 192) { LDX_LN(64, 3); return; }
     if (force == 32 && nch <= 96) { LDX_LN(32, 3); return; }
     if (nch <= 48) LDX_LN(16, 3);              // C <= 384  (SD1.5 level 0: 320)

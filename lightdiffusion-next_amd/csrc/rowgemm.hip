@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include "ldx_device.h"
 #include "ldx_kernels.h"
+#include "ldx_switches.h"
 #include "rowblock_store.h"
 
 namespace ldx {
@@ -233,13 +234,7 @@ __global__ __launch_bounds__(512, 1) void rowgemm_kernel(const RowGemmArgs p) {
     }
 }
 
-bool rowgemm_ok(const RowGemmArgs& a) {
-    if (!g_plan_sw.rowgemm || (a.K != 320 && a.K != 640) || (a.K == 640 && !g_plan_sw.rowgemm640) || a.N <= 0 || a.N % a.K || a.M <= 0 || a.ldx % 8 || a.ldy % 8 || (a.R && a.ldr % 4) || a.pro < 0 || a.pro > 2) return false;
-    const int bm = 128 * 320 / a.K;
-    if (a.pro >= 1 && (!a.g || !a.b)) return false;
-    if (a.pro == 2 && (!a.partial || a.G != 32 || a.HW % bm || a.M % a.HW || a.nchunk < 1 || a.nchunk > GN_NCHUNK)) return false;
-    return true;
-}
+// (the shapes it takes: rowgemm_ok, xf_pick.cpp)
 template <typename T, int PRO, int CC>
 static void launch_rowgemm_inst(const RowGemmArgs& a, hipStream_t s) {
     using G = RgGeom<CC>;
@@ -256,8 +251,7 @@ static void launch_rowgemm_t(const RowGemmArgs& a, hipStream_t s) {
     }
 }
 void launch_rowgemm(const RowGemmArgs& a0, DType dt, hipStream_t s) {
-    static const int abl = getenv("LDX_RG_ABL") ? atoi(getenv("LDX_RG_ABL")) : 0;
-    RowGemmArgs a = a0; a.abl = abl;
+    RowGemmArgs a = a0; a.abl = g_launch_sw.rg_abl;
     if (dt == DT_BF16) launch_rowgemm_t<__bf16>(a, s); else launch_rowgemm_t<_Float16>(a, s);
 }
 

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include "ldx_device.h"
 #include "ldx_kernels.h"
+#include "ldx_switches.h"
 #include "rowblock_store.h"
 
 namespace ldx {
@@ -27,9 +28,10 @@ __device__ int xa_dbg = 0;       // timing ablations (wrong results): 1 no phase
 #else
 #define XA_DBG(bit) false
 #endif
-constexpr int XA_C = 320, XA_H = 8, XA_D = 40, XA_BM = 128, XA_MK = 80;
+constexpr int XA_D = 40;                          // head dim (XA_C, XA_H, XA_BM, XA_MK: ldx_geometry.h, xattn_block_ok plans with them)
+static_assert(XA_H * XA_D == XA_C, "heads x head dim");
 constexpr int XA_AROW = XA_C * 2 + 16;            // 656 B: 16 consecutive rows start in 16 different 16-byte bank groups
-constexpr int XA_VROW = 96;                       // bytes per key row of a wave's V_h region (48 d; == 32 mod 64, see AttnCfg)
+constexpr int XA_VROW = 96;                       // bytes per key row of a wave's V_h region (48 d; == 32 mod 64, see attn_vrowb)
 constexpr int XA_ABYTES = XA_BM * XA_AROW, XA_VBYTES = XA_MK * XA_VROW;
 constexpr int XA_LDS = XA_ABYTES + XA_H * XA_VBYTES + 2 * XA_C * 4;       // + gamma / beta
 static_assert(XA_C == RB_C && XA_BM == RB_BM && XA_AROW == RB_AROW, "rb_layernorm_rows writes this A tile");
@@ -228,16 +230,13 @@ __global__ __launch_bounds__(512, 1) void xattn_block_kernel(const XAttnArgs p) 
     rb_store_rows<T, 8>(Hp, p.ldh, m0, p.M, 0, wave, l15, g4, tid, rr, smem + XA_ABYTES);
 }
 
-bool xattn_block_ok(const XAttnArgs& a) {
-    return g_plan_sw.xattn_fuse && a.C == XA_C && a.heads == XA_H && a.Mk >= 1 && a.Mk <= XA_MK && a.N % XA_BM == 0 && a.M % a.N == 0 && a.ldh % 8 == 0 && a.ldk % 4 == 0 && a.ldv % 8 == 0;
-}
-
+// (the shapes it takes: xattn_block_ok, xf_pick.cpp)
 template <typename T>
 static void launch_xattn_t(const XAttnArgs& a, hipStream_t s) {
     static DevOnce once;
     set_dyn_lds(once, (const void*)xattn_block_kernel<T>, XA_LDS);
 #ifdef XA_ABLATE
-    static const int dbg_once = []() { const int v = getenv("LDX_XA_DBG") ? atoi(getenv("LDX_XA_DBG")) : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(xa_dbg), &v, sizeof(int)); return v; }();
+    static const int dbg_once = []() { const int v = g_launch_sw.xa_dbg; (void)hipMemcpyToSymbol(HIP_SYMBOL(xa_dbg), &v, sizeof(int)); return v; }();
     (void)dbg_once;
 #endif
     hipLaunchKernelGGL((xattn_block_kernel<T>), dim3((unsigned)((a.M + XA_BM - 1) / XA_BM)), dim3(512), XA_LDS, s, a);

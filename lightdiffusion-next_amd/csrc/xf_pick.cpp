@@ -1,30 +1,68 @@
-// The stage choice of one SpatialTransformer of a UNet plan (ldx_kernels.h: PlanSwitches, XfPick): pure host arithmetic, no engine and no device.
+// The stage choice of one SpatialTransformer of a UNet plan (ldx_kernels.h: XfPick; ldx_switches.h: PlanSwitches), the shape rules of the row-block kernels it asks
+// (rowgemm_ok, xattn_block_ok, ff_block_ok) and the GroupNorm pick: pure host arithmetic, no engine and no device.
 // Engine::emit_xf emits what xf_pick says, Engine::fuse_gn_rowgemm asks xf_proj_in_rowgemm, ldx_op_xf_pick shows the pick to tests (tests/golden/xf_picks.json).
 #include "ldx_kernels.h"
-
-#include <cstdlib>
+#include "ldx_switches.h"
 
 namespace ldx {
 
-#ifndef LDX_LNFOLD_MAXROWS_DEFAULT
-#define LDX_LNFOLD_MAXROWS_DEFAULT 8192      // rows of a transformer level up to which its LayerNorms are folded into the consuming GEMMs (emit_xf)
-#endif
-// Read once when the library loads and deliberately NOT re-read by reload_dispatch_env(): plans bake these decisions into their op lists, and a reload between
-// planning and launching would make the two disagree (the reason gemm.hip gives for its own switches).
-static long env_long(const char* name, long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; }
-static bool env_unless_0(const char* name) { const char* v = getenv(name); return !(v && atoi(v) == 0); }
-PlanSwitches::PlanSwitches()
-    : rowblock_minwg(env_long("LDX_ROWBLOCK_MINWG", 192)), rowblock_minwg_prefix(env_long("LDX_ROWBLOCK_MINWG_PREFIX", 96)),
-      plain640_maxm(env_long("LDX_ROWGEMM_PLAIN640_MAXM", 16384)), lnfold_maxrows(env_long("LDX_LNFOLD_MAXROWS", LDX_LNFOLD_MAXROWS_DEFAULT)),
-      gn_small_max(env_long("LDX_GN_SMALL_MAX", 256 * 80)),
-      rowgemm(env_unless_0("LDX_ROWGEMM")), rowgemm640(env_unless_0("LDX_ROWGEMM640")), rowgemm_x2(env_unless_0("LDX_ROWGEMM_X2")), rowgemm_po(env_unless_0("LDX_ROWGEMM_PO")),
-      xattn_fuse(env_unless_0("LDX_XATTN_FUSE")), ff_fuse(env_unless_0("LDX_FF_FUSE")),
-      cfg_share_copy(getenv("LDX_CFG_SHARE_COPY") && atoi(getenv("LDX_CFG_SHARE_COPY")) != 0), cfg_share_minrows(env_long("LDX_CFG_SHARE_MINROWS", 8192)),
-      fused_skip(!getenv("LDX_NO_FUSED_SKIP")), q_prescale(getenv("LDX_NO_QPRESCALE") == nullptr), lnfold(env_unless_0("LDX_LNFOLD")), emb_table(env_unless_0("LDX_EMB_TABLE")),
-      plan_cache_gib(getenv("LDX_PLAN_CACHE_GIB") ? atof(getenv("LDX_PLAN_CACHE_GIB")) : 16.0), mx_fuse(getenv("LDX_MX_FUSE") ? atoi(getenv("LDX_MX_FUSE")) : 7),
-      flux_fp8_attn(env_unless_0("LDX_FLUX_FP8_ATTN")), flux_group(env_unless_0("LDX_FLUX_GROUP")), flux_mod_fp8(env_unless_0("LDX_FLUX_MOD_FP8")),
-      vae_attn_chunk_mib(env_long("LDX_VAE_ATTN_CHUNK_MIB", 2048)) {}
-const PlanSwitches g_plan_sw;
+// The shapes the row-block kernels take (rowgemm.hip, xattn_block.hip, ff_block.hip)
+bool rowgemm_ok(const RowGemmArgs& a) {
+    if (!g_plan_sw.rowgemm || (a.K != 320 && a.K != 640) || (a.K == 640 && !g_plan_sw.rowgemm640) || a.N <= 0 || a.N % a.K || a.M <= 0 || a.ldx % 8 || a.ldy % 8 || (a.R && a.ldr % 4) || a.pro < 0 || a.pro > 2) return false;
+    const int bm = 128 * 320 / a.K;
+    if (a.pro >= 1 && (!a.g || !a.b)) return false;
+    if (a.pro == 2 && (!a.partial || a.G != 32 || a.HW % bm || a.M % a.HW || a.nchunk < 1 || a.nchunk > GN_NCHUNK)) return false;
+    return true;
+}
+bool xattn_block_ok(const XAttnArgs& a) {
+    return g_plan_sw.xattn_fuse && a.C == XA_C && a.heads == XA_H && a.Mk >= 1 && a.Mk <= XA_MK && a.N % XA_BM == 0 && a.M % a.N == 0 && a.ldh % 8 == 0 && a.ldk % 4 == 0 && a.ldv % 8 == 0;
+}
+bool ff_block_ok(const FFBlockArgs& a) {
+    return g_plan_sw.ff_fuse && a.C == FB_C && a.inner == FB_I && a.M > 0 && a.ldh % 8 == 0 && a.b1 != nullptr;
+}
+
+// What launch_groupnorm launches (norm.hip)
+bool gn_uses_small_kernel(int B, long HW, int C, int G) {
+    return G > 0 && (C / G) % 8 == 0 && HW * (C / G) <= g_plan_sw.gn_small_max && (long)G * B >= 32;
+}
+struct GnGeom { int CH, TX, RY; };
+static inline GnGeom gn_geom(int C) {
+    const int cpp = C / 8;
+    int ch = 1;                                   // chunks per thread: 1, 2 or 4 (template instances)
+    while (ch < 4 && (cpp / ch > 256 || cpp % ch)) ch *= 2;
+    GnGeom g; g.CH = ch; g.TX = cpp / ch; g.RY = 256 / g.TX; if (g.RY < 1) g.RY = 1;
+    return g;
+}
+GnPick gn_pick(const GroupNormArgs& a) {
+    GnPick p{};
+    if (a.stats_chunks <= 0 && gn_uses_small_kernel(a.B, a.HW, a.C, a.G)) {
+        p.kind = GN_SMALL; p.grid1[0] = a.G; p.grid1[1] = a.B; p.launches = 1;
+        return p;
+    }
+    const GnGeom g = gn_geom(a.C);
+    p.CH = g.CH; p.TX = g.TX; p.RY = g.RY;
+    if (a.stats_chunks > 0) {           // statistics came with the producer's epilogue: apply only, behind a fold of more rows than gn_apply wants
+        p.kind = a.stats_chunks > GN_NCHUNK ? GN_FOLD_APPLY : GN_APPLY;
+        p.nchunk = p.kind == GN_FOLD_APPLY ? GN_FOLD : a.stats_chunks;
+        if (p.kind == GN_FOLD_APPLY) { p.grid1[0] = GN_FOLD; p.grid1[1] = a.B; }
+    } else {
+        p.kind = GN_STATS_APPLY;
+        // enough pixel chunks to fill the chip (~1024 workgroups), but >= 4 pixels per thread row
+        int nchunk = (1024 + a.B - 1) / a.B;
+        const int maxc = (a.HW + g.RY * 4 - 1) / (g.RY * 4);
+        if (nchunk > maxc) nchunk = maxc;
+        if (nchunk > GN_NCHUNK) nchunk = GN_NCHUNK;
+        if (nchunk < 1) nchunk = 1;
+        p.nchunk = nchunk; p.grid1[0] = nchunk; p.grid1[1] = a.B;
+        p.lds = (int)((size_t)g.RY * a.C * 2 * sizeof(float));
+    }
+    int nblk = (a.HW + g.RY * 8 - 1) / (g.RY * 8);
+    if (nblk > 512) nblk = 512;
+    if (nblk < 1) nblk = 1;
+    p.grid2[0] = nblk; p.grid2[1] = a.B;
+    p.launches = p.kind == GN_APPLY ? 1 : 2;
+    return p;
+}
 
 long rowblock_count(long M, int K) { const int bm = rowblock_rows(K); return (M + bm - 1) / bm * (K / 320); }
 // Planner rule for the row-block kernels (rowgemm / xattn_block / ff_block): one workgroup per row block and one workgroup per CU, so below ~3/4 of the
