@@ -425,6 +425,51 @@ int ldx_hdr_apply(const float* in_f32, const uint8_t* in_u8, int64_t in_pitch, i
                   const uint8_t* lum_lut, float contrast_factor, float color_factor, void* workspace, uint8_t* out_u8, int64_t out_pitch, float* out_f32,
                   void* stream);
 
+/* ---- SaveImage, the last stage of every pipeline exit (src/FileManaging/ImageSaver.py:79-220) ------------------------------------------------ */
+/* What the reference does with numpy + Pillow + zlib after AutoHDR (clip(i * 255, 0, 255).astype(uint8), Image.fromarray, img.save(pnginfo=None,
+ * compress_level=4)), on B HWC images of the device, C = 3: the finished PNG files.  The file is not Pillow's (zlib's hash chains are sequential); it
+ * decodes to the same pixels, has a comparable size (tests/golden/png.META.txt) and is a pure function of the bytes: every step below is an integer
+ * rule, so the results are the bytes of the numpy statement of the same rules (lightdiffusion-next_amd/png.py: png_host).  Stateless: every buffer
+ * is the caller's, nothing is allocated, nothing waits for the device; the launches are ordered on `stream` and can be captured in a graph.
+ *
+ * Filter.  Per row the filter type t of 0 None, 1 Sub, 2 Up, 3 Average (floor), 4 Paeth, with bpp = 3 and zeros left of and above the image, whose
+ *   residuals r (mod 256) have the smallest sum of (r < 128 ? r : 256 - r); ties go to the lowest type.  The filtered stream is H rows of the type byte
+ *   and the 3 W residuals, N = H * (1 + 3 W) bytes; N <= 2^30.
+ * Deflate.  The stream is cut into chunks of 16 384 bytes (the last may be shorter); each chunk becomes deflate blocks on its own and ends on a byte
+ *   boundary.  Tokens: a position breaks when it is the chunk's first or its byte differs from the one before.  A position that does not break lies in
+ *   a run; with a = the last break before it, R = the positions from a + 1 up to the next break or the chunk's end, k = its index among them: R < 4
+ *   makes it a literal; otherwise the run is cut into pieces of 258 from its start, a piece shorter than 3 is literals, and any other piece is one
+ *   match (length = the piece, distance 1) at its first position.  Breaks are literals.  Literal / length alphabet: the 286 symbols, counted with one
+ *   end-of-block.  Code lengths (limit 15; 7 for the code-length code): the used symbols sorted by (count, symbol); Huffman's algorithm on two queues,
+ *   a leaf before an internal node of equal weight; depths above the limit are set to it and, while the Kraft sum exceeds 1, one code of the limit
+ *   leaves and the deepest shorter code moves one down, taking the leaver along; the lengths go to the symbols in sorted order, the rarest the longest;
+ *   canonical codes.  Two distance codes of one bit each are declared, so distance 1 is the bit 0.  Header: HLIT = the last used symbol + 1 (at least
+ *   257), HDIST = 2; the lengths, greedy from the left: at a zero, a run of >= 11 zeros is (18, min(run, 138)), of >= 3 is (17, run); at a length equal
+ *   to the one before it, a run of >= 3 is (16, min(run, 6)); anything else the length itself; HCLEN trimmed to the last used, at least 4.  If the
+ *   dynamic block's bytes (rounded up) are fewer than the chunk + 5, it is written, followed, except in the last chunk, by an empty stored block (000,
+ *   pad, 00 00 FF FF); otherwise a stored block.  BFINAL is set in the last chunk's block.  The first chunk opens with the zlib header 78 01.
+ * Container.  Signature; IHDR (W, H, 8, 2, 0, 0, 0); one IDAT per chunk; one IDAT of 4 bytes with the Adler-32 of the filtered stream; IEND; CRC-32s
+ *   as PNG defines them.  No other chunks (the reference passes pnginfo=None).
+ * Sizes: a chunk of n bytes makes at most n + 9, so a file is at most 63 + N + 21 * ceil(N / 16384) bytes: ldx_png_bound_bytes. */
+/* Bytes of workspace ldx_png_encode needs for B images of H x W, and the largest file of one H x W image (LDX_EINVAL, negative, for a shape they
+ * refuse: B > 65535, H or W < 1, N > 2^30). */
+int64_t ldx_png_workspace_bytes(int B, int H, int W);
+int64_t ldx_png_bound_bytes(int H, int W);
+/* The whole encoder.  Input: in_f32 dense fp32 [B][H][W][3], quantised as the reference does, (uint8) trunc(clamp(255.0f * v, 0, 255)) (NaN -> 0), OR
+ * in_u8 [B][H][W][3] with rows of in_pitch bytes and images H * in_pitch bytes apart (ldx_hdr_apply's out_u8 in place); exactly one of the two is
+ * non-null.  Output: file b at out + b * out_stride (out_stride >= ldx_png_bound_bytes(H, W)), its length in out_len[b] (device, uint32 [B]); bytes
+ * past the length are left alone.  workspace: ldx_png_workspace_bytes(B, H, W) bytes, 16-aligned. */
+int ldx_png_encode(const float* in_f32, const uint8_t* in_u8, int64_t in_pitch, int B, int H, int W, void* workspace, uint8_t* out, int64_t out_stride,
+                   uint32_t* out_len, void* stream);
+/* The filter stage alone: filtered [B][H][1 + 3 W] (the stream of every image) and, if non-null, types [B][H]. */
+int ldx_png_filter(const float* in_f32, const uint8_t* in_u8, int64_t in_pitch, int B, int H, int W, uint8_t* filtered, uint8_t* types, void* stream);
+/* The deflate stage alone on n arbitrary device bytes (1 <= n <= 2^30): a complete zlib stream (78 01, the chunks as above, Adler-32) at out, at most
+ * ldx_zlib_bound_bytes(n) = 6 + n + 9 * ceil(n / 16384) bytes, its length in out_len[0] (device).  workspace: ldx_zlib_workspace_bytes(n) bytes,
+ * 16-aligned. */
+int64_t ldx_zlib_workspace_bytes(int64_t n);
+int64_t ldx_zlib_bound_bytes(int64_t n);
+int ldx_zlib_deflate(const uint8_t* bytes, int64_t n, void* workspace, uint8_t* out, uint32_t* out_len, void* stream);
+
 /* ---- single-op entry points (parity tests call the kernels through these) ----------------------- */
 /* 16-bit tensors are device pointers to bf16/fp16 per `dtype`.  Layouts: see csrc/ldx_kernels.h. */
 int ldx_op_convert(const float* in_f32, void* out_16, int64_t n, int dtype, int to_f32, void* stream);

@@ -15,6 +15,8 @@ Layout:
   usdu.py      UltimateSDUpscale: the img2img tile redraw / seam fix, canvas on the device (ldx_image_* kernels -> libldx_image.so)
   hdr.py       AutoHDR: the default post-effect after the VAE (LittleCMS Lab round trip as two 33^3 tables, luminance table, Pillow's contrast / colour
                blends) on device images (ldx_hdr_* kernels -> libldx_hdr.so); autohdr_host is the same in numpy
+  png.py       PNGEncoder / SaveImage: the finished PNG file of a device image (row filters, chunked deflate, CRC-32 / Adler-32: ldx_png_* kernels
+               -> libldx_png.so) and the reference's file placement around it; png_host is the same in numpy
 """
 from . import lib, weights  # noqa: F401
 from .engine import UNetEngine, UNetConfig, VAEDecoderEngine, CLIPTextEngine, FluxEngine, T5Engine, ESRGANEngine, TAESDEngine, bislerp, latent_upscale  # noqa: F401
@@ -22,7 +24,8 @@ VAEEngine = VAEDecoderEngine      # the same engine encodes when encoder.* weigh
 from .weights import VAEConfig, CLIPConfig, FluxConfig, T5Config, ESRGANConfig, TAESDConfig  # noqa: F401
 from .hook import LdxUNetPatch, LdxFluxPatch  # noqa: F401
 from . import prompt  # noqa: F401
-from . import sampling, parallel, checkpoint, usdu, hdr  # noqa: F401
+from . import sampling, parallel, checkpoint, usdu, hdr, png  # noqa: F401
 from .sampling import LatentPreviewer  # noqa: F401
 from .usdu import UltimateSDUpscale  # noqa: F401
 from .hdr import AutoHDR  # noqa: F401
+from .png import PNGEncoder, SaveImage  # noqa: F401

@@ -235,6 +235,54 @@ int ldx_hdr_apply(const float* in_f32, const uint8_t* in_u8, int64_t in_pitch, i
     launch_hdr_apply(a, (hipStream_t)stream);
     return check_launch("ldx_hdr_apply");
 }
+// ---- SaveImage (png.hip) ---------------------------------------------------------------------------------------------------------------------
+static bool png_shape_ok(int B, int H, int W) {
+    return B > 0 && B <= 65535 && H > 0 && W > 0 && W <= (1 << 28) && (int64_t)H * (1 + 3 * (int64_t)W) <= png_max_stream_bytes();
+}
+int64_t ldx_png_workspace_bytes(int B, int H, int W) {
+    if (!png_shape_ok(B, H, W)) { set_error("ldx_png_workspace_bytes: bad shape (1 <= B <= 65535, H, W >= 1, H * (1 + 3 W) <= 2^30)"); return LDX_EINVAL; }
+    return png_workspace_bytes(B, H, W);
+}
+int64_t ldx_png_bound_bytes(int H, int W) {
+    if (!png_shape_ok(1, H, W)) { set_error("ldx_png_bound_bytes: bad shape (H, W >= 1, H * (1 + 3 W) <= 2^30)"); return LDX_EINVAL; }
+    return png_bound_bytes(H, W);
+}
+int ldx_png_filter(const float* in_f32, const uint8_t* in_u8, int64_t in_pitch, int B, int H, int W, uint8_t* filtered, uint8_t* types, void* stream) {
+    if (!png_shape_ok(B, H, W) || (in_f32 != nullptr) == (in_u8 != nullptr) || (in_u8 && in_pitch < (int64_t)W * 3) || !filtered) {
+        set_error("ldx_png_filter: bad argument (1 <= B <= 65535, H, W >= 1, H * (1 + 3 W) <= 2^30, exactly one input, pitch < W * 3, null output)");
+        return LDX_EINVAL;
+    }
+    launch_png_filter(in_f32, in_u8, (long)in_pitch, B, H, W, filtered, types, (hipStream_t)stream);
+    return check_launch("ldx_png_filter");
+}
+int ldx_png_encode(const float* in_f32, const uint8_t* in_u8, int64_t in_pitch, int B, int H, int W, void* workspace, uint8_t* out, int64_t out_stride,
+                   uint32_t* out_len, void* stream) {
+    if (!png_shape_ok(B, H, W) || (in_f32 != nullptr) == (in_u8 != nullptr) || (in_u8 && in_pitch < (int64_t)W * 3) || !workspace ||
+        (uintptr_t)workspace % 16 || !out || !out_len || (uintptr_t)out_len % 4 || out_stride < png_bound_bytes(H, W)) {
+        set_error("ldx_png_encode: bad argument (1 <= B <= 65535, H, W >= 1, H * (1 + 3 W) <= 2^30, exactly one input, pitch < W * 3, workspace null or "
+                  "not 16-byte aligned, null output, out_stride < ldx_png_bound_bytes)");
+        return LDX_EINVAL;
+    }
+    PngArgs a{};
+    a.in_f32 = in_f32; a.in_u8 = in_u8; a.in_pitch = (long)in_pitch; a.B = B; a.H = H; a.W = W; a.workspace = workspace; a.out = out;
+    a.out_stride = (long)out_stride; a.out_len = out_len;
+    launch_png_encode(a, (hipStream_t)stream);
+    return check_launch("ldx_png_encode");
+}
+int64_t ldx_zlib_workspace_bytes(int64_t n) {
+    if (n <= 0 || n > png_max_stream_bytes()) { set_error("ldx_zlib_workspace_bytes: 1 <= n <= 2^30"); return LDX_EINVAL; }
+    return zlib_workspace_bytes((long)n);
+}
+int64_t ldx_zlib_bound_bytes(int64_t n) {
+    if (n <= 0 || n > png_max_stream_bytes()) { set_error("ldx_zlib_bound_bytes: 1 <= n <= 2^30"); return LDX_EINVAL; }
+    return zlib_bound_bytes((long)n);
+}
+int ldx_zlib_deflate(const uint8_t* bytes, int64_t n, void* workspace, uint8_t* out, uint32_t* out_len, void* stream) {
+    if (!bytes || n <= 0 || n > png_max_stream_bytes() || !workspace || (uintptr_t)workspace % 16 || !out || !out_len || (uintptr_t)out_len % 4) {
+        set_error("ldx_zlib_deflate: bad argument (null pointer, 1 <= n <= 2^30, workspace not 16-byte aligned)"); return LDX_EINVAL; }
+    launch_zlib_deflate(bytes, (long)n, workspace, out, out_len, (hipStream_t)stream);
+    return check_launch("ldx_zlib_deflate");
+}
 int ldx_t5_create(const ldx_t5_config* cfg, int device, ldx_engine** out) { return create_engine<T5Engine>(cfg, device, out, __func__); }
 int ldx_t5_encode(ldx_engine* e, const int32_t* ids, int B, int L, const float* bias, float* out, void* stream) {
     GUARD_BEGIN

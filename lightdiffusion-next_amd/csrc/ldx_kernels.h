@@ -608,4 +608,27 @@ void launch_hdr_apply(const HdrArgs& a, hipStream_t s);
 // one table read of an HWC byte image: out = tetrahedral read of `table` at in
 void launch_hdr_table(const uint8_t* in, long in_pitch, uint8_t* out, long out_pitch, int H, int W, const uint16_t* table, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// SaveImage (png.hip, libldx_png.so): the PNG file of B HWC images, C = 3, made on the device; include/ldx.h states each rule of the format.
+// Exactly one of in_f32 (dense [B][H][W][3]) and in_u8 (rows of in_pitch bytes, images H * in_pitch apart) is set.  The launchers take validated
+// arguments (capi.cpp): the filtered stream of one image, png_stream_bytes(H, W) = H * (1 + 3 W), is at most png_max_stream_bytes(); B <= 65535;
+// workspace of png_workspace_bytes(B, H, W) (zlib_workspace_bytes(n)) bytes, 16-aligned; out_stride >= png_bound_bytes(H, W).
+struct PngArgs {
+    const float* in_f32; const uint8_t* in_u8; long in_pitch;
+    int B, H, W;
+    void* workspace;
+    uint8_t* out; long out_stride; uint32_t* out_len;
+};
+constexpr long png_max_stream_bytes() { return 1L << 30; }         // chunk offsets and the file length are 32-bit
+long png_stream_bytes(int H, int W);
+long png_workspace_bytes(int B, int H, int W);
+long png_bound_bytes(int H, int W);
+long zlib_workspace_bytes(long n);
+long zlib_bound_bytes(long n);
+// stream [B][H][1 + 3 W]: every row's filter type and filtered bytes; types [B][H] if non-null
+void launch_png_filter(const float* in_f32, const uint8_t* in_u8, long in_pitch, int B, int H, int W, uint8_t* stream, uint8_t* types, hipStream_t s);
+void launch_png_encode(const PngArgs& a, hipStream_t s);
+// the zlib stream of n device bytes -> out, its length -> out_len[0]
+void launch_zlib_deflate(const uint8_t* bytes, long n, void* workspace, uint8_t* out, uint32_t* out_len, hipStream_t s);
+
 }  // namespace ldx

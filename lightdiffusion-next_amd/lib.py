@@ -126,6 +126,13 @@ _SIGS = {
     "ldx_hdr_table": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i64, _vp]),
     "ldx_hdr_workspace_bytes": (_i64, [_i, _i, _i]),
     "ldx_hdr_apply": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _i64, _vp, _vp]),
+    "ldx_png_workspace_bytes": (_i64, [_i, _i, _i]),
+    "ldx_png_bound_bytes": (_i64, [_i, _i]),
+    "ldx_png_encode": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i64, _vp, _vp]),
+    "ldx_png_filter": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
+    "ldx_zlib_workspace_bytes": (_i64, [_i64]),
+    "ldx_zlib_bound_bytes": (_i64, [_i64]),
+    "ldx_zlib_deflate": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "ldx_op_convert": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     "ldx_op_gemm": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
     "ldx_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
