@@ -566,6 +566,44 @@ int ldx_op_conv3x3_skip(const void* X, int ldx, const void* X2, int ldx2, int Ci
 int ldx_op_groupnorm(const void* X, int ldx, void* Y, int ldy, int B, int HW, int C, int G, float eps, int silu,
                      const float* gamma, const float* beta, float* workspace, int dtype, void* stream);
 int64_t ldx_op_groupnorm_workspace_floats(int B, int G);
+/* ---- test surface: GroupNorm statistics written by the launch in front of the GroupNorm ---------------------------------------------------------
+ * Almost every GroupNorm of a production plan skips its own statistics pass: its producer writes, next to the 16-bit output, the sum and the sum of
+ * squares of the values AS STORED, per (image, chunk of the image's rows, group), into
+ *     partial [B][nchunk][G][2] fp32 = (sum, sum of squares),  B = rows / HW images of HW rows, nchunk chunks per image,
+ * and the GroupNorm folds those rows in a fixed order (deterministic; GroupNormArgs::partial, csrc/ldx_kernels.h).  The engines plan this in
+ * Engine::fuse_gn_stats; the four entry points below build the same launch arguments and ask the same host rules (gemm_gn_fuse, rowgemm_gn_chunks), so
+ * a test reaches every producer and both consumers one op at a time.  Which rows make chunk c of an image depends on the kernel that runs
+ * (ldx_op_gemm_pick shows it): tile epilogues BM consecutive rows; the split-K reduce launch HW / nchunk consecutive rows; the patch-resident conv
+ * (N = 128) the 16-row x 32-column pixel tiles in row-major tile order; the row-block kernel 128 (K = 320) or 64 (K = 640) consecutive rows.
+ * max_chunks: the rows per image `partial` has room for; at most B * max_chunks rows are written, *nchunk_out = the chunks per image in effect, and rows
+ * behind B * nchunk are left alone.  Where the launch cannot produce the statistics — the kernel or tile picked has no such output stage, the chunk
+ * count exceeds max_chunks, or the consumer would be the one-launch small GroupNorm, which takes no producer rows — the answer is LDX_EINVAL with
+ * NOTHING launched and nothing written: the plain op (ldx_op_conv3x3 / ldx_op_gemm / ldx_op_rowgemm) is the launch the planner makes then.
+ * Split-K launches use the single-op workspace: one stream per device at a time, as for the plain ops. */
+/* ldx_op_conv3x3 (arguments as there), optionally with the fused 1x1 skip of ldx_op_conv3x3_skip (X2 [rows][ldx2], Cin2 channels, W = [Cout][9 Cin | Cin2];
+ * Cin2 = 0: none; with it stride 1, output extent = input extent, no resize), as the producer of a GroupNorm(gn_groups) over Y [B][Hout * Wout][Cout].
+ * dup_rows != 0: every row m of Y is also stored at row m + dup_rows (GemmArgs::dup_rows, the shared CFG prefix) — Y then needs dup_rows + B * Hout * Wout
+ * rows, and the statistics still count every row once. */
+int ldx_op_conv3x3_gn(const void* X, int ldx, const void* X2, int ldx2, int Cin2, const void* W, int B, int Hin, int Win, int Cin, int Cout,
+                      int stride, int Hout, int Wout, int resize_to_out, const float* bias, const float* rowvec, int rowvec_ld,
+                      const void* R, int ldr, void* Y, int ldy, int64_t dup_rows, float* partial, int gn_groups, int max_chunks, int32_t* nchunk_out,
+                      int dtype, void* stream);
+/* ldx_op_gemm without GEGLU (arguments as there; the 16-bit C is required) as the producer of a GroupNorm(gn_groups) over C [M / gn_hw][gn_hw][N]. */
+int ldx_op_gemm_gn(const void* A, int lda, const void* W, int M, int N, int K, const float* bias, const float* rowvec, int rowvec_ld, int rows_per_batch,
+                   const void* R, int ldr, void* C, int ldc, float* Cf, int ldcf, int gn_hw, float* partial, int gn_groups, int max_chunks, int32_t* nchunk_out,
+                   int dtype, void* stream);
+/* ldx_op_rowgemm with pro 0 or 1 (arguments as there) as the producer of a GroupNorm(32) over Y [M / HW][HW][N]: gn_out is `partial` above with
+ * nchunk = HW / 128 (K = 320) or HW / 64 (K = 640), dup_rows as for ldx_op_conv3x3_gn.  The planner's conditions for a row-block producer: N == K, M a multiple
+ * of HW, HW a multiple of the row block — LDX_EINVAL otherwise, as above. */
+int ldx_op_rowgemm_gn(const void* X, int ldx, void* Y, int ldy, int64_t M, int N, int K, const void* W, const float* bias, const void* R, int ldr,
+                      int pro, const float* gamma, const float* beta, float eps, int HW, int64_t dup_rows, float* gn_out, int max_chunks, int32_t* nchunk_out,
+                      int dtype, void* stream);
+/* ldx_op_groupnorm without its statistics pass: apply from the caller's rows partial [B][stats_chunks][G][2] (any split of each image's HW rows into
+ * stats_chunks chunks, 1 <= stats_chunks <= 32768).  More than 256 rows per image are first folded, in a fixed order, into 64 rows per image that
+ * the launch writes BEHIND the caller's rows: partial must hold ldx_op_groupnorm_stats_floats(B, G, stats_chunks) floats = the rows + that fold target. */
+int ldx_op_groupnorm_stats(const void* X, int ldx, void* Y, int ldy, int B, int HW, int C, int G, float eps, int silu,
+                           const float* gamma, const float* beta, float* partial, int stats_chunks, int dtype, void* stream);
+int64_t ldx_op_groupnorm_stats_floats(int B, int G, int stats_chunks);
 int ldx_op_layernorm(const void* X, int ldx, void* Y, int ldy, int rows, int C, float eps,
                      const float* gamma, const float* beta, int dtype, void* stream);
 int ldx_op_attention(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,

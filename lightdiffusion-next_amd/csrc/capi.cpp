@@ -680,7 +680,70 @@ int ldx_op_conv3x3_skip(const void* X, int ldx_, const void* X2, int ldx2, int C
     launch_gemm(g, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_conv3x3_skip");
 }
+// The producers of GroupNorm statistics as the planner launches them (Engine::fuse_gn_stats): the arguments are complete but for the statistics; ask gemm_gn_fuse,
+// refuse before anything is launched where it says no (so launch_gemm's gemm_gn_check can never fire from here), else point the launch at the caller's rows.
+static int launch_gemm_gn(GemmArgs& g, int HW, float* partial, int gn_groups, int max_chunks, int32_t* nchunk_out, int dtype, void* stream, const char* fn) {
+    if (int rc = attach_splitk(g)) return rc;
+    const int nchunk = gemm_gn_fuse(g, HW, gn_groups, max_chunks);
+    if (!nchunk) { set_error(std::string(fn) + ": this launch does not produce GroupNorm statistics (gemm_gn_fuse: kernel, tile or chunk count; the one-launch small GroupNorm)"); return LDX_EINVAL; }
+    g.gn_partial = partial;
+    launch_gemm(g, dtype_of(dtype), (hipStream_t)stream);
+    *nchunk_out = nchunk;
+    return check_launch(fn);
+}
+int ldx_op_conv3x3_gn(const void* X, int ldx_, const void* X2, int ldx2, int Cin2, const void* W, int B, int Hin, int Win, int Cin, int Cout, int stride, int Hout, int Wout,
+                      int resize_to_out, const float* bias, const float* rowvec, int rowvec_ld, const void* R, int ldr, void* Y, int ldy, int64_t dup_rows,
+                      float* partial, int gn_groups, int max_chunks, int32_t* nchunk_out, int dtype, void* stream) {
+    if (!X || !W || !Y || !partial || !nchunk_out || B <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || Cin <= 0 || Cin % 64 || Cout <= 0 || ldx_ % 8 || ldx_ < Cin ||
+        (stride != 1 && stride != 2) || ldy % 8 || ldy < Cout || (R && (ldr % 8 || ldr < Cout)) || (rowvec && rowvec_ld < Cout) || dup_rows < 0 || gn_groups <= 0 || max_chunks <= 0 ||
+        Cin2 < 0 || (Cin2 && (!X2 || Cin2 % 64 || ldx2 % 8 || ldx2 < Cin2 || stride != 1 || Hout != Hin || Wout != Win || resize_to_out))) {
+        set_error("ldx_op_conv3x3_gn: bad argument (Cin % 64, Cin2 % 64, ldx % 8, ldy % 8, ldr % 8; the fused skip: stride 1, output extent = input extent)"); return LDX_EINVAL; }
+    GemmArgs g = gemm_conv_args(X, ldx_, W, B, Hin, Win, Cin, Cout, 9 * Cin + Cin2, stride, Hout, Wout, resize_to_out != 0);
+    if (Cin2) { g.A2 = X2; g.lda2 = ldx2; g.Cin2 = Cin2; }
+    g.bias = bias; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld; g.R = R; g.ldr = ldr; g.C = Y; g.ldc = ldy; g.dup_rows = (long)dup_rows;
+    return launch_gemm_gn(g, Hout * Wout, partial, gn_groups, max_chunks, nchunk_out, dtype, stream, __func__);
+}
+int ldx_op_gemm_gn(const void* A, int lda, const void* W, int M, int N, int K, const float* bias, const float* rowvec, int rowvec_ld, int rows_per_batch,
+                   const void* R, int ldr, void* C, int ldc, float* Cf, int ldcf, int gn_hw, float* partial, int gn_groups, int max_chunks, int32_t* nchunk_out,
+                   int dtype, void* stream) {
+    if (!A || !W || !C || !partial || !nchunk_out || M <= 0 || N <= 0 || K <= 0 || K % 8 || lda % 8 || lda < K || ldc % 8 || ldc < N || (R && (ldr % 8 || ldr < N)) ||
+        (rowvec && rowvec_ld < N) || (Cf && ldcf < N) || gn_hw <= 0 || M % gn_hw || gn_groups <= 0 || max_chunks <= 0) {
+        set_error("ldx_op_gemm_gn: bad argument (K % 8, lda % 8, ldc % 8, ldr % 8, M % gn_hw; a 16-bit C is required)"); return LDX_EINVAL; }
+    GemmArgs g = gemm_linear_args(A, lda, W, M, N, K);
+    g.bias = bias; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld; if (rows_per_batch > 0) g.rows_per_batch = rows_per_batch;
+    g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc; g.Cf = Cf; g.ldcf = ldcf;
+    return launch_gemm_gn(g, gn_hw, partial, gn_groups, max_chunks, nchunk_out, dtype, stream, __func__);
+}
+int ldx_op_rowgemm_gn(const void* X, int ldx_, void* Y, int ldy, int64_t M, int N, int K, const void* W, const float* bias, const void* R, int ldr,
+                      int pro, const float* gamma, const float* beta, float eps, int HW, int64_t dup_rows, float* gn_out, int max_chunks, int32_t* nchunk_out,
+                      int dtype, void* stream) {
+    RowGemmArgs a{};
+    a.X = X; a.ldx = ldx_; a.Y = Y; a.ldy = ldy; a.M = (long)M; a.N = N; a.K = K; a.W = W; a.bias = bias; a.R = R; a.ldr = ldr;
+    a.pro = pro; a.g = gamma; a.b = beta; a.eps = eps; a.HW = HW; a.G = 32; a.dup_rows = (long)dup_rows;
+    if (!X || !Y || !W || !gn_out || !nchunk_out || ldx_ < K || ldy < N || (R && ldr < N) || pro < 0 || pro > 1 || dup_rows < 0 || max_chunks <= 0 || !rowgemm_ok(a)) {
+        set_error("ldx_op_rowgemm_gn: shape not taken (K = 320 or 640, N a multiple of K, pro 0 or 1)"); return LDX_EINVAL; }
+    const int nchunk = rowgemm_gn_chunks(a, HW, 32, max_chunks);
+    if (!nchunk) { set_error("ldx_op_rowgemm_gn: this launch does not produce GroupNorm statistics (N == K, HW a multiple of the row block, M of HW; the one-launch small GroupNorm)"); return LDX_EINVAL; }
+    a.gn_out = gn_out; a.gn_nchunk = nchunk;
+    launch_rowgemm(a, dtype_of(dtype), (hipStream_t)stream);
+    *nchunk_out = nchunk;
+    return check_launch("ldx_op_rowgemm_gn");
+}
 int64_t ldx_op_groupnorm_workspace_floats(int B, int G) { return (int64_t)B * GN_NCHUNK * G * 2; }
+int64_t ldx_op_groupnorm_stats_floats(int B, int G, int stats_chunks) {
+    if (B <= 0 || G <= 0 || stats_chunks <= 0) return 0;
+    return (int64_t)B * ((int64_t)stats_chunks + GN_FOLD) * G * 2;
+}
+int ldx_op_groupnorm_stats(const void* X, int ldx_, void* Y, int ldy, int B, int HW, int C, int G, float eps, int silu,
+                           const float* gamma, const float* beta, float* partial, int stats_chunks, int dtype, void* stream) {
+    if (!X || !Y || !gamma || !beta || !partial || B <= 0 || HW <= 0 || C <= 0 || G <= 0 || C % 8 || C % G || G > 32 || ldx_ % 8 || ldy % 8 || ldx_ < C || ldy < C ||
+        stats_chunks <= 0 || stats_chunks > GN_MAX_PRODUCER_CHUNKS) {
+        set_error("ldx_op_groupnorm_stats: bad argument (C % 8, C % G, G <= 32, 1 <= stats_chunks <= 32768)"); return LDX_EINVAL; }
+    GroupNormArgs a{X, ldx_, Y, ldy, B, HW, C, G, eps, silu, gamma, beta, partial};
+    a.stats_chunks = stats_chunks;
+    launch_groupnorm(a, dtype_of(dtype), (hipStream_t)stream);
+    return check_launch("ldx_op_groupnorm_stats");
+}
 int ldx_op_groupnorm(const void* X, int ldx_, void* Y, int ldy, int B, int HW, int C, int G, float eps, int silu,
                      const float* gamma, const float* beta, float* workspace, int dtype, void* stream) {
     if (!X || !Y || !gamma || !beta || !workspace || C % 8 || C % G || G > 32 || ldx_ % 8 || ldy % 8) { set_error("ldx_op_groupnorm: bad argument"); return LDX_EINVAL; }

@@ -420,11 +420,11 @@ void Engine::fuse_gn_stats() {
         if (cur.ops[i].kind == OP_GN && cur.ops[i - 1].kind == OP_ROWGEMM) {          // row-block producer (proj_out + residual): statistics from its output stage
             RowGemmArgs& r = cur.ops[i - 1].rg;
             GroupNormArgs& n = cur.ops[i].gn;
-            const int bm = rowblock_rows(r.K);
-            if (!gemm_gn_fuse_enabled() || r.pro == 2 || r.Y != n.X || r.ldy != n.ldx || r.N != n.C || r.N != r.K || n.G != 32 || (long)r.M != (long)n.B * n.HW || n.HW % bm || n.HW / bm > gn_ws_rows ||
-                gn_uses_small_kernel(n.B, n.HW, n.C, n.G)) continue;      // last term: the one-launch small GroupNorm kernel takes it (norm.hip)
-            r.gn_out = n.partial; r.gn_nchunk = n.HW / bm; r.HW = n.HW;
-            n.stats_chunks = n.HW / bm;
+            if (r.Y != n.X || r.ldy != n.ldx || r.N != n.C || (long)r.M != (long)n.B * n.HW) continue;
+            const int nchunk = rowgemm_gn_chunks(r, n.HW, n.G, gn_ws_rows);      // (xf_pick.cpp: whole row blocks per image, not the one-launch small GroupNorm, ...)
+            if (!nchunk) continue;
+            r.gn_out = n.partial; r.gn_nchunk = nchunk; r.HW = n.HW;
+            n.stats_chunks = nchunk;
             cur.ops[i].bytes = 2.0 * 2.0 * (double)n.B * n.HW * n.C;
             gn_label(cur.ops[i]);
             continue;

@@ -298,6 +298,10 @@ struct RowGemmArgs {
     long dup_rows;                 // != 0: row m of Y is also stored at row m + dup_rows (GemmArgs::dup_rows)
 };
 bool rowgemm_ok(const RowGemmArgs& a);
+// Can launch_rowgemm(a) produce the statistics of a consumer GroupNorm(G groups) over [a.M / HW][HW][a.N] (RowGemmArgs::gn_out)?  If yes, the row blocks per image (the
+// consumer's chunk count), else 0: LDX_GN_FUSE=0, the GroupNorm prologue (pro = 2), N != K, G != 32, images that are not whole row blocks, more chunks than max_chunks, or a
+// GroupNorm the one-launch small kernel takes.  Engine::fuse_gn_stats and ldx_op_rowgemm_gn ask it (xf_pick.cpp); the caller sets gn_out / gn_nchunk / HW.
+int rowgemm_gn_chunks(const RowGemmArgs& a, int HW, int G, int max_chunks);
 void launch_rowgemm(const RowGemmArgs& a, DType dt, hipStream_t s);
 bool xattn_block_ok(const XAttnArgs& a);
 void launch_xattn_block(const XAttnArgs& a, DType dt, hipStream_t s);

@@ -25,6 +25,13 @@ bool ff_block_ok(const FFBlockArgs& a) {
 bool gn_uses_small_kernel(int B, long HW, int C, int G) {
     return G > 0 && (C / G) % 8 == 0 && HW * (C / G) <= g_plan_sw.gn_small_max && (long)G * B >= 32;
 }
+// The row-block producer's side of the fused statistics (rowgemm.hip writes one row per row block and image): the conditions Engine::fuse_gn_stats plans under
+int rowgemm_gn_chunks(const RowGemmArgs& a, int HW, int G, int max_chunks) {
+    const int bm = a.K > 0 ? rowblock_rows(a.K) : 0;
+    if (!gemm_gn_fuse_enabled() || bm <= 0 || a.pro == 2 || a.N != a.K || G != 32 || HW <= 0 || a.M <= 0 || a.M % HW || HW % bm || HW / bm > max_chunks) return 0;
+    if (gn_uses_small_kernel((int)(a.M / HW), HW, a.N, G)) return 0;      // the one-launch small GroupNorm kernel takes it (norm.hip)
+    return HW / bm;
+}
 struct GnGeom { int CH, TX, RY; };
 static inline GnGeom gn_geom(int C) {
     const int cpp = C / 8;

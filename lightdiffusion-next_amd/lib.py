@@ -138,6 +138,11 @@ _SIGS = {
     "ldx_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
     "ldx_op_groupnorm": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _i, _vp]),
     "ldx_op_groupnorm_workspace_floats": (_i64, [_i, _i]),
+    "ldx_op_conv3x3_gn": (_i, [_vp, _i, _vp, _i, _i, _vp] + [_i] * 9 + [_vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp, _i, _i, C.POINTER(C.c_int32), _i, _vp]),
+    "ldx_op_gemm_gn": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, C.POINTER(C.c_int32), _i, _vp]),
+    "ldx_op_rowgemm_gn": (_i, [_vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _f, _i, _i64, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
+    "ldx_op_groupnorm_stats": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "ldx_op_groupnorm_stats_floats": (_i64, [_i, _i, _i]),
     "ldx_op_upconv2x": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "ldx_op_conv3x3_skip": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "ldx_op_layernorm_mx": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
