@@ -396,6 +396,24 @@ int ldx_image_composite(uint8_t* canvas, int64_t canvas_pitch, int H, int W, int
 /* img [H][W][C]: every byte of the rectangle (x0, y0, w, h) = value (ImageDraw.rectangle / Image.new for the tile masks, :471,514-518). */
 int ldx_image_fill_rect(uint8_t* img, int64_t pitch, int H, int W, int C, int x0, int y0, int w, int h, int value, void* stream);
 
+/* ---- fp32 canvas ops of the ADetailer path (DetailerForEach.do_detail, src/AutoDetailer/ADetailer.py:643-871) ----------------------------- */
+/* What the reference does in torch on the CPU around the networks of one segment.  The canvas is fp32 [H][W][3] dense on the device and stays fp32
+ * between segments; each product and each sum below is rounded on its own (no fused multiply-add), so the results are the floats of the numpy
+ * statement of the same rules (lightdiffusion-next_amd/detailer.py).  Stateless, on the caller's stream, nothing is allocated. */
+/* tensor2pil (tensor_util.py:18-40) of the rectangle (x0, y0, w, h) of the canvas, which must lie inside it: out [h][w][3] with a row pitch in bytes
+ * = (uint8) trunc(clamp(v, 0, 1) * 255.0f), ldx_image_quantize's rule: the image ldx_image_resample_pass reads. */
+int ldx_detail_crop_quantize(const float* canvas, int H, int W, int x0, int y0, int w, int h, uint8_t* out, int64_t out_pitch, void* stream);
+/* torchvision's GaussianBlur as tensor_gaussian_blur_mask calls it (tensor_util.py:218-254): in fp32 [h][w], table fp32 [k][k] (k odd, <= 63; the host
+ * builds it as the outer product of the normalised 1-D kernel, detailer.blur_table),
+ *   out[y][x] = sum over (dy, dx) in row-major order of table[dy][dx] * in[reflect(y + dy - k/2)][reflect(x + dx - k/2)],
+ * the accumulator starting at 0.0f, each tap one rounded product and one rounded add.  reflect has no edge repeat (-1 -> 1, n -> n - 2);
+ * k / 2 >= h or k / 2 >= w is LDX_EINVAL (torch refuses the same padding).  in and out must not overlap. */
+int ldx_detail_blur_mask(const float* in, int h, int w, const float* table, int k, float* out, void* stream);
+/* tensor_paste (tensor_util.py:121-151) in place: the tile src [h][w][3] with mask [h][w], both dense, is put at (x0, y0), which must lie inside the
+ * canvas; the tile is clipped at the canvas's right and bottom border.  With d the canvas value, s the tile's and m the mask's:
+ *   t0 = 1.0f - m;  t1 = t0 * d;  t2 = m * s;  d = t1 + t2. */
+int ldx_detail_paste(float* canvas, int H, int W, int x0, int y0, const float* src, const float* mask, int h, int w, void* stream);
+
 /* ---- AutoHDR, the default post-effect of every pipeline exit (src/AutoHDR/ahdr.py:83-127, HDREffects.apply_hdr2) ------------------------- */
 /* What the reference does in PIL + LittleCMS + numpy after the VAE, on B HWC images of the device, C = 3.  Every step is an integer rule or a single
  * float32 operation, so the results are the bytes of the numpy statement of the same rules (lightdiffusion-next_amd/hdr.py: autohdr_host), which

@@ -17,6 +17,8 @@ Layout:
                blends) on device images (ldx_hdr_* kernels -> libldx_hdr.so); autohdr_host is the same in numpy
   png.py       PNGEncoder / SaveImage: the finished PNG file of a device image (row filters, chunked deflate, CRC-32 / Adler-32: ldx_png_* kernels
                -> libldx_png.so) and the reference's file placement around it; png_host is the same in numpy
+  detailer.py  Detailer: ADetailer's per-segment redraw (crop, LANCZOS, encode, sample, decode, feathered fp32 paste) with the canvas on the device
+               (ldx_detail_* kernels -> libldx_detail.so, ldx_image_* for the 8-bit steps); detailer_host is the same in numpy
 """
 from . import lib, weights  # noqa: F401
 from .engine import UNetEngine, UNetConfig, VAEDecoderEngine, CLIPTextEngine, FluxEngine, T5Engine, ESRGANEngine, TAESDEngine, bislerp, latent_upscale  # noqa: F401
@@ -24,7 +26,8 @@ VAEEngine = VAEDecoderEngine      # the same engine encodes when encoder.* weigh
 from .weights import VAEConfig, CLIPConfig, FluxConfig, T5Config, ESRGANConfig, TAESDConfig  # noqa: F401
 from .hook import LdxUNetPatch, LdxFluxPatch  # noqa: F401
 from . import prompt  # noqa: F401
-from . import sampling, parallel, checkpoint, usdu, hdr, png  # noqa: F401
+from . import sampling, parallel, checkpoint, usdu, hdr, png, detailer  # noqa: F401
+from .detailer import Detailer, SEG  # noqa: F401
 from .sampling import LatentPreviewer  # noqa: F401
 from .usdu import UltimateSDUpscale  # noqa: F401
 from .hdr import AutoHDR  # noqa: F401

@@ -206,6 +206,28 @@ int ldx_image_fill_rect(uint8_t* img, int64_t pitch, int H, int W, int C, int x0
     launch_image_fill(img + (int64_t)y0 * pitch + (int64_t)x0 * C, (long)pitch, h, w * C, value, (hipStream_t)stream);
     return check_launch("ldx_image_fill_rect");
 }
+// ---- fp32 canvas ops of the ADetailer path (detail.hip) ---------------------------------------------------------------------------------
+static bool canvas_ok(const void* p, int H, int W) { return p && H > 0 && W > 0 && (int64_t)H * W <= (int64_t)1 << 29; }
+int ldx_detail_crop_quantize(const float* canvas, int H, int W, int x0, int y0, int w, int h, uint8_t* out, int64_t out_pitch, void* stream) {
+    if (!canvas_ok(canvas, H, W) || !rect_ok(x0, y0, w, h, W, H) || !image_ok(out, out_pitch, h, w, 3)) {
+        set_error("ldx_detail_crop_quantize: bad argument (null pointer, rectangle outside the canvas, pitch < w * 3)"); return LDX_EINVAL; }
+    launch_detail_crop_quantize(canvas, W, x0, y0, w, h, out, (long)out_pitch, (hipStream_t)stream);
+    return check_launch("ldx_detail_crop_quantize");
+}
+int ldx_detail_blur_mask(const float* in, int h, int w, const float* table, int k, float* out, void* stream) {
+    if (!canvas_ok(in, h, w) || !table || !out || in == out || k < 1 || k > detail_max_kernel() || k % 2 == 0 || k / 2 >= h || k / 2 >= w) {
+        set_error("ldx_detail_blur_mask: bad argument (null pointer, in == out, k even or outside 1..63, reflect padding k / 2 not below h and w)");
+        return LDX_EINVAL;
+    }
+    launch_detail_blur_mask(in, h, w, table, k, out, (hipStream_t)stream);
+    return check_launch("ldx_detail_blur_mask");
+}
+int ldx_detail_paste(float* canvas, int H, int W, int x0, int y0, const float* src, const float* mask, int h, int w, void* stream) {
+    if (!canvas_ok(canvas, H, W) || !canvas_ok(src, h, w) || !mask || x0 < 0 || y0 < 0 || x0 >= W || y0 >= H) {
+        set_error("ldx_detail_paste: bad argument (null pointer, empty tile, corner outside the canvas)"); return LDX_EINVAL; }
+    launch_detail_paste(canvas, W, x0, y0, src, mask, w, (h < H - y0 ? h : H - y0), (w < W - x0 ? w : W - x0), (hipStream_t)stream);
+    return check_launch("ldx_detail_paste");
+}
 // ---- AutoHDR (hdr.hip) -----------------------------------------------------------------------------------------------------------------------
 static bool hdr_shape_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= hdr_max_pixels(); }
 int64_t ldx_hdr_workspace_bytes(int B, int H, int W) {

@@ -635,4 +635,13 @@ void launch_png_encode(const PngArgs& a, hipStream_t s);
 // the zlib stream of n device bytes -> out, its length -> out_len[0]
 void launch_zlib_deflate(const uint8_t* bytes, long n, void* workspace, uint8_t* out, uint32_t* out_len, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// fp32 canvas ops of the ADetailer path (detail.hip, libldx_detail.so): a dense fp32 [H][W][3] device canvas; include/ldx.h states each rule.
+// The launchers take validated arguments (capi.cpp): rectangles inside the canvas, k odd, k / 2 < h and w, in != out.
+constexpr int detail_max_kernel() { return 63; }
+void launch_detail_crop_quantize(const float* canvas, int W, int x0, int y0, int w, int h, uint8_t* out, long out_pitch, hipStream_t s);
+void launch_detail_blur_mask(const float* in, int h, int w, const float* table, int k, float* out, hipStream_t s);
+// the rectangle (x0, y0, w, h) of the canvas from the first h rows and w columns of src [..][src_w][3] and mask [..][src_w]
+void launch_detail_paste(float* canvas, int W, int x0, int y0, const float* src, const float* mask, int src_w, int h, int w, hipStream_t s);
+
 }  // namespace ldx

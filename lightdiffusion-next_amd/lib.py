@@ -123,6 +123,9 @@ _SIGS = {
     "ldx_image_box_blur_pass": (_i, [_vp, _i64, _i, _i, _i, _f, _vp, _i64, _vp]),
     "ldx_image_composite": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp]),
     "ldx_image_fill_rect": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ldx_detail_crop_quantize": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "ldx_detail_blur_mask": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "ldx_detail_paste": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "ldx_hdr_table": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i64, _vp]),
     "ldx_hdr_workspace_bytes": (_i64, [_i, _i, _i]),
     "ldx_hdr_apply": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _i64, _vp, _vp]),

@@ -610,6 +610,7 @@ def sample_dpmpp_sde_cfgpp(model, x, sigmas, eta=1.0, s_noise=1.0, noise_sampler
 
 
 _MULTISCALE_WHITELIST = ("dpmpp_sde_cfgpp", "sample_euler_ancestral", "sample_euler", "sample_dpmpp_2m_cfgpp")
+_MULTISCALE_SAMPLERS = (sample_euler, sample_dpmpp_2m_cfgpp, sample_dpmpp_sde_cfgpp)       # the sampler functions with a multiscale path
 
 
 def _resolve_sampler(sampler_name):
@@ -635,7 +636,11 @@ class KSampler:
 
     def sample(self, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0,
                enable_multiscale=True, multiscale_factor=0.5, multiscale_fullres_start=3,
-               multiscale_fullres_end=8, multiscale_intermittent_fullres=False, noise=None, trace=None, preview=None, preview_every=5):
+               multiscale_fullres_end=8, multiscale_intermittent_fullres=False, noise=None, trace=None, preview=None, preview_every=5,
+               multiscale_every_sampler=False):
+        """multiscale_every_sampler: hand the multiscale options to the sampler function whatever its name, as ADetailer's ksampler2 does
+        (ADetailer.py:166-177), not only for the names on sample1's whitelist.  The two euler_*_cfgpp functions of the reference swallow the
+        options in **kwargs and have no multiscale path; theirs here take none."""
         ms = self.model_sampling
         denoise = denoise or 1.0                                   # sampling.py:875 quirk (A-12)
         latent_image = latent_image.float()
@@ -644,7 +649,7 @@ class KSampler:
         sigmas = sigmas_for(ms, scheduler, steps, denoise)
         fn, disable_cfg1 = _resolve_sampler(sampler_name)
         extra = {}
-        if sampler_name in _MULTISCALE_WHITELIST:                  # whitelist mismatch quirk (A-3)
+        if sampler_name in _MULTISCALE_WHITELIST or (multiscale_every_sampler and fn in _MULTISCALE_SAMPLERS):   # whitelist mismatch quirk (A-3)
             extra = dict(enable_multiscale=enable_multiscale, multiscale_factor=multiscale_factor,
                          multiscale_fullres_start=multiscale_fullres_start,
                          multiscale_fullres_end=multiscale_fullres_end,

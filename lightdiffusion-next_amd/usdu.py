@@ -204,44 +204,14 @@ class _Image:
         return self.buf[:, :self.w * self.c].unflatten(1, (self.w, self.c))
 
 
-class UltimateSDUpscale:
-    """UltimateSDUpscale.upscale (UltimateSDUpscale.py:904-1019) on the engines: `unet_engine` (UNetEngine), `vae_engine` (VAEEngine with encoder
-    weights), `esrgan_engine` (ESRGANEngine).
+class ImageOps:
+    """Thin wrappers of the 8-bit image C ABI (ldx_image_*) on _Image: what UltimateSDUpscale and detailer.Detailer share."""
 
-    Per tile, in the reference's order: crop -> to float, LANCZOS to the sample size when the crop differs, vae.encode, KSampler.sample, vae.decode,
-    quantise, LANCZOS back, composite through the blurred tile mask.  Every tile samples with the same `seed`; prepare_noise reseeds the global CPU
-    RNG and vae.encode draws from it, so the order of the calls is part of the result and is kept.
-
-    Quirks of the reference that are reproduced:
-      * the upscale model runs once per entry of USDUpscaler.get_factors (:326-337), which is one entry for every factor in (1, 4], and its x4 result
-        is quantised and LANCZOS-resized to (ceil(w * by / 8) * 8, ceil(h * by / 8) * 8); a factor <= 1 skips the model, one above 4 whose list
-        would hold a zero raises here (the reference divides by zero);
-      * any mode_type other than "None" runs the linear redraw ("Chess" too); any seam_fix_mode other than "None" runs the half-tile pass;
-      * seam_fix_denoise and seam_fix_width are read and never used: the seam pass samples with `denoise`;
-      * crop_cond is the identity: every tile gets the full conditioning; force_uniform_tiles is unused.
-    A batch of more than one image raises: the reference's batched tiles are not built."""
-
-    MODES = ("Linear", "Chess", "None")
-    SEAM_FIX_MODES = ("None", "Band Pass", "Half Tile", "Half Tile + Intersections")
-
-    def __init__(self, unet_engine, vae_engine, esrgan_engine, device=None):
-        self.unet, self.vae, self.esrgan = unet_engine, vae_engine, esrgan_engine
-        self.device = torch.device(device) if device is not None else next(e.device for e in (unet_engine, vae_engine, esrgan_engine) if e is not None)
+    def _init_ops(self, device):
+        self.device = torch.device(device)
         self._lib = lib.load()
         self._tables = {}
-        self.timings = None            # a dict of lists when a probe wants per-stage times (profiles/usdu_probe.py)
 
-    # the three network calls of a tile; tests replace them to pin everything else byte for byte
-    def _encode(self, pixels):
-        return self.vae.encode(pixels)
-
-    def _sample(self, latent, seed, steps, cfg, sampler_name, scheduler, positive, negative, denoise):
-        return KSampler(self.unet).sample(seed, steps, cfg, sampler_name, scheduler, positive, negative, latent, denoise=denoise)
-
-    def _decode(self, latent):
-        return self.vae.decode(latent)
-
-    # ---- thin wrappers of the C ABI ------------------------------------------------------------------------------------------
     def _st(self):
         return lib.current_stream_ptr()
 
@@ -268,7 +238,8 @@ class UltimateSDUpscale:
         return self._tables[key]
 
     def _resize(self, img, rect, out_w, out_h, filter=LANCZOS):
-        """Image.resize of the rectangle `rect` of img (None: all of it): the pass along x, then the pass along y; a pass that keeps its size is skipped."""
+        """Image.resize of the rectangle `rect` of img (None: all of it): the pass along x, then the pass along y; a pass that keeps its size is skipped
+        (the caller skips a resize that keeps both)."""
         x0, y0, x1, y1 = rect or (0, 0, img.w, img.h)
         w, h = x1 - x0, y1 - y0
         src, pitch = img.ptr(x0, y0), img.pitch
@@ -289,6 +260,42 @@ class UltimateSDUpscale:
     def _fill(self, img, rect, value):
         x0, y0, x1, y1 = rect
         lib.check(self._lib.ldx_image_fill_rect(img.ptr(), img.pitch, img.h, img.w, img.c, x0, y0, x1 - x0, y1 - y0, value, self._st()), "ldx_image_fill_rect")
+
+
+class UltimateSDUpscale(ImageOps):
+    """UltimateSDUpscale.upscale (UltimateSDUpscale.py:904-1019) on the engines: `unet_engine` (UNetEngine), `vae_engine` (VAEEngine with encoder
+    weights), `esrgan_engine` (ESRGANEngine).
+
+    Per tile, in the reference's order: crop -> to float, LANCZOS to the sample size when the crop differs, vae.encode, KSampler.sample, vae.decode,
+    quantise, LANCZOS back, composite through the blurred tile mask.  Every tile samples with the same `seed`; prepare_noise reseeds the global CPU
+    RNG and vae.encode draws from it, so the order of the calls is part of the result and is kept.
+
+    Quirks of the reference that are reproduced:
+      * the upscale model runs once per entry of USDUpscaler.get_factors (:326-337), which is one entry for every factor in (1, 4], and its x4 result
+        is quantised and LANCZOS-resized to (ceil(w * by / 8) * 8, ceil(h * by / 8) * 8); a factor <= 1 skips the model, one above 4 whose list
+        would hold a zero raises here (the reference divides by zero);
+      * any mode_type other than "None" runs the linear redraw ("Chess" too); any seam_fix_mode other than "None" runs the half-tile pass;
+      * seam_fix_denoise and seam_fix_width are read and never used: the seam pass samples with `denoise`;
+      * crop_cond is the identity: every tile gets the full conditioning; force_uniform_tiles is unused.
+    A batch of more than one image raises: the reference's batched tiles are not built."""
+
+    MODES = ("Linear", "Chess", "None")
+    SEAM_FIX_MODES = ("None", "Band Pass", "Half Tile", "Half Tile + Intersections")
+
+    def __init__(self, unet_engine, vae_engine, esrgan_engine, device=None):
+        self.unet, self.vae, self.esrgan = unet_engine, vae_engine, esrgan_engine
+        self._init_ops(device if device is not None else next(e.device for e in (unet_engine, vae_engine, esrgan_engine) if e is not None))
+        self.timings = None            # a dict of lists when a probe wants per-stage times (profiles/usdu_probe.py)
+
+    # the three network calls of a tile; tests replace them to pin everything else byte for byte
+    def _encode(self, pixels):
+        return self.vae.encode(pixels)
+
+    def _sample(self, latent, seed, steps, cfg, sampler_name, scheduler, positive, negative, denoise):
+        return KSampler(self.unet).sample(seed, steps, cfg, sampler_name, scheduler, positive, negative, latent, denoise=denoise)
+
+    def _decode(self, latent):
+        return self.vae.decode(latent)
 
     def _blur(self, mask, out, tmp, box, radius):
         """GaussianBlur(radius) of `mask` into `out` (both canvas-sized, `out` zero outside earlier windows), inside blur_window(box) only.
