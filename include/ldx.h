@@ -162,6 +162,21 @@ int ldx_unet_refresh_abort(ldx_engine* e);
 /* Diagnostic (tests): 64-bit FNV-1a over every packed weight buffer of a finalized UNet engine, in allocation order, computed on the host
  * from copies of the buffers.  Equal digests = bit-identical weights, however they were loaded. */
 int ldx_weights_digest(ldx_engine* e, uint64_t* out);
+/* The same digest for ANY finalized engine (on a UNet engine it equals ldx_weights_digest): the buffers are the packed 16-bit matrices and fp32
+ * vectors of ldx_finalize, in allocation order (a Flux engine's MX fp8 copies are derived from them and are not counted). */
+int ldx_packed_digest(ldx_engine* e, uint64_t* out);
+/* ldx_load_tensor_device for UNet, Flux and T5 engines (the same contract: not copied, valid and unchanged until ldx_finalize returns).  The F32,
+ * F16 and BF16 tensors of a GGUF file go this way.  Any other engine: LDX_ESTATE, before an argument is looked at. */
+int ldx_load_tensor_dev(ldx_engine* e, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
+/* A GGML Q8_0 tensor (the reference's Flux and T5 files, Quantize/Quantizer.py:94-112): `blocks` = numel / 32 blocks of 34 bytes, each an fp16 scale d
+ * followed by 32 int8 values q along the INNERMOST axis of `shape` (the logical torch shape).  A weight is fp16_rne(float(d) * q): torch's
+ * d.view(float16) * q.view(int8), one rounding of an exact product, so the tensor is from here on an ordinary LDX_F16 tensor of that shape.
+ * Flux and T5 engines before ldx_finalize; any other engine LDX_ESTATE before an argument is looked at.  LDX_EINVAL: ndim == 0, an innermost extent
+ * that is no multiple of 32, a null or odd pointer (blocks are 2-byte aligned, no more).
+ *   on_device = 0: `blocks` is a HOST pointer; expanded on the host (csrc/weight_convert.h) and kept like an ldx_load_tensor copy.
+ *   on_device = 1: `blocks` is a DEVICE pointer; expanded by csrc/q8.hip on the null stream into an fp16 device buffer the engine owns (released when
+ *                  ldx_finalize returns) and registered like an ldx_load_tensor_dev tensor.  `blocks` may be freed as soon as the call returns. */
+int ldx_load_tensor_q8_0(ldx_engine* e, const char* key, const void* blocks, const int64_t* shape, int ndim, int on_device);
 
 /* ---- the hot path ----------------------------------------------------------------------------- */
 /* The wrapper body: denoised = x - UNet(x / sqrt(sigma^2+1), t(sigma), ctx) * sigma — i.e. all of
@@ -491,6 +506,9 @@ int ldx_zlib_deflate(const uint8_t* bytes, int64_t n, void* workspace, uint8_t* 
 /* ---- single-op entry points (parity tests call the kernels through these) ----------------------- */
 /* 16-bit tensors are device pointers to bf16/fp16 per `dtype`.  Layouts: see csrc/ldx_kernels.h. */
 int ldx_op_convert(const float* in_f32, void* out_16, int64_t n, int dtype, int to_f32, void* stream);
+/* The Q8_0 expansion of ldx_load_tensor_q8_0 alone (csrc/q8.hip): n / 32 blocks of 34 bytes (2-byte aligned) -> out[n], n % 32 == 0.  out_dtype LDX_F16:
+ * the fp16 value; LDX_BF16 / LDX_F32: that fp16 value converted (bf16 round-to-nearest-even; fp32 exact).  out is 16-byte aligned.  LDX_EINVAL otherwise. */
+int ldx_op_dequant_q8_0(const void* blocks, int64_t n, int out_dtype, void* out, void* stream);
 int ldx_op_gemm(const void* A, int lda, const void* W, int M, int N, int K, const float* bias,
                 const float* rowvec, int rowvec_ld, int rows_per_batch, int geglu,
                 const void* R, int ldr, void* C, int ldc, float* Cf, int ldcf, int dtype, void* stream);

@@ -17,6 +17,8 @@ Layout:
                blends) on device images (ldx_hdr_* kernels -> libldx_hdr.so); autohdr_host is the same in numpy
   png.py       PNGEncoder / SaveImage: the finished PNG file of a device image (row filters, chunked deflate, CRC-32 / Adler-32: ldx_png_* kernels
                -> libldx_png.so) and the reference's file placement around it; png_host is the same in numpy
+  gguf.py      GGUF v2 / v3 container reader (F32, F16, BF16, Q8_0): the reference's Flux and T5 files as {key: GGUFTensor}, nothing expanded;
+               FluxEngine.from_gguf / T5Engine.from_gguf expand Q8_0 once at load time (ldx_load_tensor_q8_0 -> libldx_q8.so, or the host)
   detailer.py  Detailer: ADetailer's per-segment redraw (crop, LANCZOS, encode, sample, decode, feathered fp32 paste) with the canvas on the device
                (ldx_detail_* kernels -> libldx_detail.so, ldx_image_* for the 8-bit steps); detailer_host is the same in numpy
 """
@@ -26,7 +28,7 @@ VAEEngine = VAEDecoderEngine      # the same engine encodes when encoder.* weigh
 from .weights import VAEConfig, CLIPConfig, FluxConfig, T5Config, ESRGANConfig, TAESDConfig  # noqa: F401
 from .hook import LdxUNetPatch, LdxFluxPatch  # noqa: F401
 from . import prompt  # noqa: F401
-from . import sampling, parallel, checkpoint, usdu, hdr, png, detailer  # noqa: F401
+from . import sampling, parallel, checkpoint, usdu, hdr, png, detailer, gguf  # noqa: F401
 from .detailer import Detailer, SEG  # noqa: F401
 from .sampling import LatentPreviewer  # noqa: F401
 from .usdu import UltimateSDUpscale  # noqa: F401

@@ -5,6 +5,7 @@
 #include <new>
 
 #include "engine.h"
+#include "weight_convert.h"
 
 using namespace ldx;
 
@@ -355,7 +356,27 @@ int ldx_load_tensor(ldx_engine* e, const char* key, const void* data, int dtype,
 int ldx_load_tensor_device(ldx_engine* e, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
     GUARD_BEGIN
     ENGINE_AS(UNetEngine, m);
-    return m->load_tensor_device(key, dev_ptr, dtype, shape, ndim);
+    return m->load_tensor_dev(__func__, key, dev_ptr, dtype, shape, ndim);
+    GUARD_END
+}
+int ldx_load_tensor_dev(ldx_engine* e, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
+    GUARD_BEGIN
+    ENGINE_AS(Engine, m);
+    if (!m->takes_device_tensors()) { set_error("ldx_load_tensor_dev: not a UNet, Flux or T5 engine"); return LDX_ESTATE; }
+    return m->load_tensor_dev(__func__, key, dev_ptr, dtype, shape, ndim);
+    GUARD_END
+}
+int ldx_load_tensor_q8_0(ldx_engine* e, const char* key, const void* blocks, const int64_t* shape, int ndim, int on_device) {
+    GUARD_BEGIN
+    ENGINE_AS(Engine, m);
+    if (!m->takes_q8_0()) { set_error("ldx_load_tensor_q8_0: not a Flux or T5 engine"); return LDX_ESTATE; }
+    return m->load_tensor_q8_0(key, blocks, shape, ndim, on_device != 0);
+    GUARD_END
+}
+int ldx_packed_digest(ldx_engine* e, uint64_t* out) {
+    GUARD_BEGIN
+    ENGINE_AS(Engine, m);
+    return m->packed_digest(__func__, out);
     GUARD_END
 }
 int ldx_unet_refresh_begin(ldx_engine* e) {
@@ -379,7 +400,7 @@ int ldx_unet_refresh_abort(ldx_engine* e) {
 int ldx_weights_digest(ldx_engine* e, uint64_t* out) {
     GUARD_BEGIN
     ENGINE_AS(UNetEngine, m);
-    return m->weights_digest(out);
+    return m->packed_digest(__func__, out);
     GUARD_END
 }
 int ldx_set_tables(ldx_engine* e, const float* log_sigmas, int n, const float* temb, int temb_dim) {
@@ -522,6 +543,12 @@ int ldx_op_convert(const float* in_f32, void* out_16, int64_t n, int dtype, int 
     if (to_f32) launch_t_to_f32(out_16, (float*)in_f32, (size_t)n, dtype_of(dtype), (hipStream_t)stream);
     else launch_f32_to_t(in_f32, out_16, (size_t)n, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_op_convert");
+}
+int ldx_op_dequant_q8_0(const void* blocks, int64_t n, int out_dtype, void* out, void* stream) {
+    if (!blocks || (uintptr_t)blocks % 2 || !out || (uintptr_t)out % 16 || n < 0 || n % Q8_0_BLOCK || (out_dtype != LDX_F16 && out_dtype != LDX_BF16 && out_dtype != LDX_F32)) {
+        set_error("ldx_op_dequant_q8_0: bad argument (null or odd block pointer, out not 16-byte aligned, n % 32, out_dtype)"); return LDX_EINVAL; }
+    launch_dequant_q8_0(DequantQ8Args{blocks, out, (size_t)n, out_dtype}, (hipStream_t)stream);
+    return check_launch("ldx_op_dequant_q8_0");
 }
 int ldx_op_gemm(const void* A, int lda, const void* W, int M, int N, int K, const float* bias, const float* rowvec, int rowvec_ld,
                 int rows_per_batch, int geglu, const void* R, int ldr, void* C, int ldc, float* Cf, int ldcf, int dtype, void* stream) {

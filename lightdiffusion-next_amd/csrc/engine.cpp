@@ -54,6 +54,7 @@ static void parallel_for(size_t n, const std::function<void(size_t, size_t)>& fn
 Engine::~Engine() {
     (void)hipSetDevice(device);
     for (void* p : dev_allocs) (void)hipFree(p);
+    drop_staged();
     cur.release();
     for (Plan& p : plan_cache) p.release();
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
@@ -73,6 +74,77 @@ int Engine::load_tensor(const char* key, const void* data, int dtype, const int6
     t.data.resize(n * esz);
     memcpy(t.data.data(), data, n * esz);
     host[key] = std::move(t);
+    return LDX_OK;
+}
+
+int Engine::load_tensor_dev(const char* fn, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
+    const std::string f(fn);
+    if (finalized && !refreshing) { set_error(f + " after ldx_finalize"); return LDX_ESTATE; }
+    if (!key || !dev_ptr || ndim < 0 || ndim > 8 || (ndim && !shape)) { set_error(f + ": bad argument"); return LDX_EINVAL; }
+    if (dtype != LDX_F32 && dtype != LDX_F16 && dtype != LDX_BF16) { set_error(f + ": bad dtype"); return LDX_EINVAL; }
+    if ((uintptr_t)dev_ptr % (dtype == LDX_F32 ? 4 : 2)) { set_error(f + ": misaligned pointer"); return LDX_EINVAL; }
+    HostTensor t;
+    t.dtype = dtype;
+    t.numel = 1;
+    for (int i = 0; i < ndim; ++i) {
+        if (shape[i] < 0) { set_error(f + ": negative extent"); return LDX_EINVAL; }
+        t.shape.push_back(shape[i]); t.numel *= (size_t)shape[i];
+    }
+    t.dev = dev_ptr;
+    host[key] = std::move(t);
+    return LDX_OK;
+}
+
+// A Q8_0 tensor becomes an LDX_F16 one here, by the one rule of weight_convert.h (q8_0_value): nothing behind this call knows the file was quantised
+int Engine::load_tensor_q8_0(const char* key, const void* blocks, const int64_t* shape, int ndim, bool on_device) {
+    if (finalized) { set_error("ldx_load_tensor_q8_0 after ldx_finalize"); return LDX_ESTATE; }
+    if (!key || !blocks || !shape || ndim <= 0 || ndim > 8 || (uintptr_t)blocks % 2) { set_error("ldx_load_tensor_q8_0: bad argument (null or odd pointer, ndim outside 1..8)"); return LDX_EINVAL; }
+    HostTensor t;
+    t.dtype = LDX_F16;
+    t.numel = 1;
+    for (int i = 0; i < ndim; ++i) {
+        if (shape[i] < 0) { set_error("ldx_load_tensor_q8_0: negative extent"); return LDX_EINVAL; }
+        t.shape.push_back(shape[i]); t.numel *= (size_t)shape[i];
+    }
+    if (shape[ndim - 1] % Q8_0_BLOCK) { set_error("ldx_load_tensor_q8_0: the innermost extent must be a multiple of 32"); return LDX_EINVAL; }
+    if (on_device) {
+        HIP_OK(hipSetDevice(device));
+        void* p = nullptr;
+        HIP_OK(hipMalloc(&p, std::max<size_t>(t.numel * 2, 16)));
+        q8_bufs.push_back(p);
+        launch_dequant_q8_0(DequantQ8Args{blocks, p, t.numel, LDX_F16}, nullptr);
+        if (int rc = launch_status()) return rc;
+        HIP_OK(hipDeviceSynchronize());            // `blocks` may be freed when this returns
+        t.dev = p;
+    } else {
+        t.data.resize(t.numel * 2);
+        uint16_t* out = (uint16_t*)t.data.data();
+        const uint8_t* src = (const uint8_t*)blocks;
+        parallel_for(t.numel / Q8_0_BLOCK, [&](size_t b, size_t e) {
+            for (size_t i = b; i < e; ++i) {
+                const uint8_t* blk = src + i * Q8_0_BYTES;
+                const uint16_t d = (uint16_t)(blk[0] | (blk[1] << 8));
+                for (int j = 0; j < Q8_0_BLOCK; ++j) out[i * Q8_0_BLOCK + j] = q8_0_value(d, (int8_t)blk[2 + j]);
+            }
+        });
+    }
+    host[key] = std::move(t);
+    return LDX_OK;
+}
+
+int Engine::packed_digest(const char* fn, uint64_t* out) {
+    if (!finalized) { set_error(std::string(fn) + ": not a finalized engine"); return LDX_ESTATE; }
+    if (!out) { set_error(std::string(fn) + ": bad argument"); return LDX_EINVAL; }
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipDeviceSynchronize());
+    uint64_t h = 0xcbf29ce484222325ull;
+    std::vector<uint8_t> buf;
+    for (const WeightAlloc& a : weight_allocs) {
+        buf.resize(a.bytes);
+        HIP_OK(hipMemcpy(buf.data(), a.p, a.bytes, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < a.bytes; ++i) { h ^= buf[i]; h *= 0x100000001b3ull; }
+    }
+    *out = h;
     return LDX_OK;
 }
 
@@ -142,6 +214,8 @@ const void* Engine::dev_src(const HostTensor* t) {
 void Engine::drop_staged() {
     for (auto& kv : staged) (void)hipFree(kv.second);
     staged.clear();
+    for (void* p : q8_bufs) (void)hipFree(p);
+    q8_bufs.clear();
 }
 void* Engine::pack16(size_t rows, size_t cols, const std::vector<Piece>& pieces) {
     void* p = weight_buf(rows * cols * 2);
@@ -153,8 +227,9 @@ void* Engine::pack16(size_t rows, size_t cols, const std::vector<Piece>& pieces)
         // UNet it accepts (all channel counts and context_dim are multiples of 64, conv_in is padded to 64).  Tested in every walk mode, so a refresh
         // reports it before anything is written.
         if (pc.row0 + pc.N > rows || pc.col0 + pc.K > cols || (dev && (pc.K % 8 || cols % 8 || pc.col0 % 8 || pc.CinPad % 8)) ||
-            (pc.CinPad ? (pc.K != 9 * pc.CinPad || pc.Cin > pc.CinPad || pc.src->numel != (size_t)pc.N * pc.Cin * 9)
-                       : pc.src->numel != (size_t)(pc.geglu_inner ? 2 * pc.geglu_inner : pc.N) * pc.K) ||
+            (pc.CinPad ? (pc.K != 9 * pc.CinPad || pc.Cin > pc.CinPad || pc.src->numel != (size_t)pc.N * pc.Cin * 9 || pc.src_rows)
+                       : pc.src_rows ? (pc.src_row0 + pc.N > pc.src_rows || pc.src->numel != pc.src_rows * pc.K || pc.geglu_inner)
+                                     : pc.src->numel != (size_t)(pc.geglu_inner ? 2 * pc.geglu_inner : pc.N) * pc.K) ||
             (pc.geglu_inner && (pc.N != 2 * pc.geglu_inner || pc.geglu_inner % 32))) {
             walk_err = dev ? "pack16: piece outside the packed matrix or not 16-byte granular" : "pack16: piece outside the packed matrix";
             return nullptr;
@@ -166,6 +241,7 @@ void* Engine::pack16(size_t rows, size_t cols, const std::vector<Piece>& pieces)
         PackArgs a; memset(&a, 0, sizeof(a));
         a.src = piece_src(pc.src, dev); a.sdt = pc.src->dtype;
         if (!a.src) return nullptr;
+        a.src = (const char*)a.src + pc.src_row0 * (size_t)pc.K * (a.sdt == LDX_F32 ? 4 : 2);      // a sub-view starts at its first row
         a.out = (uint16_t*)(dev ? p : buf.data()) + pc.row0 * cols; a.ldo = (long)cols; a.col0 = (long)pc.col0; a.out_dt = dt;
         a.N = pc.N; a.K = pc.K; a.Cin = pc.Cin; a.CinPad = pc.CinPad; a.geglu_inner = pc.geglu_inner; a.scale = pc.scale;
         if (dev) launch_pack16(a, nullptr);
@@ -183,7 +259,8 @@ float* Engine::pack32(size_t n, const std::vector<VecPiece>& pieces) {
     bool dev = false;
     for (const VecPiece& pc : pieces) {
         dev = dev || pc.a->dev || (pc.b && pc.b->dev);
-        if (pc.off + pc.n > n || pc.a->numel != (size_t)pc.n || (pc.b && pc.b->numel != (size_t)pc.n) || (pc.geglu_inner && pc.n != 2 * pc.geglu_inner)) {
+        if (pc.off + pc.n > n || (pc.src_n ? (pc.src0 + pc.n > pc.src_n || pc.a->numel != pc.src_n || pc.b || pc.geglu_inner) : pc.a->numel != (size_t)pc.n) ||
+            (pc.b && pc.b->numel != (size_t)pc.n) || (pc.geglu_inner && pc.n != 2 * pc.geglu_inner)) {
             walk_err = "pack32: piece outside the packed vector";
             return nullptr;
         }
@@ -194,6 +271,7 @@ float* Engine::pack32(size_t n, const std::vector<VecPiece>& pieces) {
         PackVecArgs a; memset(&a, 0, sizeof(a));
         a.a = piece_src(pc.a, dev); a.a_dt = pc.a->dtype;
         if (!a.a) return nullptr;
+        a.a = (const char*)a.a + pc.src0 * (a.a_dt == LDX_F32 ? 4 : 2);
         if (pc.b) { a.b = piece_src(pc.b, dev); a.b_dt = pc.b->dtype; if (!a.b) return nullptr; }
         a.out = (dev ? p : buf.data()) + pc.off; a.n = pc.n; a.geglu_inner = pc.geglu_inner;
         if (dev) launch_pack32(a, nullptr);

@@ -29,8 +29,9 @@ int launch_status();          // LDX_EHIP (and the error text) when a kernel lau
         }                                                                                    \
     } while (0)
 
-// A state-dict tensor as registered: a host copy (ldx_load_tensor: `data`), or the caller's own device memory (ldx_load_tensor_device: `dev`,
-// not copied, `data` empty; UNet engine only).  at() reads the host copy (the getter-style upload16 / upload32; the piece packers read `data` themselves).
+// A state-dict tensor as registered: a host copy (ldx_load_tensor: `data`), or device memory (`dev`, `data` empty): the caller's own, not copied
+// (ldx_load_tensor_device / ldx_load_tensor_dev; UNet, Flux and T5 engines), or the engine's fp16 expansion of a Q8_0 tensor (ldx_load_tensor_q8_0).
+// at() reads the host copy (the getter-style upload16 / upload32; the piece packers read `data` themselves).
 struct HostTensor {
     int dtype = LDX_F32;
     std::vector<int64_t> shape;
@@ -187,6 +188,14 @@ public:
     Engine& operator=(const Engine&) = delete;
     int validate() const { return LDX_OK; }              // config checks at creation; a model that has some hides this (ldx_*_create calls it on the model's class)
     int load_tensor(const char* key, const void* data, int dtype, const int64_t* shape, int ndim);
+    // What a model's weight walk can read besides host copies: device-resident sources (every layout a piece list), Q8_0 tensors (Flux, T5: the reference's GGUF files)
+    virtual bool takes_device_tensors() const { return false; }
+    virtual bool takes_q8_0() const { return false; }
+    // fn: the entry point's name for the error text (ldx_load_tensor_device, ldx_load_tensor_dev)
+    int load_tensor_dev(const char* fn, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
+    // blocks of 34 bytes -> an LDX_F16 tensor: on the host (weight_convert.h), or by q8.hip into a device buffer of the engine's (q8_bufs, freed with the staged sources)
+    int load_tensor_q8_0(const char* key, const void* blocks, const int64_t* shape, int ndim, bool on_device);
+    int packed_digest(const char* fn, uint64_t* out);    // FNV-1a over host copies of weight_allocs, in allocation order
     virtual int finalize() = 0;
     // context cache (ldx_unet_context_cache): the caller promises that the bytes behind a ctx pointer do not change until it calls
     //     ldx_unet_context_cache again; the 16-bit copy of ctx and the batched k|v projection of every cross-attention (transformer.py:186-245 recomputes
@@ -230,11 +239,15 @@ protected:
     // the device (ldx_load_tensor_device) -> one launch per piece of pack.hip's loops over those functions, host sources of that buffer staged as raw copies
     // (freed when the walk ends); no source on the device -> a CPU loop over the same functions and one copy.  Same buffers in the same order either way:
     // either can refill what the other allocated.  16-byte granularity (K, cols, col0, CinPad multiples of 8) is asked of the launches only.
-    struct Piece { const HostTensor* src; size_t row0, col0; int N, K; float scale; int geglu_inner; int Cin, CinPad; };
+    // src_rows > 0: the piece is rows [src_row0, src_row0 + N) of a source of src_rows rows (a sub-view: the packers get the address of its first row)
+    struct Piece { const HostTensor* src; size_t row0, col0; int N, K; float scale; int geglu_inner; int Cin, CinPad; size_t src_row0 = 0, src_rows = 0; };
     static Piece rows_piece(const HostTensor* src, size_t row0, int N, int K, float scale = 1.0f, int geglu_inner = 0) { return Piece{src, row0, 0, N, K, scale, geglu_inner, 0, 0}; }
     static Piece conv_piece(const HostTensor* src, int Cout, int Cin, int CinPad) { return Piece{src, 0, 0, Cout, 9 * CinPad, 1.0f, 0, Cin, CinPad}; }      // [Cout][ky][kx][CinPad] <- [Cout][Cin][ky][kx]
-    struct VecPiece { const HostTensor* a; const HostTensor* b; size_t off; int n; int geglu_inner; };      // out[off + i] = a[i] (+ b[i])
+    static Piece rows_view(const HostTensor* src, size_t src_row0, size_t src_rows, size_t row0, int N, int K) { Piece p = rows_piece(src, row0, N, K); p.src_row0 = src_row0; p.src_rows = src_rows; return p; }
+    // out[off + i] = a[i] (+ b[i]); src_n > 0: a[src0 + i] of a source of src_n elements (b must be null)
+    struct VecPiece { const HostTensor* a; const HostTensor* b; size_t off; int n; int geglu_inner; size_t src0 = 0, src_n = 0; };
     std::unordered_map<const HostTensor*, void*> staged;
+    std::vector<void*> q8_bufs;                            // fp16 expansions of device Q8_0 tensors: sources like `staged`, dropped with them
     const void* dev_src(const HostTensor* t);
     const void* piece_src(const HostTensor* t, bool dev) { return dev ? dev_src(t) : t->numel ? (const void*)t->data.data() : (const void*)t; }      // never null for an empty host tensor (nothing is read)
     void drop_staged();
@@ -243,8 +256,6 @@ protected:
     // What no piece list describes stays on a getter, element by element on the host (all in engines that load from the host only):
     //   VaeEngine::mk_vae_attn  proj.b    Wp . bv + bp, an fp64 dot product per element
     //   VaeEngine::mk_vae_attn  qkv.b     [bq | bk | 0]: the zero tail has no source
-    //   T5Engine::finalize      wi.w      64-row slabs interleaved from TWO tensors (wi_1 value rows, wi_0 gate rows); geglu_inner permutes one
-    //   FluxEngine::finalize    lin1_*    linear1 split at a source ROW: a piece takes its whole source, from row 0
     void* upload16(size_t rows, size_t cols, const std::function<float(size_t, size_t)>& getter);
     float* upload32(size_t n, const std::function<float(size_t)>& getter);
     bool mk_linear(const std::string& pre, int N, int K, bool bias, LinearW& out, bool conv1x1 = false);
@@ -326,7 +337,7 @@ public:
     UNetEngine(const ldx_unet_config& c, int dev);
     ~UNetEngine() override;
     int validate() const;
-    int load_tensor_device(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
+    bool takes_device_tensors() const override { return true; }
     int set_tables(const float* ls, int n, const float* temb, int dim);
     int finalize() override;
     // Replace the weights of a finalized engine in place (ldx_unet_refresh_begin / _commit): begin re-opens the two loaders, commit validates
@@ -335,7 +346,6 @@ public:
     int refresh_begin();
     int refresh_commit();
     int refresh_abort();                   // forget an unfinished refresh: the loaders close again, the weights are untouched
-    int weights_digest(uint64_t* out);     // FNV-1a over host copies of every weight allocation, in allocation order
     // c_concat [B2][cc_channels][h][w] (fp32, may be null): appended unscaled behind the scaled x, which then carries in_channels - cc_channels channels
     // t_idx [B2] (device fp32, may be null; denoise only): timestep indices supplied by the caller instead of the device's own sigma -> index lookup
     int run(const float* x, const float* sigma_or_t, const float* ctx, int B2, int h, int w, int Mc, float* out, bool denoise, hipStream_t st, int xB = 0,
@@ -429,6 +439,8 @@ class T5Engine final : public Engine {
 public:
     static constexpr const char* model = "T5";
     T5Engine(const ldx_t5_config& c, int dev) : Engine(dev, c.compute_dtype, false), cfg(c) {}
+    bool takes_device_tensors() const override { return true; }
+    bool takes_q8_0() const override { return true; }
     int finalize() override;
     int run(const int* ids, int B, int L, const float* bias, float* out, hipStream_t st);
     const ldx_t5_config cfg;
@@ -472,6 +484,8 @@ class FluxEngine final : public Engine {
 public:
     static constexpr const char* model = "Flux";
     FluxEngine(const ldx_flux_config& c, int dev) : Engine(dev, c.compute_dtype, true), cfg(c) {}
+    bool takes_device_tensors() const override { return true; }
+    bool takes_q8_0() const override { return true; }
     int finalize() override;
     int run(const float* x, const float* sigma, const float* ctx, const float* y, const float* guidance,
             const float* pe_cos, const float* pe_sin, int B, int h, int w, int Lt, bool denoise, float* out, hipStream_t st);

@@ -71,12 +71,13 @@ int FluxEngine::finalize() {
         const HostTensor* b1 = ok ? get(p + ".linear1.bias", {3 * C + f.mlp_hidden}) : nullptr;
         ok = ok && w1 && b1;
         if (ok) {
+            const size_t R = (size_t)3 * C + f.mlp_hidden;
             s.lin1_qkv.N = 3 * C; s.lin1_qkv.K = C;
-            s.lin1_qkv.w = upload16((size_t)3 * C, C, [&](size_t r, size_t c) { return w1->at(r * C + c); });
-            s.lin1_qkv.b = upload32((size_t)3 * C, [&](size_t i2) { return b1->at(i2); });
+            s.lin1_qkv.w = pack16((size_t)3 * C, C, {rows_view(w1, 0, R, 0, 3 * C, C)});
+            s.lin1_qkv.b = pack32((size_t)3 * C, {{b1, nullptr, 0, 3 * C, 0, 0, R}});
             s.lin1_mlp.N = f.mlp_hidden; s.lin1_mlp.K = C;
-            s.lin1_mlp.w = upload16((size_t)f.mlp_hidden, C, [&](size_t r, size_t c) { return w1->at((r + 3 * C) * C + c); });
-            s.lin1_mlp.b = upload32((size_t)f.mlp_hidden, [&](size_t i2) { return b1->at(i2 + 3 * C); });
+            s.lin1_mlp.w = pack16((size_t)f.mlp_hidden, C, {rows_view(w1, (size_t)3 * C, R, 0, f.mlp_hidden, C)});
+            s.lin1_mlp.b = pack32((size_t)f.mlp_hidden, {{b1, nullptr, 0, f.mlp_hidden, 0, (size_t)3 * C, R}});
             ok = s.lin1_qkv.w && s.lin1_qkv.b && s.lin1_mlp.w && s.lin1_mlp.b;
         }
         ok = ok && mk_linear(p + ".linear2", C, C + f.mlp_hidden, true, s.lin2) &&
@@ -84,7 +85,11 @@ int FluxEngine::finalize() {
     }
     ok = ok && add_mod("final_layer.adaLN_modulation.1", 2, fx_final_mod_off) && mk_linear("final_layer.linear", inC, C, true, fx_final);
     ok = ok && mk_stacked(fx_mod_srcs, C, fx_mod_all);
+    // device-resident sources (ldx_load_tensor_dev, ldx_load_tensor_q8_0) were packed by launches on the null stream: they and the staged copies are read until it drains
+    const hipError_t sync = hipDeviceSynchronize();
+    drop_staged();
     if (!ok) return weights_failed();
+    if (sync != hipSuccess) { set_error(std::string("weight packing failed: ") + hipGetErrorString(sync)); return LDX_EHIP; }
     fx_mod_srcs.clear();
     host.clear();
     if (fx_fp8) {

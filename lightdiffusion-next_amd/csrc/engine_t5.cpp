@@ -48,17 +48,20 @@ int T5Engine::finalize() {
         const HostTensor *w0 = get(f + ".DenseReluDense.wi_0.weight", {F, E}), *w1 = get(f + ".DenseReluDense.wi_1.weight", {F, E});
         ok = ok && w0 && w1;
         if (ok) {
-            // 64-row slabs: 32 value rows (wi_1) then their 32 gate rows (wi_0, through tanh-GELU)
+            // 64-row slabs: 32 value rows (wi_1) then their 32 gate rows (wi_0, through tanh-GELU).  As pieces: the packed matrix read as [F / 32][64 E], a slab
+            // per row, whose left half is 32 consecutive rows of wi_1 and whose right half the same rows of wi_0
             L.wi.N = 2 * F; L.wi.K = E; L.wi.b = nullptr;
-            L.wi.w = upload16((size_t)2 * F, E, [&](size_t r, size_t cc) {
-                const size_t slab = r / 64, within = r % 64;
-                return within < 32 ? w1->at((slab * 32 + within) * E + cc) : w0->at((slab * 32 + within - 32) * E + cc); });
+            L.wi.w = pack16((size_t)F / 32, (size_t)64 * E, {Piece{w1, 0, 0, F / 32, 32 * E, 1.0f, 0, 0, 0}, Piece{w0, 0, (size_t)32 * E, F / 32, 32 * E, 1.0f, 0, 0, 0}});
             ok = L.wi.w != nullptr;
         }
         ok = ok && mk_linear(f + ".DenseReluDense.wo", E, F, false, L.wo);
     }
     ok = ok && rms("encoder.final_layer_norm", t5_final_ln);
+    // device-resident sources (ldx_load_tensor_dev, ldx_load_tensor_q8_0) were packed by launches on the null stream: they and the staged copies are read until it drains
+    const hipError_t sync = hipDeviceSynchronize();
+    drop_staged();
     if (!ok) return weights_failed();
+    if (sync != hipSuccess) { set_error(std::string("weight packing failed: ") + hipGetErrorString(sync)); return LDX_EHIP; }
     host.clear();
     finalized = true;
     return LDX_OK;

@@ -41,23 +41,6 @@ int UNetEngine::validate() const {
     return LDX_OK;
 }
 
-int UNetEngine::load_tensor_device(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
-    if (finalized && !refreshing) { set_error("ldx_load_tensor_device after ldx_finalize"); return LDX_ESTATE; }
-    if (!key || !dev_ptr || ndim < 0 || ndim > 8 || (ndim && !shape)) { set_error("ldx_load_tensor_device: bad argument"); return LDX_EINVAL; }
-    if (dtype != LDX_F32 && dtype != LDX_F16 && dtype != LDX_BF16) { set_error("ldx_load_tensor_device: bad dtype"); return LDX_EINVAL; }
-    if ((uintptr_t)dev_ptr % (dtype == LDX_F32 ? 4 : 2)) { set_error("ldx_load_tensor_device: misaligned pointer"); return LDX_EINVAL; }
-    HostTensor t;
-    t.dtype = dtype;
-    t.numel = 1;
-    for (int i = 0; i < ndim; ++i) {
-        if (shape[i] < 0) { set_error("ldx_load_tensor_device: negative extent"); return LDX_EINVAL; }
-        t.shape.push_back(shape[i]); t.numel *= (size_t)shape[i];
-    }
-    t.dev = dev_ptr;
-    host[key] = std::move(t);
-    return LDX_OK;
-}
-
 int UNetEngine::set_tables(const float* ls, int n, const float* temb, int dim) {
     // after finalize the per-timestep emb_layers table (build_emb_table) and every cached plan depend on these tables
     if (finalized) { set_error("ldx_set_tables after ldx_finalize"); return LDX_ESTATE; }
@@ -282,22 +265,6 @@ int UNetEngine::refresh_commit() {
     ++ctx_epoch;                           // cached k|v projections of the context were made with the old weights
     if ((rc = derive_up_phase())) return rc;
     return build_emb_table();
-}
-
-int UNetEngine::weights_digest(uint64_t* out) {
-    if (!finalized) { set_error("ldx_weights_digest: not a finalized UNet engine"); return LDX_ESTATE; }
-    if (!out) { set_error("ldx_weights_digest: bad argument"); return LDX_EINVAL; }
-    HIP_OK(hipSetDevice(device));
-    HIP_OK(hipDeviceSynchronize());
-    uint64_t h = 0xcbf29ce484222325ull;
-    std::vector<uint8_t> buf;
-    for (const WeightAlloc& a : weight_allocs) {
-        buf.resize(a.bytes);
-        HIP_OK(hipMemcpy(buf.data(), a.p, a.bytes, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < a.bytes; ++i) { h ^= buf[i]; h *= 0x100000001b3ull; }
-    }
-    *out = h;
-    return LDX_OK;
 }
 
 // rows [0, rows) of the view -> rows [rows, 2 * rows): the second half of a CFG batch takes over what was computed once for both (plan(): share)

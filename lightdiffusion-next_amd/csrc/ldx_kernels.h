@@ -557,6 +557,10 @@ struct LnFoldArgs {
     int N, K; int geglu_inner; float scale;
 };
 void launch_ln_fold(const LnFoldArgs& a, hipStream_t s);
+// GGML Q8_0 blocks (34 bytes: fp16 scale, 32 int8; 2-byte aligned) -> out[n] (q8.hip, libldx_q8.so): the fp16 value fp16_rne(float(d) * q) as
+// out_dt = LDX_F16, or that value as LDX_BF16 / LDX_F32.  n % 32 == 0, out 16-byte aligned.
+struct DequantQ8Args { const void* blocks; void* out; size_t n; int out_dt; };
+void launch_dequant_q8_0(const DequantQ8Args& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // 8-bit image ops of the img2img path (image.hip, libldx_image.so): HWC uint8 device images with a row pitch in bytes; include/ldx.h states each rule.

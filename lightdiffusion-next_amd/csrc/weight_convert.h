@@ -56,4 +56,9 @@ __host__ __device__ inline uint16_t float_to_bf16(float f) {
     return (uint16_t)(x >> 16);
 }
 
+// GGML Q8_0: blocks of an fp16 scale d and 32 int8 values q.  A weight is fp16_rne(float(d) * q): the product (11 x 8 significant bits) is exact in
+// fp32, so this is torch's fp16 d * q with its single rounding, NaN, overflow to inf, subnormals and -0 included.
+constexpr int Q8_0_BLOCK = 32, Q8_0_BYTES = 34;
+__host__ __device__ inline uint16_t q8_0_value(uint16_t d, int8_t q) { return float_to_half(half_to_float(d) * (float)q); }
+
 }  // namespace ldx

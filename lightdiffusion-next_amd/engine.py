@@ -101,6 +101,52 @@ class _Engine:
             torch.cuda.synchronize(self.device)      # whatever produced the device tensors (a LoRA merge on another stream) has finished
         return keep
 
+    def _load_gguf_tensors(self, state_dict, strip=(), device_weights=True):
+        """Register a state dict whose values are gguf.GGUFTensor (dense torch tensors among them take _load_state_dict's host route).
+        device_weights: each tensor's raw bytes are copied to the device and registered there, tensor by tensor, so at most one raw tensor is alive beside
+        the engine's own buffers: Q8_0 through ldx_load_tensor_q8_0(on_device = 1), which expands it into a buffer of the engine's before it returns, the
+        rest through ldx_load_tensor_dev, whose tensors are returned (the caller keeps them until ldx_finalize has returned).  Otherwise the host
+        route: ldx_load_tensor_q8_0(on_device = 0) expands on the host, ldx_load_tensor copies."""
+        from .gguf import GGUFTensor, GGML_Q8_0, _TORCH
+        keep, dense = [], {}
+        for k, t in state_dict.items():
+            if not isinstance(t, GGUFTensor):
+                dense[k] = t
+                continue
+            for pre in strip:
+                if k.startswith(pre):
+                    k = k[len(pre):]
+            shape = (C.c_int64 * len(t.tensor_shape))(*t.tensor_shape)
+            raw = t.raw.to(self.device) if device_weights else t.raw.contiguous()
+            if t.tensor_type == GGML_Q8_0:
+                lib.check(self._lib.ldx_load_tensor_q8_0(self._h, k.encode(), lib.ptr(raw), shape, len(t.tensor_shape), int(device_weights)), f"ldx_load_tensor_q8_0({k})")
+            elif device_weights:
+                keep.append(raw)
+                lib.check(self._lib.ldx_load_tensor_dev(self._h, k.encode(), lib.ptr(raw), lib.torch_dtype_code(_TORCH[t.tensor_type]), shape, len(t.tensor_shape)),
+                          f"ldx_load_tensor_dev({k})")
+            else:
+                lib.check(self._lib.ldx_load_tensor(self._h, k.encode(), lib.ptr(raw), lib.torch_dtype_code(_TORCH[t.tensor_type]), shape, len(t.tensor_shape)),
+                          f"ldx_load_tensor({k})")
+            del raw
+        if dense:
+            self._load_state_dict(dense, strip=strip)
+        if device_weights:
+            torch.cuda.synchronize(self.device)
+        return keep
+
+    def _load_any(self, state_dict, strip=(), device_weights=True):
+        """A dense torch state dict takes _load_state_dict's path; one that holds gguf.GGUFTensor values takes _load_gguf_tensors'."""
+        from .gguf import GGUFTensor
+        if any(isinstance(t, GGUFTensor) for t in state_dict.values()):
+            return self._load_gguf_tensors(state_dict, strip=strip, device_weights=device_weights)
+        return self._load_state_dict(state_dict, strip=strip)
+
+    def packed_digest(self) -> int:
+        """ldx_packed_digest: FNV-1a over every packed weight buffer (diagnostic: equal digests = bit-identical weights, however they were loaded)."""
+        d = C.c_uint64()
+        lib.check(self._lib.ldx_packed_digest(self._h, C.byref(d)), "ldx_packed_digest")
+        return d.value
+
     def _finalize(self):
         lib.check(self._lib.ldx_finalize(self._h), "ldx_finalize")
 
@@ -608,15 +654,25 @@ class T5Engine(_Engine):
     """T5.forward (src/clip/FluxClip.py:441-519): token ids -> final_layer_norm(encoder output), fp32.  Host side keeps
     the 32 x heads relative-attention embedding and builds the bias table per sequence length (cached)."""
 
-    def __init__(self, cfg, state_dict, device: int = 0, dtype: str = "bf16"):
+    def __init__(self, cfg, state_dict, device: int = 0, dtype: str = "bf16", device_weights: bool = True):
+        """state_dict: dense torch tensors, or gguf.GGUFTensor values (gguf.gguf_t5_state_dict; device_weights: _load_gguf_tensors)."""
         super().__init__(cfg, device)
         self._create(lib.ldx_t5_config, "ldx_t5_create", dtype, d_model=cfg.d_model, d_ff=cfg.d_ff, num_layers=cfg.num_layers, num_heads=cfg.num_heads,
                      vocab_size=cfg.vocab_size)
         rk = "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
-        self._rel = state_dict[rk].float().cpu()
-        self._load_state_dict({k: v for k, v in state_dict.items() if k != rk}, strip=("t5xxl.transformer.",))
+        rel = state_dict[rk]
+        self._rel = (rel.dequantize() if hasattr(rel, "dequantize") else rel).float().cpu()      # the bias table stays with the host
+        keep = self._load_any({k: v for k, v in state_dict.items() if k != rk}, strip=("t5xxl.transformer.",), device_weights=device_weights)
         self._finalize()
+        del keep
         self._bias = {}
+
+    @classmethod
+    def from_gguf(cls, path, cfg=None, device: int = 0, dtype: str = "bf16", device_weights: bool = True):
+        """The reference's t5-v1_1-xxl-encoder-Q8_0.gguf (DualCLIPLoaderGGUF, pipeline.py:218-236); cfg=None: T5-XXL."""
+        from .gguf import gguf_t5_state_dict
+        cfg = cfg or T5Config()
+        return cls(cfg, gguf_t5_state_dict(path, cfg.num_layers), device=device, dtype=dtype, device_weights=device_weights)
 
     def bias(self, length: int):
         if length not in self._bias:
@@ -659,8 +715,9 @@ def flux_rope_tables(cfg: FluxConfig, batch_txt_len: int, h: int, w: int):
 class FluxEngine(_Engine):
     """Flux3.forward behind BaseModel.apply_model with CONST prediction."""
 
-    def __init__(self, cfg: FluxConfig, state_dict, device: int = 0, dtype: str = "bf16", fp8: bool = False):
-        """fp8=True (or "linears"): the block linears (and the adaLN modulation projections) run on MX fp8 operands, attention in 16 bit (ldx_flux_set_fp8 mode 1;
+    def __init__(self, cfg: FluxConfig, state_dict, device: int = 0, dtype: str = "bf16", fp8: bool = False, device_weights: bool = True):
+        """state_dict: dense torch tensors, or gguf.GGUFTensor values (gguf.gguf_state_dict; device_weights: _load_gguf_tensors).
+        fp8=True (or "linears"): the block linears (and the adaLN modulation projections) run on MX fp8 operands, attention in 16 bit (ldx_flux_set_fp8 mode 1;
         approximate, opt-in, own parity class).  fp8="attn": explicit opt-in to the less precise full mode (mode 3): at head dim 128 QK^T / PV of the joint attention run on MX fp8 too."""
         super().__init__(cfg, device)
         self._create(lib.ldx_flux_config, "ldx_flux_create", dtype, in_channels=cfg.in_channels, vec_in_dim=cfg.vec_in_dim, context_in_dim=cfg.context_in_dim,
@@ -669,9 +726,16 @@ class FluxEngine(_Engine):
         if fp8:
             assert fp8 in (True, "linears", "attn"), "fp8 must be False, True / 'linears', or 'attn'"
             lib.check(self._lib.ldx_flux_set_fp8(self._h, 3 if fp8 == "attn" else 1), "ldx_flux_set_fp8")
-        self._load_state_dict(state_dict, strip=("model.diffusion_model.",))
+        keep = self._load_any(state_dict, strip=("model.diffusion_model.",), device_weights=device_weights)
         self._finalize()
+        del keep
         self._pe = {}
+
+    @classmethod
+    def from_gguf(cls, path, cfg=None, device: int = 0, dtype: str = "bf16", fp8: bool = False, device_weights: bool = True):
+        """The reference's flux1-dev-Q8_0.gguf (UnetLoaderGGUF, pipeline.py:218-236); cfg=None: flux-dev."""
+        from .gguf import gguf_state_dict
+        return cls(cfg or FluxConfig(), gguf_state_dict(path), device=device, dtype=dtype, fp8=fp8, device_weights=device_weights)
 
     def _run(self, x, sigma, ctx, y, guidance, denoise):
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4

@@ -71,12 +71,15 @@ _SIGS = {
     "ldx_destroy": (None, [_vp]),
     "ldx_load_tensor": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(_i64), _i]),
     "ldx_load_tensor_device": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(_i64), _i]),
+    "ldx_load_tensor_dev": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(_i64), _i]),
+    "ldx_load_tensor_q8_0": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i, _i]),
     "ldx_set_tables": (_i, [_vp, _vp, _i, _vp, _i]),
     "ldx_finalize": (_i, [_vp]),
     "ldx_unet_refresh_begin": (_i, [_vp]),
     "ldx_unet_refresh_commit": (_i, [_vp]),
     "ldx_unet_refresh_abort": (_i, [_vp]),
     "ldx_weights_digest": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "ldx_packed_digest": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "ldx_unet_denoise": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ldx_unet_denoise_cfg": (_i, [_vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ldx_unet_denoise_cfg_t": (_i, [_vp, _vp, C.c_float, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
@@ -137,6 +140,7 @@ _SIGS = {
     "ldx_zlib_bound_bytes": (_i64, [_i64]),
     "ldx_zlib_deflate": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "ldx_op_convert": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
+    "ldx_op_dequant_q8_0": (_i, [_vp, _i64, _i, _vp, _vp]),
     "ldx_op_gemm": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
     "ldx_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
     "ldx_op_groupnorm": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _i, _vp]),
