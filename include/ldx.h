@@ -102,6 +102,20 @@ typedef struct ldx_taesd_config {
     int32_t latent_channels;       /* 4 */
 } ldx_taesd_config;
 
+/* SAM image encoder (segment_anything ImageEncoderViT; the reference loads ViT-B, src/AutoDetailer/SAM.py:157-182).  Patch size 16, absolute and decomposed
+ * relative position embeddings; the head dimension embed_dim / num_heads must be 64 (ViT-B, ViT-L), anything else is LDX_EINVAL. */
+typedef struct ldx_sam_config {
+    int32_t compute_dtype;
+    int32_t image_size;            /* 1024 ; multiple of 16 */
+    int32_t embed_dim;             /* 768 */
+    int32_t depth;                 /* 12 ; at most 32 */
+    int32_t num_heads;             /* 12 */
+    int32_t mlp_dim;               /* 3072 */
+    int32_t out_chans;             /* 256 ; multiple of 64 */
+    int32_t window_size;           /* 14 */
+    uint32_t global_attn_mask;     /* bit i set: block i attends globally (ViT-B: blocks 2, 5, 8, 11 = 0x924) */
+} ldx_sam_config;
+
 /* Flux DiT — FluxParams (src/BlackForest/Flux.py:293-306); flux-dev: 16, 768, 4096, 3072, 4.0, 24, 19, 38,
  * axes [16,56,56], theta 10000, qkv_bias 1, guidance_embed 1. */
 typedef struct ldx_flux_config {
@@ -251,10 +265,10 @@ int ldx_plan_flops(ldx_engine* e, double* executed, double* shared);
  * enable = 2 keys the report by kernel class *and* op shape (tuning aid). */
 int ldx_profile(ldx_engine* e, int enable, int reset);
 int ldx_profile_report(ldx_engine* e, char* buf, int64_t cap);
-/* Capture the planned forward into a hipGraph for replay (0 = eager launches).  UNet and TAESD engines; every other engine accepts the call and
+/* Capture the planned forward into a hipGraph for replay (0 = eager launches).  UNet, TAESD and SAM engines; every other engine accepts the call and
  * keeps launching eagerly. */
 int ldx_set_graph_mode(ldx_engine* e, int enable);
-/* UNet and TAESD engines (0, 0 on every other): how many times a forward was captured into a hipGraph and how many times a captured graph was replayed since the engine was
+/* UNet, TAESD and SAM engines (0, 0 on every other): how many times a forward was captured into a hipGraph and how many times a captured graph was replayed since the engine was
  * created (a captured graph is tied to the pointers of the call that recorded it: a caller that alternates buffers re-captures instead of
  * replaying — sampling.CFGDenoiser stages such inputs through one persistent buffer per shape). */
 int ldx_graph_stats(ldx_engine* e, int64_t* captures, int64_t* replays);
@@ -311,6 +325,27 @@ int ldx_taesd_decode(ldx_engine* e, const float* latent, int B, int h, int w, fl
  * (up = 1: nearest x2 of X [B][Hin][Win][64] folded into the gather); Wt [64][(ky * 3 + kx) * 64 + ci] 16-bit; bias [64] fp32 or NULL; R like Y or NULL;
  * Rf: the residual as fp32 [B][H][W][64] instead (not both); Yf: the unrounded result as fp32 as well, or NULL. */
 int ldx_taesd_conv64(const void* X, const void* Wt, const float* bias, const void* R, const float* Rf, void* Y, float* Yf, int B, int Hin, int Win, int up, int relu, int dtype, void* stream);
+/* SAM image encoder.  State-dict keys are segment_anything's own with "image_encoder." stripped: pos_embed, patch_embed.proj.{weight,bias},
+ * blocks.<i>.norm1|norm2.{weight,bias}, blocks.<i>.attn.qkv|proj.{weight,bias}, blocks.<i>.attn.rel_pos_h|rel_pos_w, blocks.<i>.mlp.lin1|lin2.{weight,bias},
+ * neck.0.weight, neck.1.{weight,bias}, neck.2.weight, neck.3.{weight,bias}.  A rel_pos table must have 2 n - 1 rows (n = window_size, or image_size / 16 in a
+ * global block), as the official checkpoints do: ldx_finalize answers LDX_EINVAL otherwise (the interpolation of other lengths is not built). */
+int ldx_sam_create(const ldx_sam_config* cfg, int device, ldx_engine** out);
+/* ImageEncoderViT.forward: x [B][3][size][size] fp32, already preprocessed (ldx_sam_preprocess) -> out [B][out_chans][size / 16][size / 16] fp32.
+ * A handle of another model: LDX_ESTATE, nothing is launched. */
+int ldx_sam_encode(ldx_engine* e, const float* x_nchw_f32, int B, float* out_nchw_f32, void* stream);
+/* Sam.preprocess: img u8 [h][w][3] with rows `pitch` bytes apart -> out fp32 [3][size][size] = (float(img) - mean_c) / std_c with the pixel mean
+ * (123.675, 116.28, 103.53) and std (58.395, 57.12, 57.375), IEEE subtraction and division; zeros right of w and below h.  h, w <= size. */
+int ldx_sam_preprocess(const uint8_t* img, int64_t pitch, int h, int w, float* out, int size, void* stream);
+/* Test surface: ONE launch of each of the encoder's own kernels, on 16-bit rows (dtype).
+ * ldx_op_sam_window: scatter = 0: dst [B * nw * nw][win * win][C] = the window partition of src [B][S][S][C], zero rows for the padding up to nw = ceil(S / win)
+ * windows a side; scatter = 1: dst [B][S][S][C] = R + the inverse of src (the crop), R like dst (dst itself allowed) or NULL.  C % 8 == 0, src != dst.
+ * ldx_op_sam_relpos: out fp32 [BW * H][n * n][2 n]: out[.][q][j] = sum_c Q[q][c] th[q / n - j + n - 1][c] for j < n, sum_c Q[q][c] tw[q % n - (j - n) + n - 1][c]
+ * above; Q rows bw * n * n + q (row stride ldq, ldq % 8 == 0), head h at columns h * 64; th, tw fp32 [2 n - 1][64].
+ * ldx_op_sam_attention: O[bw * N + q][h * 64 + d] = sum_k softmax_k(scale * q.k + rel[q][k / n] + rel[q][n + k % n]) v[k][d] over the N = n * n tokens of
+ * (bw, h); Q, K, V share the row stride ld (ld % 8 == 0); rel as ldx_op_sam_relpos writes it; ldo % 4 == 0; BW * H <= 65535. */
+int ldx_op_sam_window(const void* src, void* dst, const void* R, int B, int S, int win, int C, int scatter, int dtype, void* stream);
+int ldx_op_sam_relpos(const void* Q, int ldq, const float* th, const float* tw, float* out, int BW, int H, int n, int dtype, void* stream);
+int ldx_op_sam_attention(const void* Q, const void* K, const void* V, int ld, const float* rel, void* O, int ldo, int BW, int H, int n, float scale, int dtype, void* stream);
 /* tiled_scale's feathered accumulation (src/Utilities/util.py:557-590): out/div [H][W][C] fp32 += tile [th][tw][C] * mask /
  * mask at (y0, x0); then ldx_tile_finish: out = out / div (div may be NULL), optionally clamped to [0,1] (USDU_upscaler.py:94). */
 int ldx_tile_blend(const float* tile, int th, int tw, float* out, float* div, int H, int W, int C, int y0, int x0, int feather, void* stream);

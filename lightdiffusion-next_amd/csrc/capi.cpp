@@ -153,6 +153,37 @@ int ldx_taesd_conv64(const void* X, const void* Wt, const float* bias, const voi
     launch_taesd_conv(a, dtype_of(dtype), (hipStream_t)stream);
     return check_launch("ldx_taesd_conv64");
 }
+int ldx_sam_create(const ldx_sam_config* cfg, int device, ldx_engine** out) { return create_engine<SamEngine>(cfg, device, out, __func__); }
+int ldx_sam_encode(ldx_engine* e, const float* x_nchw_f32, int B, float* out_nchw_f32, void* stream) {
+    GUARD_BEGIN
+    ENGINE_AS(SamEngine, m);
+    return m->run(x_nchw_f32, B, out_nchw_f32, (hipStream_t)stream);
+    GUARD_END
+}
+int ldx_sam_preprocess(const uint8_t* img, int64_t pitch, int h, int w, float* out, int size, void* stream) {
+    if (!img || !out || h <= 0 || w <= 0 || size <= 0 || size > 16384 || h > size || w > size || pitch < (int64_t)w * 3) {
+        set_error("ldx_sam_preprocess: bad argument (null pointer, h or w outside 1 .. size, pitch < w * 3)"); return LDX_EINVAL; }
+    launch_sam_preprocess(SamPreprocessArgs{img, (long)pitch, h, w, out, size}, (hipStream_t)stream);
+    return check_launch("ldx_sam_preprocess");
+}
+int ldx_op_sam_window(const void* src, void* dst, const void* R, int B, int S, int win, int C, int scatter, int dtype, void* stream) {
+    const SamWindowArgs a{src, dst, R, B, S, win, C, scatter};
+    if (!sam_window_ok(a)) { set_error("ldx_op_sam_window: bad argument (null pointer, src == dst, C % 8, scatter not 0 | 1, R without scatter)"); return LDX_EINVAL; }
+    launch_sam_window(a, dtype_of(dtype), (hipStream_t)stream);
+    return check_launch("ldx_op_sam_window");
+}
+int ldx_op_sam_relpos(const void* Q, int ldq, const float* th, const float* tw, float* out, int BW, int H, int n, int dtype, void* stream) {
+    const SamRelposArgs a{Q, ldq, th, tw, out, BW, H, n};
+    if (!sam_relpos_ok(a)) { set_error("ldx_op_sam_relpos: bad argument (null pointer, ldq % 8, ldq < H * 64, n outside 1 .. 1024)"); return LDX_EINVAL; }
+    launch_sam_relpos(a, dtype_of(dtype), (hipStream_t)stream);
+    return check_launch("ldx_op_sam_relpos");
+}
+int ldx_op_sam_attention(const void* Q, const void* K, const void* V, int ld, const float* rel, void* O, int ldo, int BW, int H, int n, float scale, int dtype, void* stream) {
+    const SamAttnArgs a{Q, K, V, ld, rel, O, ldo, BW, H, n, scale};
+    if (!sam_attn_ok(a)) { set_error("ldx_op_sam_attention: bad argument (null pointer, ld % 8, ldo % 4, rows narrower than H * 64, BW * H > 65535, n outside 1 .. 1024)"); return LDX_EINVAL; }
+    launch_sam_attention(a, dtype_of(dtype), (hipStream_t)stream);
+    return check_launch("ldx_op_sam_attention");
+}
 int ldx_tile_blend(const float* tile, int th, int tw, float* out, float* div, int H, int W, int C, int y0, int x0, int feather, void* stream) {
     if (!tile || !out || !div || th <= 0 || tw <= 0 || C <= 0 || y0 < 0 || x0 < 0 || y0 + th > H || x0 + tw > W || feather < 0) {
         set_error("ldx_tile_blend: bad argument (tile must lie inside the output)"); return LDX_EINVAL; }

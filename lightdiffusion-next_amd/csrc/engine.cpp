@@ -1,5 +1,5 @@
 // ldx engines: the host-side planner / executor every model shares, behind the C ABI (include/ldx.h).  The models themselves are the classes
-// derived from Engine (engine_unet.cpp, engine_vae.cpp, engine_clip.cpp, engine_t5.cpp, engine_esrgan.cpp, engine_flux.cpp, engine_taesd.cpp).
+// derived from Engine (engine_unet.cpp, engine_vae.cpp, engine_clip.cpp, engine_t5.cpp, engine_esrgan.cpp, engine_flux.cpp, engine_taesd.cpp, engine_sam.cpp).
 //
 // A model runs as a static launch plan over one activation arena: weights are packed once into MFMA-friendly
 // [N][K] 16-bit matrices (conv3x3 -> [Cout][ky][kx][Cin], q/k/v fused, GEGLU rows slab-interleaved),
@@ -721,6 +721,12 @@ int Engine::launch_op(const Op& o, hipStream_t ls) {
         case OP_DUP: launch_dup_rows(o.dup, dt, ls); break;
         case OP_TAESD_PREP: { TaesdPrepArgs a = o.tprep; a.z = bind.x; launch_taesd_prep(a, dt, ls); } break;
         case OP_TAESD_CONV: { TaesdConvArgs a = o.tconv; if (a.out3) { a.out_f32 = bind.out; a.out_u8 = bind.out8; a.flux = bind.flux; } launch_taesd_conv(a, dt, ls); } break;
+        case OP_SAM_PATCH: { SamPatchArgs a = o.spatch; a.img = bind.x; launch_sam_patch(a, dt, ls); } break;
+        case OP_SAM_WINDOW: launch_sam_window(o.swin, dt, ls); break;
+        case OP_SAM_RELPOS: launch_sam_relpos(o.srel, dt, ls); break;
+        case OP_SAM_ATTN: launch_sam_attention(o.sattn, dt, ls); break;
+        case OP_SAM_ROWVEC: launch_sam_rowvec(o.srv, dt, ls); break;
+        case OP_SAM_OUT: { SamOutArgs a = o.sout; a.out = bind.out; launch_sam_out(a, dt, ls); } break;
         case OP_FX_TEMB: { FluxTembArgs a = o.temb; a.t = o.of_guidance ? bind.guid : bind.s; launch_flux_temb(a, ls); } break;
         case OP_FX_SILU: launch_silu_f32(o.silu, ls); break;
         case OP_FX_PATCH: { FluxPatchArgs a = o.patch; a.x = bind.x; launch_flux_patchify(a, dt, ls); } break;
@@ -760,6 +766,7 @@ std::string Engine::prof_key(const Op& o) const {
     else if (o.kind == OP_FFBLOCK) snprintf(sh, sizeof(sh), " M%ld C%d", (long)o.fb.M, o.fb.C);
     else if (o.kind == OP_LN) snprintf(sh, sizeof(sh), " R%d C%d", o.ln.rows, o.ln.C);
     else if (o.kind == OP_MXQ) snprintf(sh, sizeof(sh), " R%d K%d", o.mq.rows, o.mq.K);
+    else if (o.kind == OP_SAM_ATTN) snprintf(sh, sizeof(sh), " B%d H%d n%d", o.sattn.BW, o.sattn.H, o.sattn.n);
     else if (o.kind == OP_GEMM2) snprintf(sh, sizeof(sh), " M%d+%d N%d K%d", o.g.M, o.g2.M, o.g.N, o.g.K);
     return key + sh;
 }

@@ -73,7 +73,8 @@ enum OpKind { OP_PREP, OP_CVT, OP_SKINNY, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_FIN
               OP_VAEPREP, OP_SOFTMAX, OP_CLAMP, OP_EMBED, OP_CVT_OUT,
               OP_PIXPREP, OP_MOMENTS, OP_COPY_OUT,
               OP_FX_PATCH, OP_FX_TEMB, OP_FX_SILU, OP_FX_ROPE, OP_FX_UNPATCH, OP_FX_SKINNY_Y, OP_MXQ, OP_GEMM2, OP_XATTN, OP_FFBLOCK, OP_ROWGEMM, OP_ATTN_MX, OP_MXVT, OP_DUP,
-              OP_TAESD_PREP, OP_TAESD_CONV };
+              OP_TAESD_PREP, OP_TAESD_CONV,
+              OP_SAM_PATCH, OP_SAM_WINDOW, OP_SAM_RELPOS, OP_SAM_ATTN, OP_SAM_ROWVEC, OP_SAM_OUT };
 // One launch of a plan.  The rule: every kind has ONE argument struct (ldx_kernels.h, beside its launcher), filled by the planner, and Engine::launch_op hands it to
 // that launcher after filling in the pointers of the call (Bindings).  Nothing here has a meaning that depends on `kind`.
 struct Op {
@@ -81,6 +82,7 @@ struct Op {
     GemmArgs g; GemmArgs g2; GroupNormArgs gn; LayerNormArgs ln; AttnArgs at; SkinnyArgs sk; QkRopeArgs rp; MxQuantArgs mq; XAttnArgs xa; FFBlockArgs fb; RowGemmArgs rg; AttnMxArgs am; MxVtArgs vt;
     PrepArgs prep; FinishArgs fin; CvtArgs cvt; CvtOutArgs out; CopyOutArgs copy; VaePrepArgs vprep; PixelsPrepArgs pix; ClampArgs clamp; SoftmaxArgs sm; ClipEmbedArgs emb; MixArgs mix; DupRowsArgs dup;
     FluxTembArgs temb; SiluArgs silu; FluxPatchArgs patch; FluxUnpatchArgs unpatch; TaesdPrepArgs tprep; TaesdConvArgs tconv;
+    SamPatchArgs spatch; SamWindowArgs swin; SamRelposArgs srel; SamAttnArgs sattn; SamRowvecArgs srv; SamOutArgs sout;
     bool ctx_only;                 // depends on the context alone (16-bit copy of ctx, the batched k|v projection): skipped while Engine::ctx_cache holds
     // which of the call's buffers (Bindings) launch_op binds, where the kind alone does not say
     bool bias_from_call;           // the attention's score bias table is the call's (T5)
@@ -102,7 +104,7 @@ using GemmEdit = OpEdit<GemmArgs, &Op::g>; using AttnEdit = OpEdit<AttnArgs, &Op
 struct ProfEntry { long count = 0; double ms = 0, flops = 0, bytes = 0; };
 
 // What a plan was built for.  Per model: UNet (B2, h, w, Mc, share), Flux (B, h, w, Lt), VAE (B, h, w, 1) decode / (B, Hpx, Wpx, 2) encode,
-// CLIP (B, T, 0, inter_layer), T5 (B, L), ESRGAN (B, H, W), TAESD (B, h, w).  B = 0: no plan.
+// CLIP (B, T, 0, inter_layer), T5 (B, L), ESRGAN (B, H, W), TAESD (B, h, w), SAM (B).  B = 0: no plan.
 struct PlanKey {
     int B = 0, h = 0, w = 0, m = 0, share = 0;
     bool operator==(const PlanKey& o) const { return B == o.B && h == o.h && w == o.w && m == o.m && share == o.share; }
@@ -174,13 +176,13 @@ struct FluxDoubleW { FluxStreamW img, txt; };
 struct FluxSingleW { LinearW lin1_qkv, lin1_mlp, lin2; float* qs = nullptr; float* ks = nullptr; int mod_off = 0; };
 
 // The planner / executor every model is built on, and what every model's weights go through.  A model is a derived class (UNetEngine, VaeEngine, ClipEngine,
-// T5Engine, EsrganEngine, FluxEngine, TaesdEngine) that owns its config, its weight tables, finalize(), its plan functions and its run entry points; the C ABI reaches a model
+// T5Engine, EsrganEngine, FluxEngine, TaesdEngine, SamEngine) that owns its config, its weight tables, finalize(), its plan functions and its run entry points; the C ABI reaches a model
 // entry point only through that class (capi.cpp engine_as), so nothing here or there asks an engine what it is.
 class Engine {
 public:
     static constexpr const char* model = "valid";
     // keep_plans: plans of other input shapes stay in plan_cache (UNet, Flux); otherwise a new shape re-plans into the current plan
-    // captures: graph_mode captures and replays this model's plans (UNet, TAESD); the other models accept the mode and ignore it
+    // captures: graph_mode captures and replays this model's plans (UNet, TAESD, SAM); the other models accept the mode and ignore it
     Engine(int dev, int compute_dtype, bool keep_plans, bool captures = false)
         : device(dev), dt(compute_dtype == LDX_F16 ? DT_F16 : DT_BF16), captures(captures), keep_plans(keep_plans) {}
     virtual ~Engine();
@@ -478,6 +480,22 @@ private:
     LinearW ta_first, ta_last, ta_up[3]; TaesdBlockW ta_blocks[10];
     bool mk_conv64(const std::string& pre, int Cout, int Cin, bool bias, LinearW& out);
     int plan(int B, int h, int w);
+};
+
+// SAM image encoder (engine_sam.cpp): the preprocessed image fp32 [B][3][size][size] -> the image embedding fp32 [B][out_chans][size / 16][size / 16]
+struct SamBlockW { NormW ln1, ln2; LinearW qkv, proj, lin1, lin2; float* rel_h = nullptr; float* rel_w = nullptr; bool global = false; };
+class SamEngine final : public Engine {
+public:
+    static constexpr const char* model = "SAM";
+    SamEngine(const ldx_sam_config& c, int dev) : Engine(dev, c.compute_dtype, false, true), cfg(c) {}
+    int validate() const;
+    int finalize() override;
+    int run(const float* x, int B, float* out, hipStream_t st);
+    const ldx_sam_config cfg;
+
+private:
+    LinearW sam_patch, sam_neck0, sam_neck2; NormW sam_neck1, sam_neck3; float* sam_pos = nullptr; std::vector<SamBlockW> sam_blocks;
+    int plan(int B);
 };
 
 class FluxEngine final : public Engine {

@@ -648,4 +648,36 @@ void launch_detail_blur_mask(const float* in, int h, int w, const float* table, 
 // the rectangle (x0, y0, w, h) of the canvas from the first h rows and w columns of src [..][src_w][3] and mask [..][src_w]
 void launch_detail_paste(float* canvas, int W, int x0, int y0, const float* src, const float* mask, int src_w, int h, int w, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// SAM image encoder (sam.hip, libldx_sam.so): what ImageEncoderViT needs beyond the shared GEMM / LayerNorm / conv kernels; include/ldx.h states each rule.
+// Head dimension 64, patch 16.  Tokens are 16-bit rows [B * S * S][E]; a window block's rows are [B * nw * nw][win * win][E], nw = ceil(S / win).
+// The launchers take validated arguments (the *_ok functions; capi.cpp and SamEngine::plan ask them).
+// Patch gather: img fp32 [B][3][16 S][16 S] -> out 16-bit [B * S * S][768], column = (c * 16 + ky) * 16 + kx (patch_embed.proj.weight's own K order)
+struct SamPatchArgs { const float* img; void* out; int B, S; };
+void launch_sam_patch(const SamPatchArgs& a, DType dt, hipStream_t s);
+// scatter = 0: dst[window row] = src[pixel row], zero rows for the padding below and right of the S x S grid.
+// scatter = 1: dst[pixel row] = R[pixel row] + src[window row] (the crop; the sum in fp32; R may be dst, or null for the bare inverse)
+struct SamWindowArgs { const void* src; void* dst; const void* R; int B, S, win, C; int scatter; };
+bool sam_window_ok(const SamWindowArgs& a);
+void launch_sam_window(const SamWindowArgs& a, DType dt, hipStream_t s);
+// out fp32 [BW * H][n * n][2 n] = rel_h | rel_w of every query: rel_h[q][j] = sum_c Q[q][c] * th[q_h - j + n - 1][c], rel_w[q][j] likewise with q_w and tw.
+// Q 16-bit rows bw * n * n + q (row stride ldq), head h at columns h * 64; th, tw fp32 [2 n - 1][64].
+struct SamRelposArgs { const void* Q; int ldq; const float* th; const float* tw; float* out; int BW, H, n; };
+bool sam_relpos_ok(const SamRelposArgs& a);
+void launch_sam_relpos(const SamRelposArgs& a, DType dt, hipStream_t s);
+// O[bw * N + q][h * 64 + d] = sum_k softmax_k(scale * q.k + rel[q][k / n] + rel[q][n + k % n]) v[k][d], N = n * n keys and queries per (bw, h); Q, K, V
+// rows bw * N + token with one row stride ld, head h at columns h * 64; rel = SamRelposArgs::out.  Flash attention: no N x N matrix is ever stored.
+struct SamAttnArgs { const void* Q; const void* K; const void* V; int ld; const float* rel; void* O; int ldo; int BW, H, n; float scale; };
+bool sam_attn_ok(const SamAttnArgs& a);
+void launch_sam_attention(const SamAttnArgs& a, DType dt, hipStream_t s);
+// X[m][c] = act(X[m][c] + vec[m % period][c]) in place: act 1 with period 1 = bias + erf-GELU (the MLP), act 0 with period S * S = + pos_embed.  C % 8 == 0.
+struct SamRowvecArgs { void* X; int ld; long rows; int C; const float* vec; int period; int act; };
+void launch_sam_rowvec(const SamRowvecArgs& a, DType dt, hipStream_t s);
+// out fp32 [B][C][HW] = X 16-bit [B * HW][ld]
+struct SamOutArgs { const void* X; int ld; float* out; int B, C, HW; };
+void launch_sam_out(const SamOutArgs& a, DType dt, hipStream_t s);
+// Sam.preprocess: out fp32 [3][size][size] = (float(in[y][x][c]) - mean_c) / std_c, zeros right of w and below h; in u8 [h][w][3], rows `pitch` bytes apart
+struct SamPreprocessArgs { const uint8_t* in; long pitch; int h, w; float* out; int size; };
+void launch_sam_preprocess(const SamPreprocessArgs& a, hipStream_t s);
+
 }  // namespace ldx

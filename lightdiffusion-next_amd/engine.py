@@ -208,7 +208,7 @@ def _encode_token_weights(token_weight_pairs, empty_tokens, encode):
 
 
 class _GraphMode:
-    """The hipGraph mode of the two engines that have one (UNetEngine, TAESDEngine); the native engines of the other models ignore ldx_set_graph_mode."""
+    """The hipGraph mode of the three engines that have one (UNetEngine, TAESDEngine, SAMImageEncoderEngine); the native engines of the other models ignore ldx_set_graph_mode."""
 
     def set_graph_mode(self, on: bool):
         lib.check(self._lib.ldx_set_graph_mode(self._h, int(on)), "ldx_set_graph_mode")
@@ -620,6 +620,84 @@ class TAESDEngine(_GraphMode, _Engine):
     def preview(self, x, flux: bool = False):
         """The tensor part of taesd_preview (taesd.py:264-304): latent [B,C,h,w] -> device uint8 [B,8h,8w,3], the bytes the reference hands to PIL."""
         return self._decode(self._latent(x), False, True, flux)[1]
+
+
+class SAMImageEncoderEngine(_GraphMode, _Engine):
+    """segment_anything's image encoder (ImageEncoderViT; the reference's SAM.py loads ViT-B): the network behind ADetailer's masks, once per image.
+    state_dict: segment_anything's own keys, with or without "image_encoder." (weights.sam_encoder_state_dict_spec); a whole Sam checkpoint may be passed,
+    the prompt encoder's and mask decoder's tensors are left out.
+    graph=True: the launches of a batch size are captured into a hipGraph on the second call and replayed from the third.  A captured graph has its
+    pointers baked in, so in graph mode the engine keeps one input and one output buffer per batch size and returns a copy of the result."""
+
+    def __init__(self, cfg=None, state_dict=None, device: int = 0, dtype: str = "bf16", graph: bool = False):
+        from .weights import SAMConfig
+        cfg = cfg or SAMConfig.vit_b()
+        super().__init__(cfg, device)
+        self.dtype = dtype
+        self._create(lib.ldx_sam_config, "ldx_sam_create", dtype, image_size=cfg.image_size, embed_dim=cfg.embed_dim, depth=cfg.depth, num_heads=cfg.num_heads,
+                     mlp_dim=cfg.mlp_dim, out_chans=cfg.out_chans, window_size=cfg.window_size, global_attn_mask=cfg.global_attn_mask)
+        try:
+            other = ("prompt_encoder.", "mask_decoder.", "pixel_mean", "pixel_std")
+            self._load_state_dict({k: v for k, v in state_dict.items() if not k.startswith(other)}, strip=("image_encoder.",))
+            self._finalize()
+        except Exception:
+            self.close()
+            raise
+        self._ops = None
+        self.set_graph_mode(graph)
+
+    def set_graph_mode(self, on: bool):
+        super().set_graph_mode(on)
+        self._graph, self._static = bool(on), {}
+
+    def encode(self, x):
+        """ImageEncoderViT.forward: the preprocessed image(s) [B,3,size,size] -> fp32 [B,out_chans,size/16,size/16] on the device."""
+        cfg = self.cfg
+        assert x.dim() == 4 and tuple(x.shape[1:]) == (3, cfg.image_size, cfg.image_size), tuple(x.shape)
+        x = x.to(self.device, torch.float32).contiguous()
+        b = x.shape[0]
+        if not self._graph:
+            out = torch.empty((b, cfg.out_chans, cfg.grid, cfg.grid), device=self.device, dtype=torch.float32)
+        else:
+            if b not in self._static:
+                if len(self._static) >= 4:
+                    self._static.clear()
+                self._static[b] = (torch.empty_like(x), torch.empty((b, cfg.out_chans, cfg.grid, cfg.grid), device=self.device, dtype=torch.float32))
+            xs, out = self._static[b]
+            xs.copy_(x)
+            x = xs
+        lib.check(self._lib.ldx_sam_encode(self._h, lib.ptr(x), b, lib.ptr(out), lib.current_stream_ptr()), "ldx_sam_encode")
+        return out.clone() if self._graph else out
+
+    def preprocess(self, image):
+        """What SamPredictor.set_image does to an image in front of the encoder, on the device: image fp32 [1,H,W,3] or [H,W,3] in [0, 1] (quantised as
+        make_sam_mask does, SAM.py:225: clip, times 255, truncate) or uint8 -> longest side to image_size with Pillow's 8-bit BILINEAR
+        (ResizeLongestSide.apply_image) -> Sam.preprocess.  Returns fp32 [1,3,size,size]."""
+        from .sam import preprocess_shape
+        from .usdu import BILINEAR, ImageOps, _Image
+        if self._ops is None:
+            self._ops = ImageOps()
+            self._ops._init_ops(self.device)
+        if image.dim() == 3:
+            image = image[None]
+        assert image.dim() == 4 and image.shape[0] == 1 and image.shape[3] == 3, tuple(image.shape)
+        _, h, w, _ = image.shape
+        size = self.cfg.image_size
+        if image.dtype == torch.uint8:
+            img = _Image(h, w, 3, self.device)
+            img.view().copy_(image[0].to(self.device))
+        else:
+            img = self._ops._quantize(image)
+        nh, nw = preprocess_shape(h, w, size)
+        if (nh, nw) != (h, w):
+            img = self._ops._resize(img, None, nw, nh, BILINEAR)
+        x = torch.empty((1, 3, size, size), device=self.device, dtype=torch.float32)
+        lib.check(self._lib.ldx_sam_preprocess(img.ptr(), img.pitch, nh, nw, lib.ptr(x), size, lib.current_stream_ptr()), "ldx_sam_preprocess")
+        return x
+
+    def set_image(self, image):
+        """preprocess + encode: the image embedding fp32 [1,out_chans,size/16,size/16] of what the pipeline holds on the device."""
+        return self.encode(self.preprocess(image))
 
 
 def t5_relative_position_bucket(relative_position, num_buckets=32, max_distance=128):

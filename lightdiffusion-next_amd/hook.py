@@ -99,3 +99,33 @@ class LdxFluxPatch:
 
     def __deepcopy__(self, memo):
         return self
+
+
+class LdxSAMPatch(torch.nn.Module):
+    """Stands in for Sam.image_encoder (segment_anything's ImageEncoderViT) in front of a SAMImageEncoderEngine: no parameters, `img_size` as SamPredictor
+    and Sam.preprocess read it, forward(x) = the engine's features on x's device and in x's dtype.
+    The reference builds a new SamPredictor and calls set_image for every segment (SAM.py:138-141, from the loop at :230-245), on the same image each
+    time.  The patch keeps its last input and features: an equal input (torch.equal) gets them back without running the engine, which turns one encode
+    per segment into one per image with the reference's code unchanged.  `encodes` / `reuses` count the two."""
+
+    def __init__(self, engine):
+        super().__init__()
+        self.engine = engine
+        self.img_size = engine.cfg.image_size
+        self.encodes = self.reuses = 0
+        self._last = self._features = None
+
+    def install(self, sam):
+        """sam.image_encoder = this patch; returns sam."""
+        sam.image_encoder = self
+        return sam
+
+    @torch.no_grad()
+    def forward(self, x):
+        if self._last is not None and self._last.shape == x.shape and self._last.dtype == x.dtype and self._last.device == x.device and torch.equal(x, self._last):
+            self.reuses += 1
+        else:
+            self._features = self.engine.encode(x).to(device=x.device, dtype=x.dtype)
+            self._last = x.detach().clone()
+            self.encodes += 1
+        return self._features

@@ -52,6 +52,11 @@ class ldx_taesd_config(C.Structure):
     _fields_ = [("compute_dtype", C.c_int32), ("latent_channels", C.c_int32)]
 
 
+class ldx_sam_config(C.Structure):
+    _fields_ = [("compute_dtype", C.c_int32), ("image_size", C.c_int32), ("embed_dim", C.c_int32), ("depth", C.c_int32), ("num_heads", C.c_int32),
+                ("mlp_dim", C.c_int32), ("out_chans", C.c_int32), ("window_size", C.c_int32), ("global_attn_mask", C.c_uint32)]
+
+
 class ldx_t5_config(C.Structure):
     _fields_ = [("compute_dtype", C.c_int32), ("d_model", C.c_int32), ("d_ff", C.c_int32), ("num_layers", C.c_int32),
                 ("num_heads", C.c_int32), ("vocab_size", C.c_int32)]
@@ -110,6 +115,12 @@ _SIGS = {
     "ldx_taesd_create": (_i, [C.POINTER(ldx_taesd_config), _i, C.POINTER(_vp)]),
     "ldx_taesd_decode": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "ldx_taesd_conv64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ldx_sam_create": (_i, [C.POINTER(ldx_sam_config), _i, C.POINTER(_vp)]),
+    "ldx_sam_encode": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "ldx_sam_preprocess": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp]),
+    "ldx_op_sam_window": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ldx_op_sam_relpos": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ldx_op_sam_attention": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "ldx_tile_blend": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ldx_tile_finish": (_i, [_vp, _vp, _i64, _i, _vp]),
     "ldx_t5_create": (_i, [C.POINTER(ldx_t5_config), _i, C.POINTER(_vp)]),

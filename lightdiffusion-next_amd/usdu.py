@@ -17,7 +17,7 @@ import torch
 from . import lib
 from .sampling import KSampler
 
-LANCZOS, BICUBIC = "lanczos", "bicubic"
+LANCZOS, BICUBIC, BILINEAR = "lanczos", "bicubic", "bilinear"
 _PRECISION_BITS = 22
 
 
@@ -39,7 +39,12 @@ def _bicubic(x, a=-0.5):
     return 0.0
 
 
-_FILTERS = {LANCZOS: (_lanczos, 3.0), BICUBIC: (_bicubic, 2.0)}
+def _bilinear(x):
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+_FILTERS = {LANCZOS: (_lanczos, 3.0), BICUBIC: (_bicubic, 2.0), BILINEAR: (_bilinear, 1.0)}
 
 
 @functools.lru_cache(maxsize=64)

@@ -565,3 +565,84 @@ def flux_state_dict_spec(cfg: FluxConfig):
     lin("final_layer.linear", inc, c)
     lin("final_layer.adaLN_modulation.1", 2 * c, c)
     return spec
+
+
+# ---- SAM image encoder (segment_anything ImageEncoderViT; the reference loads ViT-B, src/AutoDetailer/SAM.py:157-182) -------------------------------------
+@dataclass
+class SAMConfig:
+    """ImageEncoderViT's keyword arguments as build_sam's _build_sam passes them: patch 16, absolute and decomposed relative position embeddings,
+    qkv bias, head dimension embed_dim / num_heads = 64 (ViT-B and ViT-L; the engine refuses ViT-H's 80)."""
+
+    image_size: int = 1024
+    embed_dim: int = 768
+    depth: int = 12
+    num_heads: int = 12
+    mlp_dim: int = 3072
+    out_chans: int = 256
+    window_size: int = 14
+    global_attn_indexes: Tuple[int, ...] = (2, 5, 8, 11)
+
+    @staticmethod
+    def vit_b() -> "SAMConfig":
+        return SAMConfig()
+
+    @staticmethod
+    def vit_l() -> "SAMConfig":
+        return SAMConfig(embed_dim=1024, depth=24, num_heads=16, mlp_dim=4096, global_attn_indexes=(5, 11, 17, 23))
+
+    @staticmethod
+    def tiny() -> "SAMConfig":
+        return SAMConfig(image_size=128, embed_dim=128, depth=2, num_heads=2, mlp_dim=256, out_chans=64, window_size=3, global_attn_indexes=(1,))
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // 16
+
+    @property
+    def global_attn_mask(self) -> int:
+        m = 0
+        for i in self.global_attn_indexes:
+            m |= 1 << i
+        return m
+
+
+def sam_encoder_state_dict_spec(cfg: SAMConfig):
+    """segment_anything's own keys of Sam.image_encoder, "image_encoder." stripped, in creation order."""
+    E, S, C = cfg.embed_dim, cfg.grid, cfg.out_chans
+    spec = [("pos_embed", (1, S, S, E)), ("patch_embed.proj.weight", (E, 3, 16, 16)), ("patch_embed.proj.bias", (E,))]
+    for i in range(cfg.depth):
+        n = S if i in cfg.global_attn_indexes else cfg.window_size
+        p = f"blocks.{i}"
+        spec += [(f"{p}.norm1.weight", (E,)), (f"{p}.norm1.bias", (E,)), (f"{p}.attn.rel_pos_h", (2 * n - 1, E // cfg.num_heads)),
+                 (f"{p}.attn.rel_pos_w", (2 * n - 1, E // cfg.num_heads)), (f"{p}.attn.qkv.weight", (3 * E, E)), (f"{p}.attn.qkv.bias", (3 * E,)),
+                 (f"{p}.attn.proj.weight", (E, E)), (f"{p}.attn.proj.bias", (E,)), (f"{p}.norm2.weight", (E,)), (f"{p}.norm2.bias", (E,)),
+                 (f"{p}.mlp.lin1.weight", (cfg.mlp_dim, E)), (f"{p}.mlp.lin1.bias", (cfg.mlp_dim,)), (f"{p}.mlp.lin2.weight", (E, cfg.mlp_dim)),
+                 (f"{p}.mlp.lin2.bias", (E,))]
+    return spec + [("neck.0.weight", (C, E, 1, 1)), ("neck.1.weight", (C,)), ("neck.1.bias", (C,)), ("neck.2.weight", (C, C, 3, 3)),
+                   ("neck.3.weight", (C,)), ("neck.3.bias", (C,))]
+
+
+def sam_synth_tensor(key: str, shape, seed: int) -> torch.Tensor:
+    """The synthetic SAM weights' rule (fp32), per key and independent of iteration order: linear and conv weights N(0, 1 / fan_in), norm gains
+    1 + N(0, 0.1^2), biases N(0, 0.05^2), pos_embed N(0, 0.5^2), rel_pos tables N(0, 0.25^2).  Larger than synth_tensor's: the output must depend on the
+    position terms and the biases far above the 16-bit error, or a fixture could not tell a kernel that drops one of them from a correct one."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed((seed * 1000003 + zlib.crc32(key.encode())) & 0x7FFFFFFF)
+    n = torch.randn(tuple(shape), generator=g, dtype=torch.float32)
+    name = key.rsplit(".", 1)[0]
+    if key == "pos_embed":
+        return 0.5 * n
+    if "rel_pos" in key:
+        return 0.25 * n
+    if key.endswith(".bias"):
+        return 0.05 * n
+    if name.endswith("norm1") or name.endswith("norm2") or name in ("neck.1", "neck.3"):
+        return 1.0 + 0.1 * n
+    fan_in = 1
+    for s in shape[1:]:
+        fan_in *= s
+    return n / math.sqrt(fan_in)
+
+
+def sam_synth_state_dict(cfg: SAMConfig, seed: int = 1234) -> Dict[str, torch.Tensor]:
+    return {k: sam_synth_tensor(k, s, seed) for k, s in sam_encoder_state_dict_spec(cfg)}
