@@ -116,6 +116,20 @@ typedef struct ldx_sam_config {
     uint32_t global_attn_mask;     /* bit i set: block i attends globally (ViT-B: blocks 2, 5, 8, 11 = 0x924) */
 } ldx_sam_config;
 
+/* SAM prompt encoder + mask decoder (segment_anything PromptEncoder, MaskDecoder with its TwoWayTransformer; the same for ViT-B, ViT-L and ViT-H).  fp32
+ * throughout, so there is no compute_dtype.  The grid is image_size / 16 a side.  LDX_EINVAL at creation: hidden % 64 != 0, hidden / 2 not divisible by
+ * num_heads, a cross-attention head dimension hidden / 2 / num_heads other than 8, 16 or 32, depth != 2, num_multimask != 3, mlp_dim or iou_head_hidden
+ * not a positive multiple of 4, image_size not a positive multiple of 16. */
+typedef struct ldx_samdec_config {
+    int32_t image_size;            /* 1024 */
+    int32_t hidden;                /* 256 : transformer_dim = prompt embed_dim */
+    int32_t num_heads;             /* 8 */
+    int32_t mlp_dim;               /* 2048 */
+    int32_t iou_head_hidden;       /* 256 */
+    int32_t depth;                 /* 2 */
+    int32_t num_multimask;         /* 3 : with the single-mask token, 4 mask tokens */
+} ldx_samdec_config;
+
 /* Flux DiT — FluxParams (src/BlackForest/Flux.py:293-306); flux-dev: 16, 768, 4096, 3072, 4.0, 24, 19, 38,
  * axes [16,56,56], theta 10000, qkv_bias 1, guidance_embed 1. */
 typedef struct ldx_flux_config {
@@ -336,6 +350,29 @@ int ldx_sam_encode(ldx_engine* e, const float* x_nchw_f32, int B, float* out_nch
 /* Sam.preprocess: img u8 [h][w][3] with rows `pitch` bytes apart -> out fp32 [3][size][size] = (float(img) - mean_c) / std_c with the pixel mean
  * (123.675, 116.28, 103.53) and std (58.395, 57.12, 57.375), IEEE subtraction and division; zeros right of w and below h.  h, w <= size. */
 int ldx_sam_preprocess(const uint8_t* img, int64_t pitch, int h, int w, float* out, int size, void* stream);
+/* SAM prompt encoder + mask decoder.  State-dict keys are segment_anything's own: prompt_encoder.pe_layer.positional_encoding_gaussian_matrix,
+ * prompt_encoder.point_embeddings.<0..3>.weight, prompt_encoder.not_a_point_embed.weight, prompt_encoder.no_mask_embed.weight, mask_decoder.iou_token.weight,
+ * mask_decoder.mask_tokens.weight, mask_decoder.transformer.layers.<i>.{self_attn,cross_attn_token_to_image,cross_attn_image_to_token}.{q,k,v,out}_proj.*,
+ * .norm<1..4>.*, .mlp.lin<1,2>.*, mask_decoder.transformer.final_attn_token_to_image.*, .norm_final_attn.*, mask_decoder.output_upscaling.<0,1,3>.*,
+ * mask_decoder.output_hypernetworks_mlps.<0..3>.layers.<0..2>.*, mask_decoder.iou_prediction_head.layers.<0..2>.*.  Mask prompts (mask_downscaling) are not built.
+ * LayerNorm eps 1e-5 in the transformer, 1e-6 in the upscaling's LayerNorm2d.  Every model-specific call on a handle of another model: LDX_ESTATE, nothing is launched.
+ * Graph mode (ldx_set_graph_mode) captures predict per (P, n, boxes or not) once the same buffers have been seen twice, as the image encoder does. */
+int ldx_samdec_create(const ldx_samdec_config* cfg, int device, ldx_engine** out);
+/* Once per image: embedding fp32 [hidden][g][g] (the image encoder's output) -> the engine's rows embedding + no_mask_embed, and what layer 0 computes from
+ * them alone (the token-to-image k and v projections, the image-to-token q projection).  Three launches. */
+int ldx_samdec_set_image(ldx_engine* e, const float* embedding, void* stream);
+/* SamPredictor.predict_torch for P prompts at once: points fp32 [P][n][2] and labels int32 [P][n] (n <= 8; both NULL with n = 0), boxes fp32 [P][4] or NULL, all
+ * in the resized frame (ResizeLongestSide.apply_coords); a padding point (label -1) is added exactly when boxes is NULL.  lowres_out fp32 [P][4][4 g][4 g] and
+ * iou_out fp32 [P][4]: index 0 is the single-mask output, 1 .. 3 the multimask ones.  LDX_EINVAL before any launch: n outside 0 .. 8, neither points nor
+ * boxes, P outside 1 .. 64; LDX_ESTATE without ldx_samdec_set_image.  A prompt's result does not depend on what else shares the call. */
+int ldx_samdec_predict(ldx_engine* e, const float* points, const int32_t* labels, int n, const float* boxes, int P, float* lowres_out, float* iou_out, void* stream);
+/* Test surface: the prompt tokens alone, out fp32 [P][5 + ns][hidden], ns = n + (boxes ? 2 : 1): iou_token | mask_tokens | points | padding point or corners. */
+int ldx_samdec_prompt_tokens(ldx_engine* e, const float* points, const int32_t* labels, int n, const float* boxes, int P, float* out, void* stream);
+/* Sam.postprocess_masks + the threshold, stateless, one launch: lowres fp32 [n][L][L] -> bilinear (align_corners = false, no antialias) to image_size a side ->
+ * crop to [in_h][in_w] -> bilinear to [H][W]; mask_u8 [n][H][W] = value > 0, logits fp32 [n][H][W] or NULL.  Per axis: scale = (float)in / (float)out,
+ * s = max(scale * (dst + 0.5f) - 0.5f, 0), i0 = (int)s, i1 = min(i0 + 1, in - 1), l = s - i0; a sample is (v00 * (1 - lx) + v01 * lx) * (1 - ly) +
+ * (v10 * (1 - lx) + v11 * lx) * ly, every product and sum rounded to fp32 on its own.  The image_size intermediate is never stored. */
+int ldx_samdec_postprocess(const float* lowres, int n, int L, int in_h, int in_w, int H, int W, uint8_t* mask_u8, float* logits, int image_size, void* stream);
 /* Test surface: ONE launch of each of the encoder's own kernels, on 16-bit rows (dtype).
  * ldx_op_sam_window: scatter = 0: dst [B * nw * nw][win * win][C] = the window partition of src [B][S][S][C], zero rows for the padding up to nw = ceil(S / win)
  * windows a side; scatter = 1: dst [B][S][S][C] = R + the inverse of src (the crop), R like dst (dst itself allowed) or NULL.  C % 8 == 0, src != dst.

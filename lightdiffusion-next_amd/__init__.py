@@ -23,13 +23,15 @@ Layout:
                (ldx_detail_* kernels -> libldx_detail.so, ldx_image_* for the 8-bit steps); detailer_host is the same in numpy
   sam.py       SAM image encoder, host side: Sam.preprocess, ResizeLongestSide's shape rule and the network in torch (sam_encoder_host / _host16);
                SAMImageEncoderEngine runs it on the device (the shared GEMM / norm kernels + ldx_sam_* kernels -> libldx_sam.so), LdxSAMPatch binds it
-               into segment_anything's Sam
+               into segment_anything's Sam; the prompt encoder, mask decoder and post-processing likewise (sam_decoder_host, postprocess_host; SAMMaskDecoderEngine
+               on the fp32 kernels of libldx_samdec.so), and SAMDetector: SAMDetectorCombined from the device image and the detector's boxes to the mask
 """
 from . import lib, weights  # noqa: F401
-from .engine import UNetEngine, UNetConfig, VAEDecoderEngine, CLIPTextEngine, FluxEngine, T5Engine, ESRGANEngine, TAESDEngine, SAMImageEncoderEngine, bislerp, latent_upscale  # noqa: F401
+from .engine import UNetEngine, UNetConfig, VAEDecoderEngine, CLIPTextEngine, FluxEngine, T5Engine, ESRGANEngine, TAESDEngine, SAMImageEncoderEngine, SAMMaskDecoderEngine, bislerp, latent_upscale  # noqa: F401
 VAEEngine = VAEDecoderEngine      # the same engine encodes when encoder.* weights are loaded
-from .weights import VAEConfig, CLIPConfig, FluxConfig, T5Config, ESRGANConfig, TAESDConfig, SAMConfig  # noqa: F401
+from .weights import VAEConfig, CLIPConfig, FluxConfig, T5Config, ESRGANConfig, TAESDConfig, SAMConfig, SAMDecoderConfig  # noqa: F401
 from .hook import LdxUNetPatch, LdxFluxPatch, LdxSAMPatch  # noqa: F401
+from .sam import SAMDetector  # noqa: F401
 from . import prompt  # noqa: F401
 from . import sampling, parallel, checkpoint, usdu, hdr, png, detailer, gguf, sam  # noqa: F401
 from .detailer import Detailer, SEG  # noqa: F401

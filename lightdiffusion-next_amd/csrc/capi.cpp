@@ -166,6 +166,31 @@ int ldx_sam_preprocess(const uint8_t* img, int64_t pitch, int h, int w, float* o
     launch_sam_preprocess(SamPreprocessArgs{img, (long)pitch, h, w, out, size}, (hipStream_t)stream);
     return check_launch("ldx_sam_preprocess");
 }
+int ldx_samdec_create(const ldx_samdec_config* cfg, int device, ldx_engine** out) { return create_engine<SamDecoderEngine>(cfg, device, out, __func__); }
+int ldx_samdec_set_image(ldx_engine* e, const float* embedding, void* stream) {
+    GUARD_BEGIN
+    ENGINE_AS(SamDecoderEngine, m);
+    return m->set_image(embedding, (hipStream_t)stream);
+    GUARD_END
+}
+int ldx_samdec_predict(ldx_engine* e, const float* points, const int32_t* labels, int n, const float* boxes, int P, float* lowres_out, float* iou_out, void* stream) {
+    GUARD_BEGIN
+    ENGINE_AS(SamDecoderEngine, m);
+    return m->predict(points, (const int*)labels, n, boxes, P, lowres_out, iou_out, nullptr, (hipStream_t)stream);
+    GUARD_END
+}
+int ldx_samdec_prompt_tokens(ldx_engine* e, const float* points, const int32_t* labels, int n, const float* boxes, int P, float* out, void* stream) {
+    GUARD_BEGIN
+    ENGINE_AS(SamDecoderEngine, m);
+    return m->predict(points, (const int*)labels, n, boxes, P, nullptr, nullptr, out, (hipStream_t)stream);
+    GUARD_END
+}
+int ldx_samdec_postprocess(const float* lowres, int n, int L, int in_h, int in_w, int H, int W, uint8_t* mask_u8, float* logits, int image_size, void* stream) {
+    const SamDecPostArgs a{lowres, n, L, image_size, in_h, in_w, H, W, mask_u8, logits};
+    if (!samdec_post_ok(a)) { set_error("ldx_samdec_postprocess: bad argument (null pointer, a size <= 0, in_h or in_w above image_size)"); return LDX_EINVAL; }
+    launch_samdec_post(a, (hipStream_t)stream);
+    return check_launch("ldx_samdec_postprocess");
+}
 int ldx_op_sam_window(const void* src, void* dst, const void* R, int B, int S, int win, int C, int scatter, int dtype, void* stream) {
     const SamWindowArgs a{src, dst, R, B, S, win, C, scatter};
     if (!sam_window_ok(a)) { set_error("ldx_op_sam_window: bad argument (null pointer, src == dst, C % 8, scatter not 0 | 1, R without scatter)"); return LDX_EINVAL; }

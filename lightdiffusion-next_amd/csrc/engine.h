@@ -206,7 +206,7 @@ public:
     bool ctx_cache = false;
     double algorithmic_flops() const;                           // steady_flops() + flops_shared + flops_up2x
     double steady_flops() const;                                // algorithmic flops of one forward as executed in steady state (cached ops excluded)
-    int64_t n_launches() const;
+    virtual int64_t n_launches() const;
     int64_t n_graph_captures = 0, n_graph_replays = 0;      // ldx_graph_stats (tests: the sampler loops must replay, not re-capture)
     // per-kernel-class HIP-event profile of subsequent forwards (bench.py roofline leg)
     bool profiling = false, prof_detail = false;   // detail: key the report by op shape as well
@@ -496,6 +496,44 @@ public:
 private:
     LinearW sam_patch, sam_neck0, sam_neck2; NormW sam_neck1, sam_neck3; float* sam_pos = nullptr; std::vector<SamBlockW> sam_blocks;
     int plan(int B);
+};
+
+// SAM prompt encoder + mask decoder (engine_samdec.cpp), fp32: the image embedding and P prompts -> low-res mask logits and IoU predictions.  It plans no Op list:
+// a call is a fixed sequence of samdec.hip launches over buffers kept per (P, n, boxes or not), captured into a hipGraph in graph mode.
+struct SamDecAttnW { float* wq = nullptr; float* bq = nullptr; float* wkv = nullptr; float* bkv = nullptr; float* wo = nullptr; float* bo = nullptr; };      // wkv: k | v rows stacked
+struct SamDecLayerW { float* wqkv = nullptr; float* bqkv = nullptr; float* wo = nullptr; float* bo = nullptr; NormW n1, n2, n3, n4; SamDecAttnW t2i, i2t;
+                      float* w1 = nullptr; float* b1 = nullptr; float* w2 = nullptr; float* b2 = nullptr; };
+class SamDecoderEngine final : public Engine {
+public:
+    static constexpr const char* model = "SAM decoder";
+    SamDecoderEngine(const ldx_samdec_config& c, int dev) : Engine(dev, LDX_BF16, false, true), cfg(c) {}
+    ~SamDecoderEngine() override;
+    int validate() const;
+    int finalize() override;
+    int64_t n_launches() const override { return last_launches; }
+    int set_image(const float* emb, hipStream_t st);
+    // tokens_out != null: the prompt tokens alone (ldx_samdec_prompt_tokens)
+    int predict(const float* points, const int* labels, int n, const float* boxes, int P, float* lowres, float* iou, float* tokens_out, hipStream_t st);
+    const ldx_samdec_config cfg;
+
+private:
+    struct Call { const float* points; const int* labels; const float* boxes; float* lowres; float* iou; };
+    struct DecPlan {
+        int P = 0, n = 0, box = 0;
+        float* ws = nullptr; size_t ws_floats = 0;
+        hipGraphExec_t exec = nullptr; bool valid = false, warm = false; Call c{};
+    };
+    std::vector<DecPlan> plans;
+    SamDecLayerW layers[2]; SamDecAttnW fin; NormW nfin;
+    float *gauss = nullptr, *point_emb = nullptr, *not_a_point = nullptr, *no_mask = nullptr, *iou_token = nullptr, *mask_tokens = nullptr, *dense_pe = nullptr;
+    float *up1_w = nullptr, *up1_b = nullptr, *up2_w = nullptr, *up2_b = nullptr; NormW up_ln;
+    float *hyp_w[3] = {nullptr, nullptr, nullptr}, *hyp_b[3] = {nullptr, nullptr, nullptr}, *iou_w[3] = {nullptr, nullptr, nullptr}, *iou_b[3] = {nullptr, nullptr, nullptr};
+    float *src0 = nullptr, *k0v0 = nullptr, *q0 = nullptr;          // per image: rows, layer 0's k | v of the tokens' attention, layer 0's q of the rows' attention
+    bool have_image = false, capturing = false;
+    int64_t last_launches = 0;
+    bool mk_attn(const std::string& pre, int inner, SamDecAttnW& w);
+    float* stack32(const std::vector<std::string>& keys, std::initializer_list<int64_t> shape);
+    int run_ops(DecPlan& p, const Call& c, float* tokens_out, hipStream_t st);
 };
 
 class FluxEngine final : public Engine {

@@ -680,4 +680,42 @@ void launch_sam_out(const SamOutArgs& a, DType dt, hipStream_t s);
 struct SamPreprocessArgs { const uint8_t* in; long pitch; int h, w; float* out; int size; };
 void launch_sam_preprocess(const SamPreprocessArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// SAM prompt encoder + mask decoder (samdec.hip, libldx_samdec.so): fp32 throughout.  Tokens are rows [P * T][C], image rows [P * g * g][C].
+// The launchers take validated arguments (the *_ok functions; SamDecoderEngine asks them when it plans).
+// out [P][5 + ns][C]: iou_token | mask_tokens[4] | n points (labels 1 / 0 / -1) | the padding point (no box) or the two box corners; ns = n + (boxes ? 2 : 1).
+// points [P][n][2] and boxes [P][4] (x, y in the resized frame), labels int32 [P][n]; gauss [2][C / 2]; point_emb [4][C]; size = image_size
+struct SamDecPromptArgs { const float* points; const int* labels; const float* boxes; int P, n, ns, C; float size; const float* gauss; const float* point_emb; const float* not_a_point;
+                          const float* iou_token; const float* mask_tokens; float* out; };
+void launch_samdec_prompt(const SamDecPromptArgs& a, hipStream_t s);
+// out [M][C] = emb [C][M] + add [C]
+void launch_samdec_transpose(const float* emb, const float* add, float* out, int C, int M, hipStream_t s);
+// Y[z][m][n] = act(LN(X[z][m % x_period] (+ PE[m % pe_period], for the column blocks that start below pe_cols) . W[z][n] + bias[z][n] + R[m % r_period][n])).
+// W [N][K]; nb <= 256 columns per workgroup; ln_group > 0: LayerNorm over every group of ln_group consecutive columns with gamma / beta [ln_group] (N <= nb);
+// act 1 ReLU, 2 erf-GELU; a period of 0: the row itself.  K, ldx, ldpe and the z strides of X and W are multiples of 4 and X, PE, W 16-byte aligned (float4 loads).  hyper [P][4][N / 4] != null: rows are [P][g * g][2 x 2] and the N columns [2 x 2][N / 4]; instead of Y,
+// logits [P][4][4 g][4 g] = the four products of every column group with the prompt's hypernetwork vectors (MaskDecoder's `hyper_in @ upscaled_embedding`)
+struct SamDecGemmArgs {
+    const float* X; int ldx; long x_period; const float* PE; int ldpe; long pe_period; int pe_cols;
+    const float* W; const float* bias; const float* R; int ldr; long r_period;
+    const float* gamma; const float* beta; int ln_group; float eps; int act;
+    float* Y; int ldy; long M; int N, K, nb; int nz; long xz, wz, bz, yz;
+    const float* hyper; int g; float* logits;
+};
+bool samdec_gemm_ok(const SamDecGemmArgs& a);
+void launch_samdec_gemm(const SamDecGemmArgs& a, hipStream_t s);
+// O[b * Tq + q][h * hd + d] = softmax_t(scale * Q[q] . K[b * Tk + t]) V[b * Tk + t][d] over Tk <= 16 keys; q_shared: Q has Tq rows, the same for every b
+struct SamDecAttnSmallArgs { const float* Q; int ldq; int q_shared; const float* K; int ldk; const float* V; int ldv; float* O; int ldo; int B; long Tq; int Tk, H, hd; float scale; };
+bool samdec_attn_small_ok(const SamDecAttnSmallArgs& a);
+void launch_samdec_attn_small(const SamDecAttnSmallArgs& a, hipStream_t s);
+// The T <= 16 token queries of every (prompt, head) against M image keys in S ranges of `chunk` keys (samdec_t2i_ranges; two launches: partials, merge).
+// kv_shared: K, V have M rows, the same for every prompt.  part: B * H * S * 16 * (hd + 2) floats.  hd 8, 16 or 32.
+struct SamDecAttnT2IArgs { const float* Q; int ldq; const float* K; int ldk; const float* V; int ldv; int kv_shared; float* part; float* O; int ldo; int B, T, M, H, hd, S, chunk; float scale; };
+int samdec_t2i_ranges(int M);
+bool samdec_attn_t2i_ok(const SamDecAttnT2IArgs& a);
+void launch_samdec_attn_t2i(const SamDecAttnT2IArgs& a, hipStream_t s);
+// Sam.postprocess_masks + threshold: lowres [n][L][L] -> bilinear to size x size -> crop [in_h][in_w] -> bilinear to [H][W]; mask u8 = value > 0, logits optional
+struct SamDecPostArgs { const float* lowres; int n, L, size, in_h, in_w, H, W; uint8_t* mask; float* logits; };
+bool samdec_post_ok(const SamDecPostArgs& a);
+void launch_samdec_post(const SamDecPostArgs& a, hipStream_t s);
+
 }  // namespace ldx

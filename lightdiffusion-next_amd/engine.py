@@ -700,6 +700,122 @@ class SAMImageEncoderEngine(_GraphMode, _Engine):
         return self.encode(self.preprocess(image))
 
 
+class SAMMaskDecoderEngine(_GraphMode, _Engine):
+    """segment_anything's prompt encoder and mask decoder (the same for ViT-B, ViT-L and ViT-H) and Sam.postprocess_masks, in fp32 on the device: what
+    SamPredictor.predict runs behind the image encoder, for P prompts of one image at once.  state_dict: segment_anything's own keys (prompt_encoder.*,
+    mask_decoder.*; weights.sam_decoder_state_dict_spec); a whole Sam checkpoint may be passed, image_encoder.*, pixel_* and the mask prompt's
+    mask_downscaling are left out.  Mask prompts and the single-mask output are not built.
+    graph=True: predict's launches are captured per (P, n, box or not) on the second call and replayed from the third; the engine then keeps its own
+    prompt and result buffers per shape and returns copies of the results."""
+
+    def __init__(self, cfg=None, state_dict=None, device: int = 0, graph: bool = False):
+        from .weights import SAMDecoderConfig, sam_decoder_state_dict_spec
+        cfg = cfg or SAMDecoderConfig.vit_b()
+        super().__init__(cfg, device)
+        self._create(lib.ldx_samdec_config, "ldx_samdec_create", "bf16", image_size=cfg.image_size, hidden=cfg.hidden, num_heads=cfg.num_heads, mlp_dim=cfg.mlp_dim,
+                     iou_head_hidden=cfg.iou_head_hidden, depth=cfg.depth, num_multimask=cfg.num_multimask)
+        try:
+            keys = {k for k, _ in sam_decoder_state_dict_spec(cfg)}
+            self._load_state_dict({k: v.float() for k, v in (state_dict or {}).items() if k in keys})
+            self._finalize()
+        except Exception:
+            self.close()
+            raise
+        self.set_graph_mode(graph)
+
+    def set_graph_mode(self, on: bool):
+        super().set_graph_mode(on)
+        self._graph, self._static = bool(on), {}
+
+    def set_image(self, embedding):
+        """The image encoder's output [1,C,g,g] or [C,g,g] (SAMImageEncoderEngine.encode): the per-image part of the decoder, once per image."""
+        cfg = self.cfg
+        e = embedding[0] if embedding.dim() == 4 else embedding
+        assert tuple(e.shape) == (cfg.hidden, cfg.grid, cfg.grid), tuple(embedding.shape)
+        e = e.to(self.device, torch.float32).contiguous()
+        lib.check(self._lib.ldx_samdec_set_image(self._h, lib.ptr(e), lib.current_stream_ptr()), "ldx_samdec_set_image")
+
+    def _prompts(self, points, labels, boxes, original_size):
+        """Host prompts in the original image's frame -> (points [P,n,2] | None, labels int32 | None, boxes [P,4] | None, P, n) in the resized frame, fp32 as
+        SamPredictor hands them to the model.  original_size None: they are in the resized frame already."""
+        import numpy as np
+        from .sam import apply_boxes_host, apply_coords_host
+        size = self.cfg.image_size
+        pts = lab = box = None
+        if points is not None:
+            pts = np.asarray(points, dtype=np.float64)
+            pts = pts.reshape((1,) + pts.shape) if pts.ndim == 2 else pts
+            lab = np.asarray(labels, dtype=np.int32).reshape(pts.shape[:2])
+            if original_size is not None:
+                pts = apply_coords_host(pts, original_size, size)
+            pts, lab = torch.from_numpy(pts.astype(np.float32)), torch.from_numpy(lab)
+        if boxes is not None:
+            box = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+            if original_size is not None:
+                box = apply_boxes_host(box, original_size, size)
+            box = torch.from_numpy(box.astype(np.float32))
+        if pts is None and box is None:
+            raise ValueError("SAMMaskDecoderEngine.predict: neither points nor boxes")
+        P = pts.shape[0] if pts is not None else box.shape[0]
+        if pts is not None and box is not None and box.shape[0] != P:
+            raise ValueError("SAMMaskDecoderEngine.predict: points and boxes of different prompt counts")
+        return pts, lab, box, P, 0 if pts is None else pts.shape[1]
+
+    def _buffers(self, pts, lab, box, P, n):
+        cfg, dev = self.cfg, self.device
+        key = (P, n, box is not None)
+        if self._graph and key in self._static:
+            bufs = self._static[key]
+        else:
+            bufs = (None if pts is None else torch.empty((P, n, 2), device=dev, dtype=torch.float32), None if pts is None else torch.empty((P, n), device=dev, dtype=torch.int32),
+                    None if box is None else torch.empty((P, 4), device=dev, dtype=torch.float32),
+                    torch.empty((P, 4, 4 * cfg.grid, 4 * cfg.grid), device=dev, dtype=torch.float32), torch.empty((P, 4), device=dev, dtype=torch.float32))
+            if self._graph:
+                if len(self._static) >= 8:
+                    self._static.clear()
+                self._static[key] = bufs
+        for dst, src in zip(bufs[:3], (pts, lab, box)):
+            if dst is not None:
+                dst.copy_(src)
+        return bufs
+
+    def predict(self, points=None, labels=None, boxes=None, original_size=None):
+        """SamPredictor.predict with its defaults (multimask_output=True, no mask prompt) for P prompts at once: points [P][n][2] (or [n][2]) with labels, and /
+        or boxes [P][4], in the original image's frame (original_size = (H, W); None: already in the resized frame).  Returns (low-res logits [P,3,4g,4g],
+        IoU predictions [P,3]) on the device: the three multimask outputs."""
+        pts, lab, box, P, n = self._prompts(points, labels, boxes, original_size)
+        dp, dl, db, lowres, iou = self._buffers(pts, lab, box, P, n)
+        lib.check(self._lib.ldx_samdec_predict(self._h, lib.ptr(dp), lib.ptr(dl), n, lib.ptr(db), P, lib.ptr(lowres), lib.ptr(iou), lib.current_stream_ptr()), "ldx_samdec_predict")
+        lowres, iou = lowres[:, 1:], iou[:, 1:]
+        return (lowres.clone(), iou.clone()) if self._graph else (lowres, iou)
+
+    def prompt_tokens(self, points=None, labels=None, boxes=None, original_size=None):
+        """Test surface: the decoder's input tokens [P, 5 + ns, C] (iou_token | mask_tokens | prompt encodings)."""
+        pts, lab, box, P, n = self._prompts(points, labels, boxes, original_size)
+        dev = self.device
+        dp, dl, db = (None if t is None else t.to(dev) for t in (pts, lab, box))
+        out = torch.empty((P, 5 + n + (2 if box is not None else 1), self.cfg.hidden), device=dev, dtype=torch.float32)
+        lib.check(self._lib.ldx_samdec_prompt_tokens(self._h, lib.ptr(dp), lib.ptr(dl), n, lib.ptr(db), P, lib.ptr(out), lib.current_stream_ptr()), "ldx_samdec_prompt_tokens")
+        return out
+
+    def masks(self, lowres, original_size, return_logits: bool = False):
+        """Sam.postprocess_masks + threshold: low-res logits [..,L,L] -> uint8 0/1 masks [..,H,W] on the device (and the fp32 logits at that size on request).
+        One launch; the image_size-square intermediate is never stored."""
+        from .sam import preprocess_shape
+        H, W = int(original_size[0]), int(original_size[1])
+        L = lowres.shape[-1]
+        lead = tuple(lowres.shape[:-2])
+        x = lowres.to(self.device, torch.float32).reshape(-1, L, L).contiguous()
+        n = x.shape[0]
+        in_h, in_w = preprocess_shape(H, W, self.cfg.image_size)
+        mask = torch.empty((n, H, W), device=self.device, dtype=torch.uint8)
+        logits = torch.empty((n, H, W), device=self.device, dtype=torch.float32) if return_logits else None
+        lib.check(self._lib.ldx_samdec_postprocess(lib.ptr(x), n, L, in_h, in_w, H, W, lib.ptr(mask), lib.ptr(logits), self.cfg.image_size, lib.current_stream_ptr()),
+                  "ldx_samdec_postprocess")
+        mask = mask.reshape(lead + (H, W))
+        return (mask, logits.reshape(lead + (H, W))) if return_logits else mask
+
+
 def t5_relative_position_bucket(relative_position, num_buckets=32, max_distance=128):
     """T5Attention._relative_position_bucket, bidirectional (src/clip/FluxClip.py:152-205) — same torch ops in the same
     order, so bucket boundaries (float32 log) agree bit for bit with the reference."""

@@ -57,6 +57,11 @@ class ldx_sam_config(C.Structure):
                 ("mlp_dim", C.c_int32), ("out_chans", C.c_int32), ("window_size", C.c_int32), ("global_attn_mask", C.c_uint32)]
 
 
+class ldx_samdec_config(C.Structure):
+    _fields_ = [("image_size", C.c_int32), ("hidden", C.c_int32), ("num_heads", C.c_int32), ("mlp_dim", C.c_int32), ("iou_head_hidden", C.c_int32),
+                ("depth", C.c_int32), ("num_multimask", C.c_int32)]
+
+
 class ldx_t5_config(C.Structure):
     _fields_ = [("compute_dtype", C.c_int32), ("d_model", C.c_int32), ("d_ff", C.c_int32), ("num_layers", C.c_int32),
                 ("num_heads", C.c_int32), ("vocab_size", C.c_int32)]
@@ -118,6 +123,11 @@ _SIGS = {
     "ldx_sam_create": (_i, [C.POINTER(ldx_sam_config), _i, C.POINTER(_vp)]),
     "ldx_sam_encode": (_i, [_vp, _vp, _i, _vp, _vp]),
     "ldx_sam_preprocess": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp]),
+    "ldx_samdec_create": (_i, [C.POINTER(ldx_samdec_config), _i, C.POINTER(_vp)]),
+    "ldx_samdec_set_image": (_i, [_vp, _vp, _vp]),
+    "ldx_samdec_predict": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "ldx_samdec_prompt_tokens": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "ldx_samdec_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "ldx_op_sam_window": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ldx_op_sam_relpos": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ldx_op_sam_attention": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),

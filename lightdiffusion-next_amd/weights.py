@@ -646,3 +646,94 @@ def sam_synth_tensor(key: str, shape, seed: int) -> torch.Tensor:
 
 def sam_synth_state_dict(cfg: SAMConfig, seed: int = 1234) -> Dict[str, torch.Tensor]:
     return {k: sam_synth_tensor(k, s, seed) for k, s in sam_encoder_state_dict_spec(cfg)}
+
+
+# ---- SAM prompt encoder + mask decoder (segment_anything PromptEncoder / MaskDecoder; the same for ViT-B, ViT-L and ViT-H) ---------------------------------
+@dataclass
+class SAMDecoderConfig:
+    """build_sam's _build_sam arguments of PromptEncoder and MaskDecoder: prompt_embed_dim = transformer_dim = hidden, a TwoWayTransformer of depth 2,
+    three multimask outputs.  The grid is image_size / 16 a side."""
+
+    image_size: int = 1024
+    hidden: int = 256
+    num_heads: int = 8
+    mlp_dim: int = 2048
+    iou_head_hidden: int = 256
+    depth: int = 2
+    num_multimask: int = 3
+
+    @staticmethod
+    def vit_b() -> "SAMDecoderConfig":
+        return SAMDecoderConfig()
+
+    @staticmethod
+    def tiny() -> "SAMDecoderConfig":
+        return SAMDecoderConfig(image_size=128, hidden=64, num_heads=2, mlp_dim=128, iou_head_hidden=64)
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // 16
+
+
+def sam_decoder_state_dict_spec(cfg: SAMDecoderConfig):
+    """segment_anything's own keys of Sam.prompt_encoder and Sam.mask_decoder, without the mask prompt's mask_downscaling (not built)."""
+    C, F, Hh = cfg.hidden, cfg.mlp_dim, cfg.iou_head_hidden
+    spec = [("prompt_encoder.pe_layer.positional_encoding_gaussian_matrix", (2, C // 2))]
+    spec += [(f"prompt_encoder.point_embeddings.{i}.weight", (1, C)) for i in range(4)]
+    spec += [("prompt_encoder.not_a_point_embed.weight", (1, C)), ("prompt_encoder.no_mask_embed.weight", (1, C)),
+             ("mask_decoder.iou_token.weight", (1, C)), ("mask_decoder.mask_tokens.weight", (cfg.num_multimask + 1, C))]
+
+    def attn(p, inner):
+        out = []
+        for n in ("q_proj", "k_proj", "v_proj"):
+            out += [(f"{p}.{n}.weight", (inner, C)), (f"{p}.{n}.bias", (inner,))]
+        return out + [(f"{p}.out_proj.weight", (C, inner)), (f"{p}.out_proj.bias", (C,))]
+
+    def norm(p, n=None):
+        return [(f"{p}.weight", (n or C,)), (f"{p}.bias", (n or C,))]
+
+    t = "mask_decoder.transformer"
+    for i in range(cfg.depth):
+        p = f"{t}.layers.{i}"
+        spec += attn(f"{p}.self_attn", C) + norm(f"{p}.norm1") + attn(f"{p}.cross_attn_token_to_image", C // 2) + norm(f"{p}.norm2")
+        spec += [(f"{p}.mlp.lin1.weight", (F, C)), (f"{p}.mlp.lin1.bias", (F,)), (f"{p}.mlp.lin2.weight", (C, F)), (f"{p}.mlp.lin2.bias", (C,))]
+        spec += norm(f"{p}.norm3") + norm(f"{p}.norm4") + attn(f"{p}.cross_attn_image_to_token", C // 2)
+    spec += attn(f"{t}.final_attn_token_to_image", C // 2) + norm(f"{t}.norm_final_attn")
+    spec += [("mask_decoder.output_upscaling.0.weight", (C, C // 4, 2, 2)), ("mask_decoder.output_upscaling.0.bias", (C // 4,))] + norm("mask_decoder.output_upscaling.1", C // 4)
+    spec += [("mask_decoder.output_upscaling.3.weight", (C // 4, C // 8, 2, 2)), ("mask_decoder.output_upscaling.3.bias", (C // 8,))]
+    for i in range(cfg.num_multimask + 1):
+        for l, (n, k) in enumerate(((C, C), (C, C), (C // 8, C))):
+            spec += [(f"mask_decoder.output_hypernetworks_mlps.{i}.layers.{l}.weight", (n, k)), (f"mask_decoder.output_hypernetworks_mlps.{i}.layers.{l}.bias", (n,))]
+    for l, (n, k) in enumerate(((Hh, C), (Hh, Hh), (cfg.num_multimask + 1, Hh))):
+        spec += [(f"mask_decoder.iou_prediction_head.layers.{l}.weight", (n, k)), (f"mask_decoder.iou_prediction_head.layers.{l}.bias", (n,))]
+    return spec
+
+
+SAM_DECODER_QK_GAIN = 0.25
+
+
+def sam_decoder_synth_tensor(key: str, shape, seed: int) -> torch.Tensor:
+    """The synthetic decoder weights' rule (fp32), per key: the positional gaussian matrix N(0, 1) (unit scale, as segment_anything draws it); every embedding
+    N(0, 0.5^2) and every bias N(0, 0.1^2), none of them zero, so that a dropped term shows; norm gains 1 + N(0, 0.1^2); linear and transposed-conv weights
+    N(0, 1 / fan_in), the q_proj and k_proj ones times SAM_DECODER_QK_GAIN: with variance-preserving q and k the softmaxes are so sharp that torch's own fp32
+    module is 1e-3 from its fp64 self, and a fixture could then not hold an fp32 engine to anything tighter."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed((seed * 1000003 + zlib.crc32(key.encode())) & 0x7FFFFFFF)
+    n = torch.randn(tuple(shape), generator=g, dtype=torch.float32)
+    name = key.rsplit(".", 1)[0]
+    if "gaussian_matrix" in key:
+        return n
+    if "embed" in key or "token" in name.rsplit(".", 1)[-1]:
+        return 0.5 * n
+    if key.endswith(".bias"):
+        return 0.1 * n
+    if ".norm" in name or name.endswith("output_upscaling.1"):
+        return 1.0 + 0.1 * n
+    if "output_upscaling" in name:
+        return n / math.sqrt(shape[0])          # ConvTranspose2d(kernel 2, stride 2): one tap per output pixel, fan-in = input channels
+    w = n / math.sqrt(shape[1])
+    return SAM_DECODER_QK_GAIN * w if name.endswith(("q_proj", "k_proj")) else w
+
+
+def sam_decoder_synth_state_dict(cfg: SAMDecoderConfig, seed: int = 1234) -> Dict[str, torch.Tensor]:
+    return {k: sam_decoder_synth_tensor(k, s, seed) for k, s in sam_decoder_state_dict_spec(cfg)}
