@@ -576,7 +576,13 @@ int64_t ldx_zlib_bound_bytes(int64_t n);
 int ldx_zlib_deflate(const uint8_t* bytes, int64_t n, void* workspace, uint8_t* out, uint32_t* out_len, void* stream);
 
 /* ---- single-op entry points (parity tests call the kernels through these) ----------------------- */
-/* 16-bit tensors are device pointers to bf16/fp16 per `dtype`.  Layouts: see csrc/ldx_kernels.h. */
+/* 16-bit tensors are device pointers to bf16/fp16 per `dtype`.  Layouts: see csrc/ldx_kernels.h.
+ * Extent contract of every entry point of this section (and of the kernels behind them, which the engines hand strided views of one shared arena): an operand
+ * means its LOGICAL extent only — rows [0, rows) and columns [0, cols) of an ld-strided matrix, keys [0, Mk), elements [0, n) of a vector.  A kernel reads
+ * meaning only from, and writes only to, that extent: bytes in the ld padding behind a row and in rows outside [0, rows) belong to another tensor, may hold
+ * anything, non-finite values included, and neither reach a result (a masked tail is selected away, not multiplied by zero) nor are written.  A fused view
+ * (q|k|v, [K | V], [value | gate]) is one logical matrix.  tests/test_guard_bands_gpu.py holds every entry point below to this, bit for bit; the MX fp8 ones
+ * (byte and E8M0 operands) are not covered by that test yet. */
 int ldx_op_convert(const float* in_f32, void* out_16, int64_t n, int dtype, int to_f32, void* stream);
 /* The Q8_0 expansion of ldx_load_tensor_q8_0 alone (csrc/q8.hip): n / 32 blocks of 34 bytes (2-byte aligned) -> out[n], n % 32 == 0.  out_dtype LDX_F16:
  * the fp16 value; LDX_BF16 / LDX_F32: that fp16 value converted (bf16 round-to-nearest-even; fp32 exact).  out is 16-byte aligned.  LDX_EINVAL otherwise. */
